@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the orcAI hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload frontend|predict]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload frontend|predict|train|hpsearch] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic recording already resident in HBM.
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...); the
+timed steps carry no HIP event brackets.  --full adds everything else this file measures: the per-kernel roofline tables
+(event brackets inside the timed steps plus fully bracketed steps after them), the training and sweep lines attached to
+predict, the all-reduce probe, the CPU baseline and the hpsearch loss curves.  --dump-outputs DIR writes what the last
+timed step computed (the arrays a caller of that path receives) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
 For N > 1 (launched by torch.distributed.run, one rank per GPU) every rank processes its own
 recording (independent objects: weak scaling, no data-path collective); the timed region is
 bracketed by barrier + synchronize and the MAX over ranks is reported.  Rank 0 prints ONE JSON line.
@@ -79,6 +86,7 @@ class FrontendWorkload:
         self.ev = []
 
     def step(self, timed: bool):
+        """timed: bracket the STFT kernel with HIP events for roofline() (--full)."""
         N, lib = self.N, self.lib
         s = N.stream_ptr()
         ws = N.ptr(self.fe.workspace)
@@ -94,6 +102,12 @@ class FrontendWorkload:
         N.check(lib.orcai_quantile_select(N.ptr(self.out), n, self.r_lo, self.r_hi, ws, s), "select")
         N.check(lib.orcai_frontend_finalize(1, self.TOP_DB, ws, s), "finalize")
         N.check(lib.orcai_clip_normalize(N.ptr(self.out), n, ws, s), "normalize")
+
+    def outputs(self):
+        """The normalised spectrogram [T, 171] is 515 MB: a fixed, seeded sample of 32768 of its rows (and their indices)."""
+        rows = np.sort(np.random.default_rng(0).choice(self.T, size=min(self.T, 32768), replace=False))
+        sample = self.out[torch.from_numpy(rows).to(self.out.device)]
+        return {"spectrogram_rows": sample, "spectrogram_row_index": rows}
 
     def roofline(self):
         ms = [a.elapsed_time(b) for a, b in self.ev]
@@ -278,6 +292,24 @@ def dp_scaling() -> str:
     return "strong" if dp_batch_mode() == "split" else "weak"
 
 
+OUTPUT_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(arrays: dict, out_dir: str) -> None:
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float64 where the source is float64 or integer, float32 otherwise."""
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > OUTPUT_BYTES_MAX:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {OUTPUT_BYTES_MAX})")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in conv.items():
+        np.save(d / f"{name}.npy", a)
+
+
 def launch_ranks(n: int, argv: list[str]) -> int:
     """`--gpus N` (N > 1) outside a launcher: start N fresh rank processes -- one per GPU, `python -m torch.distributed.run`, rendezvous on
     127.0.0.1 -- BEFORE anything in this process touches the GPU, pass the children's output through (rank 0 prints the JSON line) and
@@ -301,9 +333,13 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; 200 for the 0.7 ms front-end step)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 3; 50 for the front end: its step is too short to bring the clocks up)")
     ap.add_argument("--workload", default="predict" if "predict" in WORKLOADS else "frontend", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the training-throughput measurement attached to the predict line")
-    ap.add_argument("--no-loss-curves", action="store_true", help="hpsearch workload: skip the 200-step f16-vs-f32 loss comparison")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: roofline / per-kernel tables, the training and sweep lines attached to predict, the all-reduce probe, "
+                         "the CPU baseline and the hpsearch loss curves")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the training-throughput measurement attached to the predict line")
+    ap.add_argument("--no-loss-curves", action="store_true", help="with --full, hpsearch workload: skip the 200-step f16-vs-f32 loss comparison")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1; gloo + --one-device rehearses the multi-rank control flow on a single GPU")
     ap.add_argument("--one-device", action="store_true", help="rehearsal only: every rank uses cuda:0 (never a measurement)")
@@ -358,7 +394,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        wl.step(True)
+        wl.step(args.full)  # True: HIP event brackets for the roofline tables (--full only: an event pair costs queue time)
     drain()  # inside the timed region: every recording's label table is complete when the clock stops
     torch.cuda.synchronize()
     if dist:
@@ -369,16 +405,18 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         _reduce(dist, t, dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # before anything else runs a step of this workload
+        dump_outputs(wl.outputs(), args.dump_outputs)
 
     secondary = None
     secondary2 = None
-    if args.workload == "predict" and "train" in WORKLOADS and not args.no_secondary:
+    if args.full and args.workload == "predict" and "train" in WORKLOADS and not args.no_secondary:
         torch.cuda.empty_cache()  # the headline workload's cached blocks back to the driver: the training buffers get fresh, contiguous ranges as in a stand-alone run
         secondary = measure_secondary(device, rank, world, dist)
         torch.cuda.empty_cache()
         secondary2 = measure_sweep(device, rank, world, dist)
 
-    ar_probe = allreduce_probe(dist, wl) if dist and args.workload in ("train", "hpsearch") else {}  # a collective: every rank
+    ar_probe = allreduce_probe(dist, wl) if args.full and dist and args.workload in ("train", "hpsearch") else {}  # a collective: every rank
     if rank == 0:
         value = wl.units_per_step * args.steps * world / elapsed
         line = {
@@ -386,22 +424,23 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": wl.dtype, "data": "synthetic",
             "config": {"workload": wl.name, "units_per_step_per_gpu": round(wl.units_per_step, 3), "parallelism": f"independent recordings x{world}"},
-            "roofline": wl.roofline(),
         }
+        if args.full:
+            line["roofline"] = wl.roofline()
         if dist:  # the world size the process group itself reports (RCCL when backend is nccl)
             line["rccl_ranks" if args.backend == "nccl" else "gloo_ranks"] = dist.get_world_size()
         if secondary is not None:
             line["secondary"] = secondary
         if secondary2 is not None:
             line["secondary2"] = secondary2
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = wl.cpu_baseline()
         if args.workload in ("train", "hpsearch"):
             line["scaling"] = dp_scaling()
             line["config"].update({"dp_batch": dp_batch_mode(), "per_rank_batch": wl.B, "global_batch": wl.B * world})
             line["config"]["parallelism"] = _dp_label(dist, world)
             line.update(ar_probe)
-        if args.workload == "hpsearch" and world == 1 and not args.no_loss_curves:
+        if args.full and args.workload == "hpsearch" and world == 1 and not args.no_loss_curves:
             line["loss_curves_f16_vs_f32"] = wl.loss_curves(args.curve_steps)
         print(json.dumps(line), flush=True)
     if dist:

@@ -150,6 +150,15 @@ class PredictWorkload:
             self.in_flight = None
             s, e, n = compute_binary_predictions(agg, cnt, CALLS, 0.5)
             self.last = compute_labels(s, e, n, 16, "*")
+            self.last_aggregate = (agg, cnt)
+
+    def outputs(self):
+        """What predict_wav hands its caller for the last recording: the overlap-averaged probabilities (with their overlap counts) and the
+        label table (start / stop in spectrogram frames, the call as its index into CALLS)."""
+        agg, cnt = self.last_aggregate
+        t = self.last
+        return {"aggregated_predictions": agg, "overlap_count": cnt, "label_start": t["start"].to_numpy(), "label_stop": t["stop"].to_numpy(),
+                "label_call": np.array([CALLS.index(x.rstrip("*")) for x in t["label"]], dtype=np.int64)}
 
     events: dict = {}
 
@@ -568,10 +577,15 @@ class TrainWorkload:
                 self.timed.events = {}
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        self.trainer.train_step(self.x, 736 * 171, self.B, self.y, world_size=self.world)
+        self.last = self.trainer.train_step(self.x, 736 * 171, self.B, self.y, world_size=self.world)
         if timed:
             e1.record()
             self.ev.append((e0, e1))
+
+    def outputs(self):
+        """After the last step: the step's probabilities and loss accumulators, the updated weights and BatchNorm moving statistics."""
+        P = self.trainer.P
+        return {"probs": self.last["probs"], "loss_accumulators": self.last["acc"], "weights": P.w, "bn_moving_stats": P.stats_flat}
 
     def roofline(self):
         """The step against the f32-MFMA peak, and the dominant kernel SYMBOL of the step against HBM.  Which symbol dominates is measured, not
@@ -767,6 +781,7 @@ class HpsearchWorkload:
             self.trainers[v], self.timed[v] = tr, tl
         self.units_per_step = float(self.B * len(self.variants))
         self.ev = {v: [] for v in self.variants}
+        self.last = {}
 
     def step(self, timed: bool):
         for v in self.variants:
@@ -776,10 +791,18 @@ class HpsearchWorkload:
                     self.timed[v].events = {}
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            tr.train_step(self.x, 736 * 171, self.B, self.y, world_size=self.world)
+            self.last[v] = tr.train_step(self.x, 736 * 171, self.B, self.y, world_size=self.world)
             if timed:
                 e1.record()
                 self.ev[v].append((e0, e1))
+
+    def outputs(self):
+        """TrainWorkload.outputs for every variant of the sweep (f32 master weights), prefixed by the variant."""
+        out = {}
+        for v in self.variants:
+            P, last = self.trainers[v].P, self.last[v]
+            out.update({f"{v}_probs": last["probs"], f"{v}_loss_accumulators": last["acc"], f"{v}_weights": P.w, f"{v}_bn_moving_stats": P.stats_flat})
+        return out
 
     def per_variant(self):
         out = {}

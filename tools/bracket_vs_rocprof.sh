@@ -1,10 +1,10 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/agree; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --workload train --no-cpu-baseline 2>/dev/null | grep "^{" > $O/train.json
-python3 $R/bench.py --workload hpsearch --steps 10 --warmup 3 --no-cpu-baseline --no-loss-curves 2>/dev/null | grep "^{" > $O/hps.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_train -- python3 $R/bench.py --workload train --no-cpu-baseline > $O/p_train.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_hps -- python3 $R/bench.py --workload hpsearch --steps 10 --warmup 3 --no-cpu-baseline --no-loss-curves > $O/p_hps.log 2>&1
+python3 $R/bench.py --full --workload train --no-cpu-baseline 2>/dev/null | grep "^{" > $O/train.json
+python3 $R/bench.py --full --workload hpsearch --steps 10 --warmup 3 --no-cpu-baseline --no-loss-curves 2>/dev/null | grep "^{" > $O/hps.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_train -- python3 $R/bench.py --full --workload train --no-cpu-baseline > $O/p_train.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_hps -- python3 $R/bench.py --full --workload hpsearch --steps 10 --warmup 3 --no-cpu-baseline --no-loss-curves > $O/p_hps.log 2>&1
 python3 - <<PY
 import json,glob,csv
 for w,f in (("train","$O/train.json"),("hps","$O/hps.json")):
