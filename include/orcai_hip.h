@@ -204,10 +204,12 @@ int orcai_gemm_bias_act(const float* A, const float* Bm, const float* bias, cons
 /* Both directions of one Bidirectional(LSTM(units, return_sequences=True)) given xz = x*W + b.
  *   xz  f32[B][T][2][4*units], Uw f32[2][units][4*units], both with the gate columns in the kernel's order:
  *       column 32*w + 16*nt + j  <-  Keras column (2*nt + (j>>3))*units + 8*w + (j&7)     (gate order i,f,c,o)
- *   out f32[B][T][2*units] = concat(forward, backward) at each time step.  units in {64, 128}. */
+ *   out f32[B][T][2*units] = concat(forward, backward) at each time step.  units a multiple of 32 in [32, 256]: up to 128 the recurrent
+ *   matrix stays in registers; 160..256 run the L2-streamed f32-MFMA family of csrc/lstm_wide.hip (for either orcai_lstm_split setting, and
+ *   for the orcai_h_ twins of the training entries below); the training backward then needs Uw and dxz 16-byte aligned (ORCAI_E_BADARG). */
 int orcai_lstm_recurrent(const float* xz, const float* Uw, int B, int T, int units, float* out, void* stream);
 
-/* out[M][N] = sigmoid(x[M][K] * w[K][N] + b[N]),  N <= 8   (architectures.py:239) */
+/* out[M][N] = sigmoid(x[M][K] * w[K][N] + b[N]),  1 <= N <= 64   (architectures.py:239) */
 int orcai_dense_sigmoid(const float* x, const float* w, const float* bias, int64_t M, int K, int N, float* out, void* stream);
 
 /* predict.py:276-293: overlay the n snippet predictions [n][P][L] at offsets i*step, count overlaps, divide.

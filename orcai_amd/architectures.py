@@ -31,6 +31,10 @@ def _bn_names(prefix):
     return [f"{prefix}/gamma", f"{prefix}/beta", f"{prefix}/mean", f"{prefix}/var"]
 
 
+LSTM_UNITS = tuple(range(32, 257, 32))  # widths of the recurrence kernels: register-resident U up to 128, L2-streamed U above (csrc/lstm_wide.hip)
+MAX_LABELS = 64  # orcai_dense_sigmoid, orcai_conv1d_sigmoid
+
+
 def lstm_column_permutation(units: int) -> np.ndarray:
     """perm[p] = Keras gate column held by kernel column p (see orcai_lstm_recurrent in orcai_hip.h)."""
     p = np.arange(4 * units)
@@ -65,12 +69,12 @@ class ResNetLSTM:
         self.lstm_units = int(lstm_units)
         if self.kernel_size not in (3, 5, 7):
             raise NotImplementedError("HIP kernels implement kernel_size 3, 5 and 7")
-        if self.lstm_units not in (64, 128):
-            raise NotImplementedError("HIP LSTM kernel implements lstm_units 64 and 128")
+        if self.lstm_units not in LSTM_UNITS:
+            raise NotImplementedError(f"HIP LSTM kernels implement lstm_units a multiple of 32 in [32, 256], got {self.lstm_units}")
         if max(self.filters + [FINAL_FILTERS]) > 64:
             raise NotImplementedError("HIP separable-conv kernel implements up to 64 filters")
-        if self.num_labels > 8:
-            raise NotImplementedError("HIP head kernel implements up to 8 labels")
+        if not 1 <= self.num_labels <= MAX_LABELS:
+            raise NotImplementedError(f"HIP head kernels implement 1 to {MAX_LABELS} labels, got {self.num_labels}")
         # "f32" (the reference's arithmetic, default) or "f16": f16 octet planes + v_mfma_f32_16x16x32_f16 contractions with f32
         # master weights (orcai_amd/half.py; BASELINE configs[4]).  An extra key of orcai_parameter["model"], swallowed by the
         # reference's **unused like any other (architectures.py:129).

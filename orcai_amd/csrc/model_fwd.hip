@@ -21,6 +21,9 @@
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
+// lstm_wide.hip: the recurrences for 128 < units <= 256 (gates == NULL: inference)
+__attribute__((visibility("hidden"))) int lstm_wide_fwd_launch(const float* xz, const float* Uw, int B, int T, int units, float* out, float* gates, float* cstate, void* stream);
+
 int g_orcai_lstm_split = 1;  // 1: the LSTM recurrences of the f32 path run on split-f16 MFMA at f32 accuracy; 0: on v_mfma_f32_16x16x4_f32 (orcai_lstm_split)
 
 namespace {
@@ -2195,6 +2198,57 @@ __global__ __launch_bounds__(256) void dense_sigmoid_rows_kernel(const float* __
   }
 }
 
+// 8 < N <= 64: the rows kernel's eight lanes per row, one tile of 16 labels per blockIdx.y (x is re-read once per tile, from L2 for all but the
+// first).  VEC: K a multiple of 4 and x 16-byte aligned (float4 reads, the rows kernel's order); otherwise lane j sums k = j, j + 8, ...
+// The eight partial sums meet by three lane exchanges; lane j then writes labels 16 tile + j and 16 tile + 8 + j.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dense_sigmoid_wide_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                                  int64_t M, int K, int N, float* __restrict__ out) {
+  constexpr int NT = 16;
+  const int j = threadIdx.x & 7;
+  const int n0 = blockIdx.y * NT;
+  const int64_t m = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 3);
+  const bool live = m < M;
+  float acc[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) acc[n] = 0.0f;
+  const float* xm = x + (live ? m : 0) * K;
+  const float* wn = w + n0;
+  if (VEC) {
+    const float4* xr = reinterpret_cast<const float4*>(xm);
+    for (int q = j; q < (K >> 2); q += 8) {
+      const float4 v = xr[q];
+      const float* wq = wn + (int64_t)q * 4 * N;
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+        if (n0 + n < N) acc[n] = fmaf(v.w, wq[3 * N + n], fmaf(v.z, wq[2 * N + n], fmaf(v.y, wq[N + n], fmaf(v.x, wq[n], acc[n]))));
+    }
+  } else {
+    for (int k = j; k < K; k += 8) {
+      const float v = xm[k];
+      const float* wk = wn + (int64_t)k * N;
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+        if (n0 + n < N) acc[n] = fmaf(v, wk[n], acc[n]);
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    acc[n] += __shfl_xor(acc[n], 1);
+    acc[n] += __shfl_xor(acc[n], 2);
+    acc[n] += __shfl_xor(acc[n], 4);
+  }
+  if (!live) return;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float a = acc[8 * h];
+#pragma unroll
+    for (int n = 1; n < 8; ++n) a = j == n ? acc[8 * h + n] : a;
+    const int col = n0 + 8 * h + j;
+    if (col < N) out[m * N + col] = 1.0f / (1.0f + expf(-(a + bias[col])));
+  }
+}
+
 // =========================================================================================
 // overlap_average: predict.py:276-293.  Output step s is covered by snippets i with step*i <= s < step*i + P.
 // float64 accumulate in snippet order, then divide by the count (bit-exact with the numpy loop).
@@ -2733,12 +2787,18 @@ int orcai_lstm_split(int on) {
 
 int orcai_lstm_recurrent(const float* xz, const float* Uw, int B, int T, int units, float* out, void* stream) {
   if (!xz || !Uw || !out || B <= 0 || T <= 0) return ORCAI_E_BADARG;
+  if (units < 32 || units > 256 || units % 32) return ORCAI_E_UNSUPPORTED;
+  // 160..256: one direction's U no longer fits a compute unit's registers -- the L2-streamed family of lstm_wide.hip (f32 MFMA, either setting of
+  // orcai_lstm_split).  32..128: U resident in registers, 8 units per wave (U * 8 threads); every multiple of 32 tiles both variants.
+  if (units > 128) return lstm_wide_fwd_launch(xz, Uw, B, T, units, out, nullptr, nullptr, stream);
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
   if (g_orcai_lstm_split) {
     switch (units) {
       case 128: hipLaunchKernelGGL(lstm_split_kernel<128>, grid, dim3(1024), 0, st, xz, Uw, B, T, out); break;
       case 64: hipLaunchKernelGGL(lstm_split_kernel<64>, grid, dim3(512), 0, st, xz, Uw, B, T, out); break;
+      case 96: hipLaunchKernelGGL(lstm_split_kernel<96>, grid, dim3(768), 0, st, xz, Uw, B, T, out); break;
+      case 32: hipLaunchKernelGGL(lstm_split_kernel<32>, grid, dim3(256), 0, st, xz, Uw, B, T, out); break;
       default: return ORCAI_E_UNSUPPORTED;
     }
     return (int)hipGetLastError();
@@ -2746,6 +2806,8 @@ int orcai_lstm_recurrent(const float* xz, const float* Uw, int B, int T, int uni
   switch (units) {
     case 128: hipLaunchKernelGGL(lstm_kernel<128>, grid, dim3(1024), 0, st, xz, Uw, B, T, out); break;
     case 64: hipLaunchKernelGGL(lstm_kernel<64>, grid, dim3(512), 0, st, xz, Uw, B, T, out); break;
+    case 96: hipLaunchKernelGGL(lstm_kernel<96>, grid, dim3(768), 0, st, xz, Uw, B, T, out); break;
+    case 32: hipLaunchKernelGGL(lstm_kernel<32>, grid, dim3(256), 0, st, xz, Uw, B, T, out); break;
     default: return ORCAI_E_UNSUPPORTED;
   }
   return (int)hipGetLastError();
@@ -2753,7 +2815,15 @@ int orcai_lstm_recurrent(const float* xz, const float* Uw, int B, int T, int uni
 
 int orcai_dense_sigmoid(const float* x, const float* w, const float* bias, int64_t M, int K, int N, float* out, void* stream) {
   if (!x || !w || !bias || !out || M <= 0 || K <= 0 || N <= 0) return ORCAI_E_BADARG;
-  if (N > 8) return ORCAI_E_UNSUPPORTED;
+  if (N > 64) return ORCAI_E_UNSUPPORTED;
+  if (N > 8) {  // label tiles of 16 on blockIdx.y; N <= 8 keeps the kernels below (and their results) exactly as they were
+    const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N + 15) / 16));
+    if ((K & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+      hipLaunchKernelGGL(dense_sigmoid_wide_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, M, K, N, out);
+    else
+      hipLaunchKernelGGL(dense_sigmoid_wide_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, M, K, N, out);
+    return (int)hipGetLastError();
+  }
   if ((K & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
     hipLaunchKernelGGL(dense_sigmoid_rows_kernel, dim3((unsigned)((M + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x, w, bias, M, K, N, out);
   else

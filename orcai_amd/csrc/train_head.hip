@@ -12,6 +12,9 @@
 #include "zero_fill.h"
 
 extern int g_orcai_lstm_split;  // model_fwd.hip: 1 = LSTM recurrences of the f32 path on split-f16 MFMA (orcai_lstm_split)
+// lstm_wide.hip: the recurrences for 128 < units <= 256, f32 MFMA with U streamed from L2 (both precisions run them)
+__attribute__((visibility("hidden"))) int lstm_wide_fwd_launch(const float* xz, const float* Uw, int B, int T, int units, float* out, float* gates, float* cstate, void* stream);
+__attribute__((visibility("hidden"))) int lstm_wide_bwd_launch(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, int units, float* dxz, void* stream);
 
 namespace {
 
@@ -1605,12 +1608,16 @@ int orcai_adam_step(float* w, const float* g, float* m, float* v, int64_t n, flo
 int orcai_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int units, float* out, float* gates, float* cstate, void* stream) {
   if (!xz || !Uw || !out || !gates || !cstate || B <= 0 || T <= 0) return ORCAI_E_BADARG;
   if ((int64_t)B * T * 8 * units >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;  // 32-bit element offsets inside the kernels
+  if (units < 32 || units > 256 || units % 32) return ORCAI_E_UNSUPPORTED;
+  if (units > 128) return lstm_wide_fwd_launch(xz, Uw, B, T, units, out, gates, cstate, stream);
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
   if (g_orcai_lstm_split) {
     switch (units) {
       case 128: hipLaunchKernelGGL(lstm_train_fwd_split_kernel<128>, grid, dim3(1024), 0, st, xz, Uw, B, T, out, gates, cstate); break;
       case 64: hipLaunchKernelGGL(lstm_train_fwd_split_kernel<64>, grid, dim3(512), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+      case 96: hipLaunchKernelGGL(lstm_train_fwd_split_kernel<96>, grid, dim3(768), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+      case 32: hipLaunchKernelGGL(lstm_train_fwd_split_kernel<32>, grid, dim3(256), 0, st, xz, Uw, B, T, out, gates, cstate); break;
       default: return ORCAI_E_UNSUPPORTED;
     }
     return (int)hipGetLastError();
@@ -1618,6 +1625,8 @@ int orcai_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int uni
   switch (units) {
     case 128: hipLaunchKernelGGL(lstm_train_fwd_kernel<128>, grid, dim3(1024), 0, st, xz, Uw, B, T, out, gates, cstate); break;
     case 64: hipLaunchKernelGGL(lstm_train_fwd_kernel<64>, grid, dim3(512), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+    case 96: hipLaunchKernelGGL(lstm_train_fwd_kernel<96>, grid, dim3(768), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+    case 32: hipLaunchKernelGGL(lstm_train_fwd_kernel<32>, grid, dim3(256), 0, st, xz, Uw, B, T, out, gates, cstate); break;
     default: return ORCAI_E_UNSUPPORTED;
   }
   return (int)hipGetLastError();
@@ -1625,6 +1634,8 @@ int orcai_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int uni
 
 int orcai_h_lstm_bwd(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, int units, float* dxz, void* stream) {
   if (!dH || !gates || !cstate || !Uw || !dxz || B <= 0 || T <= 0) return ORCAI_E_BADARG;
+  if (units < 32 || units > 256 || units % 32) return ORCAI_E_UNSUPPORTED;
+  if (units > 128) return lstm_wide_bwd_launch(dH, gates, cstate, Uw, B, T, units, dxz, stream);  // the f32 wide kernel (f32 products: more accurate than f16)
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
   if (units == 128) {
@@ -1643,8 +1654,22 @@ int orcai_h_lstm_bwd(const float* dH, const float* gates, const float* cstate, c
   } else if (units == 64) {
     const size_t lds = (size_t)2 * 16 * (4 * 64 + 4) * 4 + (size_t)2 * 16 * (4 * 64 + 8) * 2;  // 50 176 B
     hipLaunchKernelGGL(lstm_bwd_h_kernel<64>, grid, dim3(256), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-  } else {
-    return ORCAI_E_UNSUPPORTED;
+  } else if (units == 96) {
+    const size_t lds = (size_t)2 * 16 * (4 * 96 + 4) * 4 + (size_t)2 * 16 * (4 * 96 + 8) * 2;  // 74 752 B > 64 KiB: opt in once per device
+    static bool opted96_dev[64] = {};
+    int devid = 0;
+    hipError_t e = hipGetDevice(&devid);
+    if (e != hipSuccess) return (int)e;
+    if (devid < 0 || devid >= 64) return ORCAI_E_UNSUPPORTED;
+    if (!opted96_dev[devid]) {
+      e = hipFuncSetAttribute((const void*)lstm_bwd_h_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+      opted96_dev[devid] = true;
+    }
+    hipLaunchKernelGGL(lstm_bwd_h_kernel<96>, grid, dim3(384), lds, st, dH, gates, cstate, Uw, B, T, dxz);
+  } else {  // 32
+    const size_t lds = (size_t)2 * 16 * (4 * 32 + 4) * 4 + (size_t)2 * 16 * (4 * 32 + 8) * 2;  // 25 600 B
+    hipLaunchKernelGGL(lstm_bwd_h_kernel<32>, grid, dim3(128), lds, st, dH, gates, cstate, Uw, B, T, dxz);
   }
   return (int)hipGetLastError();
 }
@@ -1656,6 +1681,9 @@ int orcai_h_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int u
   switch (units) {
     case 128: hipLaunchKernelGGL(lstm_train_fwd_h_kernel<128>, grid, dim3(1024), 0, st, xz, Uw, B, T, out, gates, cstate); break;
     case 64: hipLaunchKernelGGL(lstm_train_fwd_h_kernel<64>, grid, dim3(512), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+    case 96: hipLaunchKernelGGL(lstm_train_fwd_h_kernel<96>, grid, dim3(768), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+    case 32: hipLaunchKernelGGL(lstm_train_fwd_h_kernel<32>, grid, dim3(256), 0, st, xz, Uw, B, T, out, gates, cstate); break;
+    case 160: case 192: case 224: case 256: return lstm_wide_fwd_launch(xz, Uw, B, T, units, out, gates, cstate, stream);  // the f32 wide kernel
     default: return ORCAI_E_UNSUPPORTED;
   }
   return (int)hipGetLastError();
@@ -1664,15 +1692,17 @@ int orcai_h_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int u
 int orcai_lstm_bwd(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, int units, float* dxz, void* stream) {
   if (!dH || !gates || !cstate || !Uw || !dxz || B <= 0 || T <= 0) return ORCAI_E_BADARG;
   if ((int64_t)B * T * 8 * units >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;  // 32-bit element offsets inside the split kernel
+  if (units < 32 || units > 256 || units % 32) return ORCAI_E_UNSUPPORTED;
+  if (units > 128) return lstm_wide_bwd_launch(dH, gates, cstate, Uw, B, T, units, dxz, stream);  // f32 MFMA, no gradient scale: either split setting
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
-  if (g_orcai_lstm_split && (units == 128 || units == 64)) {
+  if (g_orcai_lstm_split) {
     // per DEVICE: the address of the max accumulator (a __device__ symbol has one instance per device) and the > 64 KiB LDS opt-ins (function
     // attributes are per device too).  Looked up on a device's first call, which is never inside a stream capture (warm-up steps come first).
     // The scale itself travels through the device global g_lstm_grad_scale: ONE backward recurrence in flight per device (include/orcai_hip.h).
     constexpr int MAXDEV = 64;
     static uint32_t* maxbits_dev[MAXDEV] = {};
-    static bool opted_dev[MAXDEV][2] = {};
+    static bool opted_dev[MAXDEV][4] = {};
     int devid = 0;
     hipError_t e = hipGetDevice(&devid);
     if (e != hipSuccess) return (int)e;
@@ -1693,19 +1723,30 @@ int orcai_lstm_bwd(const float* dH, const float* gates, const float* cstate, con
         opted_dev[devid][0] = true;
       }
       hipLaunchKernelGGL(lstm_bwd_split_kernel<128>, grid, dim3(512), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-    } else {
+    } else if (units == 64) {
       if (!opted_dev[devid][1]) {  // 66 816 B
         e = hipFuncSetAttribute((const void*)lstm_bwd_split_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
         opted_dev[devid][1] = true;
       }
       hipLaunchKernelGGL(lstm_bwd_split_kernel<64>, grid, dim3(256), lds, st, dH, gates, cstate, Uw, B, T, dxz);
+    } else if (units == 96) {
+      if (!opted_dev[devid][2]) {  // 99 840 B
+        e = hipFuncSetAttribute((const void*)lstm_bwd_split_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        opted_dev[devid][2] = true;
+      }
+      hipLaunchKernelGGL(lstm_bwd_split_kernel<96>, grid, dim3(384), lds, st, dH, gates, cstate, Uw, B, T, dxz);
+    } else {  // 32: 34 304 B
+      hipLaunchKernelGGL(lstm_bwd_split_kernel<32>, grid, dim3(128), lds, st, dH, gates, cstate, Uw, B, T, dxz);
     }
     return (int)hipGetLastError();
   }
   switch (units) {
     case 128: hipLaunchKernelGGL(lstm_bwd_kernel<128>, grid, dim3(512), 0, st, dH, gates, cstate, Uw, B, T, dxz); break;
     case 64: hipLaunchKernelGGL(lstm_bwd_kernel<64>, grid, dim3(256), 0, st, dH, gates, cstate, Uw, B, T, dxz); break;
+    case 96: hipLaunchKernelGGL(lstm_bwd_kernel<96>, grid, dim3(384), 0, st, dH, gates, cstate, Uw, B, T, dxz); break;
+    case 32: hipLaunchKernelGGL(lstm_bwd_kernel<32>, grid, dim3(128), 0, st, dH, gates, cstate, Uw, B, T, dxz); break;
     default: return ORCAI_E_UNSUPPORTED;
   }
   return (int)hipGetLastError();
