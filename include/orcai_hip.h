@@ -629,6 +629,11 @@ int orcai_h_conv0_bn_bwd(const float* in, int64_t snippet_stride, const void* dy
 int orcai_h_pack_weights(const float* w, const int* desc, int n_desc, void* out, void* stream);
 int orcai_h_feat_to_planes(const float* f, int B, int C, int H, int W, int ksize, void* out, void* stream);
 int orcai_h_planes_relu_bwd(const void* dy, const void* y, int64_t n_halves, void* dx, void* stream);
+/* Dropout between the residual blocks of ResNet1DConv on the f16 path (csrc/half_dropout.hip); both count f16 elements and need 16-byte aligned buffers.
+ *   orcai_h_dropout_mask_dev   f16 0/1 mask: element i is element i of orcai_dropout_mask_dev with the same arguments (bit for bit)
+ *   orcai_h_mask_scale         y = f16((f32(x) * f32(mask)) * scale), y == x allowed (the f16 twin of orcai_mask_scale) */
+int orcai_h_dropout_mask_dev(void* mask, int64_t n, const uint64_t* counter, uint64_t seed_add, float keep, void* stream);
+int orcai_h_mask_scale(const void* x, const void* mask, float scale, int64_t n, void* y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,8 @@ _SIGNATURES = {
     "orcai_h_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_h_feat_to_planes": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "orcai_h_planes_relu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "orcai_h_dropout_mask_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]),
+    "orcai_h_mask_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_dropout_mask_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]),
     "orcai_adam_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
     "orcai_counter_advance": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -560,15 +560,16 @@ class ResNet1DConv(ResNetLSTM):
     """CNN with residual connections + frequency mean + one Conv1D over time (architectures.py:18-117).  The convolutional trunk
     is the ResNetLSTM one (the per-block Dropout layers are the identity at inference); the head is ReduceFrequencyMean
     (:10-15) and Conv1D(num_labels, kernel_size = 36, "same", sigmoid) (:107-115).  Training adds the Dropout after every block and
-    after BN_f (orcai_amd.training.Conv1DHeadTrainer, TrunkTrainer.block_masks)."""
+    after BN_f (orcai_amd.training.Conv1DHeadTrainer, TrunkTrainer.block_masks).  Both precisions: on the f16 path the trunk runs on
+    f16 octet planes and the head on the f32 kernels, as for ResNetLSTM."""
 
     architecture = "ResNet1DConv"
     conv_kind = "glorot"  # conv_initializer default "glorot_uniform" (architectures.py:24)
 
     def __init__(self, input_shape, num_labels, filters, kernel_size, dropout_rate=0.0, conv_initializer="glorot_uniform", seed=None, **unused):
-        if unused.get("precision", "f32") != "f32":
-            raise NotImplementedError("the f16 path implements ResNetLSTM only")
-        super().__init__(input_shape, num_labels, filters, kernel_size, dropout_rate, lstm_units=128, conv_initializer=conv_initializer, seed=seed)
+        # precision "f16": the ResNetLSTM f16 trunk (orcai_amd/half.py), the f16 Dropout between blocks; the head stays f32 on both paths
+        super().__init__(input_shape, num_labels, filters, kernel_size, dropout_rate, lstm_units=128, conv_initializer=conv_initializer, seed=seed,
+                         precision=unused.get("precision", "f32"))
 
     def _head_spec(self):
         k1 = FINAL_FILTERS  # k_size = x.shape[2] after the frequency mean = the channel count (architectures.py:108)

@@ -123,14 +123,16 @@ def _epoch_logs(acc: np.ndarray, prefix: str = "") -> dict:
 class FitLoop:
     def __init__(self, model, trainer: Trainer, graph_step: bool | None = None):
         self.model, self.trainer, self.stop_training = model, trainer, False
-        # One GPU, ResNetLSTM, no class weights: the whole step is captured once as a hipGraph and replayed (Trainer.train_step_graphed) --
+        # One GPU, ResNetLSTM (or f16 ResNet1DConv), no class weights: the whole step is captured once as a hipGraph and replayed (Trainer.train_step_graphed) --
         # what Keras' compiled train function is to the reference (train.py:201-219); the step then no longer depends on the host's launch
         # rate.  orcai_parameter["model"]["graph_step"] = false or ORCAI_GRAPH_STEP=0 keeps eager launches.
         if graph_step is None:
             import os
 
             graph_step = bool(getattr(model, "graph_step", True)) and os.environ.get("ORCAI_GRAPH_STEP", "1") != "0"
-        self.graph_step = bool(graph_step) and getattr(model, "architecture", "") == "ResNetLSTM"
+        # ResNet1DConv replays its step on the f16 path (its block masks are drawn inside the step from the device counter); f32 ResNet1DConv keeps eager steps
+        arch, precision = getattr(model, "architecture", ""), getattr(model, "precision", "f32")
+        self.graph_step = bool(graph_step) and (arch == "ResNetLSTM" or (arch == "ResNet1DConv" and precision == "f16"))
 
     def evaluate(self, dataset) -> dict:
         """Inference-mode pass (moving BN statistics, no dropout): mean masked BCE + L2 and masked binary accuracy."""

@@ -1,5 +1,6 @@
 """The f16 path (BASELINE configs[4], "fp16 MFMA path" of the hyper-parameter sweep; reference strategy hpsearch.py:186-205 over the
-width variants of defaults/default_hps_parameter.json:2-25): the same ResNetLSTM (architectures.py:162-241) with
+width variants of defaults/default_hps_parameter.json:2-25): the same ResNetLSTM (architectures.py:162-241) -- or ResNet1DConv, whose trunk
+is the same and whose head (frequency mean, Conv1D + sigmoid) runs on the f32 kernels -- with
   * activations stored as f16 channel-octet planes [snippet][ceil(C/8)][H + 2R][WP][8] (csrc/half_planes.h),
   * every contraction -- pointwise / residual 1x1 convolutions, LSTM input projections, Dense-128 -- on v_mfma_f32_16x16x32_f16 with
     f32 accumulation, depthwise taps in packed f16, BatchNorm / bias / activations in f32 registers,
@@ -53,12 +54,14 @@ def pack_transposed(W: np.ndarray) -> np.ndarray:
 
 
 class HalfEngine:
-    """Inference forward of a ResNetLSTM on the f16 path.  Holds the f16 weight copies and the octet-plane workspaces."""
+    """Inference forward of a ResNetLSTM or ResNet1DConv on the f16 path.  Holds the f16 weight copies and the octet-plane workspaces."""
 
     def __init__(self, model):
-        if getattr(model, "architecture", "") != "ResNetLSTM":
-            raise NotImplementedError("the f16 path implements the ResNetLSTM architecture (the one the hyper-parameter sweep trains)")
+        arch = getattr(model, "architecture", "")
+        if arch not in ("ResNetLSTM", "ResNet1DConv"):
+            raise NotImplementedError(f"the f16 path implements ResNetLSTM and ResNet1DConv, not {arch!r}")
         self.m = model
+        self.conv1d = arch == "ResNet1DConv"  # the head: frequency mean + Conv1D on the f32 kernels, no LSTM / Dense weights to pack
         self._dev = None
         self._ws = {}
 
@@ -89,6 +92,11 @@ class HalfEngine:
             d[f"b{b}/res/w"] = self._up(pack_pointwise_fragments(w[f"b{b}/res/kernel"][0, 0]))
             d[f"b{b}/res/b"] = self._up(w[f"b{b}/res/bias"], np.float32)
         sep("sep_f", "bn_f")
+        if self.conv1d:
+            d["conv1d/W"] = self._up(w["conv1d/kernel"], np.float32)
+            d["conv1d/b"] = self._up(w["conv1d/bias"], np.float32)
+            self._dev = d
+            return d
         perm = lstm_column_permutation(m.lstm_units)
         for layer in (1, 2):
             Wc = np.concatenate([w[f"lstm{layer}/{dd}/kernel"][:, perm] for dd in ("fwd", "bwd")], axis=1)  # [Fin][2*4u]
@@ -174,6 +182,15 @@ class HalfEngine:
     def head(self, feat: torch.Tensor, out: torch.Tensor, keep: dict | None = None) -> None:
         m, lib, d, st = self.m, N.lib(), self.prepare(), N.stream_ptr()
         n, h, fin = int(feat.shape[0]), int(feat.shape[1]), int(feat.shape[2])
+        launch = m._launch
+        if self.conv1d:  # sep_f (BN_f + ReLU folded) left f32 feat in the Keras Reshape layout: the head of ResNet1DConv.head_device
+            fm = torch.empty((n, h, FINAL_FILTERS), dtype=torch.float32, device=feat.device)
+            launch("h/freq_mean", "orcai_freq_mean", lib.orcai_freq_mean, N.ptr(feat), n * h, fin // FINAL_FILTERS, FINAL_FILTERS, N.ptr(fm), st)
+            launch("h/conv1d", "orcai_conv1d_sigmoid", lib.orcai_conv1d_sigmoid, N.ptr(fm), N.ptr(d["conv1d/W"]), N.ptr(d["conv1d/b"]), n, h, FINAL_FILTERS,
+                   FINAL_FILTERS, m.num_labels, out.data_ptr(), st)
+            if keep is not None:
+                keep.update({"feat": feat.clone(), "freq_mean": fm.clone()})
+            return
         u = m.lstm_units
         dev = feat.device
         xz = torch.empty((n, h, 2, 4 * u), dtype=torch.float32, device=dev)
@@ -181,7 +198,6 @@ class HalfEngine:
         h2 = torch.empty((n, h, 2 * u), dtype=torch.float32, device=dev)
         M = n * h
         x = feat
-        launch = m._launch
         for layer, hout in ((1, h1), (2, h2)):
             launch(f"h/lstm{layer}/gemm", "orcai_h_gemm_bias_act", lib.orcai_h_gemm_bias_act, N.ptr(x), N.ptr(d[f"lstm{layer}/Wt"]), N.ptr(d[f"lstm{layer}/b"]), None, None,
                    N.ptr(xz), M, 8 * u, fin, 0, st)

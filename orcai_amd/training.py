@@ -297,10 +297,11 @@ class Conv1DHeadTrainer:
     """ResNet1DConv head in training mode (architectures.py:100-115): BN_f + ReLU of the final separable conv (Keras Reshape
     layout), Dropout, ReduceFrequencyMean, Conv1D(num_labels, k = 36, same) + sigmoid, masked BCE (no weight regularisers)."""
 
-    def __init__(self, model, params: FlatParams):
+    def __init__(self, model, params: FlatParams, grad_scale: float = 1.0):
         self.model, self.P = model, params
         self.lib = N.lib()
         self.cache = None
+        self.grad_scale = float(grad_scale)  # static loss scale of the f16 path, carried by every gradient from the loss on (undone in Adam)
 
     def forward(self, featv: torch.Tensor, masks: dict | None, rate: float) -> torch.Tensor:
         lib, P, st = self.lib, self.P, N.stream_ptr()
@@ -340,7 +341,7 @@ class Conv1DHeadTrainer:
         acc = torch.zeros(4, dtype=torch.float64, device=labels.device)  # bce sum, count, correct, l2 (stays 0)
         dz = torch.empty((M, L), **f32)
         N.check(lib.orcai_masked_bce_w(c["probs"].data_ptr(), labels.contiguous().data_ptr(), M * L, MASK_VALUE, acc.data_ptr(), dz.data_ptr(),
-                                       None if loss_weight is None else loss_weight.data_ptr(), 1.0, st), "masked_bce")
+                                       None if loss_weight is None else loss_weight.data_ptr(), self.grad_scale, st), "masked_bce")
         dfm = torch.empty((n, T, FINAL_FILTERS), **f32)
         N.check(lib.orcai_conv1d_bwd(c["fm"].data_ptr(), P.W("conv1d/kernel").data_ptr(), dz.data_ptr(), n, T, FINAL_FILTERS, FINAL_FILTERS, L,
                                      P.G("conv1d/kernel").data_ptr(), dfm.data_ptr(), st), "conv1d_bwd")  # the gradient buffer was zeroed at the start of the step
@@ -383,8 +384,6 @@ class TrunkTrainer:
         self.half = bool(half)
         self.G = 8 if self.half else 4  # channels per 16-byte pixel vector
         self.adt = torch.float16 if self.half else torch.float32
-        if self.half and getattr(model, "architecture", "") != "ResNetLSTM":
-            raise NotImplementedError("the f16 path implements ResNetLSTM only")
         self._own_scratch = torch.zeros(8 * 16 * 32, dtype=torch.float64, device=self.dev)  # 8 doubles per channel quad (<= 64 channels) x the 32 accumulator copies of orcai_bn_planes_stats
         self.scratch = self._own_scratch
         # One clear per step instead of one 5-us zero-fill launch per reduction (~30 per step): every launcher that accumulates gets its own 32-KiB slot of
@@ -711,7 +710,7 @@ class TrunkTrainer:
             res_in = prev
             if self.block_masks is not None:  # ResNet1DConv: Dropout after every block; the dropped tensor feeds the next separable conv only
                 dropped = b[f"prevd{i}"]
-                N.check(lib.orcai_mask_scale(prev.data_ptr(), self.block_masks[i - 1].data_ptr(), 1.0 / (1.0 - self.block_rate), prev.numel(), dropped.data_ptr(), st),
+                N.check(self._fn("mask_scale")(prev.data_ptr(), self.block_masks[i - 1].data_ptr(), 1.0 / (1.0 - self.block_rate), prev.numel(), dropped.data_ptr(), st),
                         "mask_scale")
                 prev = dropped
         h, w, _ = shapes[-1]
@@ -781,9 +780,9 @@ class TrunkTrainer:
         return bool(self.conv0_in_dgrad and self.fused_dw_bwd and not self.v0_stored and not self.half and self.k == 3 and x.data_ptr() == self.buf["y0"].data_ptr())
 
     def _conv0_dgrad_half_ok(self, x) -> bool:
-        """f16 path: block 1's first conv takes bn0's sums and the residual gradient into its marching pass (x = the stored v0)."""
-        return bool(self.half and self.conv0_in_dgrad and self.fused_dw_bwd and self.v0_stored and self.k == 3 and self.block_masks is None
-                    and x.data_ptr() == self.buf["y0"].data_ptr())
+        """f16 path: block 1's first conv takes bn0's sums and the residual gradient into its marching pass (x = the stored v0).  Block Dropout
+        (ResNet1DConv) changes nothing here: no Dropout sits in front of block 1, and the residual gradient it adds is taken w.r.t. the un-dropped y0."""
+        return bool(self.half and self.conv0_in_dgrad and self.fused_dw_bwd and self.v0_stored and self.k == 3 and x.data_ptr() == self.buf["y0"].data_ptr())
 
     def _dw_bwd_fused(self, name, x, relu_in, Cin, H, W, du, dr, epi, x_bn):
         """orcai_dw_bwd_fused for one separable conv: dr, the depthwise weight gradient and the epilogue extra `epi` of _dgrad in one pass over
@@ -904,7 +903,7 @@ class TrunkTrainer:
             ho, wo, _ = shapes[i]
             x_in, prev = self.block_in[i]  # input of sep_a (dropped for ResNet1DConv) / input of the residual conv
             if self.block_masks is not None and i == L:  # sep_f read Dropout(prev_L): its input gradient goes back through that Dropout
-                N.check(lib.orcai_mask_scale(dprev.data_ptr(), self.block_masks[i - 1].data_ptr(), 1.0 / (1.0 - self.block_rate), dprev.numel(), dprev.data_ptr(), st),
+                N.check(self._fn("mask_scale")(dprev.data_ptr(), self.block_masks[i - 1].data_ptr(), 1.0 / (1.0 - self.block_rate), dprev.numel(), dprev.data_ptr(), st),
                         "mask_scale")
             dout = dprev  # gradient w.r.t. prev_i (planes of f channels, ho x wo)
             bias_in_pool = self.bias_in_pool
@@ -952,7 +951,7 @@ class TrunkTrainer:
             if i > 1 and not relu_done:
                 N.check(self._fn("planes_relu_bwd")(dr.data_ptr(), x_in.data_ptr(), dr.numel(), dr.data_ptr(), st), "planes_relu_bwd")
             if self.block_masks is not None and i > 1:  # x_in = Dropout(prev_{i-1}): back to the un-dropped tensor before the residual gradient joins
-                N.check(lib.orcai_mask_scale(dr.data_ptr(), self.block_masks[i - 2].data_ptr(), 1.0 / (1.0 - self.block_rate), dr.numel(), dr.data_ptr(), st), "mask_scale")
+                N.check(self._fn("mask_scale")(dr.data_ptr(), self.block_masks[i - 2].data_ptr(), 1.0 / (1.0 - self.block_rate), dr.numel(), dr.data_ptr(), st), "mask_scale")
             if not (i == 1 and self._resq is not None and self.bn0_sums_ready):  # (block 1 with the residual gradient already inside dr)
                 self._sep(dout, f, ho, wo, 1, 0, self._w_ones_dw(f), wrt, self._zeros(64), cprev, dr, layout=3, H2=h, W2=w)
             self._resq = None
@@ -994,7 +993,7 @@ class Trainer:
             self.grad_scale = 1.0
         self.trunk = TrunkTrainer(model, self.P, half=self.half)
         self.conv1d = getattr(model, "architecture", "") == "ResNet1DConv"
-        self.head = Conv1DHeadTrainer(model, self.P) if self.conv1d else HeadTrainer(model, self.P, half=self.half, grad_scale=self.grad_scale)
+        self.head = Conv1DHeadTrainer(model, self.P, grad_scale=self.grad_scale) if self.conv1d else HeadTrainer(model, self.P, half=self.half, grad_scale=self.grad_scale)
         self.skipped = torch.zeros(1, dtype=torch.int64, device=self.dev)  # f16 path: steps voided by a non-finite gradient / batch statistic
         self.ok_dev = torch.ones(1, dtype=torch.int32, device=self.dev)  # this step's verdict (orcai_step_ok), read by the guarded update kernels
         # Step state the kernels read from DEVICE memory (so that a captured hipGraph of the step stays valid from replay to replay):
@@ -1047,14 +1046,17 @@ class Trainer:
         if self.conv1d:  # one mask per residual block (plane layout, drawn over the whole buffer: the pads are zero anyway) + one after BN_f
             shapes = self.model.stage_shapes()
             R = self.model.kernel_size // 2
-            todo = [(f"block{i}", (n, (shapes[i][2] + 3) // 4, shapes[i][0] + 2 * R, self.model.padded_width(shapes[i][1]), 4)) for i in range(1, len(self.model.filters) + 1)]
-            todo.append(("final", (n, T, shapes[-1][1] * FINAL_FILTERS)))
+            G = self.trunk.G  # f16 path: octet planes of f16 0/1 values, like the activations they multiply
+            todo = [(f"block{i}", (n, (shapes[i][2] + G - 1) // G, shapes[i][0] + 2 * R, self.model.padded_width(shapes[i][1]), G), self.half)
+                    for i in range(1, len(self.model.filters) + 1)]
+            todo.append(("final", (n, T, shapes[-1][1] * FINAL_FILTERS), False))  # the Conv1D head is f32 on both paths
         else:
-            todo = [("drop1", (n, T, 2 * self.model.lstm_units)), ("drop2", (n, T, 2 * self.model.lstm_units)), ("drop3", (n, T, DENSE_UNITS))]
-        for idx, (j, shape) in enumerate(todo):
-            mk = torch.empty(shape, dtype=torch.float32, device=self.dev)
+            todo = [(j, shape, False) for j, shape in (("drop1", (n, T, 2 * self.model.lstm_units)), ("drop2", (n, T, 2 * self.model.lstm_units)), ("drop3", (n, T, DENSE_UNITS)))]
+        for idx, (j, shape, f16) in enumerate(todo):
+            mk = torch.empty(shape, dtype=torch.float16 if f16 else torch.float32, device=self.dev)
             seed = (self.seed * 1000003 + self.rank * 0x9E3779B1 + idx + 1) & 0xFFFFFFFFFFFFFFFF  # + the step counter, on the device
-            N.check(lib.orcai_dropout_mask_dev(mk.data_ptr(), mk.numel(), self.counter.data_ptr(), seed, 1.0 - rate, st), "dropout_mask")
+            draw = lib.orcai_h_dropout_mask_dev if f16 else lib.orcai_dropout_mask_dev
+            N.check(draw(mk.data_ptr(), mk.numel(), self.counter.data_ptr(), seed, 1.0 - rate, st), "dropout_mask")
             out[j] = mk
         return out
 
@@ -1065,6 +1067,12 @@ class Trainer:
         if isinstance(masks, str):
             masks = self._masks(B, self.model.out_steps)
         self.trunk.block_masks = [masks[f"block{i}"] for i in range(1, len(self.model.filters) + 1)] if (self.conv1d and masks is not None) else None
+        if self.trunk.block_masks is not None:  # the mask kernels walk the buffers flat: a mask must have the layout of the planes it multiplies
+            shapes, R, G = self.model.stage_shapes(), self.model.kernel_size // 2, self.trunk.G
+            for i, mk in enumerate(self.trunk.block_masks, start=1):
+                want = (B, (shapes[i][2] + G - 1) // G, shapes[i][0] + 2 * R, self.model.padded_width(shapes[i][1]), G)
+                if mk.dtype != self.trunk.adt or tuple(mk.shape) != want or not mk.is_contiguous():
+                    raise ValueError(f"block{i} mask: expected a contiguous {self.trunk.adt} tensor of shape {want}, got {mk.dtype} {tuple(mk.shape)}")
         self.trunk.begin_step()  # one clear for every reduction scratch of the step
         try:
             featv = self.trunk.forward(src, snippet_stride, B)
