@@ -28,7 +28,6 @@ _SIGNATURES = {
     "orcai_frontend_workspace_bytes": (C.c_size_t, []),
     "orcai_frontend_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "orcai_stft_db": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "orcai_stft_blocks": (C.c_int, [C.c_int]),
     "orcai_stft_occupancy": (C.c_int, []),
     "orcai_hist_level1": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_quantile_select": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
@@ -115,7 +114,6 @@ _SIGNATURES = {
     "orcai_planes_sum": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "orcai_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "orcai_outer_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "orcai_outer_reduce_pixels": (C.c_int, [C.c_int]),
     "orcai_dw_wgrad": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "orcai_conv0_wgrad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "orcai_feat_to_planes": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),

@@ -167,7 +167,7 @@ constexpr int ROW_BYTES = 144;               // 16 complex (128 B) + 16 B pad: c
 constexpr int FRAME_BYTES = 16 * ROW_BYTES;  // 2304
 constexpr int WAVE_BYTES = 4 * FRAME_BYTES;  // 9216, also holds the 4 x k_crop output staging (<= 4112 B)
 
-int g_stft_blocks = 1536;  // persistent workgroups of the STFT launch (orcai_stft_blocks): six per compute unit, three resident (profiles/r03_ab_stft_blocks.log: 768 -> 1536 = -3 %)
+constexpr int STFT_BLOCKS = 1536;  // persistent workgroups of the STFT launch: six per compute unit, three resident (profiles/r03_ab_stft_blocks.log: 768 -> 1536 = -3 %)
 
 struct __attribute__((aligned(16))) StftLds {
   unsigned char tile[4][WAVE_BYTES];  // per wave: PCM staging (5 hops) -> 16x16 transpose tile -> output staging
@@ -817,7 +817,7 @@ int orcai_stft_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64
   const int64_t n_groups = (n_frames + 15) / 16;
   Workspace* ws = (Workspace*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < g_stft_blocks ? n : g_stft_blocks)); };
+  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
   if ((hop & 1) != 0) {
     hipLaunchKernelGGL((stft_db_kernel<false, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws,
                        (int64_t)0, n_groups);
@@ -849,12 +849,6 @@ int orcai_stft_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64
                        n_groups);
   }
   return (int)hipGetLastError();
-}
-
-int orcai_stft_blocks(int blocks) {  // experiments: workgroups of the persistent STFT launch (default 1536 = twice the three resident per compute unit); < 0 queries
-  const int prev = g_stft_blocks;
-  if (blocks > 0) g_stft_blocks = blocks;
-  return prev;
 }
 
 int orcai_stft_occupancy(void) {  // workgroups of stft_db_kernel<true, true, 171> the runtime says fit one compute unit (LDS: 52 KiB each)

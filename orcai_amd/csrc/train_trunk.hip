@@ -1956,8 +1956,6 @@ int orcai_pool_bwd(const float* dout, const float* ybn, int B, int C, int H, int
   return orcai_pool_bwd_bn(dout, ybn, B, C, H, W, ksize, dy, nullptr, nullptr, nullptr, 0.0f, nullptr, stream);
 }
 
-static int g_outer_pp = 0;  // 0: by operand width; 128 / 256: forced (orcai_outer_reduce_pixels, experiments)
-
 int orcai_outer_reduce(const float* A, int Ca, const float* Bq, int Cb, int B, int H, int W, int ksize, int a_stride2, int Ha, int Wa, float* D,
                        float* workspace, int64_t workspace_floats, void* stream) {
   if (!A || !Bq || !D || !workspace || Ca <= 0 || Cb <= 0 || Ca > 64 || Cb > 64 || B <= 0 || H <= 0 || W <= 0) return ORCAI_E_BADARG;
@@ -1968,8 +1966,8 @@ int orcai_outer_reduce(const float* A, int Ca, const float* Bq, int Cb, int B, i
   // difference between the test shapes that ran and the one that aborted in round 1
   const int MTN = (Ca + 15) / 16 + (Cb + 15) / 16;
   // 256 pixels per pass while two workgroups fit a compute unit (<= 32 channels per operand: 66 KiB), 128 beyond (50-66 KiB instead
-  // of 99-132); g_outer_pp overrides for experiments
-  const int PP = g_outer_pp ? g_outer_pp : (MTN <= 4 ? 256 : 128);
+  // of 99-132)
+  const int PP = MTN <= 4 ? 256 : 128;
   const size_t lds = (size_t)(MTN * 16) * (PP + 2) * sizeof(float);
   static size_t lds_set[2] = {0, 0};
   if (lds > lds_set[PP == 256]) {
@@ -1993,12 +1991,6 @@ int orcai_outer_reduce(const float* A, int Ca, const float* Bq, int Cb, int B, i
                        a_stride2 ? orcai_padded_width(Wa, ksize) : 0, workspace, magic_for(WP));
   hipLaunchKernelGGL(add_partials_kernel, dim3(blocks_for((int64_t)Ca * Cb), 8), dim3(256), 0, st, workspace, (int)grid, Ca * Cb, D);
   return (int)hipGetLastError();
-}
-
-int orcai_outer_reduce_pixels(int pixels) {
-  const int prev = g_outer_pp;
-  if (pixels == 0 || pixels == 128 || pixels == 256) g_outer_pp = pixels;
-  return prev;
 }
 
 static int g_dw_wgrad_march = 1;  // k = 3, planes at least 100 pixels wide: dw_wgrad_march_kernel (orcai_dw_wgrad_march: A/B)

@@ -392,34 +392,20 @@ class TrunkTrainer:
         self.arena_slots = 96
         self.arena = torch.empty(self.arena_slots * 4096, dtype=torch.float64, device=self.dev)
         self._slot = self.arena_slots  # no step in flight: _fresh() hands out the private buffers
-        self.use_arena = True  # A/B: tools/ab_flags.py
         # ResNet1DConv drops out the output of every residual block (architectures.py:97); ResNetLSTM has no Dropout in the trunk
         self.block_rate = float(model.dropout_rate) if getattr(model, "architecture", "") == "ResNet1DConv" else 0.0
         self.block_masks = None  # list of 0/1 plane tensors (one per block) for the current step, or None
-        self._own_res_scratch = torch.zeros(8 * 16, dtype=torch.float64, device=self.dev)  # planes_sum of the residual bias gradient: pool_bwd_bn's sums stay in self.scratch
+        self._own_res_scratch = torch.zeros(8 * 16, dtype=torch.float64, device=self.dev)  # the residual bias gradient's sums of pool_bwd_bn_bias: bn_b's stay in self.scratch
         self.res_scratch = self._own_res_scratch
-        self.stats_in_epilogue = True  # block-1-shaped separable convs reduce their BatchNorm statistics in the epilogue (A/B: tools/ab_train_order.py)
-        self.dgrad_first = True  # order of a separable conv's backward kernels (A/B: tools/ab_train_order.py)
-        self.bias_in_pool = True  # residual bias gradients reduced inside the pooling backward (no planes_sum pass over dout)
-        self.conv0_two_pass = True  # entry conv: statistics pass + conv/bn0/ReLU pass, v0 never stored, rebuilt in the backward pass (A/B: tools/ab_flags.py)
-        self.apply_on_load = True  # bn_a + ReLU applied where sep_b / its depthwise weight gradient load their input: y_a is never written (A/B: tools/ab_flags.py)
-        self.dgrad_epilogues = True  # BatchNorm backward sums / ReLU backward in the epilogue of the input-gradient passes (A/B: tools/ab_flags.py)
-        self.conv0_stats_from_input = True  # f16 path: bn0's statistics from the snippet (orcai_conv0_stats_march) instead of a pass over the stored v0 (A/B: tools/ab_sweep_flags.py)
-        self.conv0_march = True  # entry conv statistics on the marching kernel (A/B: tools/ab_flags.py; its backward twin: orcai_conv0_march)
-        self.conv0_in_dgrad = True  # block 1's first conv: y0 rebuilt from the snippet inside the marching depthwise backward, bn0's sums in its epilogue (A/B: tools/ab_flags.py)
-        self.bn0_sums_ready = False
+        self.bn0_sums_ready = False  # bn0's backward sums were left in self.scratch by block 1's first conv (its input gradient pass)
         self._resq = None
-        self.fused_dw_bwd = True  # input gradient + its epilogue extra + depthwise weight gradient of a k = 3 separable conv in one marching pass (A/B: tools/ab_flags.py)
-        self.fused_pw_wgrad = True  # BN backward apply + du + pointwise weight gradient in one pass where the layer is narrow enough (A/B: tools/ab_train.py)
-        self.fused_stats_under_capture = True  # the epilogue statistics also inside a captured step (tools/debug_graph_divergence.py)
         self.partials = torch.empty(512 * 64 * 64, dtype=torch.float32, device=self.dev)  # per-workgroup partial weight gradients (outer_reduce)
 
     # ------------------------------------------------------------- helpers
     def begin_step(self) -> None:
         """Clear the accumulator arena (one launch) and start handing out its slots."""
-        if self.use_arena:
-            N.check(self.lib.orcai_scratch_arena(self.arena.data_ptr(), self.arena.numel() * 8, N.stream_ptr()), "scratch_arena")
-            self._slot = 0
+        N.check(self.lib.orcai_scratch_arena(self.arena.data_ptr(), self.arena.numel() * 8, N.stream_ptr()), "scratch_arena")
+        self._slot = 0
 
     def end_step(self) -> None:
         """No launcher may skip its zero fill outside a step (the arena's memory may be anybody's by then)."""
@@ -491,8 +477,6 @@ class TrunkTrainer:
     def _sep_stats(self, x, Cin, H, W, relu_in, dw, pw, shift, Cout, out, u_out) -> bool:
         """Training forward of a k = 3 separable conv with the batch statistics of its output reduced in the kernel's epilogue (sums into
         self.scratch); False when the shape is not one of the strip-tile kernel's: the caller then runs the two separate launches."""
-        if not self.fused_stats_under_capture and torch.cuda.is_current_stream_capturing():
-            return False  # A/B switch of tools/debug_graph_divergence.py
         self._fresh()
         rc = (self.lib.orcai_h_sepconv_stats if self.half else self.lib.orcai_sepconv_planes_stats)(x.data_ptr(), self.B, Cin, H, W, relu_in, dw.data_ptr(), pw.data_ptr(), self._ones(64).data_ptr(), shift.data_ptr(), Cout,
                                                  out.data_ptr(), u_out.data_ptr(), self.scratch.data_ptr(), N.stream_ptr())
@@ -537,14 +521,6 @@ class TrunkTrainer:
         N.check(rc, "orcai_sepconv_planes_stats_bn")
         return True
 
-    def _bn_bwd(self, dy, v, bn, C, H, W, relu, dv):
-        lib, P, st = self.lib, self.P, N.stream_ptr()
-        mean, var = self.stats[bn]
-        self._fresh()
-        N.check(lib.orcai_bn_planes_bwd(dy.data_ptr(), v.data_ptr(), self.B, C, H, W, self.k, mean.data_ptr(), var.data_ptr(), P.W(bn + "/gamma").data_ptr(),
-                                        P.W(bn + "/beta").data_ptr(), BN_EPS, relu, self.scratch.data_ptr(), P.G(bn + "/beta").data_ptr(),
-                                        P.G(bn + "/gamma").data_ptr(), dv.data_ptr(), st), "bn_planes_bwd")
-
     def _alloc(self, B):
         if self.B == B:
             return
@@ -553,8 +529,10 @@ class TrunkTrainer:
         shapes = m.stage_shapes()
         b = {}
         h, w, _ = shapes[0]
-        b["v0"], b["y0"] = self._planes(B, 16, h, w), self._planes(B, 16, h, w)
-        b["rq1"] = self._planes(B, 16, shapes[1][0], shapes[1][1])  # block 1's residual gradient w.r.t. y0 at the even pixels (compact; see conv0_in_dgrad)
+        b["y0"] = self._planes(B, 16, h, w)
+        if self.half:  # the f16 entry conv stores v0 for the backward pass (the f32 one rebuilds it from the snippet)
+            b["v0"] = self._planes(B, 16, h, w)
+        b["rq1"] = self._planes(B, 16, shapes[1][0], shapes[1][1])  # block 1's residual gradient w.r.t. y0 at the even pixels (compact; see _conv0_dgrad_ok)
         for i, f in enumerate(m.filters, start=1):
             h, w, cprev = shapes[i - 1]
             for n in ("va", "ya", "vb"):  # y_b = BN_b(v_b) is never materialised (the pooling kernels apply BN on the fly)
@@ -635,13 +613,9 @@ class TrunkTrainer:
         H, W = m.input_hw
         k = self.k
         shapes = m.stage_shapes()
-        self.v0_stored = self.half or not self.conv0_two_pass
-        if self.v0_stored:
-            stats_first = bool(self.half and self.conv0_stats_from_input and self.conv0_march and k == 3)
-            if not stats_first:
-                N.check(self._fn("conv0_affine")(src.data_ptr(), snippet_stride, B, H, W, k, P.W("conv0/kernel").data_ptr(), self._ones(16).data_ptr(), P.W("conv0/bias").data_ptr(),
-                                                 0, b["v0"].data_ptr(), st), "orcai_conv0_affine")
-            if stats_first:
+        if self.half:
+            # f16: v0 is stored for the backward pass
+            if k == 3:
                 # bn0's batch statistics from the 1-channel snippet (the f32 path's marching statistics pass: 4 bytes per pixel read) instead of a pass over
                 # the stored 16-channel v0 (32 bytes per pixel).  They are the statistics of the conv BEFORE its rounding to f16: the mean moves by < 2^-12 of
                 # a standard deviation, the variance by 2^-24 relative -- below what the f16 storage of v0 itself does to the normalised values
@@ -656,14 +630,16 @@ class TrunkTrainer:
                                                     mean0.data_ptr(), var0.data_ptr(), P.W("bn0/gamma").data_ptr(), P.W("bn0/beta").data_ptr(), BN_EPS, b["v0"].data_ptr(),
                                                     b["y0"].data_ptr(), st), "orcai_h_conv0_affine_bn")
             else:
+                N.check(lib.orcai_h_conv0_affine(src.data_ptr(), snippet_stride, B, H, W, k, P.W("conv0/kernel").data_ptr(), self._ones(16).data_ptr(), P.W("conv0/bias").data_ptr(),
+                                                 0, b["v0"].data_ptr(), st), "orcai_h_conv0_affine")
                 self._bn_fwd(b["v0"], "bn0", 16, H, W, 1, b["y0"])
         else:
-            # two passes over the 1-channel input instead of three over the 16-channel v0: statistics only, then conv + bn0 + ReLU -> y0; v0 itself
+            # f32: two passes over the 1-channel input instead of three over the 16-channel v0: statistics only, then conv + bn0 + ReLU -> y0; v0 itself
             # is never written (the backward pass rebuilds it from the input taps: orcai_conv0_bn_bwd_x)
             w0, b0, ones = P.W("conv0/kernel").data_ptr(), P.W("conv0/bias").data_ptr(), self._ones(16).data_ptr()
             mean0, var0 = P.B("bn0/mean"), P.B("bn0/var")
             self._fresh()
-            if self.conv0_march and k == 3:  # the marching form: no tiles, LDS or barriers (csrc/train_trunk.hip conv0_march_kernel)
+            if k == 3:  # the marching form: no tiles, LDS or barriers (csrc/train_trunk.hip conv0_march_kernel)
                 N.check(lib.orcai_conv0_stats_march(src.data_ptr(), snippet_stride, B, H, W, w0, ones, b0, self.scratch.data_ptr(), st), "conv0_stats_march")
             else:
                 N.check(lib.orcai_conv0_stats(src.data_ptr(), snippet_stride, B, H, W, k, w0, ones, b0, self.scratch.data_ptr(), st), "conv0_stats")
@@ -685,10 +661,10 @@ class TrunkTrainer:
             na, nb = f"b{i}/sep_a", f"b{i}/sep_b"
             self.dwl[na], self.dwl[nb] = self._w_dw(na), self._w_dw(nb)
             va, ya, vb = b[f"va{i}"], b[f"ya{i}"], b[f"vb{i}"]
-            fused = self.stats_in_epilogue and k == 3 and self._sep_stats(prev, c, h, w, 1, self.dwl[na], self._w_pw(na + "/pointwise"), P.W(na + "/bias"), f, va, b[f"u_a{i}"])
+            fused = k == 3 and self._sep_stats(prev, c, h, w, 1, self.dwl[na], self._w_pw(na + "/pointwise"), P.W(na + "/bias"), f, va, b[f"u_a{i}"])
             if not fused:
                 self._sep(prev, c, h, w, k, 1, self.dwl[na], self._w_pw(na + "/pointwise"), P.W(na + "/bias"), f, va, u_out=b[f"u_a{i}"])
-            on_load = self.apply_on_load and self.stats_in_epilogue and k == 3
+            on_load = k == 3
             self._bn_fwd(va, f"b{i}/bn_a", f, h, w, 1, None if on_load else ya, sums_in_shards=fused)
             if on_load:
                 on_load = self._sep_stats_bn(va, f"b{i}/bn_a", f, h, w, self.dwl[nb], self._w_pw(nb + "/pointwise"), P.W(nb + "/bias"), f, vb, b[f"u_b{i}"])
@@ -697,7 +673,7 @@ class TrunkTrainer:
             self.on_load[i] = on_load
             fused = on_load
             if not on_load:
-                fused = self.stats_in_epilogue and k == 3 and self._sep_stats(ya, f, h, w, 0, self.dwl[nb], self._w_pw(nb + "/pointwise"), P.W(nb + "/bias"), f, vb, b[f"u_b{i}"])
+                fused = k == 3 and self._sep_stats(ya, f, h, w, 0, self.dwl[nb], self._w_pw(nb + "/pointwise"), P.W(nb + "/bias"), f, vb, b[f"u_b{i}"])
                 if not fused:
                     self._sep(ya, f, h, w, k, 0, self.dwl[nb], self._w_pw(nb + "/pointwise"), P.W(nb + "/bias"), f, vb, u_out=b[f"u_b{i}"])
             self._bn_fwd(vb, f"b{i}/bn_b", f, h, w, 0, None, sums_in_shards=fused)
@@ -736,15 +712,15 @@ class TrunkTrainer:
         wt = self._w_pwT(name + "/pointwise", Cin, Cout)  # pointwise^T [Cout][Cin]
         if not sums_ready:  # the launcher reduces the BatchNorm backward sums itself (otherwise it READS them from self.scratch)
             self._fresh()
-        if self.fused_pw_wgrad:
-            # one pass: dv formed per pixel, du = Wpw dv, AND the pointwise weight gradient u (x) dv -- dv is never written or re-read
-            rc = (lib.orcai_h_bn_bwd_pointwise_wgrad if self.half else lib.orcai_bn_bwd_pointwise_wgrad)(dy.data_ptr(), v.data_ptr(), u.data_ptr(), self.B, Cout, H, W, k, mean.data_ptr(), var.data_ptr(), P.W(bn + "/gamma").data_ptr(),
-                                                  P.W(bn + "/beta").data_ptr(), BN_EPS, relu, self.scratch.data_ptr(), sums_ready, P.G(bn + "/beta").data_ptr(),
-                                                  P.G(bn + "/gamma").data_ptr(), wt.data_ptr(), Cin, du.data_ptr(), P.G(name + "/pointwise").data_ptr(), self.partials.data_ptr(),
-                                                  self.partials.numel(), st)
-            if rc != N.E_UNSUPPORTED:
-                N.check(rc, "bn_bwd_pointwise_wgrad")
-                return self._sep_backward(name, x, relu_in, Cin, Cout, H, W, None, u, du, dr, have_du=True, have_pw_wgrad=True, epi=epi, x_bn=x_bn)
+        # one pass: dv formed per pixel, du = Wpw dv, AND the pointwise weight gradient u (x) dv -- dv is never written or re-read
+        rc = (lib.orcai_h_bn_bwd_pointwise_wgrad if self.half else lib.orcai_bn_bwd_pointwise_wgrad)(dy.data_ptr(), v.data_ptr(), u.data_ptr(), self.B, Cout, H, W, k, mean.data_ptr(), var.data_ptr(), P.W(bn + "/gamma").data_ptr(),
+                                              P.W(bn + "/beta").data_ptr(), BN_EPS, relu, self.scratch.data_ptr(), sums_ready, P.G(bn + "/beta").data_ptr(),
+                                              P.G(bn + "/gamma").data_ptr(), wt.data_ptr(), Cin, du.data_ptr(), P.G(name + "/pointwise").data_ptr(), self.partials.data_ptr(),
+                                              self.partials.numel(), st)
+        if rc != N.E_UNSUPPORTED:
+            N.check(rc, "bn_bwd_pointwise_wgrad")
+            return self._sep_backward(name, x, relu_in, Cin, Cout, H, W, None, u, du, dr, have_du=True, have_pw_wgrad=True, epi=epi, x_bn=x_bn)
+        # a layer too wide for the fused pass: BN backward + du in one pass (dv written in place of dy), the pointwise weight gradient separately
         N.check(self._fn("bn_bwd_pointwise")(dy.data_ptr(), v.data_ptr(), self.B, Cout, H, W, k, mean.data_ptr(), var.data_ptr(), P.W(bn + "/gamma").data_ptr(),
                                            P.W(bn + "/beta").data_ptr(), BN_EPS, relu, self.scratch.data_ptr(), sums_ready, P.G(bn + "/beta").data_ptr(),
                                            P.G(bn + "/gamma").data_ptr(), wt.data_ptr(), Cin, dy.data_ptr(), du.data_ptr(), st), "bn_bwd_pointwise")
@@ -758,7 +734,7 @@ class TrunkTrainer:
         does the separate launches."""
         k, P = self.k, self.P
         dw, eye, zeros = self._w_dw(name, reverse=True), self._w_eye(Cin), self._zeros(64)
-        if epi is not None and self.dgrad_epilogues and k == 3 and not self.half:
+        if epi is not None and k == 3 and not self.half:
             if epi[0] == "bsums":
                 _, ref, bn, relu = epi
                 mean, var = self.stats[bn]
@@ -776,20 +752,17 @@ class TrunkTrainer:
         return False
 
     def _conv0_dgrad_ok(self, x) -> bool:
-        """Block 1's first conv may rebuild its input y0 from the snippet (orcai_dw_bwd_fused_conv0): f32, k = 3, the two-pass entry conv (v0 not stored)."""
-        return bool(self.conv0_in_dgrad and self.fused_dw_bwd and not self.v0_stored and not self.half and self.k == 3 and x.data_ptr() == self.buf["y0"].data_ptr())
-
-    def _conv0_dgrad_half_ok(self, x) -> bool:
-        """f16 path: block 1's first conv takes bn0's sums and the residual gradient into its marching pass (x = the stored v0).  Block Dropout
-        (ResNet1DConv) changes nothing here: no Dropout sits in front of block 1, and the residual gradient it adds is taken w.r.t. the un-dropped y0."""
-        return bool(self.half and self.conv0_in_dgrad and self.fused_dw_bwd and self.v0_stored and self.k == 3 and x.data_ptr() == self.buf["y0"].data_ptr())
+        """Block 1's first conv (k = 3, input x = y0) takes bn0's backward sums and the residual gradient into its marching pass: f32 rebuilds y0
+        from the snippet (orcai_dw_bwd_fused_conv0), f16 forms it from the stored v0 (orcai_h_dw_bwd_fused_res).  Block Dropout (ResNet1DConv)
+        changes nothing here: no Dropout sits in front of block 1, and the residual gradient it adds is taken w.r.t. the un-dropped y0."""
+        return bool(self.k == 3 and x.data_ptr() == self.buf["y0"].data_ptr())
 
     def _dw_bwd_fused(self, name, x, relu_in, Cin, H, W, du, dr, epi, x_bn):
         """orcai_dw_bwd_fused for one separable conv: dr, the depthwise weight gradient and the epilogue extra `epi` of _dgrad in one pass over
         (du, x).  Returns whether the epilogue extra ran (True / False), or None when the launch is not this kernel's (the caller runs the
         separate passes): the extras read the conv's own input, so ("bsums", ref, ...) needs ref to be the pre-normalisation tensor x."""
         P = self.P
-        if name == "b1/sep_a" and epi is None and x_bn is None and self._resq is not None and self._conv0_dgrad_half_ok(x):
+        if self.half and name == "b1/sep_a" and epi is None and x_bn is None and self._resq is not None and self._conv0_dgrad_ok(x):
             # f16 path: the entry conv's stored v0 is the pass's x (y0 formed from it on load), bn0's backward sums over the total gradient in its
             # epilogue, the residual branch's even-pixel gradient added inside (orcai_h_dw_bwd_fused_res + orcai_h_conv0_bn_bwd_ready)
             mean0, var0 = self.stats["bn0"]
@@ -801,7 +774,7 @@ class TrunkTrainer:
                 N.check(rc, "orcai_h_dw_bwd_fused_res")
                 self.bn0_sums_ready = True
                 return False
-        if name == "b1/sep_a" and epi is None and x_bn is None and self._conv0_dgrad_ok(x):
+        if not self.half and name == "b1/sep_a" and epi is None and x_bn is None and self._conv0_dgrad_ok(x):
             # block 1's first conv: y0 rebuilt from the snippet's taps instead of read, bn0's backward sums left in self.scratch for orcai_conv0_bn_bwd_x_ready
             mean0, var0 = self.stats["bn0"]
             self._fresh()
@@ -814,7 +787,7 @@ class TrunkTrainer:
                 self.bn0_sums_ready = True
                 return False
         mode, bn, bn_relu = 0, x_bn, 0
-        if epi is not None and self.dgrad_epilogues:
+        if epi is not None:
             if epi[0] == "bsums":
                 if self.half and x_bn is None and relu_in == 0 and epi[3] == 1:
                     # f16 path: the forward materialised x = y_a = f16(relu(BN(v_a))); the kernel forms exactly that value from v_a on load,
@@ -828,8 +801,6 @@ class TrunkTrainer:
                 if x_bn is not None or not relu_in or epi[1].data_ptr() != x.data_ptr():
                     return None
                 mode = 3
-        elif epi is not None:
-            return None
         bnp = [None] * 4
         if bn is not None:
             mean, var = self.stats[bn]
@@ -853,8 +824,7 @@ class TrunkTrainer:
         if not have_du:  # du = Wpw dv   (pointwise conv with the transposed weights)
             wt = self._w_pwT(name + "/pointwise", Cin, Cout)
             self._sep(dv, Cout, H, W, 1, 0, self._w_ones_dw(Cout), wt, self._zeros(64), Cin, du)
-        epi_ran = False
-        if self.fused_dw_bwd and k == 3:
+        if k == 3:
             # one marching pass over (du, x): input gradient, its epilogue extra and the depthwise weight gradient (csrc/train_trunk.hip: dw_bwd_march_kernel)
             fused = self._dw_bwd_fused(name, x, relu_in, Cin, H, W, du, dr, epi, x_bn)
             if fused is not None:
@@ -862,11 +832,10 @@ class TrunkTrainer:
                     N.check(self._fn("outer_reduce")(u.data_ptr(), Cin, dv.data_ptr(), Cout, self.B, H, W, k, 0, 0, 0, P.G(name + "/pointwise").data_ptr(), self.partials.data_ptr(),
                                                      self.partials.numel(), st), "outer_reduce")
                 return fused
-        if self.dgrad_first:
-            # the input gradient (the only kernel of this layer the next layer waits for) first; the two weight-gradient passes are
-            # read-only, and a read-only pass runs faster behind a kernel that wrote ANOTHER tensor (dr) than directly behind the writer
-            # of its own input (dv, du) -- DESIGN.md 4.4
-            epi_ran = self._dgrad(name, du, Cin, H, W, dr, epi)
+        # the input gradient (the only kernel of this layer the next layer waits for) first; the two weight-gradient passes are
+        # read-only, and a read-only pass runs faster behind a kernel that wrote ANOTHER tensor (dr) than directly behind the writer
+        # of its own input (dv, du) -- DESIGN.md 4.4
+        epi_ran = self._dgrad(name, du, Cin, H, W, dr, epi)
         if not have_pw_wgrad:
             N.check(self._fn("outer_reduce")(u.data_ptr(), Cin, dv.data_ptr(), Cout, self.B, H, W, k, 0, 0, 0, P.G(name + "/pointwise").data_ptr(), self.partials.data_ptr(),
                                              self.partials.numel(), st), "outer_reduce")
@@ -883,8 +852,6 @@ class TrunkTrainer:
                                           P.W(x_bn + "/beta").data_ptr(), BN_EPS, P.G(name + "/depthwise").data_ptr(), st), "dw_wgrad_bn")
         else:
             N.check(self._fn("dw_wgrad")(x.data_ptr(), du.data_ptr(), self.B, Cin, H, W, k, k, relu_in, P.G(name + "/depthwise").data_ptr(), st), "dw_wgrad")
-        if not self.dgrad_first:
-            epi_ran = self._dgrad(name, du, Cin, H, W, dr, epi)
         return epi_ran
 
     def backward(self, dfeatv: torch.Tensor) -> None:
@@ -906,30 +873,19 @@ class TrunkTrainer:
                 N.check(self._fn("mask_scale")(dprev.data_ptr(), self.block_masks[i - 1].data_ptr(), 1.0 / (1.0 - self.block_rate), dprev.numel(), dprev.data_ptr(), st),
                         "mask_scale")
             dout = dprev  # gradient w.r.t. prev_i (planes of f channels, ho x wo)
-            bias_in_pool = self.bias_in_pool
-            def residual_wgrad():  # residual 1x1 stride-2 conv: weight / bias gradients (read-only passes over prev and dout)
-                N.check(self._fn("outer_reduce")(prev.data_ptr(), cprev, dout.data_ptr(), f, B, ho, wo, k, 1, h, w, P.G(f"b{i}/res/kernel").data_ptr(),
-                                                 self.partials.data_ptr(), self.partials.numel(), st), "outer_reduce")
-                if not bias_in_pool:
-                    self._fresh_res()
-                    N.check(self._fn("planes_sum")(dout.data_ptr(), B, f, ho, wo, k, self.res_scratch.data_ptr(), P.G(f"b{i}/res/bias").data_ptr(), 0, st), "planes_sum")
-
-            if not self.dgrad_first:
-                residual_wgrad()
-            # max-pool branch
+            # max-pool branch; the pooling backward also accumulates bn_b's backward reductions (sum dy, sum dy*xhat) and the residual conv's bias
+            # gradient (the sum of dout, reduced where the pass reads dout anyway)
             dyb = b[f"dyb{i}"]
-            bmean, bvar = self.stats[f"b{i}/bn_b"]  # the pooling backward also accumulates bn_b's backward reductions (sum dy, sum dy*xhat)
+            bmean, bvar = self.stats[f"b{i}/bn_b"]
             self._fresh()
-            if bias_in_pool:  # the residual conv's bias gradient (sum of dout) reduced where the pooling backward reads dout anyway
-                self._fresh_res()
-                N.check((lib.orcai_h_pool_bwd_bn_bias if self.half else lib.orcai_pool_bwd_bn_bias)(dout.data_ptr(), b[f"vb{i}"].data_ptr(), B, f, h, w, k, dyb.data_ptr(), P.W(f"b{i}/bn_b/gamma").data_ptr(), bmean.data_ptr(),
-                                                   bvar.data_ptr(), BN_EPS, self.scratch.data_ptr(), self.res_scratch.data_ptr(), P.G(f"b{i}/res/bias").data_ptr(), st),
-                        "pool_bwd_bn_bias")
-            else:
-                N.check(self._fn("pool_bwd_bn")(dout.data_ptr(), b[f"vb{i}"].data_ptr(), B, f, h, w, k, dyb.data_ptr(), P.W(f"b{i}/bn_b/gamma").data_ptr(), bmean.data_ptr(),
-                                                bvar.data_ptr(), BN_EPS, self.scratch.data_ptr(), st), "pool_bwd_bn")
-            if self.dgrad_first:  # behind the kernel that wrote dyb, not behind the one that wrote dout (see _sep_backward)
-                residual_wgrad()
+            self._fresh_res()
+            N.check((lib.orcai_h_pool_bwd_bn_bias if self.half else lib.orcai_pool_bwd_bn_bias)(dout.data_ptr(), b[f"vb{i}"].data_ptr(), B, f, h, w, k, dyb.data_ptr(), P.W(f"b{i}/bn_b/gamma").data_ptr(), bmean.data_ptr(),
+                                               bvar.data_ptr(), BN_EPS, self.scratch.data_ptr(), self.res_scratch.data_ptr(), P.G(f"b{i}/res/bias").data_ptr(), st),
+                    "pool_bwd_bn_bias")
+            # residual 1x1 stride-2 conv: weight gradient (a read-only pass over prev and dout), behind the kernel that wrote dyb, not behind the one
+            # that wrote dout (see _sep_backward)
+            N.check(self._fn("outer_reduce")(prev.data_ptr(), cprev, dout.data_ptr(), f, B, ho, wo, k, 1, h, w, P.G(f"b{i}/res/kernel").data_ptr(),
+                                             self.partials.data_ptr(), self.partials.numel(), st), "outer_reduce")
             dya = b[f"dya{i}"]
             # the input-gradient pass of sep_b writes dy_a = the gradient of bn_a's output: bn_a's backward sums are reduced in its epilogue
             on_load = self.on_load.get(i, False)  # sep_b read bn_a + ReLU of v_a on load: its depthwise weight gradient does the same
@@ -941,7 +897,7 @@ class TrunkTrainer:
             # applies anyway (mask * mask = mask)
             wrt = self._w_pwT(f"b{i}/res/kernel", cprev, f)  # residual weights transposed [f][cprev]
             self._resq = None
-            if i == 1 and (self._conv0_dgrad_ok(x_in) or self._conv0_dgrad_half_ok(x_in)):
+            if i == 1 and self._conv0_dgrad_ok(x_in):
                 # the residual branch's gradient w.r.t. y0 lives on the even pixels only: one plain pointwise pass at the pooled resolution, added inside
                 # the marching pass below (where bn0's sums are taken over the TOTAL gradient) instead of scatter-added to dr afterwards
                 self._resq = b["rq1"]
@@ -960,12 +916,12 @@ class TrunkTrainer:
         mean0, var0 = self.stats["bn0"]  # bn0 (+ReLU) backward fused into the entry conv's weight gradient: dv0 is never written
         if not self.bn0_sums_ready:
             self._fresh()
-        if self.v0_stored:
-            c0bwd = self.lib.orcai_h_conv0_bn_bwd_ready if (self.half and self.bn0_sums_ready) else self._fn("conv0_bn_bwd")
+        if self.half:  # f16: the stored v0
+            c0bwd = lib.orcai_h_conv0_bn_bwd_ready if self.bn0_sums_ready else lib.orcai_h_conv0_bn_bwd
             N.check(c0bwd(self.src.data_ptr(), self.snippet_stride, dprev.data_ptr(), b["v0"].data_ptr(), B, H, W, k, mean0.data_ptr(), var0.data_ptr(),
                                              P.W("bn0/gamma").data_ptr(), P.W("bn0/beta").data_ptr(), BN_EPS, self.scratch.data_ptr(), P.G("bn0/beta").data_ptr(),
                                              P.G("bn0/gamma").data_ptr(), P.G("conv0/kernel").data_ptr(), st), "conv0_bn_bwd")
-        else:
+        else:  # f32: v0 rebuilt from the input taps (two-pass entry conv)
             N.check((lib.orcai_conv0_bn_bwd_x_ready if self.bn0_sums_ready else lib.orcai_conv0_bn_bwd_x)(self.src.data_ptr(), self.snippet_stride, dprev.data_ptr(), B, H, W, k, P.W("conv0/kernel").data_ptr(), P.W("conv0/bias").data_ptr(),
                                              mean0.data_ptr(), var0.data_ptr(), P.W("bn0/gamma").data_ptr(), P.W("bn0/beta").data_ptr(), BN_EPS, self.scratch.data_ptr(),
                                              P.G("bn0/beta").data_ptr(), P.G("bn0/gamma").data_ptr(), P.G("conv0/kernel").data_ptr(), self.partials.data_ptr(), self.partials.numel(),

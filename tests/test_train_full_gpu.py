@@ -288,7 +288,7 @@ def test_multi_step_trajectory_matches_oracle():
     assert not worst, worst
 
 
-def test_training_step_replays_as_one_hip_graph():
+def test_training_step_replays_as_one_hip_graph_with_epilogue_stats():
     """The whole step (dropout masks, forward with the BatchNorm statistics in the conv epilogues, loss, backward, Adam, BatchNorm moving
     statistics, step counter) captured once as a hipGraph and replayed: the per-step state lives in device memory (Trainer.counter,
     lr_dev), so replays draw fresh dropout masks, advance Adam's bias correction and honour a learning-rate change made between replays.
@@ -311,7 +311,22 @@ def test_training_step_replays_as_one_hip_graph():
     xs = [torch.from_numpy(rng.random((B, H, W), dtype=np.float32)).cuda().view(-1) for _ in range(3)]
     ys = [torch.from_numpy((rng.random((B, 16, 3)) > 0.5).astype(np.float32)).cuda() for _ in range(3)]
     E, G = (Trainer(ResNetLSTM((H, W, 1), 3, [30, 40], 3, 0.3, 64, seed=1), learning_rate=3e-3, seed=5) for _ in range(2))
-    assert E.trunk.stats_in_epilogue and G.trunk.stats_in_epilogue and G.trunk.fused_stats_under_capture
+
+    class CaptureRecordingLib(RecordingLib):  # also notes per call whether the stream was being captured (the first call runs eager warm-up steps too)
+        def __init__(self, lib):
+            super().__init__(lib)
+            self.capturing = []
+
+        def __getattr__(self, name):
+            call = super().__getattr__(name)
+
+            def noted(*args):
+                self.capturing.append(torch.cuda.is_current_stream_capturing())
+                return call(*args)
+
+            return noted
+
+    rec = G.trunk.lib = CaptureRecordingLib(G.trunk.lib)
     masks_seen = []
     for step in range(12):
         if step == 6:
@@ -333,6 +348,9 @@ def test_training_step_replays_as_one_hip_graph():
         assert int(E.counter.item()) == int(G.counter.item()) == step + 1 and G.step_count == step + 1
         masks_seen.append(float(og["probs"].sum()))
     assert len(set(np.round(masks_seen, 5))) > 6  # replays are not repeating one frozen step
+    # the captured step holds the separable convs with the BatchNorm statistics in their epilogue
+    captured = [(n, rc) for (n, rc, _), cap in zip(rec.calls, rec.capturing) if cap]
+    assert any(n in ("orcai_sepconv_planes_stats", "orcai_sepconv_planes_stats_bn") and rc == 0 for n, rc in captured), captured
 
     # (2) free-running: eager and graph trainers from the same seed (the capture's warm-up steps leave no trace in the trainer's state).  The
     # first steps agree to float-atomic noise; later ones are only required to learn -- whether a 24-step trajectory of a dropout network

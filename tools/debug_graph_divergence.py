@@ -2,10 +2,11 @@
 
 Round 2 saw a captured step with the fused-statistics kernels (orcai_sepconv_planes_stats) "drift" from an eager trainer over 24 steps and
 switched the fused kernels off under capture.  A drift between two TRAJECTORIES does not separate a wrong replay from the amplification
-of float-atomic reordering by a dropout network under Adam, so this tool measures both:
+of float-atomic reordering by a dropout network under Adam, so this tool measures both (its leg with the separate statistics pass went with
+the switch that selected it, retired once this comparison had decided for the fused kernels; profiles/r03_graph_divergence.log keeps it):
 
-  A. noise floor:   two EAGER trainers (same seed, same batches, fused statistics) against each other over 24 steps;
-  B. trajectories:  eager vs graph, fused statistics on in both, and eager vs graph with the separate statistics pass;
+  A. noise floor:   two EAGER trainers (same seed, same batches) against each other over 24 steps;
+  B. trajectories:  eager vs graph;
   C. step by step:  before every step the eager trainer's complete state (weights, Adam moments, BatchNorm moving statistics, step
                     counter) is copied into the graph trainer; both then take ONE step on the same batch: loss, every gradient tensor,
                     every batch statistic and the updated weights are compared.  A replay that computes something else than the eager step
@@ -24,11 +25,8 @@ CFGS = [dict(shape=(32, 12, 1), filters=[10, 20], units=64, labels=3, B=8, lr=3e
         dict(shape=(64, 171, 1), filters=[30, 40], units=64, labels=3, B=4, lr=3e-3, drop=0.3)]  # the second one reaches the strip-tile kernel (two strips of 62 columns)
 
 
-def make(cfg, fused, fused_capture=True):
-    tr = Trainer(ResNetLSTM(cfg["shape"], cfg["labels"], cfg["filters"], 3, cfg["drop"], cfg["units"], seed=1), learning_rate=cfg["lr"], seed=5)
-    tr.trunk.stats_in_epilogue = fused
-    tr.trunk.fused_stats_under_capture = fused_capture
-    return tr
+def make(cfg):
+    return Trainer(ResNetLSTM(cfg["shape"], cfg["labels"], cfg["filters"], 3, cfg["drop"], cfg["units"], seed=1), learning_rate=cfg["lr"], seed=5)
 
 
 def batches(cfg):
@@ -40,8 +38,8 @@ def batches(cfg):
     return [torch.from_numpy(x[b]).cuda().view(-1) for b in range(4)], [torch.from_numpy(y[b]).cuda() for b in range(4)], H * W
 
 
-def trajectory(cfg, mode, fused):
-    tr = make(cfg, fused)
+def trajectory(cfg, mode):
+    tr = make(cfg)
     xs, ys, stride = batches(cfg)
     losses = []
     for s in range(steps):
@@ -69,28 +67,24 @@ def named_max_rel(P, a, b):
 
 for cfg in CFGS:
     print("=== config", {k: cfg[k] for k in ("shape", "filters", "B")}, flush=True)
-    e1, w1 = trajectory(cfg, "eager", True)
-    e2, w2 = trajectory(cfg, "eager", True)
-    g1, wg = trajectory(cfg, "graph", True)
-    es, ws = trajectory(cfg, "eager", False)
-    gs, wgs = trajectory(cfg, "graph", False)
-    print(f"A noise floor   eager(fused) vs eager(fused):   max|dloss| {np.abs(e1 - e2).max():.3e}  max|dw| {np.abs(w1 - w2).max():.3e}")
-    print(f"B trajectories  eager(fused) vs graph(fused):   max|dloss| {np.abs(e1 - g1).max():.3e}  max|dw| {np.abs(w1 - wg).max():.3e}")
-    print(f"B trajectories  eager(sep)   vs graph(sep):     max|dloss| {np.abs(es - gs).max():.3e}  max|dw| {np.abs(ws - wgs).max():.3e}")
-    print(f"  (fused vs separate, both eager:               max|dloss| {np.abs(e1 - es).max():.3e}  max|dw| {np.abs(w1 - ws).max():.3e})")
+    e1, w1 = trajectory(cfg, "eager")
+    e2, w2 = trajectory(cfg, "eager")
+    g1, wg = trajectory(cfg, "graph")
+    print(f"A noise floor   eager vs eager:   max|dloss| {np.abs(e1 - e2).max():.3e}  max|dw| {np.abs(w1 - w2).max():.3e}")
+    print(f"B trajectories  eager vs graph:   max|dloss| {np.abs(e1 - g1).max():.3e}  max|dw| {np.abs(w1 - wg).max():.3e}")
     # divergence is an event (a ReLU / arg-max / dropout-scaled unit flips), so compare DISTRIBUTIONS: first step with |dloss| > 1e-4 over several pairs
     def first_over(a, b, thr=1e-4):
         d = np.abs(a - b)
         return int(np.argmax(d > thr)) if (d > thr).any() else -1
-    ee = [first_over(trajectory(cfg, "eager", True)[0], trajectory(cfg, "eager", True)[0]) for _ in range(4)]
-    eg = [first_over(trajectory(cfg, "eager", True)[0], trajectory(cfg, "graph", True)[0]) for _ in range(4)]
+    ee = [first_over(trajectory(cfg, "eager")[0], trajectory(cfg, "eager")[0]) for _ in range(4)]
+    eg = [first_over(trajectory(cfg, "eager")[0], trajectory(cfg, "graph")[0]) for _ in range(4)]
     print(f"  first step with |dloss| > 1e-4 (-1 = never) over 4 fresh pairs: eager-eager {ee}   eager-graph {eg}")
     print("  per-step |dloss| eager-eager:", np.array2string(np.abs(e1 - e2), precision=1, max_line_width=250))
     print("  per-step |dloss| eager-graph:", np.array2string(np.abs(e1 - g1), precision=1, max_line_width=250), flush=True)
 
     # C. one step from a common state, every step
     xs, ys, stride = batches(cfg)
-    E, G, E2 = make(cfg, True), make(cfg, True), make(cfg, True)
+    E, G, E2 = make(cfg), make(cfg), make(cfg)
     G.train_step_graphed(xs[0], stride, cfg["B"], ys[0])  # warm-up + capture + first replay
     worst = {"loss": 0.0, "grad": 0.0, "stat": 0.0, "w": 0.0, "grad_ee": 0.0, "stat_ee": 0.0}
     for s in range(steps):
@@ -122,7 +116,7 @@ for cfg in CFGS:
 # trainers show at the same step.
 for cfg in CFGS[:1]:
     xs, ys, stride = batches(cfg)
-    E, E2, G = make(cfg, True), make(cfg, True), make(cfg, True)
+    E, E2, G = make(cfg), make(cfg), make(cfg)
     for s in range(8):
         E.train_step(xs[s % 4], stride, cfg["B"], ys[s % 4]); E2.train_step(xs[s % 4], stride, cfg["B"], ys[s % 4]); G.train_step_graphed(xs[s % 4], stride, cfg["B"], ys[s % 4])
         row = {}

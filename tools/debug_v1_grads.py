@@ -1,5 +1,6 @@
 """Which kernel deviates at the orcai-V1 shape?  The whole-step gradient comparison of tests/test_train_full_gpu.py at 736 x 171, B = 2, under
-different TrunkTrainer switches; prints every gradient tensor whose error exceeds 2e-4 of the tensor's largest element."""
+the default configuration (the TrunkTrainer switches it once also compared were retired once their A/B was decided); prints every gradient tensor
+whose error exceeds 2e-4 of the tensor's largest element."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -28,25 +29,16 @@ print("f32 CPU autograd vs f64 (what plain f32 arithmetic gives):", {n: f"{float
 xd = torch.from_numpy(np.ascontiguousarray(x[..., 0])).cuda().view(-1)
 yd = torch.from_numpy(y).cuda()
 md = {k: torch.from_numpy(v).cuda() for k, v in masks.items()}
-configs = [{}, {"fused_dw_bwd": False}, {"fused_pw_wgrad": False}, {"apply_on_load": False}, {"stats_in_epilogue": False}, {"conv0_two_pass": False}, {"bias_in_pool": False},
-           {"dgrad_epilogues": False, "fused_dw_bwd": False},
-           {"fused_dw_bwd": False, "fused_pw_wgrad": False, "apply_on_load": False, "stats_in_epilogue": False, "conv0_two_pass": False, "bias_in_pool": False, "dgrad_epilogues": False, "conv0_march": False, "conv0_in_dgrad": False}]
-for flags in configs:
-    model = ResNetLSTM(cfg["input_shape"], L, list(cfg["filters"]), 3, rate, u)
-    model.set_weights_dict(p)
-    tr = Trainer(model, learning_rate=1e-3)
-    for k, v in flags.items():
-        setattr(tr.trunk, k, v)
-    out = tr.forward_backward(xd, H * W, B, yd, masks=md)
-    acc = out["acc"].cpu().numpy()
-    errs = {}
-    for name, g in ref["grads"].items():
-        got = tr.P.G(name).cpu().numpy()
-        zb = name.endswith("/bias") and not name.startswith(("dense2", "lstm", "dense1")) and "res" not in name
-        scale = max(1e-3, float(np.abs(g).max())) if not zb else 1.0
-        errs[name] = float(np.abs(got - g).max()) / scale
-    bad = {k: f"{v:.1e}" for k, v in sorted(errs.items(), key=lambda kv: -kv[1]) if v > 2e-4}
-    st = {}
-    tr.trunk.update_moving_stats()
-    print(f"flags {flags}: dprobs {np.abs(out['probs'].cpu().numpy() - ref['probs']).max():.1e} loss err {abs(acc[0] / acc[1] + acc[3] - ref['loss']):.1e}  tensors over 2e-4: {bad}", flush=True)
-    del tr, model
+model = ResNetLSTM(cfg["input_shape"], L, list(cfg["filters"]), 3, rate, u)
+model.set_weights_dict(p)
+tr = Trainer(model, learning_rate=1e-3)
+out = tr.forward_backward(xd, H * W, B, yd, masks=md)
+acc = out["acc"].cpu().numpy()
+errs = {}
+for name, g in ref["grads"].items():
+    got = tr.P.G(name).cpu().numpy()
+    zb = name.endswith("/bias") and not name.startswith(("dense2", "lstm", "dense1")) and "res" not in name
+    scale = max(1e-3, float(np.abs(g).max())) if not zb else 1.0
+    errs[name] = float(np.abs(got - g).max()) / scale
+bad = {k: f"{v:.1e}" for k, v in sorted(errs.items(), key=lambda kv: -kv[1]) if v > 2e-4}
+print(f"flags {{}}: dprobs {np.abs(out['probs'].cpu().numpy() - ref['probs']).max():.1e} loss err {abs(acc[0] / acc[1] + acc[3] - ref['loss']):.1e}  tensors over 2e-4: {bad}", flush=True)
