@@ -181,6 +181,17 @@ int orcai_sepconv_bn(const float* in, int B, int Cin, int H, int W, int ksize, i
  *   -> out f32[B][C][ceil(H/2) + 2*(k/2)][orcai_padded_width(ceil(W/2), k)] padded planes */
 int orcai_pool_res_add(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br,
                        float* out, int xpooled, void* stream);
+/* orcai_pool_res_add (xpooled bit 0 set) over B windows of one recording, each output row stored into the per-snippet planes that hold it
+ * (50 %-overlapping snippets whose first blocks are computed once per recording row).  Window b's output row r is
+ * recording row R = base + b * img_step + r of this stage; R is row R - k * period of snippet k = R / period and row R - (k-1) * period of
+ * snippet k - 1.  A row is stored only for r_lo <= r < r_hi (also r < r_lo for a window starting at recording row 0: the first snippet's
+ * own top edge), and only into rows keep_lo <= y < keep_hi of snippets 0 <= k < nsnip.
+ *   out f32[nsnip][ceil(C/4)][Hd + 2*(k/2)][orcai_padded_width(ceil(W/2), k)][4] padded planes (pads untouched), Hd = 2 * period.
+ * Bit for bit the values orcai_pool_res_add writes for the same window.  ORCAI_E_UNSUPPORTED, before anything is launched, for every
+ * shape orcai_pool_res_add does not run on its x-pooled kernel. */
+int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br,
+                               float* out, int xpooled, int Hd, int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo,
+                               int keep_hi, void* stream);
 /* A residual block's second separable convolution WITH the block's tail in its epilogue (architectures.py:172-196, predict.py:265-268):
  *   out = MaxPooling2D((3,2), strides 2, "same")(scale * SepConv(relu_in ? relu(in) : in) + shift [relu_out]) + Conv2D(C, 1, strides 2)(prev) + br
  * = orcai_sepconv_bn(out_layout = 2) followed by orcai_pool_res_add(xpooled bit 0), bit for bit, without the x-pooled tensor in HBM.

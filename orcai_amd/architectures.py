@@ -98,6 +98,8 @@ class ResNetLSTM:
         # later blocks (planes of a few thousand pixels: a chunk of 128 snippets is < 2 waves per SIMD) over up to tail_chunk snippets.
         self.tail_from_block = int(os.environ.get("ORCAI_TAIL_FROM_BLOCK", "3"))
         self.tail_chunk = int(os.environ.get("ORCAI_TAIL_CHUNK", "2048"))
+        # predict_spectrogram: blocks before tail_from_block computed once per recording row, not once per snippet
+        self.share_overlap = os.environ.get("ORCAI_SHARE_OVERLAP", "1") != "0"
 
     # ------------------------------------------------------------------ structure
     @property
@@ -112,9 +114,10 @@ class ResNetLSTM:
     def time_reduction(self) -> int:
         return 2 ** len(self.filters)
 
-    def stage_shapes(self):
-        """[(H, W, C)] after the entry conv and after each block (SAME pooling: ceil(n/2))."""
+    def stage_shapes(self, height: int | None = None):
+        """[(H, W, C)] after the entry conv and after each block (SAME pooling: ceil(n/2)); `height`: of an image other than a snippet."""
         h, w = self.input_hw
+        h = h if height is None else height
         shapes = [(h, w, ENTRY_FILTERS)]
         for f in self.filters:
             h, w = -(-h // 2), -(-w // 2)
@@ -280,16 +283,16 @@ class ResNetLSTM:
     def padded_width(self, w: int) -> int:
         return (w + self.kernel_size // 2 + 3) & ~3
 
-    def _buffers(self, B: int, first: int = 1, last: int | None = None, need_input: bool = True) -> dict:
+    def _buffers(self, B: int, first: int = 1, last: int | None = None, need_input: bool = True, height: int | None = None) -> dict:
         """Zero-padded activation planes of residual blocks first..last for a trunk chunk of B snippets (see "Padded plane
-        layout" in csrc/model_fwd.hip).  Allocated ZEROED once for the largest chunk seen; the kernels never write the pads.
-        `prev{first-1}` (the input of block `first`) is included when need_input."""
+        layout" in csrc/model_fwd.hip), or of B images `height` rows tall.  Allocated ZEROED once for the largest chunk seen; the
+        kernels never write the pads.  `prev{first-1}` (the input of block `first`) is included when need_input."""
         last = len(self.filters) if last is None else last
-        key = (first, last)
+        key = (first, last) if height is None else (first, last, height)
         have = self._ws.get(key)
         if have is not None and have[0] >= B:  # planes are snippet-major: a smaller chunk uses the head of a larger workspace
             return have[1]
-        shapes = self.stage_shapes()
+        shapes = self.stage_shapes(height)
         dev = torch.device("cuda", torch.cuda.current_device())
         R = self.kernel_size // 2
 
@@ -349,20 +352,24 @@ class ResNetLSTM:
         return True
 
     def trunk_device(self, src: torch.Tensor, snippet_stride: int, B: int, feat: torch.Tensor, keep: dict | None = None, first: int = 0,
-                     last: int | None = None, ws: dict | None = None) -> dict:
+                     last: int | None = None, ws: dict | None = None, height: int | None = None, scatter: tuple | None = None) -> dict:
         """Convolutional trunk for one chunk of B snippets, stages first..last: stage 0 = entry conv, b = residual block b,
         len(filters)+1 = final separable conv (writes the LSTM input features feat[B][steps][W_last*36]).  Returns the workspace
-        (its `prev{last}` planes are the input of stage last+1)."""
+        (its `prev{last}` planes are the input of stage last+1).
+        height: the B images are `height` rows tall instead of snippets.  scatter = (out planes, orcai_pool_res_add_scatter's row map
+        (Hd, nsnip, period, base, img_step, r_lo, r_hi, keep_lo, keep_hi)): block `last`'s tail stores through the row map into the
+        per-snippet planes `out` instead of ws[prev{last}] (the shared stage of overlapping snippets, forward_device)."""
         lib = N.lib()
         d = self.prepare()
         nb = len(self.filters)
         last = nb + 1 if last is None else last
         if ws is None:
-            ws = self._buffers(B, max(first, 1), min(last, nb))
+            ws = self._buffers(B, max(first, 1), min(last, nb), height=height)
         st = N.stream_ptr()
         H, W = self.input_hw
+        H = H if height is None else height
         k = self.kernel_size
-        shapes = self.stage_shapes()
+        shapes = self.stage_shapes(height)
         fuse_entry = first == 0 and last >= 1 and k == 3 and self.fuse_entry and keep is None and self.filters[0] <= 64
         if first == 0 and not fuse_entry:
             self._launch("conv0", "orcai_conv0_bn_relu", lib.orcai_conv0_bn_relu, src.data_ptr(), snippet_stride, B, H, W, k, N.ptr(d["conv0/w"]),
@@ -384,12 +391,17 @@ class ResNetLSTM:
                              N.ptr(d[pa + "/scale"]), N.ptr(d[pa + "/shift"]), f, 1, 0, N.ptr(a), st)
             # second separable conv + the block's tail (pool, residual conv, add) in one launch where the marching kernel has the shape (orcai-V1
             # block 1): the x-pooled tensor never reaches HBM; otherwise the two launches -- the same bits either way
-            if keep is None and self._launch(f"b{b}/sep_b+pool_res", "orcai_sepconv_pool_res", lib.orcai_sepconv_pool_res, N.ptr(a), N.ptr(prev), B, f, f, c, h, wd, k, 0,
+            scattered = scatter is not None and b == last
+            if keep is None and not scattered and self._launch(f"b{b}/sep_b+pool_res", "orcai_sepconv_pool_res", lib.orcai_sepconv_pool_res, N.ptr(a), N.ptr(prev), B, f, f, c, h, wd, k, 0,
                                              N.ptr(d[pb + "/dw"]), N.ptr(d[pb + "/pw"]), N.ptr(d[pb + "/scale"]), N.ptr(d[pb + "/shift"]), 0, N.ptr(d[f"b{b}/res/w"]),
                                              N.ptr(d[f"b{b}/res/b"]), N.ptr(nxt), 1 if entry else 0, st, may_refuse=True):
                 continue
             self._launch(pb, "orcai_sepconv_bn", lib.orcai_sepconv_bn, N.ptr(a), B, f, h, wd, k, 0, N.ptr(d[pb + "/dw"]), N.ptr(d[pb + "/pw"]),
                          N.ptr(d[pb + "/scale"]), N.ptr(d[pb + "/shift"]), f, 0, 2, N.ptr(bb), st)
+            if scattered:
+                self._launch(f"b{b}/pool_res", "orcai_pool_res_add_scatter", lib.orcai_pool_res_add_scatter, N.ptr(bb), N.ptr(prev), B, f, c, h, wd, k,
+                             N.ptr(d[f"b{b}/res/w"]), N.ptr(d[f"b{b}/res/b"]), N.ptr(scatter[0]), 3 if entry else 1, *scatter[1], st)
+                continue
             self._launch(f"b{b}/pool_res", "orcai_pool_res_add", lib.orcai_pool_res_add, N.ptr(bb), N.ptr(prev), B, f, c, h, wd, k, N.ptr(d[f"b{b}/res/w"]),
                          N.ptr(d[f"b{b}/res/b"]), N.ptr(nxt), 3 if entry else 1, st)
         if last == nb + 1:
@@ -459,7 +471,16 @@ class ResNetLSTM:
         feat = torch.empty((n, steps, wd * FINAL_FILTERS), dtype=torch.float32, device=src.device)
         nb = len(self.filters)
         split = self.tail_from_block  # blocks >= split (small planes) run over `tail_chunk` snippets per launch to fill the chip
-        if keep is not None or split > nb or n <= chunk:
+        geo = self.shared_geometry(snippet_stride) if keep is None and 2 <= split <= nb else None  # decided before anything is launched
+        if geo is not None:
+            big = min(n, self.tail_chunk)
+            tail = self._buffers(big, split, nb, need_input=True)
+            carry = tail[f"prev{split - 1}"]  # the shared stage stores every snippet's rows straight into the tail's input planes
+            for t0 in range(0, n, big):  # tail chunks stay independent: each computes its own first and last stride
+                nt = min(big, n - t0)
+                self._shared_stage(src[t0 * snippet_stride :], nt, carry, geo, chunk)
+                self.trunk_device(None, snippet_stride, nt, feat[t0:], first=split, last=nb + 1, ws=tail)
+        elif keep is not None or split > nb or n <= chunk:
             for s in range(0, n, chunk):
                 B = min(chunk, n - s)
                 self.trunk_device(src[s * snippet_stride :], snippet_stride, B, feat[s:], keep=keep if s == 0 else None)
@@ -476,6 +497,51 @@ class ResNetLSTM:
                     self.trunk_device(src[s * snippet_stride :], snippet_stride, B, None, first=0, last=split - 1, ws=head)
                 self.trunk_device(None, snippet_stride, nt, feat[t0:], first=split, last=nb + 1, ws=tail)
         self.head_device(feat, out, keep=keep)
+
+    shared_strides = 8  # snippet strides a super-snippet keeps (its halo adds ~1 %)
+
+    def shared_geometry(self, snippet_stride: int):
+        """overlap.SharedStage for the blocks before tail_from_block when the snippets overlap by half (predict_spectrogram), None
+        for every layout or shape that takes the per-snippet path.  Refuses what orcai_pool_res_add_scatter would refuse."""
+        from orcai_amd.overlap import shared_stage
+
+        H, W = self.input_hw
+        S = self.tail_from_block - 1
+        if self.precision != "f32" or not 1 <= S <= len(self.filters) or not self.share_overlap:
+            return None
+        geo = shared_stage(H, W, self.kernel_size, S, snippet_stride)
+        if geo is None:
+            return None
+        hi = self.shared_strides * (H // 2) + 2 * geo.halo  # the tallest image: every plane stays inside the kernels' 32-bit offset checks
+        for h, wd, _ in self.stage_shapes(hi)[:S]:
+            if 16 * (h + 2 * (self.kernel_size // 2)) * self.padded_width(wd) >= 1 << 27:
+                return None
+        h, wd, _ = self.stage_shapes(hi)[S - 1]
+        if (self.filters[S - 1] + 3) // 4 * h * (((wd + 1) // 2 + 3) & ~3) >= 1 << 28:
+            return None
+        return geo
+
+    def _shared_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, chunk: int) -> None:
+        """Entry conv and blocks 1 .. geo.blocks of nt consecutive 50 %-overlapping snippets (snippet 0 at src), computed once per
+        recording row: super-snippets for the rows away from snippet edges, crops of every snippet's first / last rows for its
+        edge patches (orcai_amd/overlap.py).  Every row of every snippet lands in carry[0:nt] exactly once.  Activation memory
+        stays within what `chunk` snippets use on the per-snippet path."""
+        from orcai_amd.overlap import plan_windows
+
+        H, W = self.input_hw
+        S = geo.blocks
+        supers, crops = plan_windows(geo, H, nt, self.shared_strides)
+        budget = chunk * H  # image rows per launch group, as on the per-snippet path
+        n_crop = max(1, min(nt, budget // (4 * geo.crop)))
+        n_super = max(1, (budget - n_crop * geo.crop) // max(w.height for w in supers))
+        for group, per in ((supers, n_super), (crops, n_crop)):
+            for w in group:
+                for b0 in range(0, w.count, per):
+                    B = min(per, w.count - b0)
+                    ws = self._buffers(min(per, w.count), 1, S, height=w.height)
+                    rowmap = (geo.rows, nt, geo.period, w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)
+                    self.trunk_device(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=S, ws=ws, height=w.height,
+                                      scatter=(carry, rowmap))
 
     def half_engine(self):
         if self._half_engine is None:

@@ -1702,11 +1702,21 @@ __global__ __launch_bounds__(256) void pool_res_add_kernel(const float* __restri
 // different tiles of neighbouring waves, are requested at about the same time and BOTH miss (PMC: 1.64 GB fetched per block-1 launch for 0.99 GB
 // of x-pooled input, the 3 / 2 of an unshared row; the kernel moves 5.9 TB/s of actual traffic).  Stacked, the shared row is one register set:
 // 9 row loads per wave and quad instead of 12.  Same maxima, same sums: bit-identical.  Used where 16-column tiles waste few lanes (Wo >= 40).
-template <int MT, bool VERT = false>
+// SCATTER (orcai_pool_res_add_scatter): the images of the launch are windows of one recording, not snippets, and every output row
+// is stored into the per-snippet planes that hold it.  Image b's output row r is recording row Rr = base + b * img_step + r (rows of
+// this stage); Rr lies in snippet k = Rr / period at row Rr - k * period and in snippet k - 1 at row Rr - (k - 1) * period (50 %
+// overlap: Hd = 2 * period).  A row is stored only for r in [r_lo, r_hi) and into rows [keep_lo, keep_hi) of snippets [0, nsnip); a
+// window that starts at recording row 0 (the first snippet's own top edge, no halo above it) also stores its rows above r_lo.
+struct RowMap {
+  int Hd, nsnip, period, base, img_step, r_lo, r_hi, keep_lo, keep_hi;
+};
+
+template <int MT, bool VERT = false, bool SCATTER = false>
 __global__ __launch_bounds__(256, MT <= 2 ? 4 : 2) void pool_res_add_x_kernel(const float* __restrict__ s /*[B][CQ][H][WPx][4]*/, const float* __restrict__ prev, int C, int Cp, int H,
                                                               int W, int WP, int R, int Ho, int Wo, int WPo, int pad_top, const float* __restrict__ wr /*[Cp][C]*/,
                                                               const float* __restrict__ br, float* __restrict__ out /*[B][CQ][Ho+2R][WPo][4]*/, int prev_compact,
-                                                              int tasks, uint32_t magic_WPo, int ntc = 0 /*VERT: 16-column tiles per output row*/) {
+                                                              int tasks, uint32_t magic_WPo, int ntc = 0 /*VERT: 16-column tiles per output row*/,
+                                                              RowMap rm = RowMap{} /*SCATTER: out is [nsnip][CQ][Hd+2R][WPo][4]*/) {
   const int lane = threadIdx.x & 63;
   int bx, b;
   xcd_remap(bx, b);
@@ -1838,7 +1848,21 @@ __global__ __launch_bounds__(256, MT <= 2 ? 4 : 2) void pool_res_add_x_kernel(co
         float o[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = (oq * 4 + r < C) ? mx[r] + (acc[m][t][r] + br_r[m][r]) : 0.0f;
-        reinterpret_cast<float4*>(out)[((int64_t)b * CQ + oq) * plane_o + oidx[t]] = make_float4(o[0], o[1], o[2], o[3]);
+        if (!SCATTER) {
+          reinterpret_cast<float4*>(out)[((int64_t)b * CQ + oq) * plane_o + oidx[t]] = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+          const int orow = oidx[t] / WPo - R, ocol = oidx[t] - (orow + R) * WPo;
+          const int rr = rm.base + b * rm.img_step + orow, k = rr / rm.period;
+          if ((orow >= rm.r_lo || rr == orow) && orow < rm.r_hi) {  // rr == orow: the window starts at the first snippet's own top edge
+            const int64_t plane_d = (int64_t)(rm.Hd + 2 * R) * WPo;
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+              const int sn = k - d, y = rr - sn * rm.period;
+              if (sn >= 0 && sn < rm.nsnip && y >= rm.keep_lo && y < rm.keep_hi)
+                reinterpret_cast<float4*>(out)[((int64_t)sn * CQ + oq) * plane_d + (int64_t)(y + R) * WPo + ocol] = make_float4(o[0], o[1], o[2], o[3]);
+            }
+          }
+        }
       }
     }
     if (t + DEPTH < 4) {
@@ -2768,6 +2792,46 @@ int orcai_pool_vertical(int on) {
 int orcai_pool_res_add(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br, float* out,
                        int xpooled, void* stream) {
   return orcai_pool_res_add_bn(s, prev, B, C, Cp, H, W, ksize, wr, br, out, xpooled, nullptr, nullptr, nullptr, nullptr, 0.0f, stream);
+}
+
+int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br, float* out,
+                               int xpooled, int Hd, int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo, int keep_hi,
+                               void* stream) {
+  if (!s || !prev || !wr || !br || !out || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || nsnip <= 0 || period <= 0) return ORCAI_E_BADARG;
+  if (xpooled & ~3) return ORCAI_E_BADARG;
+  if (keep_lo < 0 || keep_hi > Hd || keep_lo >= keep_hi || Hd != 2 * period || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const int tot_w = (Wo - 1) * 2 + 2 - W;
+  // only the x-pooled kernel stores through the row map: refuse, before anything is launched, every shape orcai_pool_res_add sends elsewhere
+  if (!(xpooled & 1) || (tot_w > 0 ? tot_w : 0) / 2 != 0 || (C + 15) / 16 > 4 || (int64_t)((C + 3) / 4) * H * ((Wo + 3) & ~3) >= (1ll << 28))
+    return ORCAI_E_UNSUPPORTED;
+  if ((int64_t)base + (int64_t)(B - 1) * img_step + Ho >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  int tot_h = (Ho - 1) * 2 + 3 - H;
+  if (tot_h < 0) tot_h = 0;
+  const int WP = orcai_padded_width(W, ksize), WPo = orcai_padded_width(Wo, ksize), R = ksize / 2;
+  const RowMap rm{Hd, nsnip, period, base, img_step, r_lo < 0 ? 0 : r_lo, r_hi > Ho ? Ho : r_hi, keep_lo, keep_hi};
+  const int tasks = (Ho * WPo + 63) / 64;
+  const int ntc = (Wo + 15) / 16, vtasks = ntc * ((Ho + 3) / 4);
+  const bool vert = g_pool_vert && Wo >= 40;
+  const dim3 grid((tasks + 3) / 4, B), vgrid((vtasks + 3) / 4, B);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t mg = magic_for(WPo);
+  const int compact = (xpooled >> 1) & 1;
+#define ORCAI_POOL_SCATTER(MT)                                                                                                                                  \
+  if (vert)                                                                                                                                                      \
+    hipLaunchKernelGGL((pool_res_add_x_kernel<MT, true, true>), vgrid, dim3(256), 0, st, s, prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, tot_h / 2, wr, br, out, compact, \
+                       vtasks, mg, ntc, rm);                                                                                                                     \
+  else                                                                                                                                                           \
+    hipLaunchKernelGGL((pool_res_add_x_kernel<MT, false, true>), grid, dim3(256), 0, st, s, prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, tot_h / 2, wr, br, out, compact, \
+                       tasks, mg, 0, rm)
+  switch ((C + 15) / 16) {
+    case 1: ORCAI_POOL_SCATTER(1); break;
+    case 2: ORCAI_POOL_SCATTER(2); break;
+    case 3: ORCAI_POOL_SCATTER(3); break;
+    case 4: ORCAI_POOL_SCATTER(4); break;
+  }
+#undef ORCAI_POOL_SCATTER
+  return (int)hipGetLastError();
 }
 
 int orcai_gemm_bias_act(const float* A, const float* Bm, const float* bias, const float* scale, const float* shift, float* C, int64_t M, int N,
