@@ -642,6 +642,21 @@ int orcai_h_planes_relu_bwd(const void* dy, const void* y, int64_t n_halves, voi
 int orcai_h_dropout_mask_dev(void* mask, int64_t n, const uint64_t* counter, uint64_t seed_add, float keep, void* stream);
 int orcai_h_mask_scale(const void* x, const void* mask, float scale, int64_t n, void* y, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PyTorch custom ops (orcai_amd/torch_ops.py; csrc/interop.hip)
+ *   orcai_sigmoid_bwd        dz[i] = g[i] * (1 - p[i]) * p[i]: the gradient at the logit of a head's final sigmoid (orcai_dense_sigmoid,
+ *                            orcai_conv1d_sigmoid) from an upstream gradient g w.r.t. the probabilities p; the bits of aten::sigmoid_backward(g, p).
+ *   orcai_prepare_inference  the inference weights from the flat trainable weights w and BatchNorm moving statistics `stats` on the device:
+ *                            desc int32[n_desc][8] = {kind, dst, count, a0, a1, a2, a3, a4} (offsets in floats into w / stats / out);
+ *                            kind 0: BatchNorm fold of `count` channels (gamma w[a0], beta w[a1], mean stats[a2], var stats[a3], conv bias w[a4] or
+ *                              a4 < 0 for none): scale = gamma / sqrt(var + eps), shift = beta - mean * scale (+ bias * scale) in double, each
+ *                              rounded once to float, scale at out[dst], shift at out[dst + roundup(count, 64)];
+ *                            kind 1: depthwise kernel (k, k, count, 1) at w[a0], k = a1 -> [ceil(count/4)][k*k][4] at out[dst] (zero pad channels);
+ *                            kind 2: copy of `count` floats from w[a0] to out[dst].
+ *                            The LSTM layouts come from orcai_pack_lstm (mode 0) on the same w. */
+int orcai_sigmoid_bwd(const float* p, const float* g, int64_t n, float* dz, void* stream);
+int orcai_prepare_inference(const float* w, const float* stats, const int* desc, int n_desc, double eps, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

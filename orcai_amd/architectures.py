@@ -280,6 +280,104 @@ class ResNetLSTM:
         self._dev = d
         return d
 
+    # ------------------------------------------------------------------ prepare() from device weights (orcai_prepare_inference)
+    def _device_plan(self) -> dict:
+        """Descriptor tables of prepare_device, built once: {"desc": int32 [n][8] for orcai_prepare_inference, "lstm": int32 [n][7] for
+        orcai_pack_lstm (or None), "views": {prepare() key: (offset, shape)}, "size": floats}.  Every tensor starts 256-byte aligned."""
+        if getattr(self, "_plan", None) is not None:
+            return self._plan
+        woff, soff, o1, o2 = {}, {}, 0, 0
+        for name, shape, _, trainable in self.variable_spec():
+            n = int(np.prod(shape))
+            if trainable:
+                woff[name], o1 = o1, o1 + n
+            else:
+                soff[name], o2 = o2, o2 + n
+        plan = {"desc": [], "lstm": [], "views": {}, "size": 0}
+
+        def region(numel):
+            off = plan["size"]
+            plan["size"] += (numel + 63) // 64 * 64
+            return off
+
+        def copy(key, src, shape):
+            n = int(np.prod(shape))
+            off = region(n)
+            plan["desc"].append([2, off, n, woff[src], 0, 0, 0, 0])
+            plan["views"][key] = (off, tuple(shape))
+
+        def fold(prefix, bn, bias=None):
+            c = self.weights[bn + "/gamma"].shape[0]
+            off = region(2 * ((c + 63) // 64 * 64))
+            plan["desc"].append([0, off, c, woff[bn + "/gamma"], woff[bn + "/beta"], soff[bn + "/mean"], soff[bn + "/var"], -1 if bias is None else woff[bias]])
+            plan["views"][prefix + "/scale"] = (off, (c,))
+            plan["views"][prefix + "/shift"] = (off + (c + 63) // 64 * 64, (c,))
+
+        k = self.kernel_size
+        copy("conv0/w", "conv0/kernel", (k * k, ENTRY_FILTERS))
+        fold("conv0", "bn0", "conv0/bias")
+
+        def sep(name, bn):
+            k_, _, c, _ = self.weights[name + "/depthwise"].shape
+            cq = (c + 3) // 4
+            off = region(cq * k * k * 4)
+            plan["desc"].append([1, off, c, woff[name + "/depthwise"], k, 0, 0, 0])
+            plan["views"][name + "/dw"] = (off, (cq, k * k, 4))
+            copy(name + "/pw", name + "/pointwise", self.weights[name + "/pointwise"].shape[2:])
+            fold(name, bn, name + "/bias")
+
+        for b in range(1, len(self.filters) + 1):
+            sep(f"b{b}/sep_a", f"b{b}/bn_a")
+            sep(f"b{b}/sep_b", f"b{b}/bn_b")
+            copy(f"b{b}/res/w", f"b{b}/res/kernel", self.weights[f"b{b}/res/kernel"].shape[2:])
+            copy(f"b{b}/res/b", f"b{b}/res/bias", self.weights[f"b{b}/res/bias"].shape)
+        sep("sep_f", "bn_f")
+        self._device_plan_head(plan, woff, region, copy, fold)
+        plan["desc"] = torch.tensor(plan["desc"], dtype=torch.int32)
+        plan["lstm"] = torch.tensor(plan["lstm"], dtype=torch.int32) if plan["lstm"] else None
+        self._plan = plan
+        return plan
+
+    def _device_plan_head(self, plan, woff, region, copy, fold) -> None:
+        u = self.lstm_units
+        for layer in (1, 2):
+            fin = self.weights[f"lstm{layer}/fwd/kernel"].shape[0]
+            W, bvec, U = region(fin * 8 * u), region(8 * u), region(2 * u * 4 * u)
+            for d, name in enumerate(("fwd", "bwd")):  # _prepare_head's permuted columns, concatenation and stack: orcai_pack_lstm, mode 0
+                plan["lstm"].append([woff[f"lstm{layer}/{name}/kernel"], W, fin, u, 8 * u, d * 4 * u, 0])
+                plan["lstm"].append([woff[f"lstm{layer}/{name}/bias"], bvec, 1, u, 8 * u, d * 4 * u, 0])
+                plan["lstm"].append([woff[f"lstm{layer}/{name}/recurrent"], U + d * u * 4 * u, u, u, 4 * u, 0, 0])
+            plan["views"].update({f"lstm{layer}/W": (W, (fin, 8 * u)), f"lstm{layer}/b": (bvec, (8 * u,)), f"lstm{layer}/U": (U, (2, u, 4 * u))})
+        copy("dense1/W", "dense1/kernel", self.weights["dense1/kernel"].shape)
+        copy("dense1/b", "dense1/bias", self.weights["dense1/bias"].shape)
+        fold("dense1", "bn_d")
+        copy("dense2/W", "dense2/kernel", self.weights["dense2/kernel"].shape)
+        copy("dense2/b", "dense2/bias", self.weights["dense2/bias"].shape)
+
+    def prepare_device(self, wflat: torch.Tensor, sflat: torch.Tensor) -> dict:
+        """prepare()'s tensors, bit for bit, built on the device from f32 cuda tensors wflat = the trainable variables and sflat = the BatchNorm
+        moving statistics, each flattened and concatenated in variable_spec() order: no host round trip.  Views of one fresh buffer; the model's
+        own cache (prepare()) is not touched."""
+        plan = self._device_plan()
+        dev = wflat.device
+        if not (wflat.is_cuda and wflat.dtype == torch.float32 and wflat.is_contiguous() and sflat.is_cuda and sflat.dtype == torch.float32 and sflat.is_contiguous()):
+            raise ValueError("prepare_device: wflat / sflat must be contiguous f32 cuda tensors")
+        n_w = sum(int(np.prod(s)) for _, s, _, t in self.variable_spec() if t)
+        n_s = sum(int(np.prod(s)) for _, s, _, t in self.variable_spec() if not t)
+        if wflat.numel() != n_w or sflat.numel() != n_s:
+            raise ValueError(f"prepare_device: expected {n_w} weights and {n_s} statistics, got {wflat.numel()} and {sflat.numel()}")
+        if plan.get("dev") != dev:  # the descriptor tables on this device (uploaded once)
+            plan["desc_dev"] = plan["desc"].to(dev)
+            plan["lstm_dev"] = None if plan["lstm"] is None else plan["lstm"].to(dev)
+            plan["dev"] = dev
+        lib, st = N.lib(), N.stream_ptr()
+        out = torch.empty(plan["size"], dtype=torch.float32, device=dev)
+        N.check(lib.orcai_prepare_inference(wflat.data_ptr(), sflat.data_ptr(), plan["desc_dev"].data_ptr(), int(plan["desc"].shape[0]), BN_EPS, out.data_ptr(), st),
+                "orcai_prepare_inference")
+        if plan["lstm_dev"] is not None:
+            N.check(lib.orcai_pack_lstm(wflat.data_ptr(), plan["lstm_dev"].data_ptr(), int(plan["lstm"].shape[0]), out.data_ptr(), None, st), "orcai_pack_lstm")
+        return {key: out[o : o + int(np.prod(shape))].view(shape) for key, (o, shape) in plan["views"].items()}
+
     def padded_width(self, w: int) -> int:
         return (w + self.kernel_size // 2 + 3) & ~3
 
@@ -640,6 +738,10 @@ class ResNet1DConv(ResNetLSTM):
     def _head_spec(self):
         k1 = FINAL_FILTERS  # k_size = x.shape[2] after the frequency mean = the channel count (architectures.py:108)
         return [("conv1d/kernel", (k1, FINAL_FILTERS, self.num_labels), self.conv_kind, True), ("conv1d/bias", (self.num_labels,), "zeros", True)]
+
+    def _device_plan_head(self, plan, woff, region, copy, fold) -> None:
+        copy("conv1d/W", "conv1d/kernel", self.weights["conv1d/kernel"].shape)
+        copy("conv1d/b", "conv1d/bias", self.weights["conv1d/bias"].shape)
 
     def _prepare_head(self, d: dict) -> None:
         d["conv1d/W"] = self._upload(self.weights["conv1d/kernel"])

@@ -1,0 +1,385 @@
+"""PyTorch custom ops in the ``orcai`` namespace: the front end, the model's forward (inference and training mode, with autograd w.r.t.
+the weights) and the whole-recording predict, so that the HIP path composes with a caller's own loss, ``torch.optim`` and
+``torch.compile``.  Every op calls the library through its C ABI only (orcai_amd/_native.py); each has a fake implementation, so shapes are
+known without a GPU.
+
+    torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
+    torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
+
+``weights`` / ``stats`` are the trainable variables and the BatchNorm moving statistics in ``variable_spec()`` order (Keras layouts);
+``config`` is the JSON string ``model_config`` makes.  ``OrcaiModule`` wraps all of it as a ``torch.nn.Module``.
+
+Training mode keeps the activations of its forward for the backward (``Trainer.forward_train`` / ``backward_from_probs``): per config and
+device ONE step is open at a time, from the forward to its backward.  A second training forward while the autograd graph of the first is
+still alive raises instead of overwriting what that graph's backward needs.  f32 models only; no gradient w.r.t. the input.
+"""
+
+from __future__ import annotations
+
+import functools
+import json
+import math
+import os
+import weakref
+from pathlib import Path
+
+import torch
+
+from orcai_amd.architectures import ResNet1DConv, ResNetLSTM
+
+Tensor = torch.Tensor
+CONFIG_KEYS = ("architecture", "input_shape", "filters", "kernel_size", "lstm_units", "num_labels", "dropout_rate")
+
+
+# ---------------------------------------------------------------------------------------------------------------- configs
+def model_config(model) -> str:
+    """The ``config`` string of the ops for a ResNetLSTM / ResNet1DConv (canonical JSON of CONFIG_KEYS)."""
+    precision = getattr(model, "precision", "f32")
+    if precision != "f32":
+        raise NotImplementedError(f"orcai torch ops: precision {precision!r} is not supported (f32 models only)")
+    H, W = model.input_hw
+    cfg = {"architecture": model.architecture, "input_shape": [H, W, 1], "filters": list(model.filters), "kernel_size": model.kernel_size,
+           "lstm_units": model.lstm_units, "num_labels": model.num_labels, "dropout_rate": model.dropout_rate}
+    return json.dumps(cfg, sort_keys=True)
+
+
+@functools.lru_cache(maxsize=None)
+def _parse(config: str) -> dict:
+    cfg = json.loads(config)
+    if cfg.get("precision", "f32") != "f32":
+        raise NotImplementedError(f"orcai torch ops: precision {cfg['precision']!r} is not supported (f32 models only)")
+    missing = [k for k in CONFIG_KEYS if k not in cfg and not (k == "lstm_units" and cfg.get("architecture") == "ResNet1DConv")]
+    if missing:
+        raise ValueError(f"orcai torch ops: config lacks {missing}")
+    if cfg["architecture"] not in ("ResNetLSTM", "ResNet1DConv"):
+        raise ValueError(f"orcai torch ops: unknown architecture {cfg['architecture']!r}")
+    return cfg
+
+
+def _build(config: str):
+    cfg = _parse(config)
+    args = (tuple(cfg["input_shape"]), cfg["num_labels"], list(cfg["filters"]), cfg["kernel_size"], cfg["dropout_rate"])
+    if cfg["architecture"] == "ResNet1DConv":
+        return ResNet1DConv(*args, seed=0)
+    return ResNetLSTM(*args, lstm_units=cfg.get("lstm_units", 128), seed=0)
+
+
+@functools.lru_cache(maxsize=None)
+def _skeleton(config: str):
+    """Host-only model of the config: shapes and variable_spec for the fake implementations (never touches a device)."""
+    return _build(config)
+
+
+def _out_steps(config: str) -> int:
+    cfg = _parse(config)
+    h = int(cfg["input_shape"][0])
+    for _ in cfg["filters"]:
+        h = -(-h // 2)
+    return h
+
+
+def _spec_split(config: str):
+    spec = _skeleton(config).variable_spec()
+    return [tuple(s) for _, s, _, t in spec if t], [tuple(s) for _, s, _, t in spec if not t]
+
+
+def _check_vars(config: str, weights, stats) -> None:
+    ws, ss = _spec_split(config)
+    got_w, got_s = [tuple(w.shape) for w in weights], [tuple(s.shape) for s in stats]
+    if got_w != ws or got_s != ss:
+        raise ValueError(f"orcai torch ops: weights / stats do not follow variable_spec() of the config ({len(ws)} weights, {len(ss)} statistics expected, "
+                         f"got {len(got_w)} and {len(got_s)} with other shapes)")
+    for t in list(weights) + list(stats):
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError("orcai torch ops: weights and stats must be f32 cuda tensors")
+
+
+# ---------------------------------------------------------------------------------------------------------------- per (config, device) state
+class _Engine:
+    """The model object of a config on one device: its inference workspaces, and the training engine (flat parameters, activations of the
+    open training step)."""
+
+    def __init__(self, config: str, device: torch.device):
+        self.config, self.device = config, device
+        self.model = _build(config)
+        self._trainer = None
+        self.token = None  # weakref to the autograd node's token of the open training step (None: no graph was built for it)
+
+    def trainer(self):
+        if self._trainer is None:
+            from orcai_amd.training import Trainer
+
+            class OpTrainer(Trainer):
+                def broadcast_parameters(self, src: int = 0) -> None:  # the ops pass the weights in on every call: nothing to broadcast
+                    return
+
+            with torch.cuda.device(self.device):
+                self._trainer = OpTrainer(self.model)
+        return self._trainer
+
+    def flat(self, weights, stats):
+        return torch.cat([w.detach().reshape(-1) for w in weights]), torch.cat([s.detach().reshape(-1) for s in stats])
+
+    def eval_forward(self, x: Tensor, weights, stats) -> Tensor:
+        m = self.model
+        H, W = m.input_hw
+        B = int(x.shape[0])
+        out = torch.empty((B, m.out_steps, m.num_labels), dtype=torch.float32, device=x.device)
+        if B == 0:
+            return out
+        m._dev = m.prepare_device(*self.flat(weights, stats))
+        try:
+            m.forward_device(x.detach().contiguous().view(-1), H * W, B, out)
+        finally:
+            m._dev = None
+        return out
+
+    def predict(self, spec: Tensor, weights, stats) -> Tensor:
+        m = self.model
+        m._dev = m.prepare_device(*self.flat(weights, stats))
+        try:
+            return m.predict_spectrogram(spec.detach().contiguous())
+        finally:
+            m._dev = None
+
+    def train_forward(self, x: Tensor, weights, stats, dropout_seed: int) -> Tensor:
+        from orcai_amd.training import BN_MOMENTUM
+
+        tr = self.trainer()
+        if tr._pending is not None:
+            if self.token is not None and self.token() is not None:
+                raise RuntimeError("orcai::forward(training=True): the previous training forward of this model has not been backpropagated, and its autograd "
+                                   "graph is still alive; its backward needs the activations this forward would overwrite.  Call backward on the "
+                                   "previous result first.")
+            tr.abandon_forward()  # its graph is gone (or was never built: no_grad): nobody will run its backward
+        self.token = None
+        m, P = self.model, tr.P
+        H, W = m.input_hw
+        torch.cat([w.detach().reshape(-1) for w in weights], out=P.w)
+        n_s = sum(k for _, k in P.stat_offsets.values())
+        torch.cat([s.detach().reshape(-1) for s in stats], out=P.stats_flat[:n_s])
+        tr.seed = int(dropout_seed)  # the masks Trainer(seed=dropout_seed) draws at its step 0 (the counter is never advanced here)
+        probs = tr.forward_train(x.detach().contiguous().view(-1), H * W, int(x.shape[0]))
+        P.ema_all(BN_MOMENTUM)  # batch statistics -> moving statistics, the kernel Trainer.apply runs
+        names = [n for n, _, t in P.spec if not t]
+        for s, n in zip(stats, names):
+            s.copy_(P.stats[n].view(s.shape))
+        return probs
+
+    def backward(self, grad: Tensor, probs: Tensor) -> Tensor:
+        tr = self._trainer
+        if tr is None or tr._pending is None:
+            raise RuntimeError("orcai::forward backward: no training forward of this model is waiting for its backward (a backward runs once per forward)")
+        self.token = None
+        tr.backward_from_probs(grad.contiguous(), probs)
+        return tr.P.g.clone()
+
+
+_ENGINES: dict = {}
+
+
+def _key(config: str, device: torch.device):
+    return config, device.index if device.index is not None else torch.cuda.current_device()
+
+
+def _engine(config: str, device: torch.device) -> _Engine:
+    if device.type != "cuda":
+        raise RuntimeError(f"orcai torch ops run on a ROCm GPU only (got a tensor on {device}); there is no CPU fallback")
+    key = _key(config, device)
+    eng = _ENGINES.get(key)
+    if eng is None:
+        _parse(config)
+        eng = _ENGINES[key] = _Engine(config, torch.device("cuda", key[1]))
+    return eng
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::spectrogram
+def _bins(sampling_rate: int, nfft: int, freq_hi: float) -> int:
+    from orcai_amd.frontend import crop_indices, fft_frequencies
+
+    return crop_indices(fft_frequencies(sampling_rate, nfft), [0, freq_hi])[1]
+
+
+@torch.library.custom_op("orcai::spectrogram", mutates_args=())
+def spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate): frequencies 0 .. freq_hi, quantile normalisation (q_lo, q_hi)."""
+    from orcai_amd.frontend import get_frontend
+
+    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
+        raise ValueError("orcai::spectrogram: pcm must be a 1-d f32 cuda tensor")
+    sp = {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(pcm, sp)
+
+
+@spectrogram.register_fake
+def _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
+    T = 1 + (pcm.shape[0] - (nfft & 1)) // hop
+    return pcm.new_empty((T, _bins(sampling_rate, nfft, freq_hi)), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::forward
+# torch.library.custom_op registers no autograd formula for an op that mutates an argument (the moving statistics), so orcai::forward is
+# defined with torch.library directly: a CUDA kernel, the fake implementation, and an Autograd kernel around a torch.autograd.Function that
+# redispatches below autograd.  Its backward is the functional op orcai::forward_backward.
+_LIB = torch.library.Library("orcai", "FRAGMENT")
+_LIB.define("forward(Tensor x, Tensor[] weights, Tensor(a!)[] stats, str config, bool training, SymInt dropout_seed) -> Tensor")
+
+
+def forward(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, training: bool, dropout_seed: int) -> Tensor:
+    """The model on snippets x[B][H][W].  training=False: the inference kernels on weights prepared on the device (BatchNorm with the moving
+    statistics).  training=True: the training-mode forward (batch statistics, Dropout drawn from dropout_seed); the moving statistics in
+    `stats` are updated in place (momentum 0.99) and the step stays open for the backward."""
+    return torch.ops.orcai.forward(x, weights, stats, config, training, dropout_seed)
+
+
+def _forward_impl(x, weights, stats, config, training, dropout_seed):
+    cfg = _parse(config)
+    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
+    if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32:
+        raise ValueError(f"orcai::forward: x must be f32 [B, {H}, {W}], got {x.dtype} {tuple(x.shape)}")
+    _check_vars(config, weights, stats)
+    eng = _engine(config, x.device)
+    with torch.cuda.device(x.device):
+        if training:
+            if x.shape[0] == 0:
+                raise ValueError("orcai::forward(training=True): empty batch")
+            return eng.train_forward(x, weights, stats, dropout_seed)
+        return eng.eval_forward(x, weights, stats)
+
+
+_LIB.impl("forward", _forward_impl, "CUDA")
+_LIB.impl("forward", _forward_impl, "CPU")  # (refuses: the checks name the missing GPU)
+
+
+@torch.library.register_fake("orcai::forward", lib=_LIB)
+def _forward_fake(x, weights, stats, config, training, dropout_seed):
+    _parse(config)
+    return x.new_empty((x.shape[0], _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
+
+
+@torch.library.custom_op("orcai::forward_backward", mutates_args=())
+def forward_backward(grad: Tensor, probs: Tensor, config: str) -> Tensor:
+    """The backward of the open training forward of `config` from dL/dprobs: the flat weight gradient (variable_spec order, no L2 term)."""
+    with torch.cuda.device(grad.device):
+        return _engine(config, grad.device).backward(grad, probs)
+
+
+@forward_backward.register_fake
+def _forward_backward_fake(grad, probs, config):
+    return grad.new_empty((sum(math.prod(s) for s in _spec_split(config)[0]),), dtype=torch.float32)
+
+
+class _GraphToken:
+    """Lives on the autograd node of a training forward: while it does, that forward's backward may still come."""
+
+
+class _ForwardFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, stats, config, training, dropout_seed, *weights):
+        with torch._C._AutoDispatchBelowAutograd():
+            out = torch.ops.orcai.forward(x, list(weights), stats, config, training, dropout_seed)
+        ctx.training, ctx.config = bool(training), config
+        ctx.shapes = [tuple(w.shape) for w in weights]
+        ctx.save_for_backward(out)
+        if training and not torch._subclasses.fake_tensor.is_fake(out):
+            ctx.token = _GraphToken()
+            eng = _ENGINES.get(_key(config, out.device))
+            if eng is not None:
+                eng.token = weakref.ref(ctx.token)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        if not ctx.training:
+            raise RuntimeError("orcai::forward(training=False) has no backward (BatchNorm with moving statistics); run the forward with training=True to train")
+        (probs,) = ctx.saved_tensors
+        flat = torch.ops.orcai.forward_backward(grad, probs, ctx.config)
+        sizes = [math.prod(s) for s in ctx.shapes]
+        return (None, None, None, None, None, *[t.view(s) for t, s in zip(torch.split(flat, sizes), ctx.shapes)])
+
+
+def _forward_autograd(x, weights, stats, config, training, dropout_seed):
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError("orcai::forward computes no gradient w.r.t. its input x (only w.r.t. the weights): pass x with requires_grad=False")
+    if torch.is_grad_enabled() and any(w.requires_grad for w in weights):
+        return _ForwardFunction.apply(x, stats, config, training, dropout_seed, *weights)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.forward(x, weights, stats, config, training, dropout_seed)
+
+
+_LIB.impl("forward", _forward_autograd, "Autograd")
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
+@torch.library.custom_op("orcai::predict_spectrogram", mutates_args=())
+def predict_spectrogram(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
+    """All 50 %-overlapping snippets of spec[T][W] (model.predict_spectrogram: blocks 1-2 shared between overlapping snippets), eval mode."""
+    cfg = _parse(config)
+    if spec.dim() != 2 or spec.shape[1] != int(cfg["input_shape"][1]) or spec.dtype != torch.float32:
+        raise ValueError(f"orcai::predict_spectrogram: spec must be f32 [T, {cfg['input_shape'][1]}], got {spec.dtype} {tuple(spec.shape)}")
+    _check_vars(config, weights, stats)
+    with torch.cuda.device(spec.device):
+        return _engine(config, spec.device).predict(spec, weights, stats)
+
+
+@predict_spectrogram.register_fake
+def _predict_spectrogram_fake(spec, weights, stats, config):
+    H = int(_parse(config)["input_shape"][0])
+    n = torch.sym_max((spec.shape[0] - H) // (H // 2) + 1, 0)
+    return spec.new_empty((n, _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- nn.Module
+def param_name(keras_name: str) -> str:
+    """Module attribute of a Keras variable name: '/' -> '__' (reversible: no variable name holds '__')."""
+    return keras_name.replace("/", "__")
+
+
+class OrcaiModule(torch.nn.Module):
+    """A ResNetLSTM / ResNet1DConv as a torch.nn.Module: the trainable variables are parameters, the BatchNorm moving statistics buffers,
+    both named after the Keras variables (param_name).  forward(x f32[B, H, W]) follows self.training; gradients reach the parameters
+    only.  Built from a model object or a model directory (io.load_orcai_model).  dropout_seed of the n-th training forward:
+    seed * 1000003 + n."""
+
+    def __init__(self, model, seed: int = 0):
+        super().__init__()
+        if isinstance(model, (str, os.PathLike)):
+            from orcai_amd.io import load_orcai_model
+
+            model = load_orcai_model(Path(model))[0]
+        self.config = model_config(model)  # raises for f16 models
+        self._model = model
+        self._trainable, self._stats = [], []
+        for name, _, _, trainable in model.variable_spec():
+            t = torch.from_numpy(model.weights[name].copy())
+            if trainable:
+                self.register_parameter(param_name(name), torch.nn.Parameter(t))
+                self._trainable.append(name)
+            else:
+                self.register_buffer(param_name(name), t)
+                self._stats.append(name)
+        self.seed = int(seed)
+        self.dropout_draws = 0
+
+    def weights_list(self) -> list:
+        return [getattr(self, param_name(n)) for n in self._trainable]
+
+    def stats_list(self) -> list:
+        return [getattr(self, param_name(n)) for n in self._stats]
+
+    def forward(self, x: Tensor) -> Tensor:
+        seed = 0
+        if self.training:
+            seed = (self.seed * 1000003 + self.dropout_draws) & 0x7FFFFFFFFFFFFFFF
+            self.dropout_draws += 1
+        return torch.ops.orcai.forward(x, self.weights_list(), self.stats_list(), self.config, self.training, seed)
+
+    def predict_spectrogram(self, spec: Tensor) -> Tensor:
+        return torch.ops.orcai.predict_spectrogram(spec, self.weights_list(), self.stats_list(), self.config)
+
+    def to_model(self):
+        """Writes the parameters and buffers back into the model object (for .save, predict, `orcai predict`) and returns it."""
+        self._model.set_weights_dict({n: getattr(self, param_name(n)).detach().cpu().numpy() for n in self._trainable + self._stats})
+        return self._model

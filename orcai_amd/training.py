@@ -83,6 +83,18 @@ def _gemm(lib, A, sam, sak, B, sbk, sbn, C, M, Nn, K, alpha=1.0, accumulate=0, w
                                    None if wreg is None else wreg.data_ptr(), beta_w, N.stream_ptr()), "orcai_gemm_strided")
 
 
+def _masked_bce_seed(head, labels: torch.Tensor, loss_weight: torch.Tensor | None):
+    """The training step's own seed of the head's backward: masked BCE over the cached probabilities -> (acc, dz), acc = device float64
+    [bce sum, count, correct, l2 (left 0 here)], dz = dL/dlogits [n*T][L] (the sigmoid's derivative folded in: orcai_masked_bce_w)."""
+    c = head.cache
+    M, L = c["n"] * c["T"], head.model.num_labels
+    acc = torch.zeros(4, dtype=torch.float64, device=labels.device)
+    dz = torch.empty((M, L), dtype=torch.float32, device=labels.device)
+    N.check(head.lib.orcai_masked_bce_w(c["probs"].data_ptr(), labels.contiguous().data_ptr(), M * L, MASK_VALUE, acc.data_ptr(), dz.data_ptr(),
+                                        None if loss_weight is None else loss_weight.data_ptr(), head.grad_scale, N.stream_ptr()), "masked_bce")
+    return acc, dz
+
+
 class HeadTrainer:
     """Training forward / backward of everything after the convolutional trunk: BN+ReLU of the final separable conv
     (Keras Reshape layout), two BiLSTM layers with dropout, Dense-128 + BN + dropout, Dense-labels + sigmoid, loss."""
@@ -215,22 +227,25 @@ class HeadTrainer:
 
     def loss_and_backward(self, labels: torch.Tensor, loss_weight: torch.Tensor | None = None) -> dict:
         """labels: f32 cuda [n][T][L] in {0,1} or -1 (masked).  Fills the head's slices of the flat gradient buffer,
-        returns {"loss", "bce", "count", "correct", "dfeatv"} (device scalars stay on the device until .item()).
+        returns {"acc", "dfeatv"}: acc = device float64 [bce sum, count, correct, l2] (stays on the device until .item()).
         loss_weight: optional device float[1], the batch mean of Keras' class_weight sample weights (orcai_masked_bce_w)."""
+        acc, dz2 = _masked_bce_seed(self, labels, loss_weight)
+        return self.backward_from_dz(dz2, l2=True, acc=acc)
+
+    def backward_from_dz(self, dz2: torch.Tensor, l2: bool = True, acc: torch.Tensor | None = None) -> dict:
+        """The head's backward from dz2 = dL/dlogits of the final sigmoid, [n*T][L] (the masked-BCE seed, or orcai_sigmoid_bwd of an
+        external dL/dprobs).  l2: add the L2 regularisers' gradients and write their value into acc[3]; without it the gradients are those
+        of the seed's loss alone."""
         lib, P, u, c = self.lib, self.P, self.u, self.cache
         st = N.stream_ptr()
         n, T = c["n"], c["T"]
         M = n * T
         L = self.model.num_labels
-        dev = labels.device
+        dev = dz2.device
         f32 = dict(dtype=torch.float32, device=dev)
         keep = 1.0 - c["rate"]
         masks = c["masks"]
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)  # bce sum, count, correct, l2
-        dz2 = torch.empty((M, L), **f32)
-        N.check(lib.orcai_masked_bce_w(c["probs"].data_ptr(), labels.contiguous().data_ptr(), M * L, MASK_VALUE, acc.data_ptr(), dz2.data_ptr(),
-                                       None if loss_weight is None else loss_weight.data_ptr(), self.grad_scale, st), "masked_bce")
-        l2g = 2 * L2_LAMBDA * self.grad_scale  # the regularisers' gradients join loss-scaled gradients
+        l2g = 2 * L2_LAMBDA * self.grad_scale if l2 else 0.0  # the regularisers' gradients join loss-scaled gradients
         # Dense(labels): dW2 = d1d^T dz2, db2 = colsum(dz2), dd1d = dz2 W2^T
         _gemm(lib, c["d1d"], 1, DENSE_UNITS, dz2, L, 1, P.G("dense2/kernel"), DENSE_UNITS, L, M)
         N.check(lib.orcai_colsum(dz2.data_ptr(), M, L, P.G("dense2/bias").data_ptr(), 0, st), "colsum")
@@ -245,13 +260,13 @@ class HeadTrainer:
                                       dpre.data_ptr(), st), "bn_rows_bwd")
         N.check(lib.orcai_relu_bwd(dpre.data_ptr(), c["pre1"].data_ptr(), dpre.numel(), dpre.data_ptr(), st), "relu_bwd")
         # Dense-128: dW1 = h2d^T dpre + 2 lambda W1, db1, dh2d = dpre W1^T
-        _gemm(lib, c["h2d"], 1, 2 * u, dpre, DENSE_UNITS, 1, P.G("dense1/kernel"), 2 * u, DENSE_UNITS, M, wreg=P.W("dense1/kernel"), beta_w=l2g)
+        _gemm(lib, c["h2d"], 1, 2 * u, dpre, DENSE_UNITS, 1, P.G("dense1/kernel"), 2 * u, DENSE_UNITS, M, wreg=P.W("dense1/kernel") if l2 else None, beta_w=l2g)
         N.check(lib.orcai_colsum(dpre.data_ptr(), M, DENSE_UNITS, P.G("dense1/bias").data_ptr(), 0, st), "colsum")
-        # the value of the L2 penalty over the five regularised kernels: one launch over their slices of the flat weight buffer
-        l2_names = ["dense1/kernel"] + [f"lstm{layer}/{name}/kernel" for layer in (1, 2) for name in ("fwd", "bwd")]
-        offs = (N.c_i64 * len(l2_names))(*[P.offsets[n][0] for n in l2_names])
-        cnts = (N.c_i64 * len(l2_names))(*[P.offsets[n][1] for n in l2_names])
-        N.check(lib.orcai_l2_values(P.w.data_ptr(), offs, cnts, len(l2_names), L2_LAMBDA, acc[3:].data_ptr(), st), "l2_values")
+        if l2:  # the value of the L2 penalty over the five regularised kernels: one launch over their slices of the flat weight buffer
+            l2_names = ["dense1/kernel"] + [f"lstm{layer}/{name}/kernel" for layer in (1, 2) for name in ("fwd", "bwd")]
+            offs = (N.c_i64 * len(l2_names))(*[P.offsets[n][0] for n in l2_names])
+            cnts = (N.c_i64 * len(l2_names))(*[P.offsets[n][1] for n in l2_names])
+            N.check(lib.orcai_l2_values(P.w.data_ptr(), offs, cnts, len(l2_names), L2_LAMBDA, acc[3:].data_ptr(), st), "l2_values")
         unpack, alive = [], []  # kernel-order LSTM gradients -> the Keras-layout gradient buffer: ONE launch for both layers at the end (sources kept alive until then)
         dh = torch.empty((M, 2 * u), **f32)
         _gemm(lib, dpre, DENSE_UNITS, 1, P.W("dense1/kernel"), 1, DENSE_UNITS, dh, M, 2 * u, DENSE_UNITS)
@@ -276,7 +291,7 @@ class HeadTrainer:
                 Wk = P.W(f"lstm{layer}/{name}/kernel")
                 # kernel-order gradients back into the Keras-layout gradient buffer (+ the L2 term of the input kernel)
                 unpack.append(N.UnpackDesc(dU.data_ptr(), 4 * u, 0, u, P.G(f"lstm{layer}/{name}/recurrent").data_ptr(), None, 0.0))
-                unpack.append(N.UnpackDesc(dWc.data_ptr(), 8 * u, d * 4 * u, fin, P.G(f"lstm{layer}/{name}/kernel").data_ptr(), Wk.data_ptr(), l2g))
+                unpack.append(N.UnpackDesc(dWc.data_ptr(), 8 * u, d * 4 * u, fin, P.G(f"lstm{layer}/{name}/kernel").data_ptr(), Wk.data_ptr() if l2 else None, l2g))
                 unpack.append(N.UnpackDesc(dbc.data_ptr(), 8 * u, d * 4 * u, 1, P.G(f"lstm{layer}/{name}/bias").data_ptr(), None, 0.0))
                 alive += [dU, dWc, dbc]
             dx = torch.empty((M, fin), **f32)
@@ -333,15 +348,16 @@ class Conv1DHeadTrainer:
         S["bn_f/var"].mul_(BN_MOMENTUM).add_(c["f_var"], alpha=1 - BN_MOMENTUM)
 
     def loss_and_backward(self, labels: torch.Tensor, loss_weight: torch.Tensor | None = None) -> dict:
+        acc, dz = _masked_bce_seed(self, labels, loss_weight)  # acc[3] (the L2 value) stays 0: this head has no weight regularisers
+        return self.backward_from_dz(dz, acc=acc)
+
+    def backward_from_dz(self, dz: torch.Tensor, l2: bool = False, acc: torch.Tensor | None = None) -> dict:
+        """The head's backward from dz = dL/dlogits of the final sigmoid, [n*T][L]; `l2` is accepted for HeadTrainer's signature (no regularisers here)."""
         lib, P, c, st = self.lib, self.P, self.cache, N.stream_ptr()
         n, T, Wd = c["n"], c["T"], c["Wd"]
         M, L = n * T, self.model.num_labels
-        f32 = dict(dtype=torch.float32, device=labels.device)
+        f32 = dict(dtype=torch.float32, device=dz.device)
         keep = 1.0 - c["rate"]
-        acc = torch.zeros(4, dtype=torch.float64, device=labels.device)  # bce sum, count, correct, l2 (stays 0)
-        dz = torch.empty((M, L), **f32)
-        N.check(lib.orcai_masked_bce_w(c["probs"].data_ptr(), labels.contiguous().data_ptr(), M * L, MASK_VALUE, acc.data_ptr(), dz.data_ptr(),
-                                       None if loss_weight is None else loss_weight.data_ptr(), self.grad_scale, st), "masked_bce")
         dfm = torch.empty((n, T, FINAL_FILTERS), **f32)
         N.check(lib.orcai_conv1d_bwd(c["fm"].data_ptr(), P.W("conv1d/kernel").data_ptr(), dz.data_ptr(), n, T, FINAL_FILTERS, FINAL_FILTERS, L,
                                      P.G("conv1d/kernel").data_ptr(), dfm.data_ptr(), st), "conv1d_bwd")  # the gradient buffer was zeroed at the start of the step
@@ -961,6 +977,7 @@ class Trainer:
         self.seed = int(seed)
         self.rank = 0
         self._graph = None
+        self._pending = None  # the probabilities of an open forward_train step
         self.broadcast_parameters()
 
     @property
@@ -1016,9 +1033,9 @@ class Trainer:
             out[j] = mk
         return out
 
-    def forward_backward(self, src: torch.Tensor, snippet_stride: int, B: int, labels: torch.Tensor, masks: dict | None = "auto",
-                         loss_weight: torch.Tensor | None = None) -> dict:
-        """Gradients of (masked BCE + L2) into the flat gradient buffer.  Returns device accumulators {bce sum, count, correct, l2}."""
+    def _open_step(self, B: int, masks):
+        """The common start of a training step: zeroed gradient buffer, dropout masks ("auto": drawn from the seed and the step counter), the trunk's
+        block masks checked against the planes they multiply."""
         self.P.g.zero_()
         if isinstance(masks, str):
             masks = self._masks(B, self.model.out_steps)
@@ -1029,6 +1046,14 @@ class Trainer:
                 want = (B, (shapes[i][2] + G - 1) // G, shapes[i][0] + 2 * R, self.model.padded_width(shapes[i][1]), G)
                 if mk.dtype != self.trunk.adt or tuple(mk.shape) != want or not mk.is_contiguous():
                     raise ValueError(f"block{i} mask: expected a contiguous {self.trunk.adt} tensor of shape {want}, got {mk.dtype} {tuple(mk.shape)}")
+        return masks
+
+    def forward_backward(self, src: torch.Tensor, snippet_stride: int, B: int, labels: torch.Tensor, masks: dict | None = "auto",
+                         loss_weight: torch.Tensor | None = None) -> dict:
+        """Gradients of (masked BCE + L2) into the flat gradient buffer.  Returns device accumulators {bce sum, count, correct, l2}."""
+        if self._pending is not None:
+            raise RuntimeError("Trainer.forward_backward: a forward_train step is still waiting for its backward_from_probs (its activations would be overwritten)")
+        masks = self._open_step(B, masks)
         self.trunk.begin_step()  # one clear for every reduction scratch of the step
         try:
             featv = self.trunk.forward(src, snippet_stride, B)
@@ -1038,6 +1063,53 @@ class Trainer:
         finally:
             self.trunk.end_step()
         return {"acc": out["acc"], "probs": probs}
+
+    # ------------------------------------------------------------- a step split at the probabilities (orcai_amd/torch_ops.py)
+    def forward_train(self, src: torch.Tensor, snippet_stride: int, B: int, masks: dict | None = "auto") -> torch.Tensor:
+        """The training-mode forward of forward_backward alone: returns the probabilities [B][steps][labels] and keeps every activation the
+        backward needs; the step (its scratch arena included) stays open until backward_from_probs.  BatchNorm batch statistics are in
+        P.batch_flat afterwards (apply / P.ema_all fold them into the moving statistics).  Raises while a step is open."""
+        if self.half:
+            raise NotImplementedError("Trainer.forward_train: the f16 path has no backward from an external gradient (precision 'f16')")
+        if self._pending is not None:
+            raise RuntimeError("Trainer.forward_train: the previous training forward has not been backpropagated yet; a second forward would overwrite "
+                               "the activations its backward needs (run backward first, or abandon_forward() to drop it)")
+        masks = self._open_step(B, masks)
+        self.trunk.begin_step()
+        try:
+            featv = self.trunk.forward(src, snippet_stride, B)
+            probs = self.head.forward(featv, masks, self.model.dropout_rate)
+        except BaseException:
+            self.trunk.end_step()
+            raise
+        self._pending = probs
+        return probs
+
+    def backward_from_probs(self, dprobs: torch.Tensor, probs: torch.Tensor | None = None) -> None:
+        """Backward of the open forward_train step from an external dL/dprobs (same shape as the probabilities): the gradient at the logits is
+        orcai_sigmoid_bwd, then the head's and the trunk's backward without the L2 term.  Fills P.g and closes the step.  probs: the tensor that
+        forward_train returned, checked to be the open step's."""
+        pend = self._pending
+        if pend is None:
+            raise RuntimeError("Trainer.backward_from_probs: no training forward is waiting for its backward")
+        if probs is not None and probs.data_ptr() != pend.data_ptr():
+            raise RuntimeError("Trainer.backward_from_probs: these probabilities are not those of the open training forward (a later forward replaced it)")
+        if tuple(dprobs.shape) != tuple(pend.shape) or dprobs.dtype != torch.float32 or dprobs.device != pend.device:
+            raise ValueError(f"Trainer.backward_from_probs: expected f32 {tuple(pend.shape)} on {pend.device}, got {dprobs.dtype} {tuple(dprobs.shape)} on {dprobs.device}")
+        try:
+            g = dprobs.contiguous()
+            dz = torch.empty_like(pend)
+            N.check(N.lib().orcai_sigmoid_bwd(pend.data_ptr(), g.data_ptr(), pend.numel(), dz.data_ptr(), N.stream_ptr()), "orcai_sigmoid_bwd")
+            out = self.head.backward_from_dz(dz.view(-1, self.model.num_labels), l2=False)
+            self.trunk.backward(out["dfeatv"])
+        finally:
+            self.abandon_forward()
+
+    def abandon_forward(self) -> None:
+        """Close an open forward_train step without its backward (nothing happens when none is open)."""
+        if self._pending is not None:
+            self._pending = None
+            self.trunk.end_step()
 
     def apply(self, world_size: int = 1) -> None:
         """(all-reduce) + Adam + BN moving statistics."""
