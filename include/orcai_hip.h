@@ -192,6 +192,21 @@ int orcai_pool_res_add(const float* s, const float* prev, int B, int C, int Cp, 
 int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br,
                                float* out, int xpooled, int Hd, int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo,
                                int keep_hi, void* stream);
+/* orcai_pool_res_add_scatter with up to ORCAI_ROW_FAMILIES destination families instead of the snippets: window b's output row r is recording
+ * row R = base + b * img_step + r, stored for r_lo <= r < r_hi (also r < r_lo for a window starting at recording row 0) into row
+ * y = R - offset - j * period of image j of every family, for 0 <= j < count and keep_lo <= y < keep_hi.  Image j of a family holds
+ * recording rows [offset + j * period, offset + j * period + Hd); out f32[count][ceil(C/4)][Hd + 2*(k/2)][orcai_padded_width(ceil(W/2), k)][4]
+ * padded planes (pads untouched).  `fams` is a HOST array, read during the call.  Bit for bit the values orcai_pool_res_add writes for the
+ * same window.  ORCAI_E_UNSUPPORTED, before anything is launched, for every shape orcai_pool_res_add does not run on its x-pooled kernel,
+ * more than ORCAI_ROW_FAMILIES families, or a family with keep_hi - keep_lo > 2 * period (a row in more than two of its images). */
+#define ORCAI_ROW_FAMILIES 4
+typedef struct {
+  float* out;
+  int Hd, period, offset, count, keep_lo, keep_hi;
+} orcai_row_family;
+int orcai_pool_res_add_scatter_families(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr,
+                                        const float* br, int xpooled, int base, int img_step, int r_lo, int r_hi, const orcai_row_family* fams,
+                                        int nfam, void* stream);
 /* A residual block's second separable convolution WITH the block's tail in its epilogue (architectures.py:172-196, predict.py:265-268):
  *   out = MaxPooling2D((3,2), strides 2, "same")(scale * SepConv(relu_in ? relu(in) : in) + shift [relu_out]) + Conv2D(C, 1, strides 2)(prev) + br
  * = orcai_sepconv_bn(out_layout = 2) followed by orcai_pool_res_add(xpooled bit 0), bit for bit, without the x-pooled tensor in HBM.

@@ -23,6 +23,12 @@ class UnpackDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ld_src", C.c_int), ("col_off", C.c_int), ("rows", C.c_int), ("G", C.c_void_p), ("W", C.c_void_p), ("l2g", C.c_float)]
 
 
+class RowFamily(C.Structure):
+    """orcai_row_family of include/orcai_hip.h."""
+
+    _fields_ = [("out", C.c_void_p), ("Hd", C.c_int), ("period", C.c_int), ("offset", C.c_int), ("count", C.c_int), ("keep_lo", C.c_int), ("keep_hi", C.c_int)]
+
+
 _SIGNATURES = {
     "orcai_version": (C.c_char_p, []),
     "orcai_frontend_workspace_bytes": (C.c_size_t, []),
@@ -40,6 +46,7 @@ _SIGNATURES = {
     "orcai_sepconv_bn": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_pool_res_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "orcai_pool_res_add_scatter": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] * 10 + [C.c_void_p]),
+    "orcai_pool_res_add_scatter_families": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "orcai_padded_width": (C.c_int, [C.c_int, C.c_int]),
     "orcai_sepconv_tile_mode": (C.c_int, [C.c_int]),
     "orcai_entry_windows": (C.c_int, [C.c_int]),

@@ -12,6 +12,7 @@ Weights are kept on the host as a dict of numpy arrays with Keras variable layou
 
 from __future__ import annotations
 
+import ctypes
 import math
 from pathlib import Path
 
@@ -454,9 +455,10 @@ class ResNetLSTM:
         """Convolutional trunk for one chunk of B snippets, stages first..last: stage 0 = entry conv, b = residual block b,
         len(filters)+1 = final separable conv (writes the LSTM input features feat[B][steps][W_last*36]).  Returns the workspace
         (its `prev{last}` planes are the input of stage last+1).
-        height: the B images are `height` rows tall instead of snippets.  scatter = (out planes, orcai_pool_res_add_scatter's row map
-        (Hd, nsnip, period, base, img_step, r_lo, r_hi, keep_lo, keep_hi)): block `last`'s tail stores through the row map into the
-        per-snippet planes `out` instead of ws[prev{last}] (the shared stage of overlapping snippets, forward_device)."""
+        height: the B images are `height` rows tall instead of snippets.  scatter = [(b0, count, C entry, arguments before xpooled,
+        arguments after it)]: block `last`'s tail runs as one launch of orcai_pool_res_add_scatter or orcai_pool_res_add_scatter_families
+        per segment of images b0 .. b0 + count - 1, storing through its row map instead of into ws[prev{last}] (the shared stages of
+        overlapping snippets, forward_device)."""
         lib = N.lib()
         d = self.prepare()
         nb = len(self.filters)
@@ -497,8 +499,9 @@ class ResNetLSTM:
             self._launch(pb, "orcai_sepconv_bn", lib.orcai_sepconv_bn, N.ptr(a), B, f, h, wd, k, 0, N.ptr(d[pb + "/dw"]), N.ptr(d[pb + "/pw"]),
                          N.ptr(d[pb + "/scale"]), N.ptr(d[pb + "/shift"]), f, 0, 2, N.ptr(bb), st)
             if scattered:
-                self._launch(f"b{b}/pool_res", "orcai_pool_res_add_scatter", lib.orcai_pool_res_add_scatter, N.ptr(bb), N.ptr(prev), B, f, c, h, wd, k,
-                             N.ptr(d[f"b{b}/res/w"]), N.ptr(d[f"b{b}/res/b"]), N.ptr(scatter[0]), 3 if entry else 1, *scatter[1], st)
+                for b0, cnt, what, pre, post in scatter:
+                    self._launch(f"b{b}/pool_res", what, getattr(lib, what), N.ptr(bb[b0:]), N.ptr(prev[b0:]), cnt, f, c, h, wd, k,
+                                 N.ptr(d[f"b{b}/res/w"]), N.ptr(d[f"b{b}/res/b"]), *pre, 3 if entry else 1, *post, st)
                 continue
             self._launch(f"b{b}/pool_res", "orcai_pool_res_add", lib.orcai_pool_res_add, N.ptr(bb), N.ptr(prev), B, f, c, h, wd, k, N.ptr(d[f"b{b}/res/w"]),
                          N.ptr(d[f"b{b}/res/b"]), N.ptr(nxt), 3 if entry else 1, st)
@@ -570,7 +573,16 @@ class ResNetLSTM:
         nb = len(self.filters)
         split = self.tail_from_block  # blocks >= split (small planes) run over `tail_chunk` snippets per launch to fill the chip
         geo = self.shared_geometry(snippet_stride) if keep is None and 2 <= split <= nb else None  # decided before anything is launched
-        if geo is not None:
+        geo2 = self.tail_geometry(snippet_stride) if geo is not None else None
+        if geo2 is not None:  # two levels: blocks split .. nb once per recording row too, only the final conv and the head per snippet
+            big = min(n, self.tail_chunk)
+            tail = self._buffers(big, nb + 1, nb, need_input=True)
+            carry = tail[f"prev{nb}"]  # level 2 stores every snippet's rows straight into the final conv's input planes
+            for t0 in range(0, n, big):  # tail chunks stay independent: each computes its own first and last stride
+                nt = min(big, n - t0)
+                self._two_level_stage(src[t0 * snippet_stride :], nt, carry, geo, geo2, chunk)
+                self.trunk_device(None, snippet_stride, nt, feat[t0:], first=nb + 1, last=nb + 1, ws=tail)
+        elif geo is not None:
             big = min(n, self.tail_chunk)
             tail = self._buffers(big, split, nb, need_input=True)
             carry = tail[f"prev{split - 1}"]  # the shared stage stores every snippet's rows straight into the tail's input planes
@@ -639,7 +651,70 @@ class ResNetLSTM:
                     ws = self._buffers(min(per, w.count), 1, S, height=w.height)
                     rowmap = (geo.rows, nt, geo.period, w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)
                     self.trunk_device(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=S, ws=ws, height=w.height,
-                                      scatter=(carry, rowmap))
+                                      scatter=[(0, B, "orcai_pool_res_add_scatter", (N.ptr(carry),), rowmap)])
+
+    def tail_geometry(self, snippet_stride: int):
+        """overlap.tail_stage for blocks tail_from_block .. last (level 2 of the shared trunk) where shared_geometry applies, None
+        where only blocks before tail_from_block are shared.  Refuses what the launchers would refuse at the level-2 image heights."""
+        from orcai_amd.overlap import tail_stage
+
+        if self.shared_geometry(snippet_stride) is None:
+            return None
+        H, W = self.input_hw
+        nb, split = len(self.filters), self.tail_from_block
+        geo2 = tail_stage(H, W, self.kernel_size, split, nb, snippet_stride)
+        if geo2 is None:
+            return None
+        P2 = H // 2 // 2 ** (split - 1)  # level-1 output rows per snippet stride
+        m2 = max(self.shared_strides, -(-2 * geo2.halo // P2))
+        hi = (m2 * P2 + 2 * geo2.halo) * 2 ** (split - 1)  # the tallest level-2 image, in spectrogram rows
+        shapes = self.stage_shapes(hi)
+        for h, wd, _ in shapes[split - 1 : nb]:
+            if 16 * (h + 2 * (self.kernel_size // 2)) * self.padded_width(wd) >= 1 << 27:
+                return None
+        h, wd, _ = shapes[nb - 1]
+        if (self.filters[nb - 1] + 3) // 4 * h * (((wd + 1) // 2 + 3) & ~3) >= 1 << 28:
+            return None
+        return geo2
+
+    def _two_level_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, geo2, chunk: int) -> None:
+        """Entry conv and blocks 1 .. nb of nt consecutive 50 %-overlapping snippets (snippet 0 at src), computed once per recording
+        row in two levels (orcai_amd/overlap.py, plan_two_level).  Level 1 (blocks 1 .. geo.blocks) runs as _shared_stage, its last
+        tail storing into the level-2 images: super-images of level-1 output rows and crops of every snippet's first / last rows.
+        Level 2 runs the remaining blocks on those images, its last tail storing every snippet's rows into carry[0:nt] exactly once."""
+        from orcai_amd.overlap import plan_two_level
+
+        H, W = self.input_hw
+        S, nb = geo.blocks, len(self.filters)
+        plan = plan_two_level(geo, geo2, H, nt, self.shared_strides)
+        up = geo.scale  # spectrogram rows per level-1 output row
+        planes = {"super": self._buffers(plan.super_images, S + 1, S, height=plan.super_height * up)[f"prev{S}"],
+                  "crop": self._buffers(2 * nt, S + 1, S, height=plan.crop_height * up)[f"prev{S}"]}
+        img_bytes = {key: t[0].numel() * t.element_size() for key, t in planes.items()}
+
+        # level 1: as _shared_stage; the families are host arrays read during each launch call
+        budget = chunk * H
+        n_crop = max(1, min(nt, budget // (4 * geo.crop)))
+        n_super = max(1, (budget - n_crop * geo.crop) // max(w.height for w, _ in plan.level1[:-2]))
+        for i, (w, fams) in enumerate(plan.level1):
+            per = n_super if i < len(plan.level1) - 2 else n_crop
+            arr = (N.RowFamily * len(fams))(*[N.RowFamily(N.ptr(planes[f.planes]) + f.image * img_bytes[f.planes], f.height, f.period, f.offset, f.count,
+                                                          f.keep_lo, f.keep_hi) for f in fams])
+            for b0 in range(0, w.count, per):
+                B = min(per, w.count - b0)
+                ws = self._buffers(min(per, w.count), 1, S, height=w.height)
+                post = (w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, ctypes.addressof(arr), len(fams))
+                self.trunk_device(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=S, ws=ws, height=w.height,
+                                  scatter=[(0, B, "orcai_pool_res_add_scatter_families", (), post)])
+
+        # level 2: all super-images in one launch group, all crops in another; the last tail once per window
+        for key, windows, height in (("super", plan.supers, plan.super_height), ("crop", plan.crops, plan.crop_height)):
+            count = sum(w.count for w, _ in windows)
+            ws = dict(self._buffers(count, S + 1, nb, need_input=False, height=height * up))
+            ws[f"prev{S}"] = planes[key]
+            segs = [(j, w.count, "orcai_pool_res_add_scatter", (N.ptr(carry),),
+                     (geo2.rows, nt, geo2.period, w.base, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)) for w, j in windows]
+            self.trunk_device(None, 0, count, None, first=S + 1, last=nb, ws=ws, height=height * up, scatter=segs)
 
     def half_engine(self):
         if self._half_engine is None:

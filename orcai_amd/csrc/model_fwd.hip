@@ -1702,13 +1702,21 @@ __global__ __launch_bounds__(256) void pool_res_add_kernel(const float* __restri
 // different tiles of neighbouring waves, are requested at about the same time and BOTH miss (PMC: 1.64 GB fetched per block-1 launch for 0.99 GB
 // of x-pooled input, the 3 / 2 of an unshared row; the kernel moves 5.9 TB/s of actual traffic).  Stacked, the shared row is one register set:
 // 9 row loads per wave and quad instead of 12.  Same maxima, same sums: bit-identical.  Used where 16-column tiles waste few lanes (Wo >= 40).
-// SCATTER (orcai_pool_res_add_scatter): the images of the launch are windows of one recording, not snippets, and every output row
-// is stored into the per-snippet planes that hold it.  Image b's output row r is recording row Rr = base + b * img_step + r (rows of
-// this stage); Rr lies in snippet k = Rr / period at row Rr - k * period and in snippet k - 1 at row Rr - (k - 1) * period (50 %
-// overlap: Hd = 2 * period).  A row is stored only for r in [r_lo, r_hi) and into rows [keep_lo, keep_hi) of snippets [0, nsnip); a
-// window that starts at recording row 0 (the first snippet's own top edge, no halo above it) also stores its rows above r_lo.
+// SCATTER (orcai_pool_res_add_scatter, orcai_pool_res_add_scatter_families): the images of the launch are windows of one recording, not
+// snippets, and every output row is stored into every destination image that holds it.  Image b's output row r is recording row
+// Rr = base + b * img_step + r (rows of this stage); a row is stored only for r in [r_lo, r_hi) -- a window that starts at recording row 0
+// (the first snippet's own top edge, no halo above it) also stores its rows above r_lo.  Each of up to kRowFamilies destination families
+// is `count` images of Hd rows, image j holding recording rows [offset + j * period, offset + j * period + Hd); Rr goes to row
+// y = Rr - offset - j * period of every image j in [0, count) with y in [keep_lo, keep_hi).  keep_hi - keep_lo <= 2 * period (checked by the
+// launchers): at most two images j of a family hold a kept row, the largest being (Rr - offset - keep_lo) / period.
+struct RowFamily {
+  float* out;  // [count][CQ][Hd + 2R][WPo][4] padded planes, pads untouched
+  int Hd, period, offset, count, keep_lo, keep_hi;
+};
+constexpr int kRowFamilies = ORCAI_ROW_FAMILIES;
 struct RowMap {
-  int Hd, nsnip, period, base, img_step, r_lo, r_hi, keep_lo, keep_hi;
+  int base, img_step, r_lo, r_hi, nfam;
+  RowFamily f[kRowFamilies];
 };
 
 template <int MT, bool VERT = false, bool SCATTER = false>
@@ -1716,7 +1724,7 @@ __global__ __launch_bounds__(256, MT <= 2 ? 4 : 2) void pool_res_add_x_kernel(co
                                                               int W, int WP, int R, int Ho, int Wo, int WPo, int pad_top, const float* __restrict__ wr /*[Cp][C]*/,
                                                               const float* __restrict__ br, float* __restrict__ out /*[B][CQ][Ho+2R][WPo][4]*/, int prev_compact,
                                                               int tasks, uint32_t magic_WPo, int ntc = 0 /*VERT: 16-column tiles per output row*/,
-                                                              RowMap rm = RowMap{} /*SCATTER: out is [nsnip][CQ][Hd+2R][WPo][4]*/) {
+                                                              RowMap rm = RowMap{} /*SCATTER: out unused, the families' planes instead*/) {
   const int lane = threadIdx.x & 63;
   int bx, b;
   xcd_remap(bx, b);
@@ -1852,14 +1860,23 @@ __global__ __launch_bounds__(256, MT <= 2 ? 4 : 2) void pool_res_add_x_kernel(co
           reinterpret_cast<float4*>(out)[((int64_t)b * CQ + oq) * plane_o + oidx[t]] = make_float4(o[0], o[1], o[2], o[3]);
         } else {
           const int orow = oidx[t] / WPo - R, ocol = oidx[t] - (orow + R) * WPo;
-          const int rr = rm.base + b * rm.img_step + orow, k = rr / rm.period;
+          const int rr = rm.base + b * rm.img_step + orow;
           if ((orow >= rm.r_lo || rr == orow) && orow < rm.r_hi) {  // rr == orow: the window starts at the first snippet's own top edge
-            const int64_t plane_d = (int64_t)(rm.Hd + 2 * R) * WPo;
+            const float4 val = make_float4(o[0], o[1], o[2], o[3]);
 #pragma unroll
-            for (int d = 0; d < 2; ++d) {
-              const int sn = k - d, y = rr - sn * rm.period;
-              if (sn >= 0 && sn < rm.nsnip && y >= rm.keep_lo && y < rm.keep_hi)
-                reinterpret_cast<float4*>(out)[((int64_t)sn * CQ + oq) * plane_d + (int64_t)(y + R) * WPo + ocol] = make_float4(o[0], o[1], o[2], o[3]);
+            for (int fi = 0; fi < kRowFamilies; ++fi) {
+              if (fi >= rm.nfam) break;  // uniform: the family count is a kernel argument
+              const RowFamily& fm = rm.f[fi];
+              const int rel = rr - fm.offset - fm.keep_lo;
+              if (rel < 0) continue;
+              const int jhi = rel / fm.period;
+              const int64_t plane_d = (int64_t)(fm.Hd + 2 * R) * WPo;
+#pragma unroll
+              for (int d = 0; d < 2; ++d) {
+                const int j = jhi - d, y = rr - fm.offset - j * fm.period;
+                if (j >= 0 && j < fm.count && y < fm.keep_hi)
+                  reinterpret_cast<float4*>(fm.out)[((int64_t)j * CQ + oq) * plane_d + (int64_t)(y + R) * WPo + ocol] = val;
+              }
             }
           }
         }
@@ -2794,22 +2811,20 @@ int orcai_pool_res_add(const float* s, const float* prev, int B, int C, int Cp, 
   return orcai_pool_res_add_bn(s, prev, B, C, Cp, H, W, ksize, wr, br, out, xpooled, nullptr, nullptr, nullptr, nullptr, 0.0f, stream);
 }
 
-int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br, float* out,
-                               int xpooled, int Hd, int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo, int keep_hi,
-                               void* stream) {
-  if (!s || !prev || !wr || !br || !out || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || nsnip <= 0 || period <= 0) return ORCAI_E_BADARG;
-  if (xpooled & ~3) return ORCAI_E_BADARG;
-  if (keep_lo < 0 || keep_hi > Hd || keep_lo >= keep_hi || Hd != 2 * period || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+// the x-pooled kernel's store through a row map: ORCAI_E_UNSUPPORTED, before anything is launched, for every shape orcai_pool_res_add sends
+// elsewhere and for recording rows past 32 bits
+static int pool_res_scatter_launch(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br,
+                                   int xpooled, RowMap rm, void* stream) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const int tot_w = (Wo - 1) * 2 + 2 - W;
-  // only the x-pooled kernel stores through the row map: refuse, before anything is launched, every shape orcai_pool_res_add sends elsewhere
   if (!(xpooled & 1) || (tot_w > 0 ? tot_w : 0) / 2 != 0 || (C + 15) / 16 > 4 || (int64_t)((C + 3) / 4) * H * ((Wo + 3) & ~3) >= (1ll << 28))
     return ORCAI_E_UNSUPPORTED;
-  if ((int64_t)base + (int64_t)(B - 1) * img_step + Ho >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  if ((int64_t)rm.base + (int64_t)(B - 1) * rm.img_step + Ho >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
   int tot_h = (Ho - 1) * 2 + 3 - H;
   if (tot_h < 0) tot_h = 0;
   const int WP = orcai_padded_width(W, ksize), WPo = orcai_padded_width(Wo, ksize), R = ksize / 2;
-  const RowMap rm{Hd, nsnip, period, base, img_step, r_lo < 0 ? 0 : r_lo, r_hi > Ho ? Ho : r_hi, keep_lo, keep_hi};
+  rm.r_lo = rm.r_lo < 0 ? 0 : rm.r_lo;
+  rm.r_hi = rm.r_hi > Ho ? Ho : rm.r_hi;
   const int tasks = (Ho * WPo + 63) / 64;
   const int ntc = (Wo + 15) / 16, vtasks = ntc * ((Ho + 3) / 4);
   const bool vert = g_pool_vert && Wo >= 40;
@@ -2817,6 +2832,7 @@ int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, 
   hipStream_t st = (hipStream_t)stream;
   const uint32_t mg = magic_for(WPo);
   const int compact = (xpooled >> 1) & 1;
+  float* out = rm.f[0].out;
 #define ORCAI_POOL_SCATTER(MT)                                                                                                                                  \
   if (vert)                                                                                                                                                      \
     hipLaunchKernelGGL((pool_res_add_x_kernel<MT, true, true>), vgrid, dim3(256), 0, st, s, prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, tot_h / 2, wr, br, out, compact, \
@@ -2832,6 +2848,46 @@ int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, 
   }
 #undef ORCAI_POOL_SCATTER
   return (int)hipGetLastError();
+}
+
+int orcai_pool_res_add_scatter(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br, float* out,
+                               int xpooled, int Hd, int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo, int keep_hi,
+                               void* stream) {
+  if (!s || !prev || !wr || !br || !out || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || nsnip <= 0 || period <= 0) return ORCAI_E_BADARG;
+  if (xpooled & ~3) return ORCAI_E_BADARG;
+  if (keep_lo < 0 || keep_hi > Hd || keep_lo >= keep_hi || Hd != 2 * period || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+  // one family: the snippets themselves (snippet k = rows [k * period, k * period + Hd) of the recording)
+  RowMap rm{};
+  rm.base = base;
+  rm.img_step = img_step;
+  rm.r_lo = r_lo;
+  rm.r_hi = r_hi;
+  rm.nfam = 1;
+  rm.f[0] = RowFamily{out, Hd, period, 0, nsnip, keep_lo, keep_hi};
+  return pool_res_scatter_launch(s, prev, B, C, Cp, H, W, ksize, wr, br, xpooled, rm, stream);
+}
+
+int orcai_pool_res_add_scatter_families(const float* s, const float* prev, int B, int C, int Cp, int H, int W, int ksize, const float* wr, const float* br,
+                                        int xpooled, int base, int img_step, int r_lo, int r_hi, const orcai_row_family* fams, int nfam, void* stream) {
+  if (!s || !prev || !wr || !br || !fams || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || nfam <= 0) return ORCAI_E_BADARG;
+  if ((xpooled & ~3) || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+  if (nfam > kRowFamilies) return ORCAI_E_UNSUPPORTED;
+  RowMap rm{};
+  rm.base = base;
+  rm.img_step = img_step;
+  rm.r_lo = r_lo;
+  rm.r_hi = r_hi;
+  rm.nfam = nfam;
+  for (int i = 0; i < nfam; ++i) {
+    const orcai_row_family& f = fams[i];
+    if (!f.out || f.Hd <= 0 || f.period <= 0 || f.count <= 0 || f.offset < 0 || f.keep_lo < 0 || f.keep_hi > f.Hd || f.keep_lo >= f.keep_hi)
+      return ORCAI_E_BADARG;
+    // the kernel visits the two images whose kept rows can hold a row: a family whose kept rows overlap more is not run
+    if (f.keep_hi - f.keep_lo > 2 * f.period) return ORCAI_E_UNSUPPORTED;
+    if ((int64_t)f.offset + (int64_t)(f.count - 1) * f.period + f.Hd >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+    rm.f[i] = RowFamily{f.out, f.Hd, f.period, f.offset, f.count, f.keep_lo, f.keep_hi};
+  }
+  return pool_res_scatter_launch(s, prev, B, C, Cp, H, W, ksize, wr, br, xpooled, rm, stream);
 }
 
 int orcai_gemm_bias_act(const float* A, const float* Bm, const float* bias, const float* scale, const float* shift, float* C, int64_t M, int N,
