@@ -483,6 +483,19 @@ int orcai_dw_bwd_fused_conv0(const float* in, int64_t snippet_stride, const floa
 int orcai_conv0_bn_bwd_x_ready(const float* in, int64_t snippet_stride, const float* dy, int B, int H, int W, int ksize, const float* w0, const float* bias, const float* mean,
                                const float* var, const float* gamma, const float* beta, float eps, double* scratch2C, float* dbeta, float* dgamma, float* dW, float* workspace,
                                int64_t workspace_floats, void* stream);
+/* Input gradient of Conv2D(16, k, same) -> BatchNormalization (batch statistics) -> ReLU  (architectures.py:164-168; Keras forms it whenever
+ * something differentiable sits in front of the model, train.py:201-219 never asks for it):
+ *   v0 = conv(in) + bias, xh = (v0 - mean) * rsqrt(var + eps), g = dy where fma(xh, gamma, beta) > 0 else 0,
+ *   dv = gamma * rsqrt(var + eps) * (g - dbeta / N - xh * dgamma / N),   N = B * H * W,
+ *   dx[b][p] = sum over taps t, channels c of w0[t][c] * dv[c][p - off(t)]   (dv = 0 outside the image).
+ * v0, xh, the ReLU decision and dv are formed as orcai_conv0_bn_bwd_x[_ready] forms them, so the dv behind dx is the dv behind dW0.
+ * sums2C: dbeta[16] | dgamma[16] as doubles, as orcai_conv0_bn_bwd_x / orcai_dw_bwd_fused_conv0 leave them in scratch2C (still there after
+ * orcai_conv0_bn_bwd_x[_ready]).  dy: padded channel-quad planes [B][4][H + 2R][WP][4], 16-byte aligned; only its interior is read.
+ * dx: f32 [B][H][W], dense (its own stride H * W whatever snippet_stride is), every element written, nothing accumulated; no atomics, so dx is
+ * bit-reproducible.  k = 3: a marching kernel without LDS (csrc/train_trunk.hip conv0_dx_march_kernel); k = 5, 7: LDS tiles.
+ * ORCAI_E_BADARG: ksize not in {3, 5, 7}, non-positive sizes, null or misaligned pointers. */
+int orcai_conv0_bn_bwd_dx(const float* in, int64_t snippet_stride, const float* dy, int B, int H, int W, int ksize, const float* w0, const float* bias, const float* mean,
+                          const float* var, const float* gamma, const float* beta, float eps, const double* sums2C, float* dx, void* stream);
 /* The entry conv's two reduction passes on a marching kernel (k = 3; csrc/train_trunk.hip conv0_march_kernel): orcai_conv0_stats_march is
  * orcai_conv0_stats (shards: [32][4][8] sums | sums of squares for orcai_bn_finish_sharded) without tiles, LDS or barriers; orcai_conv0_march(1)
  * (default) lets orcai_conv0_bn_bwd_x_ready run its weight-gradient pass the same way (0: the tile kernel; < 0 queries; returns the previous value). */

@@ -1652,6 +1652,197 @@ __global__ void conv0_sums_compact_kernel(double* __restrict__ shards) {
   shards[t] = tot;
 }
 
+// ---------------------------------------------------------------- the entry conv's input gradient
+// dx[b][p] = sum over taps t, channels c of w0[t][c] * dv[c][p - off(t)], dv = bn0's (+ReLU) input gradient -- the value conv0_march_kernel<1> /
+// conv0_bn_bwd_x_kernel<.., true> contract with the input taps for dW0, formed here with their expressions in their order (the fma chain of
+// conv0_kernel, fma(cv, 1, bias), (float)dbeta * inv_count) from the snippet, dy and the sums those passes left in scratch2C.  Every dx element has
+// one owner: no atomics, no reduction across lanes or workgroups, so dx is the same from run to run.
+//
+// k = 3, marching: a wave owns a 62-column strip over a segment of rows; lane l works on column strip * 62 - 1 + l and forms dv for ALL 16 channels of
+// its pixel (four float4 loads from the four quad planes, each dy quad loaded once per strip).  dv at the two halo lanes needs one snippet column
+// beyond the wave: lanes 0 and 63 load it themselves (4 bytes per row).  Per pixel the nine scalars s[t] = sum_c w0[t][c] * dv[c] are formed (the
+// taps and the per-channel constants are wave-uniform), the six off-centre ones move one lane left / right (DPP) and all nine are added into three
+// rotating output-row accumulators: row y - 1 is complete, and stored, when dv row y has passed.  No LDS, no barriers.
+__global__ __launch_bounds__(256) void conv0_dx_march_kernel(const float* __restrict__ in, int64_t snippet_stride, const float* __restrict__ dy /*[B][4][H + 2][WP][4]*/, int H,
+                                                              int W, int WP, const float* __restrict__ w0 /*[9][16]*/, const float* __restrict__ bias,
+                                                              const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps, const double* __restrict__ sums /*dbeta[16] | dgamma[16]*/,
+                                                              float inv_count, float* __restrict__ dx /*[B][H][W]*/, int nstrip, int nseg, int rps) {
+  constexpr int KK = 9;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.z;
+  const int task = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (task >= nstrip * nseg) return;  // wave-uniform; the kernel has no barrier
+  const int strip = task % nstrip, seg = task / nstrip;
+  const int xcol = strip * 62 - 1 + lane;
+  const bool col_ok = xcol >= 0 && xcol < W;
+  const bool out_lane = lane >= 1 && lane <= 62 && xcol < W;
+  const bool edge_lane = lane == 0 || lane == 63;
+  const int ecol = lane == 0 ? xcol - 1 : xcol + 1;  // the snippet column beyond the wave that a halo lane's own conv needs
+  const bool ecol_ok = ecol >= 0 && ecol < W;
+  const int cc = xcol < 0 ? 0 : (xcol >= W ? W - 1 : xcol), ec = ecol < 0 ? 0 : (ecol >= W ? W - 1 : ecol);
+  const int r_begin = seg * rps, r_end = min(r_begin + rps, H);
+  const int plane = (H + 2) * WP;
+  const float* inb = in + (int64_t)b * snippet_stride;
+  const float4* dp = reinterpret_cast<const float4*>(dy) + (int64_t)b * 4 * plane;
+  float* dxb = dx + (int64_t)b * H * W;
+  struct InRow { float c, l, r; };
+  struct Raw { float v, e; };
+  struct DyRow { float4 q[4]; };
+  auto iload = [&](int row) -> Raw {  // zero outside the image (the conv's "same" padding); the addresses are clamped into the snippet
+    const int rr = row < 0 ? 0 : (row >= H ? H - 1 : row);
+    const bool row_ok = row >= 0 && row < H;
+    Raw o;
+    const float v = inb[(int64_t)rr * W + cc];
+    o.v = (row_ok && col_ok) ? v : 0.0f;
+    o.e = 0.0f;
+    if (edge_lane) {
+      const float e = inb[(int64_t)rr * W + ec];
+      o.e = (row_ok && ecol_ok) ? e : 0.0f;
+    }
+    return o;
+  };
+  auto dload = [&](int row) -> DyRow {  // interior addresses only (clamped); what a clamped load delivers is masked where dv is formed
+    const int rr = row < 0 ? 0 : (row >= H ? H - 1 : row);
+    DyRow o;
+#pragma unroll
+    for (int cq = 0; cq < 4; ++cq) o.q[cq] = dp[(int64_t)cq * plane + (rr + 1) * WP + cc];
+    return o;
+  };
+  auto iarrive = [&](const Raw& raw, InRow& o) {
+    o.c = raw.v;
+    const float l = lsh<3, -1>(raw.v), r = lsh<3, 1>(raw.v);
+    o.l = lane == 0 ? raw.e : l;
+    o.r = lane == 63 ? raw.e : r;
+  };
+  // The pass needs 272 wave-uniform values per pixel row (144 taps, 8 constants for each of 16 channels): more than a wave has scalar registers.
+  // The channels are therefore worked on quad by quad in a loop that is NOT unrolled: a quad's taps and raw constants are scalar loads inside
+  // it (68 values, the budget conv0_march_kernel lives in), and the four derived constants of every channel (values no load can deliver) sit in
+  // one vector register, lane kind * 16 + c, formed once per wave by the lane that holds them and read with v_readlane.
+  float ctab;
+  {
+    const int c = lane & 15, kind = lane >> 4;
+    const float inv = rsqrtf(var[c] + eps);
+    ctab = kind == 0 ? inv : kind == 1 ? (float)sums[c] * inv_count : kind == 2 ? (float)sums[16 + c] * inv_count : gamma[c] * inv;
+  }
+  auto tab = [&](int i) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ctab), i)); };
+  InRow up, mid, dn;
+  iarrive(iload(r_begin - 2), up);
+  iarrive(iload(r_begin - 1), mid);
+  Raw pin = iload(r_begin);
+  DyRow pd = dload(r_begin - 1);
+  float accA = 0.0f, accB = 0.0f;  // dx rows y - 1 and y while dv row y is worked on
+  for (int y = r_begin - 1; y <= r_end; ++y) {
+    iarrive(pin, dn);
+    float4 q0 = pd.q[0], q1 = pd.q[1], q2 = pd.q[2], q3 = pd.q[3];
+    pin = iload(y + 2);
+    pd = dload(y + 1);
+    const bool valid = col_ok && y >= 0 && y < H;  // dv is zero outside the image
+    const float a[KK] = {up.l, up.c, up.r, mid.l, mid.c, mid.r, dn.l, dn.c, dn.r};
+    float s[KK];
+#pragma unroll
+    for (int t = 0; t < KK; ++t) s[t] = 0.0f;
+#pragma clang loop unroll(disable)
+    for (int cq = 0; cq < 4; ++cq) {
+      const float dd[4] = {q0.x, q0.y, q0.z, q0.w};
+      q0 = q1; q1 = q2; q2 = q3;  // the quads take turns in q0: no register array is indexed by the loop counter
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = cq * 4 + j;
+        const float mu = mean[c], g = gamma[c], bt = beta[c];
+        const float inv = tab(c), c1 = tab(16 + c), c2 = tab(32 + c), gi = tab(48 + c);  // gi = g * inv, the first product of conv0_march_kernel's dv
+        float cv = 0.0f;
+#pragma unroll
+        for (int t = 0; t < KK; ++t) cv = fmaf(a[t], w0[t * 16 + c], cv);  // conv0_kernel's chain, taps in (dy, dx) order
+        const float v = fmaf(cv, 1.0f, bias[c]);
+        const float xh = (v - mu) * inv;
+        const float de = (valid && fmaf(xh, g, bt) > 0.0f) ? dd[j] : 0.0f;  // bn0 is followed by a ReLU
+        const float gq = valid ? gi * (de - c1 - xh * c2) : 0.0f;
+#pragma unroll
+        for (int t = 0; t < KK; ++t) s[t] = fmaf(w0[t * 16 + c], gq, s[t]);
+      }
+    }
+    // dv at (y, x) reaches dx at (y + ty - 1, x + tx - 1) through tap (ty, tx): lane l takes tx = 0 from lane l + 1 and tx = 2 from lane l - 1
+    accA += lsh<3, 1>(s[0]) + s[1] + lsh<3, -1>(s[2]);
+    accB += lsh<3, 1>(s[3]) + s[4] + lsh<3, -1>(s[5]);
+    const float accC = lsh<3, 1>(s[6]) + s[7] + lsh<3, -1>(s[8]);
+    if (out_lane && y - 1 >= r_begin) dxb[(int64_t)(y - 1) * W + xcol] = accA;  // y <= r_end: row y - 1 is inside the segment
+    accA = accB;
+    accB = accC;
+    up = mid;
+    mid = dn;
+  }
+}
+
+// k = 5 / 7 (and k = 3 beyond the marching kernel's limits): the plain tile form.  8 x 32 output pixels per workgroup; the snippet halo (2R around the
+// tile) is staged in LDS, dv of all 16 channels is formed once per pixel of the tile + R and kept in LDS, a thread then gathers its k x k x 16 products.
+template <int KS>
+__global__ __launch_bounds__(256) void conv0_dx_tile_kernel(const float* __restrict__ in, int64_t snippet_stride, const float* __restrict__ dy, int H, int W, int WP,
+                                                             const float* __restrict__ w0 /*[KS*KS][16]*/, const float* __restrict__ bias, const float* __restrict__ mean,
+                                                             const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                             const double* __restrict__ sums, float inv_count, float* __restrict__ dx, int tx, int ty) {
+  constexpr int R = KS / 2, KK = KS * KS, TH = 8, TW = 32, DH = TH + 2 * R, DW = TW + 2 * R, IH = TH + 4 * R, IW = TW + 4 * R;
+  __shared__ float tin[IH][IW + 1];
+  __shared__ float tdv[16][DH][DW + 1];
+  __shared__ float wl[KK][16];
+  __shared__ float cst[8][16];  // bias | mean | inv | gamma | beta | dbeta / N | dgamma / N | gamma * inv
+  const int tile = blockIdx.x;
+  const int b = tile / (tx * ty), rem = tile - b * (tx * ty);
+  const int y0 = (rem / tx) * TH, x0 = (rem - (rem / tx) * tx) * TW;
+  const int plane = (H + 2 * R) * WP;
+  const float* src = in + (int64_t)b * snippet_stride;
+  const float4* dp = reinterpret_cast<const float4*>(dy) + (int64_t)b * 4 * plane;
+  if (threadIdx.x < 16) {
+    const int c = threadIdx.x;
+    const float inv = rsqrtf(var[c] + eps), g = gamma[c];
+    cst[0][c] = bias[c]; cst[1][c] = mean[c]; cst[2][c] = inv; cst[3][c] = g; cst[4][c] = beta[c];
+    cst[5][c] = (float)sums[c] * inv_count; cst[6][c] = (float)sums[16 + c] * inv_count; cst[7][c] = g * inv;
+  }
+  for (int i = threadIdx.x; i < KK * 16; i += 256) wl[i / 16][i % 16] = w0[i];
+  for (int i = threadIdx.x; i < IH * IW; i += 256) {
+    const int r = i / IW, c = i - r * IW;
+    const int yy = y0 + r - 2 * R, xx = x0 + c - 2 * R;
+    tin[r][c] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? src[(int64_t)yy * W + xx] : 0.0f;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < DH * DW; i += 256) {
+    const int r = i / DW, cl = i - r * DW;
+    const int yy = y0 + r - R, xx = x0 + cl - R;
+    const bool valid = yy >= 0 && yy < H && xx >= 0 && xx < W;  // dv is zero outside the image
+    float a[KK];
+#pragma unroll
+    for (int dyy = 0; dyy < KS; ++dyy)
+#pragma unroll
+      for (int dxx = 0; dxx < KS; ++dxx) a[dyy * KS + dxx] = tin[r + dyy][cl + dxx];
+    for (int cq = 0; cq < 4; ++cq) {
+      const float4 d4 = valid ? dp[(int64_t)cq * plane + (yy + R) * WP + xx] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = cq * 4 + j;
+        float cv = 0.0f;
+#pragma unroll
+        for (int t = 0; t < KK; ++t) cv = fmaf(a[t], wl[t][c], cv);  // conv0_kernel's chain, taps in (dy, dx) order
+        const float v = fmaf(cv, 1.0f, cst[0][c]);
+        const float xh = (v - cst[1][c]) * cst[2][c];
+        const float de = (valid && fmaf(xh, cst[3][c], cst[4][c]) > 0.0f) ? dd[j] : 0.0f;
+        tdv[c][r][cl] = valid ? cst[7][c] * (de - cst[5][c] - xh * cst[6][c]) : 0.0f;
+      }
+    }
+  }
+  __syncthreads();
+  const int py = threadIdx.x / TW, px = threadIdx.x % TW;
+  const int y = y0 + py, x = x0 + px;
+  if (y < H && x < W) {
+    float acc = 0.0f;
+    for (int dyy = 0; dyy < KS; ++dyy)
+      for (int dxx = 0; dxx < KS; ++dxx)
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc = fmaf(wl[dyy * KS + dxx][c], tdv[c][py + 2 * R - dyy][px + 2 * R - dxx], acc);
+    dx[(int64_t)b * H * W + (int64_t)y * W + x] = acc;
+  }
+}
+
 // ---------------------------------------------------------------- kernel-layout copies of the trunk weights, one launch per step
 // desc[i] = {type, src offset, dst offset, C, aux}: type 0 = Keras depthwise (k,k,C,1) -> [ceil(C/4)][k*k][4] (aux = k*k; zero taps for
 // the padding channels), type 1 = the same with the taps reversed (input-gradient conv), type 2 = pointwise (1,1,Cin,Cout) ->
@@ -2264,6 +2455,44 @@ int orcai_conv0_bn_bwd_x(const float* in, int64_t snippet_stride, const float* d
 #undef ORCAI_C0X
   hipLaunchKernelGGL(add_partials_kernel, dim3(blocks_for(KK * 16), 8), dim3(256), 0, st, workspace, gx, KK * 16, dW);
   hipLaunchKernelGGL(f64_to_f32_pair_kernel, dim3(1), dim3(64), 0, st, db, dbeta, dg, dgamma, C);
+  return (int)hipGetLastError();
+}
+
+int orcai_conv0_bn_bwd_dx(const float* in, int64_t snippet_stride, const float* dy, int B, int H, int W, int ksize, const float* w0, const float* bias, const float* mean,
+                          const float* var, const float* gamma, const float* beta, float eps, const double* sums2C, float* dx, void* stream) {
+  if (!in || !dy || !w0 || !bias || !mean || !var || !gamma || !beta || !sums2C || !dx || B <= 0 || H <= 0 || W <= 0) return ORCAI_E_BADARG;
+  if (ksize != 3 && ksize != 5 && ksize != 7) return ORCAI_E_BADARG;
+  if ((uintptr_t)dy & 15) return ORCAI_E_BADARG;
+  const int R = ksize / 2, WP = orcai_padded_width(W, ksize);
+  const int64_t plane = (int64_t)(H + 2 * R) * WP;
+  const int64_t ntiles = (int64_t)((W + 31) / 32) * ((H + 7) / 8) * B;
+  if ((int64_t)H * W >= (1ll << 30) || plane >= (1ll << 27) || ntiles >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const float inv_count = (float)(1.0 / ((double)B * H * W));
+  if (ksize == 3 && B <= 65535) {
+    // segments of rows: enough waves to fill the device (each segment forms two dv rows beyond its own, so not shorter than 16 rows)
+    const int nstrip = (W + 61) / 62;
+    const int64_t cols = (int64_t)B * nstrip;
+    int nseg = (int)((8192 + cols - 1) / cols);
+    if (nseg > (H + 15) / 16) nseg = (H + 15) / 16;
+    if (nseg < 1) nseg = 1;
+    const int rps = (H + nseg - 1) / nseg;
+    nseg = (H + rps - 1) / rps;
+    dim3 grid((nstrip * nseg + 3) / 4, 1, B);
+    hipLaunchKernelGGL(conv0_dx_march_kernel, grid, dim3(256), 0, st, in, snippet_stride, dy, H, W, WP, w0, bias, mean, var, gamma, beta, eps, sums2C, inv_count, dx, nstrip, nseg,
+                       rps);
+    return (int)hipGetLastError();
+  }
+  const int tx = (W + 31) / 32, ty = (H + 7) / 8;
+#define ORCAI_C0DX(KS_)                                                                                                                                          \
+  hipLaunchKernelGGL(conv0_dx_tile_kernel<KS_>, dim3((unsigned)ntiles), dim3(256), 0, st, in, snippet_stride, dy, H, W, WP, w0, bias, mean, var, gamma, beta, eps, sums2C, \
+                     inv_count, dx, tx, ty)
+  switch (ksize) {
+    case 3: ORCAI_C0DX(3); break;
+    case 5: ORCAI_C0DX(5); break;
+    default: ORCAI_C0DX(7); break;
+  }
+#undef ORCAI_C0DX
   return (int)hipGetLastError();
 }
 

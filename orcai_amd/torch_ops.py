@@ -1,10 +1,11 @@
 """PyTorch custom ops in the ``orcai`` namespace: the front end, the model's forward (inference and training mode, with autograd w.r.t.
-the weights) and the whole-recording predict, so that the HIP path composes with a caller's own loss, ``torch.optim`` and
-``torch.compile``.  Every op calls the library through its C ABI only (orcai_amd/_native.py); each has a fake implementation, so shapes are
+the weights and, through ``forward_wrt_input``, the input) and the whole-recording predict, so that the HIP path composes with a caller's
+own loss, ``torch.optim`` and ``torch.compile``.  Every op calls the library through its C ABI only (orcai_amd/_native.py); each has a fake implementation, so shapes are
 known without a GPU.
 
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
+    torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
 
 ``weights`` / ``stats`` are the trainable variables and the BatchNorm moving statistics in ``variable_spec()`` order (Keras layouts);
@@ -12,7 +13,12 @@ known without a GPU.
 
 Training mode keeps the activations of its forward for the backward (``Trainer.forward_train`` / ``backward_from_probs``): per config and
 device ONE step is open at a time, from the forward to its backward.  A second training forward while the autograd graph of the first is
-still alive raises instead of overwriting what that graph's backward needs.  f32 models only; no gradient w.r.t. the input.
+still alive raises instead of overwriting what that graph's backward needs (``forward`` and ``forward_wrt_input`` share that step).
+
+``forward`` differentiates w.r.t. the weights only and refuses an ``x`` that requires grad; ``forward_wrt_input`` is the same computation
+whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
+detector.  What does not exist: an input gradient in eval mode (there is no eval-mode backward at all), on the f16 path (f32 models
+only), or through ``orcai::spectrogram`` (the front end has no backward).
 """
 
 from __future__ import annotations
@@ -167,13 +173,21 @@ class _Engine:
             s.copy_(P.stats[n].view(s.shape))
         return probs
 
-    def backward(self, grad: Tensor, probs: Tensor) -> Tensor:
+    def backward(self, grad: Tensor, probs: Tensor, want_dx: bool = False):
+        """The flat weight gradient of the open step; with want_dx also dL/dx f32[B, H, W] (one more launch: orcai_conv0_bn_bwd_dx)."""
         tr = self._trainer
         if tr is None or tr._pending is None:
             raise RuntimeError("orcai::forward backward: no training forward of this model is waiting for its backward (a backward runs once per forward)")
         self.token = None
-        tr.backward_from_probs(grad.contiguous(), probs)
-        return tr.P.g.clone()
+        if not want_dx:
+            tr.backward_from_probs(grad.contiguous(), probs)
+            return tr.P.g.clone()
+        H, W = self.model.input_hw
+        dx = torch.empty((int(tr._pending.shape[0]), H, W), dtype=torch.float32, device=grad.device)
+        if probs.data_ptr() != tr._pending.data_ptr() and probs.shape == tr._pending.shape and torch.equal(probs, tr._pending):
+            probs = tr._pending  # a copy of the open step's probabilities (torch.library.opcheck clones the arguments) names the same step
+        tr.backward_from_probs(grad.contiguous(), probs, dx=dx)
+        return tr.P.g.clone(), dx
 
 
 _ENGINES: dict = {}
@@ -312,6 +326,78 @@ def _forward_autograd(x, weights, stats, config, training, dropout_seed):
 _LIB.impl("forward", _forward_autograd, "Autograd")
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::forward_wrt_input
+# orcai::forward with the gradient w.r.t. the snippets as well: for something trainable or differentiable IN FRONT of the detector (a learnable
+# gain / equaliser / denoiser on the spectrogram, differentiable augmentation, adversarial or gradient-penalty training, saliency of a training
+# loss).  Its own op, because orcai::forward's refusal of x.requires_grad is part of that op's contract; the CUDA / CPU / fake implementations
+# are orcai::forward's, and both share the per-(config, device) engine and its one open step.  Training mode only: the eval-mode forward
+# (moving statistics) has no backward at all.
+_LIB.define("forward_wrt_input(Tensor x, Tensor[] weights, Tensor(a!)[] stats, str config, bool training, SymInt dropout_seed) -> Tensor")
+
+
+def forward_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, training: bool, dropout_seed: int) -> Tensor:
+    """orcai::forward whose training-mode backward also returns dL/dx (f32 [B, H, W]) when x requires grad."""
+    return torch.ops.orcai.forward_wrt_input(x, weights, stats, config, training, dropout_seed)
+
+
+_LIB.impl("forward_wrt_input", _forward_impl, "CUDA")
+_LIB.impl("forward_wrt_input", _forward_impl, "CPU")  # (refuses: the checks name the missing GPU)
+torch.library.register_fake("orcai::forward_wrt_input", _forward_fake, lib=_LIB)
+
+
+@torch.library.custom_op("orcai::forward_wrt_input_backward", mutates_args=())
+def forward_wrt_input_backward(grad: Tensor, probs: Tensor, config: str) -> tuple[Tensor, Tensor]:
+    """The backward of the open training forward of `config` from dL/dprobs: the flat weight gradient (as orcai::forward_backward) and the
+    gradient w.r.t. the snippets, f32 [B, H, W] (orcai_conv0_bn_bwd_dx behind the entry conv's weight gradient)."""
+    with torch.cuda.device(grad.device):
+        return _engine(config, grad.device).backward(grad, probs, want_dx=True)
+
+
+@forward_wrt_input_backward.register_fake
+def _forward_wrt_input_backward_fake(grad, probs, config):
+    H, W = (int(v) for v in _parse(config)["input_shape"][:2])
+    flat = grad.new_empty((sum(math.prod(s) for s in _spec_split(config)[0]),), dtype=torch.float32)
+    return flat, grad.new_empty((probs.shape[0], H, W), dtype=torch.float32)
+
+
+class _ForwardWrtInputFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, stats, config, training, dropout_seed, *weights):
+        with torch._C._AutoDispatchBelowAutograd():
+            out = torch.ops.orcai.forward_wrt_input(x, list(weights), stats, config, training, dropout_seed)
+        ctx.training, ctx.config = bool(training), config
+        ctx.shapes = [tuple(w.shape) for w in weights]
+        ctx.save_for_backward(out)
+        if training and not torch._subclasses.fake_tensor.is_fake(out):
+            ctx.token = _GraphToken()
+            eng = _ENGINES.get(_key(config, out.device))
+            if eng is not None:
+                eng.token = weakref.ref(ctx.token)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        if not ctx.training:
+            raise RuntimeError("orcai::forward_wrt_input(training=False) has no backward (BatchNorm with moving statistics): the gradient w.r.t. the "
+                               "input, too, needs the forward with training=True")
+        (probs,) = ctx.saved_tensors
+        flat, dx = torch.ops.orcai.forward_wrt_input_backward(grad, probs, ctx.config)
+        sizes = [math.prod(s) for s in ctx.shapes]
+        need = ctx.needs_input_grad
+        wgrads = [t.view(s) if n else None for t, s, n in zip(torch.split(flat, sizes), ctx.shapes, need[5:])]
+        return (dx if need[0] else None, None, None, None, None, *wgrads)
+
+
+def _forward_wrt_input_autograd(x, weights, stats, config, training, dropout_seed):
+    if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
+        return _ForwardWrtInputFunction.apply(x, stats, config, training, dropout_seed, *weights)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.forward_wrt_input(x, weights, stats, config, training, dropout_seed)
+
+
+_LIB.impl("forward_wrt_input", _forward_wrt_input_autograd, "Autograd")
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
 @torch.library.custom_op("orcai::predict_spectrogram", mutates_args=())
 def predict_spectrogram(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
@@ -340,10 +426,11 @@ def param_name(keras_name: str) -> str:
 class OrcaiModule(torch.nn.Module):
     """A ResNetLSTM / ResNet1DConv as a torch.nn.Module: the trainable variables are parameters, the BatchNorm moving statistics buffers,
     both named after the Keras variables (param_name).  forward(x f32[B, H, W]) follows self.training; gradients reach the parameters
-    only.  Built from a model object or a model directory (io.load_orcai_model).  dropout_seed of the n-th training forward:
-    seed * 1000003 + n."""
+    only, and an x that requires grad raises -- unless input_grad=True: the module then calls orcai::forward_wrt_input, whose training-mode
+    backward also returns dL/dx (not in eval mode, not for f16 models).  Built from a model object or a model directory
+    (io.load_orcai_model).  dropout_seed of the n-th training forward: seed * 1000003 + n."""
 
-    def __init__(self, model, seed: int = 0):
+    def __init__(self, model, seed: int = 0, input_grad: bool = False):
         super().__init__()
         if isinstance(model, (str, os.PathLike)):
             from orcai_amd.io import load_orcai_model
@@ -361,6 +448,7 @@ class OrcaiModule(torch.nn.Module):
                 self.register_buffer(param_name(name), t)
                 self._stats.append(name)
         self.seed = int(seed)
+        self.input_grad = bool(input_grad)
         self.dropout_draws = 0
 
     def weights_list(self) -> list:
@@ -374,7 +462,8 @@ class OrcaiModule(torch.nn.Module):
         if self.training:
             seed = (self.seed * 1000003 + self.dropout_draws) & 0x7FFFFFFFFFFFFFFF
             self.dropout_draws += 1
-        return torch.ops.orcai.forward(x, self.weights_list(), self.stats_list(), self.config, self.training, seed)
+        op = torch.ops.orcai.forward_wrt_input if self.input_grad else torch.ops.orcai.forward
+        return op(x, self.weights_list(), self.stats_list(), self.config, self.training, seed)
 
     def predict_spectrogram(self, spec: Tensor) -> Tensor:
         return torch.ops.orcai.predict_spectrogram(spec, self.weights_list(), self.stats_list(), self.config)

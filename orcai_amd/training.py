@@ -870,9 +870,25 @@ class TrunkTrainer:
             N.check(self._fn("dw_wgrad")(x.data_ptr(), du.data_ptr(), self.B, Cin, H, W, k, k, relu_in, P.G(name + "/depthwise").data_ptr(), st), "dw_wgrad")
         return epi_ran
 
-    def backward(self, dfeatv: torch.Tensor) -> None:
-        """dfeatv: gradient w.r.t. the pre-BN output of the final separable conv, Keras Reshape layout [B][T][W*36]."""
+    def check_dx(self, dx, B: int, who: str) -> None:
+        """dx of backward(): a contiguous f32 tensor [B, H, W] on the trainer's device (ValueError before anything is launched); the f16 path has
+        no input gradient."""
+        if dx is None:
+            return
+        if self.half:
+            raise NotImplementedError(f"{who}: the f16 path computes no gradient w.r.t. the input (precision 'f16')")
+        H, W = self.model.input_hw
+        if not isinstance(dx, torch.Tensor):
+            raise ValueError(f"{who}: dx must be a contiguous f32 tensor of shape {(B, H, W)} on {self.dev}, got {type(dx).__name__}")
+        if dx.dtype != torch.float32 or dx.device != self.dev or tuple(dx.shape) != (B, H, W) or not dx.is_contiguous():
+            raise ValueError(f"{who}: dx must be a contiguous f32 tensor of shape {(B, H, W)} on {self.dev}, got {dx.dtype} {tuple(dx.shape)} on {dx.device}"
+                             + ("" if dx.is_contiguous() else " (not contiguous)"))
+
+    def backward(self, dfeatv: torch.Tensor, dx: torch.Tensor | None = None) -> None:
+        """dfeatv: gradient w.r.t. the pre-BN output of the final separable conv, Keras Reshape layout [B][T][W*36].  dx (optional, f32 [B][H][W]):
+        receives the gradient w.r.t. the snippets (one more launch, orcai_conv0_bn_bwd_dx; nothing else changes)."""
         lib, P, m, b, st, k, B = self.lib, self.P, self.model, self.buf, N.stream_ptr(), self.k, self.B
+        self.check_dx(dx, B, "TrunkTrainer.backward")
         shapes = m.stage_shapes()
         L = len(m.filters)
         h, w, c = shapes[-1]
@@ -942,6 +958,13 @@ class TrunkTrainer:
                                              mean0.data_ptr(), var0.data_ptr(), P.W("bn0/gamma").data_ptr(), P.W("bn0/beta").data_ptr(), BN_EPS, self.scratch.data_ptr(),
                                              P.G("bn0/beta").data_ptr(), P.G("bn0/gamma").data_ptr(), P.G("conv0/kernel").data_ptr(), self.partials.data_ptr(), self.partials.numel(),
                                              st), "conv0_bn_bwd_x")
+            if dx is not None:
+                # the input gradient: dv0 formed once more from (snippet, dr1, bn0's batch statistics) and the sums both entry points above leave in
+                # self.scratch (dbeta | dgamma), contracted with the taps.  Block Dropout (ResNet1DConv) does not touch this: no Dropout sits in front
+                # of block 1 (see _conv0_dgrad_ok), so dr1 is the gradient w.r.t. the un-dropped y0 whichever architecture runs
+                N.check(lib.orcai_conv0_bn_bwd_dx(self.src.data_ptr(), self.snippet_stride, dprev.data_ptr(), B, H, W, k, P.W("conv0/kernel").data_ptr(), P.W("conv0/bias").data_ptr(),
+                                                  mean0.data_ptr(), var0.data_ptr(), P.W("bn0/gamma").data_ptr(), P.W("bn0/beta").data_ptr(), BN_EPS, self.scratch.data_ptr(),
+                                                  dx.data_ptr(), st), "orcai_conv0_bn_bwd_dx")
         # conv0/bias feeds bn0: zero gradient (see _sep_backward)
 
 
@@ -1049,17 +1072,19 @@ class Trainer:
         return masks
 
     def forward_backward(self, src: torch.Tensor, snippet_stride: int, B: int, labels: torch.Tensor, masks: dict | None = "auto",
-                         loss_weight: torch.Tensor | None = None) -> dict:
-        """Gradients of (masked BCE + L2) into the flat gradient buffer.  Returns device accumulators {bce sum, count, correct, l2}."""
+                         loss_weight: torch.Tensor | None = None, dx: torch.Tensor | None = None) -> dict:
+        """Gradients of (masked BCE + L2) into the flat gradient buffer.  Returns device accumulators {bce sum, count, correct, l2}.  dx (optional,
+        contiguous f32 [B][H][W]): receives the loss gradient w.r.t. the snippets (f32 path only)."""
         if self._pending is not None:
             raise RuntimeError("Trainer.forward_backward: a forward_train step is still waiting for its backward_from_probs (its activations would be overwritten)")
+        self.trunk.check_dx(dx, B, "Trainer.forward_backward")
         masks = self._open_step(B, masks)
         self.trunk.begin_step()  # one clear for every reduction scratch of the step
         try:
             featv = self.trunk.forward(src, snippet_stride, B)
             probs = self.head.forward(featv, masks, self.model.dropout_rate)
             out = self.head.loss_and_backward(labels, loss_weight)
-            self.trunk.backward(out["dfeatv"])
+            self.trunk.backward(out["dfeatv"], dx=dx)
         finally:
             self.trunk.end_step()
         return {"acc": out["acc"], "probs": probs}
@@ -1085,10 +1110,10 @@ class Trainer:
         self._pending = probs
         return probs
 
-    def backward_from_probs(self, dprobs: torch.Tensor, probs: torch.Tensor | None = None) -> None:
+    def backward_from_probs(self, dprobs: torch.Tensor, probs: torch.Tensor | None = None, dx: torch.Tensor | None = None) -> None:
         """Backward of the open forward_train step from an external dL/dprobs (same shape as the probabilities): the gradient at the logits is
         orcai_sigmoid_bwd, then the head's and the trunk's backward without the L2 term.  Fills P.g and closes the step.  probs: the tensor that
-        forward_train returned, checked to be the open step's."""
+        forward_train returned, checked to be the open step's.  dx (optional, contiguous f32 [B][H][W]): receives dL/d(snippets)."""
         pend = self._pending
         if pend is None:
             raise RuntimeError("Trainer.backward_from_probs: no training forward is waiting for its backward")
@@ -1096,12 +1121,13 @@ class Trainer:
             raise RuntimeError("Trainer.backward_from_probs: these probabilities are not those of the open training forward (a later forward replaced it)")
         if tuple(dprobs.shape) != tuple(pend.shape) or dprobs.dtype != torch.float32 or dprobs.device != pend.device:
             raise ValueError(f"Trainer.backward_from_probs: expected f32 {tuple(pend.shape)} on {pend.device}, got {dprobs.dtype} {tuple(dprobs.shape)} on {dprobs.device}")
+        self.trunk.check_dx(dx, int(pend.shape[0]), "Trainer.backward_from_probs")
         try:
             g = dprobs.contiguous()
             dz = torch.empty_like(pend)
             N.check(N.lib().orcai_sigmoid_bwd(pend.data_ptr(), g.data_ptr(), pend.numel(), dz.data_ptr(), N.stream_ptr()), "orcai_sigmoid_bwd")
             out = self.head.backward_from_dz(dz.view(-1, self.model.num_labels), l2=False)
-            self.trunk.backward(out["dfeatv"])
+            self.trunk.backward(out["dfeatv"], dx=dx)
         finally:
             self.abandon_forward()
 
