@@ -110,6 +110,32 @@ int orcai_frontend_stats_host(const void* workspace, float stats_host[6], void* 
 int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop,
                            int64_t rank_lo, int64_t rank_hi, float top_db, float* out, void* workspace, void* stream);
 
+/* The statistics of the front-end run that just finished on `stream`, {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} as
+ * orcai_frontend_stats_host returns them, copied by a one-thread launch into the caller's device buffer f32[6]: no host
+ * synchronisation (capturable).  The workspace is overwritten by the next recording, the copy is the caller's to keep -- it is what
+ * orcai_spectrogram_bwd reads, so the backward never reruns the selection. */
+int orcai_frontend_stats_dev(const void* workspace, float* stats_dev, void* stream);
+
+/* Gradient of orcai_make_spectrogram w.r.t. the audio (the reference has no counterpart: spectrogram.py:90-147 is numpy / librosa and is
+ * never differentiated).  With out = (clip(v, p_lo, p_hi) - p_lo) / (p_hi - p_lo), v = max(db - ref_db, -top_db),
+ * db = 10 log10(max(P, 1e-10)), P = Re^2 + Im^2 of the centred, zero-padded, Hann-windowed STFT, and g = dL/dout:
+ *   g_db    = g / (p_hi - p_lo)  where P > 1e-10, db - ref_db > -top_db and p_lo < v < p_hi (all strict); 0 otherwise
+ *   dP      = g_db * 10 / (ln 10 * P);  dRe[k] = 2 Re[k] dP, dIm[k] = 2 Im[k] dP for k < k_crop, 0 for the bins above
+ *   dframe_t[n] = w[n] * sum_k (dRe[k] cos(2 pi k n / N) - dIm[k] sin(2 pi k n / N)),  N = n_fft
+ *   dpcm[s] = sum over the frames t that cover s of dframe_t[s - t * hop + N/2]   (positions in the zero padding receive nothing)
+ * The three global statistics ref_db, p_lo, p_hi are HELD CONSTANT: mathematically they depend on the data, but only through single STFT
+ * bins (the maximum-power bin, the two order-statistic bins), and that dependence is ill-defined under ties.
+ *   pcm, n_samples, n_fft, hop, n_frames, k_crop   as for orcai_stft_db (the forward's arguments; Re / Im are recomputed, the forward stores dB only)
+ *   gout       f32[n_frames * k_crop], layout [frame][bin]
+ *   stats_dev  f32[6] from orcai_frontend_stats_dev after the forward of the same pcm (ref_db, p_lo, p_hi are read on the device)
+ *   dpcm       f32[n_samples]: every element is WRITTEN (nothing accumulated, no need to clear it); summed without float atomics in a
+ *              fixed order, so two launches give identical bits
+ * n_fft: powers of two from 32 to 4096 (512 included); every other size is ORCAI_E_UNSUPPORTED (the forward keeps running them).  hop is
+ * arbitrary (it need not divide n_fft).  ORCAI_E_BADARG: null pointer, non-positive size, k_crop outside 1..1 + n_fft/2, n_frames other than
+ * librosa's 1 + n_samples / hop. */
+int orcai_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout,
+                          const float* stats_dev, float top_db, float* dpcm, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Model forward, inference (architectures.py:162-241 as executed by model.predict, predict.py:265-268)

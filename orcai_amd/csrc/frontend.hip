@@ -10,6 +10,7 @@
 //   pass C  hist2_kernel        re-read L, histogram the keys inside the two intervals (<= 2 rounds)
 //   scan2   select_scan2_kernel interval -> exact key
 //   final   clip_normalize      in place: max(L - ref_db, -80) -> clip -> (v - lo)/(hi - lo)     (HBM: R L, W out)
+//   backward spectrogram_bwd     dL/dout -> dL/dpcm with ref_db / lo / hi held constant (orcai_spectrogram_bwd)   (HBM: R pcm, R g, W dpcm)
 //
 // The order statistic is selected on the un-referenced values L: v = max(L - ref_db, -80) is monotone
 // non-decreasing in L, so the k-th smallest v is that function of the k-th smallest L (exact).
@@ -727,6 +728,126 @@ __global__ __launch_bounds__(256) void crop_transpose_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------- backward of the spectrogram w.r.t. the audio (orcai_spectrogram_bwd; definition in
+// include/orcai_hip.h).  A GROUP of NT threads -- a wavefront for n_fft <= 512, the whole workgroup above -- owns a run of `run` consecutive output
+// samples and walks over every frame that touches it, in frame order: the windowed frame goes through a radix-2 decimation-in-frequency transform in
+// LDS (natural order in, X[k] at the bit-reversed position out), the complex gradient G[k] = (dRe, dIm) replaces X[k] where it stands (zero for
+// k > n_fft/2 and k >= k_crop), a decimation-in-time transform with conjugated twiddles takes the bit-reversed positions back to natural order -- the
+// real part of sum_k G[k] exp(+2 pi i k n / N) is the Hermitian-to-real inverse of the half spectrum -- and w[n] * Re lands in the group's LDS
+// accumulator.  One thread owns one n per frame and frames follow each other behind a group barrier, so every output sample is summed in frame
+// order by plain adds: no float atomics, identical bits on every launch.  Frames that straddle two runs are transformed by both groups (the halo:
+// (run + n_fft) / run of the transforms, 1.25 for 512 / 2048); nothing but pcm, g and the three statistics is read and nothing but dpcm written.
+template <int NT>
+__device__ __forceinline__ void group_sync() {
+  if constexpr (NT == 64) wave_lds_fence();
+  else __syncthreads();
+}
+
+constexpr float DB_GRAD = 4.3429448190325183f;  // 10 / ln 10
+
+template <int NT>
+__global__ __launch_bounds__(256) void spectrogram_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                               int k_crop, const float* __restrict__ gout, const float* __restrict__ stats, float top_db,
+                                                               float* __restrict__ dpcm, int run, int64_t n_runs) {
+  extern __shared__ float4 bwd_lds[];  // tw[n_fft/2] | per group: buf[n_fft] complex | per group: acc[run]
+  constexpr int GROUPS = 256 / NT;
+  const int half = n_fft >> 1;
+  float2* tw = reinterpret_cast<float2*>(bwd_lds);
+  const int grp = threadIdx.x / NT, gid = threadIdx.x % NT;
+  float2* buf = tw + half + grp * n_fft;
+  float* acc = reinterpret_cast<float*>(tw + half + GROUPS * n_fft) + grp * run;
+  for (int j = threadIdx.x; j < half; j += 256) {  // exp(-2 pi i j / n_fft)
+    float sn, cs;
+    sincospif(-2.0f * (float)j / (float)n_fft, &sn, &cs);
+    tw[j] = make_float2(cs, sn);
+  }
+  __syncthreads();
+  const float ref_db = stats[1], p_lo = stats[2], p_hi = stats[3];
+  const float range = p_hi - p_lo;
+  auto window = [&](int n) { return 0.5f - 0.5f * (n < half ? tw[n].x : -tw[n - half].x); };  // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
+
+  for (int64_t r = (int64_t)blockIdx.x * GROUPS + grp; r < n_runs; r += (int64_t)gridDim.x * GROUPS) {  // (NT == 256: uniform over the workgroup)
+    const int64_t s0 = r * run;
+    const int len = (int)(n_samples - s0 < run ? n_samples - s0 : run);
+    for (int i = gid; i < len; i += NT) acc[i] = 0.0f;
+    // frames with [t hop - N/2, t hop + N/2) meeting [s0, s0 + len)
+    const int64_t t_lo = s0 - half < 0 ? 0 : (s0 - half) / hop + 1;
+    int64_t t_hi = (s0 + len + half - 1) / hop;
+    if (t_hi > n_frames - 1) t_hi = n_frames - 1;
+    for (int64_t t = t_lo; t <= t_hi; ++t) {
+      const int64_t base = t * hop - half;
+      for (int n = gid; n < n_fft; n += NT) {
+        const int64_t i = base + n;
+        const float x = (i >= 0 && i < n_samples) ? pcm[i] : 0.0f;
+        buf[n] = make_float2(x * window(n), 0.0f);
+      }
+      group_sync<NT>();
+      for (int st = log2n; st >= 1; --st) {  // forward, decimation in frequency
+        const int hm = 1 << (st - 1);
+        for (int j = gid; j < half; j += NT) {
+          const int k = j & (hm - 1);
+          const int i0 = ((j >> (st - 1)) << st) + k, i1 = i0 + hm;
+          const float2 w = tw[k << (log2n - st)];
+          const float2 a = buf[i0], b = buf[i1];
+          const float2 d = make_float2(a.x - b.x, a.y - b.y);
+          buf[i0] = make_float2(a.x + b.x, a.y + b.y);
+          buf[i1] = make_float2(fmaf(d.x, w.x, -d.y * w.y), fmaf(d.x, w.y, d.y * w.x));
+        }
+        group_sync<NT>();
+      }
+      const float* g = gout + t * (int64_t)k_crop;
+      for (int p = gid; p < n_fft; p += NT) {  // X[k] -> G[k] where it stands
+        const int k = (int)(__brev((uint32_t)p) >> (32 - log2n));
+        float2 G = make_float2(0.0f, 0.0f);
+        if (k < k_crop) {  // k_crop <= 1 + n_fft / 2
+          const float2 z = buf[p];
+          const float P = fmaf(z.x, z.x, z.y * z.y);
+          if (P > AMIN_POW) {
+            const float v = power_to_db(P) - ref_db;
+            if (v > -top_db && v > p_lo && v < p_hi) {
+              const float dP = (g[k] / range) * DB_GRAD / P;
+              G = make_float2(2.0f * z.x * dP, 2.0f * z.y * dP);
+            }
+          }
+        }
+        buf[p] = G;
+      }
+      group_sync<NT>();
+      for (int st = 1; st <= log2n; ++st) {  // inverse (unnormalised), decimation in time
+        const int hm = 1 << (st - 1);
+        for (int j = gid; j < half; j += NT) {
+          const int k = j & (hm - 1);
+          const int i0 = ((j >> (st - 1)) << st) + k, i1 = i0 + hm;
+          const float2 w = tw[k << (log2n - st)];  // conjugated below
+          const float2 a = buf[i0], b = buf[i1];
+          const float2 tb = make_float2(fmaf(b.x, w.x, b.y * w.y), fmaf(b.y, w.x, -b.x * w.y));
+          buf[i0] = make_float2(a.x + tb.x, a.y + tb.y);
+          buf[i1] = make_float2(a.x - tb.x, a.y - tb.y);
+        }
+        group_sync<NT>();
+      }
+      for (int n = gid; n < n_fft; n += NT) {  // overlap-add: one thread per n, frames in order
+        const int64_t q = base + n - s0;
+        if (q >= 0 && q < len) acc[q] += window(n) * buf[n].x;
+      }
+      group_sync<NT>();
+    }
+    group_sync<NT>();
+    for (int i = gid; i < len; i += NT) dpcm[s0 + i] = acc[i];
+    group_sync<NT>();
+  }
+}
+
+__global__ void stats_dev_kernel(const Workspace* __restrict__ ws, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  out[0] = __uint_as_float(ws->pmax_bits);
+  out[1] = ws->ref_db;
+  out[2] = ws->p_lo;
+  out[3] = ws->p_hi;
+  out[4] = ws->sel_raw[0];
+  out[5] = ws->sel_raw[1];
+}
+
 std::once_flag g_tables_once;
 int g_tables_err = 0;
 
@@ -925,6 +1046,38 @@ int orcai_frontend_stats_host(const void* workspace, float stats_host[6], void* 
   }
   delete h;
   return (int)e;
+}
+
+int orcai_frontend_stats_dev(const void* workspace, float* stats_dev, void* stream) {
+  if (!workspace || !stats_dev) return ORCAI_E_BADARG;
+  hipLaunchKernelGGL(stats_dev_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const Workspace*)workspace, stats_dev);
+  return (int)hipGetLastError();
+}
+
+int orcai_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout, const float* stats_dev,
+                          float top_db, float* dpcm, void* stream) {
+  if (!pcm || !gout || !stats_dev || !dpcm || n_samples <= 0 || hop <= 0 || n_frames <= 0 || k_crop < 1 || n_fft < 2) return ORCAI_E_BADARG;
+  if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // powers of two from 32 to 4096 only
+  if (k_crop > 1 + n_fft / 2 || n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;         // librosa's centred frame count (n_fft is even)
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  // Run of output samples per group: 2048 for the wave-per-run kernel (LDS 2 KiB twiddles + 4 x (4 + 8) KiB at 512: three workgroups per compute unit),
+  // 4 n_fft for the workgroup-per-run kernel, n_fft at 4096 (twiddles + frame + accumulator = 64 KiB, the most a launch gets without opting in).
+  const bool wave = n_fft <= 512;
+  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  const int groups = wave ? 4 : 1;
+  const int64_t n_runs = (n_samples + run - 1) / run;
+  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run);
+  if (lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: 64 KiB at n_fft = 4096 is the largest request)
+  int64_t blocks = (n_runs + groups - 1) / groups;
+  if (blocks > 256 * 12) blocks = 256 * 12;
+  if (wave)
+    hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop,
+                       gout, stats_dev, top_db, dpcm, run, n_runs);
+  else
+    hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop,
+                       gout, stats_dev, top_db, dpcm, run, n_runs);
+  return (int)hipGetLastError();
 }
 
 int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, int64_t rank_lo,

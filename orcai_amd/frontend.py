@@ -62,9 +62,11 @@ class FrontEnd:
                                       "need the reference's CPU path")
 
     # -- the whole of make_spectrogram after decode (spectrogram.py:90-147) -----------------
-    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
+    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False):
         """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
-        Returns f32[T, K] on the device, values in [0, 1]."""
+        Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
+        sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which spectrogram_backward needs -- the
+        workspace itself is overwritten by the next recording."""
         n_fft = int(spectrogram_parameter["nfft"])
         hop = int(spectrogram_parameter["n_overlap"])
         self._check_nfft(n_fft)
@@ -84,7 +86,50 @@ class FrontEnd:
             self.lib.orcai_make_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()),
             "orcai_make_spectrogram",
         )
+        if return_stats:
+            stats = torch.empty(6, dtype=torch.float32, device=self.device)
+            N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
+            return out, stats
         return out
+
+    # -- the gradient of make_spectrogram w.r.t. the audio (orcai_spectrogram_bwd; the statistics are held constant) -----------------
+    @staticmethod
+    def _check_nfft_backward(n_fft: int) -> None:
+        n = int(n_fft)
+        if n < 32 or n > 4096 or n & (n - 1):
+            raise NotImplementedError(f"spectrogram parameter nfft = {n_fft}: the gradient w.r.t. the audio is implemented for powers of two from 32 to "
+                                      "4096 (512, the value of orcai-V1, included); the forward runs every size from 2 to 4096")
+
+    def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
+        """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
+        returned for the same pcm.  ref_db, p_lo and p_hi are constants of the backward (include/orcai_hip.h: orcai_spectrogram_bwd)."""
+        n_fft = int(spectrogram_parameter["nfft"])
+        hop = int(spectrogram_parameter["n_overlap"])
+        self._check_nfft(n_fft)
+        self._check_nfft_backward(n_fft)
+        if hop < 1:
+            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
+        freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
+        f_lo, f_hi = crop_indices(freqs, spectrogram_parameter["freq_range"])
+        if f_lo != 0:
+            raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
+        pcm = self._check_pcm(pcm)
+        n = pcm.numel()
+        T = 1 + n // hop
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, f_hi)):
+            raise ValueError(f"spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {f_hi}] (nfft = {n_fft}, hop = {hop}, {n} samples), got "
+                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
+            raise ValueError(f"spectrogram_backward (nfft = {n_fft}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
+        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dpcm
+        N.check(
+            self.lib.orcai_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, f_hi, N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm),
+                                           N.stream_ptr()),
+            "orcai_spectrogram_bwd",
+        )
+        return dpcm
 
     # -- calculate_spectrogram (spectrogram.py:15-55): dB of all bins, referenced and floored ----
     def calculate_db(self, pcm: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:

@@ -4,6 +4,7 @@ own loss, ``torch.optim`` and ``torch.compile``.  Every op calls the library thr
 known without a GPU.
 
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
@@ -17,8 +18,10 @@ still alive raises instead of overwriting what that graph's backward needs (``fo
 
 ``forward`` differentiates w.r.t. the weights only and refuses an ``x`` that requires grad; ``forward_wrt_input`` is the same computation
 whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
-detector.  What does not exist: an input gradient in eval mode (there is no eval-mode backward at all), on the f16 path (f32 models
-only), or through ``orcai::spectrogram`` (the front end has no backward).
+detector.  ``spectrogram_wrt_pcm`` is ``spectrogram`` (same bits) whose backward delivers dL/dpcm (``orcai_spectrogram_bwd``; the three
+normalisation statistics are held constant), so the chain pcm -> spectrogram -> snippets -> probabilities is differentiable down to the
+waveform.  What does not exist: an input gradient in eval mode (there is no eval-mode backward at all) or on the f16 path (f32 models
+only); ``orcai::spectrogram`` itself has no backward, and the resampler is not differentiated.
 """
 
 from __future__ import annotations
@@ -396,6 +399,93 @@ def _forward_wrt_input_autograd(x, weights, stats, config, training, dropout_see
 
 
 _LIB.impl("forward_wrt_input", _forward_wrt_input_autograd, "Autograd")
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::spectrogram_wrt_pcm
+# orcai::spectrogram with the gradient w.r.t. the audio, for anything trainable or differentiable in the WAVEFORM domain in front of the detector
+# (a learnable band-pass or denoiser on the hydrophone signal, adversarial or gradient-penalty robustness on audio, saliency of a detection in the
+# recording).  Its own op, as forward_wrt_input is: orcai::spectrogram's schema and behaviour stay what they are.  The forward is the same launch
+# sequence (same bits); with a pcm that requires grad it also keeps the run's six statistics (orcai_frontend_stats_dev), and the backward is the
+# functional op orcai::spectrogram_backward (orcai_spectrogram_bwd), which holds ref_db, p_lo and p_hi constant (include/orcai_hip.h).
+def _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo=0.0, q_hi=1.0) -> dict:
+    return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
+
+
+@torch.library.custom_op("orcai::spectrogram_with_stats", mutates_args=())
+def spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> tuple[Tensor, Tensor]:
+    """orcai::spectrogram and the f32[6] statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the run, on the device."""
+    from orcai_amd.frontend import get_frontend
+
+    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
+        raise ValueError("orcai::spectrogram_with_stats: pcm must be a 1-d f32 cuda tensor")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi), return_stats=True)
+
+
+@spectrogram_with_stats.register_fake
+def _spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
+    return _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi), pcm.new_empty((6,), dtype=torch.float32)
+
+
+@torch.library.custom_op("orcai::spectrogram_backward", mutates_args=())
+def spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float) -> Tensor:
+    """dL/dpcm f32[n] from grad = dL/dspectrogram f32[T, K], the pcm of the forward and the statistics orcai::spectrogram_with_stats returned."""
+    from orcai_amd.frontend import get_frontend
+
+    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
+        raise ValueError("orcai::spectrogram_backward: pcm must be a 1-d f32 cuda tensor")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).spectrogram_backward(pcm.detach(), grad.contiguous(), stats, _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi))
+
+
+@spectrogram_backward.register_fake
+def _spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, freq_hi):
+    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
+
+
+_LIB.define("spectrogram_wrt_pcm(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi) -> Tensor")
+
+
+def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
+    """orcai::spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 to 4096."""
+    return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+
+
+def _spectrogram_wrt_pcm_impl(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
+    return torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+
+
+_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_impl, "CUDA")
+_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_impl, "CPU")  # (refuses: the check names the missing GPU)
+torch.library.register_fake("orcai::spectrogram_wrt_pcm", _spectrogram_fake, lib=_LIB)
+
+
+class _SpectrogramFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
+        from orcai_amd.frontend import FrontEnd
+
+        FrontEnd._check_nfft_backward(nfft)  # refuse before the forward what the backward could not differentiate
+        with torch._C._AutoDispatchBelowAutograd():
+            spec, stats = torch.ops.orcai.spectrogram_with_stats(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+        ctx.args = (sampling_rate, nfft, hop, freq_hi)
+        ctx.save_for_backward(pcm, stats)
+        return spec
+
+    @staticmethod
+    def backward(ctx, grad):
+        pcm, stats = ctx.saved_tensors
+        return (torch.ops.orcai.spectrogram_backward(grad, pcm, stats, *ctx.args), None, None, None, None, None, None)
+
+
+def _spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _SpectrogramFunction.apply(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+
+
+_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_autograd, "Autograd")
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
