@@ -706,10 +706,42 @@ int orcai_h_mask_scale(const void* x, const void* mask, float scale, int64_t n, 
  *                              a4 < 0 for none): scale = gamma / sqrt(var + eps), shift = beta - mean * scale (+ bias * scale) in double, each
  *                              rounded once to float, scale at out[dst], shift at out[dst + roundup(count, 64)];
  *                            kind 1: depthwise kernel (k, k, count, 1) at w[a0], k = a1 -> [ceil(count/4)][k*k][4] at out[dst] (zero pad channels);
- *                            kind 2: copy of `count` floats from w[a0] to out[dst].
+ *                            kind 2: copy of `count` floats from w[a0] to out[dst];
+ *                            kind 3: orcai_sepconv_dgrad's wts: count = Cout, gamma w[a0], var stats[a1], pointwise kernel [Cin = a3][Cout] at w[a2]:
+ *                              out[dst + co * Cin + ci] = gamma[co] / sqrt(var[co] + eps) * pw[ci][co], the product in double, rounded once;
+ *                            kind 4: kind 1 with the taps reversed (tap t <- tap k*k - 1 - t);
+ *                            kind 5: transpose of the [a1][a2] matrix at w[a0], count = a1 * a2: out[dst + c * a1 + r] = w[a0 + r * a2 + c].
  *                            The LSTM layouts come from orcai_pack_lstm (mode 0) on the same w. */
 int orcai_sigmoid_bwd(const float* p, const float* g, int64_t n, float* dz, void* stream);
 int orcai_prepare_inference(const float* w, const float* stats, const int* desc, int n_desc, double eps, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Input gradient of the INFERENCE network (orcai_amd/eval_grad.py; csrc/eval_grad.hip): BatchNorm with its moving statistics, i.e. the folded
+ * per-channel (scale, shift) of the inference path, no Dropout, no weight gradients.  The reference never differentiates its predict path
+ * (predict.py:265-268); this is what Keras forms for the frozen model (architectures.py:162-241, training=False) behind anything trainable.
+ * ------------------------------------------------------------------------------------------ */
+
+/* The folded separable conv y = [relu](scale (.) (pw . dw(relu_in ? relu(x) : x)) + shift) of orcai_sepconv_bn run TRANSPOSED, one pass:
+ *   gg[co][q] = g[co][q] where y_gate[co][q] > 0 (everywhere when y_gate is NULL: a conv without ReLU behind it), else 0
+ *   du[ci][q] = sum_co wts[co][ci] * gg[co][q]                       (0 outside the image; never written to memory)
+ *   dr[ci][p] = sum_t dw_rev[ci][t] * du[ci][p + off(t)],  off(t) = (t / k - k/2) rows, (t % k - k/2) columns
+ *   dr[ci][p] = 0 where x_gate[ci][p] <= 0                           (x_gate != NULL: the ReLU in front of the conv; epi 3 of orcai_sepconv_planes_epi)
+ *   g, y_gate  padded channel-quad planes of Cout channels [B][ceil(Cout/4)][H + 2R][orcai_padded_width(W, k)][4]: the gradient at y and the stored y
+ *   x_gate, dr planes of Cin channels: the stored conv input and the gradient w.r.t. it
+ *   wts        f32[Cout][Cin] = scale[co] * pw[ci][co]; dw_rev f32[ceil(Cin/4)][k*k][4], tap t = forward tap k*k - 1 - t (orcai_prepare_inference kinds 3, 4)
+ * Only the interior of g and the gates is read (their pads may hold anything); only the interior of dr is written, every element of it, nothing
+ * accumulated; no atomics: two launches give the same bits.  k = 3 runs the fused kernel (v_mfma_f32_16x16x4_f32 contraction, du rows in an LDS ring);
+ * k = 5, 7, Cin or Cout > 64, B > 65535: ORCAI_E_UNSUPPORTED before anything is touched -- the caller composes orcai_planes_relu_bwd,
+ * orcai_sepconv_planes(ktap = 1, wts), orcai_sepconv_planes(ktap = k, dw_rev, identity pointwise), orcai_planes_relu_bwd.
+ * ORCAI_E_BADARG: null g / wts / dw_rev / dr, planes or taps not 16-byte aligned, non-positive sizes, ksize not in {3, 5, 7}. */
+int orcai_sepconv_dgrad(const float* g, const float* y_gate, const float* x_gate, int B, int Cin, int Cout, int H, int W, int ksize, const float* wts,
+                        const float* dw_rev, float* dr, void* stream);
+/* A folded BatchNorm on a row tensor f32[M][cols], channel = column % C, and its backward (Dense(128, relu) -> BatchNormalization with moving
+ * statistics, architectures.py:231-237: the eval-mode forward keeps the ReLU output `ref` in front of the affine map):
+ *   orcai_rows_affine           y = [relu](x * scale[c] + shift[c])
+ *   orcai_rows_affine_relu_bwd  dx = ref > 0 ? dy * scale[c] : 0   (ref may be NULL: no gate; dx may alias dy) */
+int orcai_rows_affine(const float* x, int64_t M, int cols, int C, const float* scale, const float* shift, int relu, float* y, void* stream);
+int orcai_rows_affine_relu_bwd(const float* dy, const float* ref, int64_t M, int cols, int C, const float* scale, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,11 @@ unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 //   kind 1  depthwise kernel (k, k, count, 1) at w[a0], k = a1 -> [ceil(count/4)][k*k][4] at out[dst], zero taps for the padding channels
 //           (architectures.depthwise_kernel_layout)
 //   kind 2  copy of `count` floats from w[a0]
+//   kind 3  transposed pointwise kernel with the BatchNorm scale of its OUTPUT channel folded in (orcai_sepconv_dgrad's wts): count = Cout,
+//           gamma = w[a0], var = stats[a1], pointwise [Cin = a3][Cout] at w[a2]: out[dst + co * Cin + ci] = gamma / sqrt(var + eps) * pw[ci][co],
+//           the product in double, rounded once
+//   kind 4  kind 1 with the taps reversed (tap t <- tap k*k - 1 - t)
+//   kind 5  transpose of the [a1][a2] matrix at w[a0] (count = a1 * a2): out[dst + c * a1 + r] = w[a0 + r * a2 + c]
 // One workgroup row per descriptor (blockIdx.y), a grid-stride loop over its elements.
 __global__ __launch_bounds__(256) void prepare_kernel(const float* __restrict__ w, const float* __restrict__ stats, const int* __restrict__ desc, double eps,
                                                       float* __restrict__ out) {
@@ -60,11 +65,25 @@ __global__ __launch_bounds__(256) void prepare_kernel(const float* __restrict__ 
       out[dst + c] = (float)scale;
       out[dst + ((count + 63) & ~63) + c] = (float)shift;
     }
-  } else if (kind == 1) {
+  } else if (kind == 1 || kind == 4) {
     const int k = d[4], kk = k * k, cq = (count + 3) / 4, n = cq * kk * 4;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
       const int j = i & 3, t = (i >> 2) % kk, q = (i >> 2) / kk, ch = 4 * q + j;
-      out[dst + i] = ch < count ? w[d[3] + t * count + ch] : 0.0f;
+      out[dst + i] = ch < count ? w[d[3] + (kind == 4 ? kk - 1 - t : t) * count + ch] : 0.0f;
+    }
+  } else if (kind == 3) {
+    const int cin = d[6], n = count * cin;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      const int co = i / cin, ci = i - co * cin;
+      const double g = w[d[3] + co], v = stats[d[4] + co];
+      const double scale = g / sqrt(v + eps);
+      out[dst + i] = (float)(scale * (double)w[d[5] + ci * count + co]);
+    }
+  } else if (kind == 5) {
+    const int rows = d[4], cols = d[5];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < count; i += gridDim.x * 256) {
+      const int c = i / rows, r = i - c * rows;
+      out[dst + i] = w[d[3] + r * cols + c];
     }
   } else {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < count; i += gridDim.x * 256) out[dst + i] = w[d[3] + i];

@@ -1,0 +1,387 @@
+"""The gradient of the PREDICT-TIME network w.r.t. its input snippets: BatchNorm with the moving statistics (the folded scale / shift of the
+inference path), no Dropout, nothing written to the model -- saliency / attribution, robustness probes, training something in front of the
+detector that will be deployed.  f32 models, both architectures, kernel sizes 3, 5 and 7; no autograd is needed:
+
+    eg = EvalGrad(model)
+    probs, saved = eg.forward(x)          # x f32 cuda [B, H, W]
+    dx = eg.backward(dprobs, saved)       # f32 [B, H, W]
+
+The forward runs the INFERENCE launchers on the weights ``prepare_device`` folds (the unfused sequence of ``trunk_device(keep=...)``:
+orcai_conv0_bn_relu, orcai_sepconv_bn with plane output, orcai_pool_res_add on the full-resolution tensor) and leaves what the backward reads in
+ONE flat tensor ``saved`` the caller owns -- y0, every block's y_a, pre-pool s_b and output prev_b, the features, the LSTM gates / cell states
+and Dense-128's ReLU output (or the frequency mean of ResNet1DConv), the probabilities and the snippets themselves -- so any number of forwards
+may be alive at once (integrated gradients, several losses).  The backward runs no weight-gradient launcher and stores no depthwise output:
+every separable conv is ONE orcai_sepconv_dgrad (k = 3; for k = 5 / 7 that launcher refuses and ``compose_dgrad`` runs the existing launchers, as
+it does for the large launches beyond 32 input channels where the fused kernel measured slower: EvalGrad.fused),
+the pooling is orcai_pool_bwd, the residual 1x1 stride-2 gradient is scatter-added by orcai_sepconv_planes(out_layout = 3), the heads use the
+training kernels' data-gradient halves (orcai_lstm_bwd, orcai_conv1d_bwd into a scratch weight gradient) and dgrad GEMMs on the forward GEMM
+kernel (no split-K atomics: two runs give the same bits).
+
+The entry conv REUSES orcai_conv0_bn_bwd_dx: called with the moving statistics and zeroed sums it evaluates the eval-mode formula
+(dv = gamma * rsqrt(var + eps) * dy where the ReLU fired).  Its ReLU decision is formed from the unfolded BatchNorm, the forward's from the folded
+one; the two can only differ for a pre-activation within rounding of zero, and dr1 is already zero where the stored y0 is (x_gate of block 1's
+first conv), so a differing decision can only zero a residual-branch term at such a pixel.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from orcai_amd import _native as N
+from orcai_amd.architectures import BN_EPS, DENSE_UNITS, ENTRY_FILTERS, FINAL_FILTERS
+
+Tensor = torch.Tensor
+
+
+def compose_dgrad(lib, g: Tensor, y_gate, x_gate, B: int, Cin: int, Cout: int, H: int, W: int, k: int, wts: Tensor, dw_rev: Tensor, dr: Tensor, du: Tensor, st) -> None:
+    """orcai_sepconv_dgrad's result from the launchers that existed before it (what the launcher's refusal for k = 5 / 7 falls back to, and what its
+    tests and tools/time_eval_grad.py compare it with): ReLU gate of g IN PLACE, pointwise pass with wts, depthwise pass with the reversed taps and an
+    identity pointwise factor, ReLU gate of dr.  g, du (planes of Cin channels, scratch) and dr need zero pads."""
+    dev = g.device
+    ones, zeros = torch.ones(64, device=dev), torch.zeros(64, device=dev)
+    eye = torch.eye(Cin, device=dev).contiguous()
+    if y_gate is not None:
+        N.check(lib.orcai_planes_relu_bwd(g.data_ptr(), y_gate.data_ptr(), g.numel(), g.data_ptr(), st), "orcai_planes_relu_bwd")
+    N.check(lib.orcai_sepconv_planes(g.data_ptr(), B, Cout, H, W, k, 1, 0, ones.data_ptr(), wts.data_ptr(), ones.data_ptr(), zeros.data_ptr(), Cin, 0, 0, 0, 0,
+                                     du.data_ptr(), st), "orcai_sepconv_planes")
+    N.check(lib.orcai_sepconv_planes(du.data_ptr(), B, Cin, H, W, k, k, 0, dw_rev.data_ptr(), eye.data_ptr(), ones.data_ptr(), zeros.data_ptr(), Cin, 0, 0, 0, 0,
+                                     dr.data_ptr(), st), "orcai_sepconv_planes")
+    if x_gate is not None:
+        N.check(lib.orcai_planes_relu_bwd(dr.data_ptr(), x_gate.data_ptr(), dr.numel(), dr.data_ptr(), st), "orcai_planes_relu_bwd")
+
+
+def saved_layout(model) -> tuple[list, int]:
+    """[(name, offset, shape)] per snippet and the floats per snippet of ``saved``: tensor `name` of a batch of B snippets is
+    saved[B * offset : B * (offset + prod(shape))] viewed as [B, *shape].  Host arithmetic only (the fake implementations use it)."""
+    k = model.kernel_size
+    R = k // 2
+    shapes = model.stage_shapes()
+    H, W = model.input_hw
+
+    def planes(c, h, w):
+        return ((c + 3) // 4, h + 2 * R, model.padded_width(w), 4)
+
+    items = [("y0", planes(ENTRY_FILTERS, H, W))]
+    for b, f in enumerate(model.filters, start=1):
+        h, w, _ = shapes[b - 1]
+        items += [(f"a{b}", planes(f, h, w)), (f"s{b}", planes(f, h, w)), (f"prev{b}", planes(f, shapes[b][0], shapes[b][1]))]
+    T, wd, _ = shapes[-1]
+    items.append(("feat", (T, wd * FINAL_FILTERS)))
+    if model.architecture == "ResNet1DConv":
+        items.append(("fm", (T, FINAL_FILTERS)))
+    else:
+        u = model.lstm_units
+        for layer in (1, 2):
+            items += [(f"gates{layer}", (T, 2, 4 * u)), (f"cs{layer}", (T, 2, u))]
+        items.append(("pre1", (T, DENSE_UNITS)))
+    items += [("probs", (T, model.num_labels)), ("x", (H, W))]  # the snippets last: H * W need not be a multiple of 4 floats
+    out, off = [], 0
+    for name, shape in items:
+        out.append((name, off, shape))
+        off += int(np.prod(shape))
+    return out, off
+
+
+class EvalGrad:
+    """Eval-mode forward that keeps what its backward needs, and that backward (module docstring).  `params` of forward / backward: (wflat, sflat),
+    the trainable variables and the BatchNorm moving statistics as flat f32 cuda tensors in variable_spec() order; None: the model's own weights."""
+
+    # Where the fused kernel loses to the composition (tools/time_eval_grad.py, DESIGN 4.7: beyond 32 input channels its LDS ring leaves one workgroup of
+    # four waves per compute unit, and planes narrower than a 62-column strip idle most of its lanes) the composition runs -- unless the launch is so
+    # small that the number of launches decides.
+    FUSED_MAX_CHANNELS = 32
+    FUSED_ANY_CHANNELS_BELOW_PIXELS = 1 << 14
+
+    def __init__(self, model):
+        precision = getattr(model, "precision", "f32")
+        if precision != "f32":
+            raise NotImplementedError(f"EvalGrad: precision {precision!r} computes no gradient w.r.t. the input (f32 models only)")
+        self.model = model
+        self.conv1d = model.architecture == "ResNet1DConv"
+        self.layout, self.per_snippet = saved_layout(model)
+        self.lib = None
+        self._own = None
+        self._ws = {}
+        self._plan = None
+
+    # ------------------------------------------------------------------ weights
+    def _lib(self):
+        if self.lib is None:
+            self.lib = N.lib()
+        return self.lib
+
+    def _offsets(self):
+        woff, soff, o1, o2 = {}, {}, 0, 0
+        for name, shape, _, trainable in self.model.variable_spec():
+            n = int(np.prod(shape))
+            if trainable:
+                woff[name], o1 = (o1, tuple(shape)), o1 + n
+            else:
+                soff[name], o2 = (o2, tuple(shape)), o2 + n
+        return woff, soff
+
+    def _extra_plan(self):
+        """Descriptors of the backward's own operands for orcai_prepare_inference (kinds 3, 4, 5): per separable conv wts = scale (.) pointwise^T
+        and the reversed taps, per block the transposed residual kernel."""
+        if self._plan is not None:
+            return self._plan
+        m, k = self.model, self.model.kernel_size
+        woff, soff = self._offsets()
+        desc, views, size = [], {}, 0
+
+        def region(numel):
+            nonlocal size
+            off = size
+            size += (numel + 63) // 64 * 64
+            return off
+
+        convs, c = [], ENTRY_FILTERS
+        for b, f in enumerate(m.filters, start=1):
+            convs += [(f"b{b}/sep_a", f"b{b}/bn_a", c, f), (f"b{b}/sep_b", f"b{b}/bn_b", f, f)]
+            off = region(c * f)
+            desc.append([5, off, c * f, woff[f"b{b}/res/kernel"][0], c, f, 0, 0])
+            views[f"b{b}/res/wT"] = (off, (f, c))
+            c = f
+        convs.append(("sep_f", "bn_f", c, FINAL_FILTERS))
+        for name, bn, cin, cout in convs:
+            off = region(cin * cout)
+            desc.append([3, off, cout, woff[bn + "/gamma"][0], soff[bn + "/var"][0], woff[name + "/pointwise"][0], cin, 0])
+            views[name + "/wts"] = (off, (cout, cin))
+            cq = (cin + 3) // 4
+            off = region(cq * k * k * 4)
+            desc.append([4, off, cin, woff[name + "/depthwise"][0], k, 0, 0, 0])
+            views[name + "/dw_rev"] = (off, (cq, k * k, 4))
+        self._plan = {"desc": torch.tensor(desc, dtype=torch.int32), "views": views, "size": size, "convs": convs, "dev": None}
+        return self._plan
+
+    def bind(self, wflat: Tensor, sflat: Tensor) -> dict:
+        """Everything forward and backward read, from flat device weights: prepare_device's folded inference tensors, the backward's operands
+        (one more orcai_prepare_inference launch) and views of the raw entry-conv variables."""
+        m, plan = self.model, self._extra_plan()
+        d = dict(m.prepare_device(wflat, sflat))
+        dev = wflat.device
+        if plan["dev"] != dev:
+            plan["desc_dev"], plan["dev"] = plan["desc"].to(dev), dev
+        out = torch.empty(plan["size"], dtype=torch.float32, device=dev)
+        N.check(self._lib().orcai_prepare_inference(wflat.data_ptr(), sflat.data_ptr(), plan["desc_dev"].data_ptr(), int(plan["desc"].shape[0]), BN_EPS, out.data_ptr(),
+                                                    N.stream_ptr()), "orcai_prepare_inference")
+        for key, (o, shape) in plan["views"].items():
+            d[key] = out[o : o + int(np.prod(shape))].view(shape)
+        # the heads' data-gradient GEMMs run on the forward GEMM kernel with transposed operands: orcai_gemm_strided splits K with float atomics
+        # for these shapes, and this gradient is bit-reproducible
+        for key in ("dense2/W", "dense1/W", "lstm1/W", "lstm2/W"):
+            if key in d:
+                d[key + "T"] = d[key].t().contiguous()
+        woff, soff = self._offsets()
+        for name in ("conv0/kernel", "conv0/bias", "bn0/gamma", "bn0/beta"):
+            o, shape = woff[name]
+            d["raw/" + name] = wflat[o : o + int(np.prod(shape))]
+        for name in ("bn0/mean", "bn0/var"):
+            o, shape = soff[name]
+            d["raw/" + name] = sflat[o : o + int(np.prod(shape))]
+        return d
+
+    def _params(self, params, device) -> dict:
+        if params is not None:
+            return self.bind(*params)
+        if self._own is None or self._own[0] != device:
+            spec = self.model.variable_spec()
+            flat = lambda tr: torch.from_numpy(np.concatenate([self.model.weights[n].reshape(-1) for n, _, _, t in spec if t == tr]).astype(np.float32)).to(device)  # noqa: E731
+            self._own = (device, self.bind(flat(True), flat(False)))
+        return self._own[1]
+
+    def invalidate(self) -> None:
+        """Forget the device copies of the model's own weights (after model.set_weights_dict)."""
+        self._own = None
+
+    # ------------------------------------------------------------------ saved
+    def views(self, saved: Tensor) -> dict:
+        if saved.dim() != 1 or saved.dtype != torch.float32 or not saved.is_cuda or not saved.is_contiguous() or saved.numel() % self.per_snippet:
+            raise ValueError(f"EvalGrad: saved must be the contiguous f32 cuda tensor forward() returned ({self.per_snippet} floats per snippet)")
+        B = saved.numel() // self.per_snippet
+        return {name: saved[B * off : B * (off + int(np.prod(shape)))].view(B, *shape) for name, off, shape in self.layout}
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, x: Tensor, params=None) -> tuple[Tensor, Tensor]:
+        m = self.model
+        H, W = m.input_hw
+        if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError(f"EvalGrad.forward: x must be an f32 cuda tensor [B, {H}, {W}], got {x.dtype} {tuple(x.shape)} on {x.device}")
+        B = int(x.shape[0])
+        if B == 0:
+            raise ValueError("EvalGrad.forward: empty batch")
+        with torch.cuda.device(x.device):
+            return self._forward(x, B, params)
+
+    def _forward(self, x, B, params):
+        m, lib, st = self.model, self._lib(), N.stream_ptr()
+        d = self._params(params, x.device)
+        H, W = m.input_hw
+        k = m.kernel_size
+        shapes = m.stage_shapes()
+        saved = torch.zeros(B * self.per_snippet, dtype=torch.float32, device=x.device)  # zero pads of every plane tensor
+        v = self.views(saved)
+        v["x"].copy_(x.detach())
+        p = N.ptr
+        N.check(lib.orcai_conv0_bn_relu(p(v["x"]), H * W, B, H, W, k, p(d["conv0/w"]), p(d["conv0/scale"]), p(d["conv0/shift"]), p(v["y0"]), st), "orcai_conv0_bn_relu")
+        prev, c = v["y0"], ENTRY_FILTERS
+        for b, f in enumerate(m.filters, start=1):
+            h, w, _ = shapes[b - 1]
+            pa, pb = f"b{b}/sep_a", f"b{b}/sep_b"
+            N.check(lib.orcai_sepconv_bn(p(prev), B, c, h, w, k, 1, p(d[pa + "/dw"]), p(d[pa + "/pw"]), p(d[pa + "/scale"]), p(d[pa + "/shift"]), f, 1, 0, p(v[f"a{b}"]), st),
+                    "orcai_sepconv_bn")
+            N.check(lib.orcai_sepconv_bn(p(v[f"a{b}"]), B, f, h, w, k, 0, p(d[pb + "/dw"]), p(d[pb + "/pw"]), p(d[pb + "/scale"]), p(d[pb + "/shift"]), f, 0, 0, p(v[f"s{b}"]), st),
+                    "orcai_sepconv_bn")
+            N.check(lib.orcai_pool_res_add(p(v[f"s{b}"]), p(prev), B, f, c, h, w, k, p(d[f"b{b}/res/w"]), p(d[f"b{b}/res/b"]), p(v[f"prev{b}"]), 0, st), "orcai_pool_res_add")
+            prev, c = v[f"prev{b}"], f
+        T, wd, _ = shapes[-1]
+        N.check(lib.orcai_sepconv_bn(p(prev), B, c, T, wd, k, 0, p(d["sep_f/dw"]), p(d["sep_f/pw"]), p(d["sep_f/scale"]), p(d["sep_f/shift"]), FINAL_FILTERS, 1, 1, p(v["feat"]), st),
+                "orcai_sepconv_bn")
+        M, L = B * T, m.num_labels
+        f32 = dict(dtype=torch.float32, device=x.device)
+        if self.conv1d:
+            N.check(lib.orcai_freq_mean(p(v["feat"]), M, wd, FINAL_FILTERS, p(v["fm"]), st), "orcai_freq_mean")
+            N.check(lib.orcai_conv1d_sigmoid(p(v["fm"]), p(d["conv1d/W"]), p(d["conv1d/b"]), B, T, FINAL_FILTERS, FINAL_FILTERS, L, p(v["probs"]), st), "orcai_conv1d_sigmoid")
+        else:
+            u = m.lstm_units
+            xin, fin = v["feat"], wd * FINAL_FILTERS
+            xz = torch.empty((B, T, 2, 4 * u), **f32)
+            for layer in (1, 2):
+                N.check(lib.orcai_gemm_bias_act(p(xin), p(d[f"lstm{layer}/W"]), p(d[f"lstm{layer}/b"]), None, None, p(xz), M, 8 * u, fin, 0, st), "orcai_gemm_bias_act")
+                hout = torch.empty((B, T, 2 * u), **f32)
+                N.check(lib.orcai_lstm_train_fwd(p(xz), p(d[f"lstm{layer}/U"]), B, T, u, p(hout), p(v[f"gates{layer}"]), p(v[f"cs{layer}"]), st), "orcai_lstm_train_fwd")
+                xin, fin = hout, 2 * u
+            # Dense-128: relu(h W + b) is kept for the backward, the folded BatchNorm behind it is a pass of its own
+            N.check(lib.orcai_gemm_bias_act(p(xin), p(d["dense1/W"]), p(d["dense1/b"]), None, None, p(v["pre1"]), M, DENSE_UNITS, 2 * u, 1, st), "orcai_gemm_bias_act")
+            d1 = torch.empty((M, DENSE_UNITS), **f32)
+            N.check(lib.orcai_rows_affine(p(v["pre1"]), M, DENSE_UNITS, DENSE_UNITS, p(d["dense1/scale"]), p(d["dense1/shift"]), 0, p(d1), st), "orcai_rows_affine")
+            N.check(lib.orcai_dense_sigmoid(p(d1), p(d["dense2/W"]), p(d["dense2/b"]), M, DENSE_UNITS, L, p(v["probs"]), st), "orcai_dense_sigmoid")
+        return v["probs"].clone(), saved
+
+    # ------------------------------------------------------------------ backward
+    def _workspace(self, B: int, device) -> dict:
+        """Gradient planes (zero pads; only interiors are ever written, so they persist) for a batch of B snippets."""
+        key = (B, device)
+        ws = self._ws.get(key)
+        if ws is not None:
+            return ws
+        m = self.model
+        R = m.kernel_size // 2
+        shapes = m.stage_shapes()
+
+        def planes(c, h, w):
+            return torch.zeros((B, (c + 3) // 4, h + 2 * R, m.padded_width(w), 4), dtype=torch.float32, device=device)
+
+        ws = {"sums0": torch.zeros(32, dtype=torch.float64, device=device), "ones": torch.ones(64, device=device), "zeros": torch.zeros(64, device=device)}
+        c = ENTRY_FILTERS
+        for b, f in enumerate(m.filters, start=1):
+            h, w, _ = shapes[b - 1]
+            ws[f"dyb{b}"], ws[f"dya{b}"], ws[f"dr{b}"] = planes(f, h, w), planes(f, h, w), planes(c, h, w)
+            c = f
+        T, wd, _ = shapes[-1]
+        ws["dvf"], ws["dprev_f"] = planes(FINAL_FILTERS, T, wd), planes(c, T, wd)
+        self._ws = {key: ws}  # one batch size at a time
+        return ws
+
+    def fused(self, B: int, Cin: int, h: int, w: int) -> bool:
+        """Whether this separable conv's backward asks orcai_sepconv_dgrad (k = 5 / 7 ask too: the launcher answers ORCAI_E_UNSUPPORTED)."""
+        return self.model.kernel_size != 3 or Cin <= self.FUSED_MAX_CHANNELS or B * h * w < self.FUSED_ANY_CHANNELS_BELOW_PIXELS
+
+    def _dgrad(self, d, ws, name, g, y_gate, x_gate, B, Cin, Cout, h, w, dr):
+        lib, st, k = self._lib(), N.stream_ptr(), self.model.kernel_size
+        wts, dw_rev = d[name + "/wts"], d[name + "/dw_rev"]
+        if self.fused(B, Cin, h, w):
+            rc = lib.orcai_sepconv_dgrad(g.data_ptr(), None if y_gate is None else y_gate.data_ptr(), None if x_gate is None else x_gate.data_ptr(), B, Cin, Cout, h, w, k,
+                                         wts.data_ptr(), dw_rev.data_ptr(), dr.data_ptr(), st)
+            if rc != N.E_UNSUPPORTED:
+                N.check(rc, "orcai_sepconv_dgrad")
+                return
+        du = ws.get("du/" + name)  # the pointwise product of the composed path (zero pads, interior rewritten by every call)
+        if du is None:
+            du = ws["du/" + name] = torch.zeros_like(dr)
+        compose_dgrad(lib, g, y_gate, x_gate, B, Cin, Cout, h, w, k, wts, dw_rev, dr, du, st)
+
+    def _gemm(self, A, BT, C, M, Nn, K):
+        """C[M][Nn] = A[M][K] BT[K][Nn] (a dgrad GEMM: BT = the layer's weight matrix transposed)."""
+        N.check(self._lib().orcai_gemm_bias_act(A.data_ptr(), BT.data_ptr(), None, None, None, C.data_ptr(), M, Nn, K, 0, N.stream_ptr()), "orcai_gemm_bias_act")
+
+    def backward(self, dprobs: Tensor, saved: Tensor, params=None) -> Tensor:
+        v = self.views(saved)
+        if tuple(dprobs.shape) != tuple(v["probs"].shape) or dprobs.dtype != torch.float32 or dprobs.device != saved.device:
+            raise ValueError(f"EvalGrad.backward: dprobs must be f32 {tuple(v['probs'].shape)} on {saved.device}, got {dprobs.dtype} {tuple(dprobs.shape)} on {dprobs.device}")
+        with torch.cuda.device(saved.device):
+            return self._backward(dprobs.detach().contiguous(), v, params)
+
+    def _backward(self, dprobs, v, params):
+        m, lib, st = self.model, self._lib(), N.stream_ptr()
+        dev = dprobs.device
+        d = self._params(params, dev)
+        B = int(v["x"].shape[0])
+        H, W = m.input_hw
+        k = m.kernel_size
+        shapes = m.stage_shapes()
+        T, wd, c_last = shapes[-1]
+        M, L = B * T, m.num_labels
+        cols = wd * FINAL_FILTERS
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = self._workspace(B, dev)
+        p = N.ptr
+        dz = torch.empty((M, L), **f32)
+        N.check(lib.orcai_sigmoid_bwd(p(v["probs"]), p(dprobs), M * L, p(dz), st), "orcai_sigmoid_bwd")
+        if self.conv1d:
+            dfm = torch.empty((B, T, FINAL_FILTERS), **f32)
+            dW = torch.zeros((FINAL_FILTERS, FINAL_FILTERS, L), **f32)  # orcai_conv1d_bwd has no data-gradient-only form: its weight gradient lands here and is dropped
+            N.check(lib.orcai_conv1d_bwd(p(v["fm"]), p(d["conv1d/W"]), p(dz), B, T, FINAL_FILTERS, FINAL_FILTERS, L, p(dW), p(dfm), st), "orcai_conv1d_bwd")
+            dfeat = torch.empty((M, cols), **f32)
+            N.check(lib.orcai_freq_mean_bwd(p(dfm), M, wd, FINAL_FILTERS, p(dfeat), st), "orcai_freq_mean_bwd")
+        else:
+            u = m.lstm_units
+            dd1 = torch.empty((M, DENSE_UNITS), **f32)
+            self._gemm(dz, d["dense2/WT"], dd1, M, DENSE_UNITS, L)
+            N.check(lib.orcai_rows_affine_relu_bwd(p(dd1), p(v["pre1"]), M, DENSE_UNITS, DENSE_UNITS, p(d["dense1/scale"]), p(dd1), st), "orcai_rows_affine_relu_bwd")
+            dh = torch.empty((M, 2 * u), **f32)
+            self._gemm(dd1, d["dense1/WT"], dh, M, 2 * u, DENSE_UNITS)
+            for layer, fin in ((2, 2 * u), (1, cols)):
+                dxz = torch.empty((B, T, 2, 4 * u), **f32)
+                N.check(lib.orcai_lstm_bwd(p(dh), p(v[f"gates{layer}"]), p(v[f"cs{layer}"]), p(d[f"lstm{layer}/U"]), B, T, u, p(dxz), st), "orcai_lstm_bwd")
+                dxl = torch.empty((M, fin), **f32)
+                self._gemm(dxz, d[f"lstm{layer}/WT"], dxl, M, fin, 8 * u)
+                dh = dxl
+            dfeat = dh
+        # the ReLU behind bn_f (its scale is inside sep_f's wts), then into planes
+        N.check(lib.orcai_relu_bwd(p(dfeat), p(v["feat"]), M * cols, p(dfeat), st), "orcai_relu_bwd")
+        N.check(lib.orcai_feat_to_planes(p(dfeat), B, FINAL_FILTERS, T, wd, k, p(ws["dvf"]), st), "orcai_feat_to_planes")
+        nb = len(m.filters)
+        dprev = ws["dprev_f"]
+        self._dgrad(d, ws, "sep_f", ws["dvf"], None, None, B, c_last, FINAL_FILTERS, T, wd, dprev)
+        for b in range(nb, 0, -1):
+            f = m.filters[b - 1]
+            h, w, cprev = shapes[b - 1]
+            ho, wo, _ = shapes[b]
+            x_in = v["y0"] if b == 1 else v[f"prev{b - 1}"]
+            dout = dprev
+            dyb, dya, dr = ws[f"dyb{b}"], ws[f"dya{b}"], ws[f"dr{b}"]
+            N.check(lib.orcai_pool_bwd(p(dout), p(v[f"s{b}"]), B, f, h, w, k, p(dyb), st), "orcai_pool_bwd")
+            self._dgrad(d, ws, f"b{b}/sep_b", dyb, None, None, B, f, f, h, w, dya)
+            self._dgrad(d, ws, f"b{b}/sep_a", dya, v[f"a{b}"], x_in, B, cprev, f, h, w, dr)
+            # the residual 1x1 stride-2 conv reads the block input in front of the ReLU: its gradient joins at the even pixels
+            N.check(lib.orcai_sepconv_planes(p(dout), B, f, ho, wo, k, 1, 0, p(ws["ones"]), p(d[f"b{b}/res/wT"]), p(ws["ones"]), p(ws["zeros"]), cprev, 0, 3, h, w, p(dr), st),
+                    "orcai_sepconv_planes")
+            dprev = dr
+        dx = torch.empty((B, H, W), **f32)
+        N.check(lib.orcai_conv0_bn_bwd_dx(p(v["x"]), H * W, p(dprev), B, H, W, k, p(d["raw/conv0/kernel"]), p(d["raw/conv0/bias"]), p(d["raw/bn0/mean"]), p(d["raw/bn0/var"]),
+                                          p(d["raw/bn0/gamma"]), p(d["raw/bn0/beta"]), BN_EPS, p(ws["sums0"]), p(dx), st), "orcai_conv0_bn_bwd_dx")
+        return dx
+
+
+def saliency(model, x: Tensor, label: int | None = None) -> Tensor:
+    """d(sum over snippets and steps of probs[:, t, label]) / dx of the predict-time network, f32 [B, H, W]; label=None sums over all labels."""
+    eg = EvalGrad(model)
+    probs, saved = eg.forward(x)
+    g = torch.zeros_like(probs)
+    if label is None:
+        g.fill_(1.0)
+    else:
+        g[:, :, label] = 1.0
+    return eg.backward(g, saved)

@@ -7,6 +7,7 @@ known without a GPU.
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
+    torch.ops.orcai.detect_wrt_input(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
     torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
 
 ``weights`` / ``stats`` are the trainable variables and the BatchNorm moving statistics in ``variable_spec()`` order (Keras layouts);
@@ -20,8 +21,16 @@ still alive raises instead of overwriting what that graph's backward needs (``fo
 whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
 detector.  ``spectrogram_wrt_pcm`` is ``spectrogram`` (same bits) whose backward delivers dL/dpcm (``orcai_spectrogram_bwd``; the three
 normalisation statistics are held constant), so the chain pcm -> spectrogram -> snippets -> probabilities is differentiable down to the
-waveform.  What does not exist: an input gradient in eval mode (there is no eval-mode backward at all) or on the f16 path (f32 models
-only); ``orcai::spectrogram`` itself has no backward, and the resampler is not differentiated.
+waveform.
+
+``detect_wrt_input`` is the PREDICT-TIME network (BatchNorm with the moving statistics, no Dropout, nothing written to ``stats``) with
+autograd w.r.t. ``x`` only: saliency, robustness probes, training something in front of the detector that will be deployed
+(orcai_amd/eval_grad.py: one orcai_sepconv_dgrad per separable conv, no weight-gradient launcher).  Its forward keeps what the backward
+reads in a tensor of its own, so any number of forwards may be alive at once.  ``forward`` / ``forward_wrt_input`` with training=False keep
+refusing a backward: they run the fused inference path, which stores nothing.
+
+What does not exist: a gradient w.r.t. the weights in eval mode, any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
+itself has no backward, and the resampler is not differentiated.
 """
 
 from __future__ import annotations
@@ -488,6 +497,116 @@ def _spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, 
 _LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_autograd, "Autograd")
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::detect_wrt_input
+# The inference network with the gradient w.r.t. the snippets (orcai_amd/eval_grad.py), built the way spectrogram_wrt_pcm is: an inner op that
+# also returns what the backward reads (`saved`, owned by the autograd graph: no "one open step" rule), and a functional backward op.  Weights
+# and statistics get no gradient; nothing is mutated.
+def _eval_grad(config: str, device: torch.device):
+    eng = _engine(config, device)
+    if getattr(eng, "_eval_grad", None) is None:
+        from orcai_amd.eval_grad import EvalGrad
+
+        eng._eval_grad = EvalGrad(eng.model)
+    return eng, eng._eval_grad
+
+
+@functools.lru_cache(maxsize=None)
+def _saved_per_snippet(config: str) -> int:
+    from orcai_amd.eval_grad import saved_layout
+
+    return saved_layout(_skeleton(config))[1]
+
+
+@torch.library.custom_op("orcai::detect_with_saved", mutates_args=())
+def detect_with_saved(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> tuple[Tensor, Tensor]:
+    """EvalGrad.forward: the eval-mode probabilities f32[B, steps, labels] and the flat f32 tensor of stored activations its backward reads."""
+    cfg = _parse(config)
+    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
+    if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32:
+        raise ValueError(f"orcai::detect_wrt_input: x must be f32 [B, {H}, {W}], got {x.dtype} {tuple(x.shape)}")
+    _check_vars(config, weights, stats)
+    eng, eg = _eval_grad(config, x.device)
+    if x.shape[0] == 0:
+        return x.new_empty((0, _out_steps(config), cfg["num_labels"])), x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        return eg.forward(x.detach().contiguous(), params=eng.flat(weights, stats))
+
+
+@detect_with_saved.register_fake
+def _detect_with_saved_fake(x, weights, stats, config):
+    cfg = _parse(config)
+    return (x.new_empty((x.shape[0], _out_steps(config), cfg["num_labels"]), dtype=torch.float32),
+            x.new_empty((x.shape[0] * _saved_per_snippet(config),), dtype=torch.float32))
+
+
+@torch.library.custom_op("orcai::detect_backward", mutates_args=())
+def detect_backward(grad: Tensor, saved: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
+    """EvalGrad.backward: dL/dx f32[B, H, W] from grad = dL/dprobs and the `saved` tensor orcai::detect_with_saved returned for the same weights."""
+    cfg = _parse(config)
+    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
+    _check_vars(config, weights, stats)
+    eng, eg = _eval_grad(config, grad.device)
+    if grad.shape[0] == 0:
+        return grad.new_empty((0, H, W))
+    with torch.cuda.device(grad.device):
+        return eg.backward(grad, saved, params=eng.flat(weights, stats))
+
+
+@detect_backward.register_fake
+def _detect_backward_fake(grad, saved, weights, stats, config):
+    H, W = (int(v) for v in _parse(config)["input_shape"][:2])
+    return grad.new_empty((grad.shape[0], H, W), dtype=torch.float32)
+
+
+_LIB.define("detect_wrt_input(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor")
+
+
+def detect_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
+    """The model in eval mode on snippets x[B][H][W]; its backward returns dL/dx when x requires grad (never a weight gradient)."""
+    return torch.ops.orcai.detect_wrt_input(x, weights, stats, config)
+
+
+def _detect_impl(x, weights, stats, config):
+    return torch.ops.orcai.detect_with_saved(x, weights, stats, config)[0]
+
+
+def _detect_fake(x, weights, stats, config):
+    return x.new_empty((x.shape[0], _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
+
+
+_LIB.impl("detect_wrt_input", _detect_impl, "CUDA")
+_LIB.impl("detect_wrt_input", _detect_impl, "CPU")  # (refuses: the checks name the missing GPU)
+torch.library.register_fake("orcai::detect_wrt_input", _detect_fake, lib=_LIB)
+
+
+class _DetectFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, config, n_weights, *variables):
+        weights, stats = list(variables[:n_weights]), list(variables[n_weights:])
+        with torch._C._AutoDispatchBelowAutograd():
+            probs, saved = torch.ops.orcai.detect_with_saved(x, weights, stats, config)
+        ctx.config, ctx.n_weights = config, n_weights
+        ctx.save_for_backward(saved, *[t.detach() for t in variables])
+        return probs
+
+    @staticmethod
+    def backward(ctx, grad):
+        saved, *variables = ctx.saved_tensors
+        n = ctx.n_weights
+        dx = torch.ops.orcai.detect_backward(grad.contiguous(), saved, list(variables[:n]), list(variables[n:]), ctx.config)
+        return (dx, None, None, *([None] * len(variables)))
+
+
+def _detect_autograd(x, weights, stats, config):
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _DetectFunction.apply(x, config, len(weights), *weights, *stats)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.detect_wrt_input(x, weights, stats, config)
+
+
+_LIB.impl("detect_wrt_input", _detect_autograd, "Autograd")
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
 @torch.library.custom_op("orcai::predict_spectrogram", mutates_args=())
 def predict_spectrogram(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
@@ -517,10 +636,12 @@ class OrcaiModule(torch.nn.Module):
     """A ResNetLSTM / ResNet1DConv as a torch.nn.Module: the trainable variables are parameters, the BatchNorm moving statistics buffers,
     both named after the Keras variables (param_name).  forward(x f32[B, H, W]) follows self.training; gradients reach the parameters
     only, and an x that requires grad raises -- unless input_grad=True: the module then calls orcai::forward_wrt_input, whose training-mode
-    backward also returns dL/dx (not in eval mode, not for f16 models).  Built from a model object or a model directory
-    (io.load_orcai_model).  dropout_seed of the n-th training forward: seed * 1000003 + n."""
+    backward also returns dL/dx (not in eval mode, not for f16 models).  input_grad="eval": as input_grad=True in .train(); in .eval() the
+    module calls orcai::detect_wrt_input, the predict-time network with a backward w.r.t. x (the parameters get no gradient, the statistics are
+    not touched).  Built from a model object or a model directory (io.load_orcai_model).  dropout_seed of the n-th training forward:
+    seed * 1000003 + n."""
 
-    def __init__(self, model, seed: int = 0, input_grad: bool = False):
+    def __init__(self, model, seed: int = 0, input_grad: bool | str = False):
         super().__init__()
         if isinstance(model, (str, os.PathLike)):
             from orcai_amd.io import load_orcai_model
@@ -538,7 +659,9 @@ class OrcaiModule(torch.nn.Module):
                 self.register_buffer(param_name(name), t)
                 self._stats.append(name)
         self.seed = int(seed)
-        self.input_grad = bool(input_grad)
+        if isinstance(input_grad, str) and input_grad != "eval":
+            raise ValueError(f"OrcaiModule: input_grad must be False, True or 'eval', got {input_grad!r}")
+        self.input_grad = input_grad if input_grad == "eval" else bool(input_grad)
         self.dropout_draws = 0
 
     def weights_list(self) -> list:
@@ -548,6 +671,8 @@ class OrcaiModule(torch.nn.Module):
         return [getattr(self, param_name(n)) for n in self._stats]
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.input_grad == "eval" and not self.training:
+            return torch.ops.orcai.detect_wrt_input(x, self.weights_list(), self.stats_list(), self.config)
         seed = 0
         if self.training:
             seed = (self.seed * 1000003 + self.dropout_draws) & 0x7FFFFFFFFFFFFFFF
