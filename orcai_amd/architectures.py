@@ -12,6 +12,7 @@ Weights are kept on the host as a dict of numpy arrays with Keras variable layou
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 from pathlib import Path
@@ -53,6 +54,82 @@ def depthwise_kernel_layout(dwk: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(out.reshape(cq, 4, k * k).transpose(0, 2, 1))
 
 
+class ParamLayout:
+    """Where each variable sits in the two flat f32 buffers the device code reads -- the trainable variables (w) and the BatchNorm moving statistics
+    (s), each concatenated in variable_spec() order: {name: (offset, numel, shape)}.  Host arithmetic only; built once per model (model.layout())."""
+
+    def __init__(self, spec):
+        self.w, self.s, self.n_w, self.n_s = {}, {}, 0, 0
+        for name, shape, _, trainable in spec:
+            n = int(np.prod(shape))
+            if trainable:
+                self.w[name], self.n_w = (self.n_w, n, tuple(shape)), self.n_w + n
+            else:
+                self.s[name], self.n_s = (self.n_s, n, tuple(shape)), self.n_s + n
+        self.w_names, self.s_names = list(self.w), list(self.s)
+
+    def flatten(self, weights: dict, device) -> tuple:
+        """(wflat, sflat) on `device`, contiguous f32, from {name: numpy array or tensor} (tensors already there are not moved)."""
+        def cat(names):
+            return torch.cat([torch.as_tensor(weights[n]).detach().reshape(-1) for n in names]).to(device=device, dtype=torch.float32)
+
+        return cat(self.w_names), cat(self.s_names)
+
+    def split_w(self, flat: torch.Tensor) -> list:
+        """Views of a flat tensor of the trainable variables (weights or their gradient), in spec order and variable shapes."""
+        return [flat[o : o + n].view(shape) for o, n, shape in self.w.values()]
+
+
+class PreparePlan:
+    """Kernel-layout tensors made on the device from flat weights (ParamLayout order): rows of int32[8] for ONE orcai_prepare_inference launch (and
+    of int32[7] for one orcai_pack_lstm, if any), the 256-byte aligned regions of one f32 buffer they fill, and {key: (offset, shape)} views of it."""
+
+    def __init__(self, layout: ParamLayout):
+        self.layout, self.desc, self.lstm, self.views, self.size = layout, [], [], {}, 0
+        self._tables = {}  # device -> the descriptor tensors, uploaded once
+
+    def region(self, numel: int) -> int:
+        off = self.size
+        self.size += (numel + 63) // 64 * 64
+        return off
+
+    def add(self, kind: int, key: str, shape, *fields) -> None:
+        """One row [kind, offset of a new region viewed as `shape` under `key`, *fields, 0 ...] (the kinds: include/orcai_hip.h)."""
+        off = self.region(math.prod(shape))
+        self.desc.append(([kind, off, *fields] + [0] * 6)[:8])
+        self.views[key] = (off, tuple(shape))
+
+    def copy(self, key: str, src: str, shape=None) -> None:
+        """The variable `src` as it is, viewed as `shape` (default: its own)."""
+        off, n, own = self.layout.w[src]
+        self.add(2, key, own if shape is None else shape, n, off)
+
+    def dw(self, key: str, src: str, kind: int = 1) -> None:
+        """Depthwise taps (k, k, c, 1) as [ceil(c/4)][k*k][4] (depthwise_kernel_layout); kind 4: reversed, for the data gradient."""
+        k, _, c, _ = self.layout.w[src][2]
+        self.add(kind, key, ((c + 3) // 4, k * k, 4), c, self.layout.w[src][0], k)
+
+    def fold(self, prefix: str, bn: str, bias: str | None = None) -> None:
+        """`prefix`/scale and /shift of a BatchNorm with its moving statistics, the bias in front of it folded in."""
+        w, s = self.layout.w, self.layout.s
+        c = w[bn + "/gamma"][1]
+        self.add(0, prefix + "/scale", (c,), c, w[bn + "/gamma"][0], w[bn + "/beta"][0], s[bn + "/mean"][0], s[bn + "/var"][0], -1 if bias is None else w[bias][0])
+        self.views[prefix + "/shift"] = (self.region(c), (c,))  # the row writes both: the shift goes into the next region
+
+    def run(self, wflat: torch.Tensor, sflat: torch.Tensor) -> dict:
+        """The views, in one fresh buffer on wflat's device."""
+        dev = wflat.device
+        if dev not in self._tables:
+            self._tables[dev] = [torch.tensor(rows, dtype=torch.int32).to(dev) if rows else None for rows in (self.desc, self.lstm)]
+        desc, lstm = self._tables[dev]
+        lib, st = N.lib(), N.stream_ptr()
+        out = torch.empty(self.size, dtype=torch.float32, device=dev)
+        N.check(lib.orcai_prepare_inference(wflat.data_ptr(), sflat.data_ptr(), desc.data_ptr(), len(self.desc), BN_EPS, out.data_ptr(), st), "orcai_prepare_inference")
+        if lstm is not None:
+            N.check(lib.orcai_pack_lstm(wflat.data_ptr(), lstm.data_ptr(), len(self.lstm), out.data_ptr(), None, st), "orcai_pack_lstm")
+        return {key: out[o : o + math.prod(shape)].view(shape) for key, (o, shape) in self.views.items()}
+
+
 class ResNetLSTM:
     """CNN with residual connections + 2 bidirectional LSTM layers (architectures.py:120-241)."""
 
@@ -88,6 +165,8 @@ class ResNetLSTM:
         self._init_weights(np.random.default_rng(seed))
         self._dev = None  # folded device copies
         self._ws = {}
+        self._layout = self._plan = None
+        self.weights_version = 0  # bumped by set_weights_dict: what caches of device copies outside the model compare (EvalGrad)
         import os
 
         # inference, k = 3: the entry convolution is computed inside the first separable convolution (orcai_conv0_sepconv); the
@@ -199,16 +278,21 @@ class ResNetLSTM:
             self.weights[name] = np.ascontiguousarray(w, dtype=np.float32)
 
     # ------------------------------------------------------------------ keras-shaped accessors
+    def layout(self) -> ParamLayout:
+        if self._layout is None:
+            self._layout = ParamLayout(self.variable_spec())
+        return self._layout
+
     @property
     def trainable_weights(self):
-        return [self.weights[n] for n, _, _, t in self.variable_spec() if t]
+        return [self.weights[n] for n in self.layout().w_names]
 
     @property
     def non_trainable_weights(self):
-        return [self.weights[n] for n, _, _, t in self.variable_spec() if not t]
+        return [self.weights[n] for n in self.layout().s_names]
 
     def count_params(self) -> int:
-        return int(sum(int(np.prod(s)) for _, s, _, _ in self.variable_spec()))
+        return self.layout().n_w + self.layout().n_s
 
     def set_weights_dict(self, weights: dict) -> None:
         for name, shape, _, _ in self.variable_spec():
@@ -219,6 +303,7 @@ class ResNetLSTM:
                 raise ValueError(f"weight {name}: shape {w.shape} != {shape}")
             self.weights[name] = np.ascontiguousarray(w)
         self._dev = None
+        self.weights_version += 1
         if self._half_engine is not None:
             self._half_engine._dev = None
 
@@ -282,105 +367,71 @@ class ResNetLSTM:
         return d
 
     # ------------------------------------------------------------------ prepare() from device weights (orcai_prepare_inference)
-    def _device_plan(self) -> dict:
-        """Descriptor tables of prepare_device, built once: {"desc": int32 [n][8] for orcai_prepare_inference, "lstm": int32 [n][7] for
-        orcai_pack_lstm (or None), "views": {prepare() key: (offset, shape)}, "size": floats}.  Every tensor starts 256-byte aligned."""
-        if getattr(self, "_plan", None) is not None:
+    def _device_plan(self) -> PreparePlan:
+        """prepare_device's plan, filled once: one view per prepare() key."""
+        if self._plan is not None:
             return self._plan
-        woff, soff, o1, o2 = {}, {}, 0, 0
-        for name, shape, _, trainable in self.variable_spec():
-            n = int(np.prod(shape))
-            if trainable:
-                woff[name], o1 = o1, o1 + n
-            else:
-                soff[name], o2 = o2, o2 + n
-        plan = {"desc": [], "lstm": [], "views": {}, "size": 0}
-
-        def region(numel):
-            off = plan["size"]
-            plan["size"] += (numel + 63) // 64 * 64
-            return off
-
-        def copy(key, src, shape):
-            n = int(np.prod(shape))
-            off = region(n)
-            plan["desc"].append([2, off, n, woff[src], 0, 0, 0, 0])
-            plan["views"][key] = (off, tuple(shape))
-
-        def fold(prefix, bn, bias=None):
-            c = self.weights[bn + "/gamma"].shape[0]
-            off = region(2 * ((c + 63) // 64 * 64))
-            plan["desc"].append([0, off, c, woff[bn + "/gamma"], woff[bn + "/beta"], soff[bn + "/mean"], soff[bn + "/var"], -1 if bias is None else woff[bias]])
-            plan["views"][prefix + "/scale"] = (off, (c,))
-            plan["views"][prefix + "/shift"] = (off + (c + 63) // 64 * 64, (c,))
-
-        k = self.kernel_size
-        copy("conv0/w", "conv0/kernel", (k * k, ENTRY_FILTERS))
-        fold("conv0", "bn0", "conv0/bias")
+        plan, k = PreparePlan(self.layout()), self.kernel_size
+        plan.copy("conv0/w", "conv0/kernel", (k * k, ENTRY_FILTERS))
+        plan.fold("conv0", "bn0", "conv0/bias")
 
         def sep(name, bn):
-            k_, _, c, _ = self.weights[name + "/depthwise"].shape
-            cq = (c + 3) // 4
-            off = region(cq * k * k * 4)
-            plan["desc"].append([1, off, c, woff[name + "/depthwise"], k, 0, 0, 0])
-            plan["views"][name + "/dw"] = (off, (cq, k * k, 4))
-            copy(name + "/pw", name + "/pointwise", self.weights[name + "/pointwise"].shape[2:])
-            fold(name, bn, name + "/bias")
+            plan.dw(name + "/dw", name + "/depthwise")
+            plan.copy(name + "/pw", name + "/pointwise", plan.layout.w[name + "/pointwise"][2][2:])
+            plan.fold(name, bn, name + "/bias")
 
         for b in range(1, len(self.filters) + 1):
             sep(f"b{b}/sep_a", f"b{b}/bn_a")
             sep(f"b{b}/sep_b", f"b{b}/bn_b")
-            copy(f"b{b}/res/w", f"b{b}/res/kernel", self.weights[f"b{b}/res/kernel"].shape[2:])
-            copy(f"b{b}/res/b", f"b{b}/res/bias", self.weights[f"b{b}/res/bias"].shape)
+            plan.copy(f"b{b}/res/w", f"b{b}/res/kernel", plan.layout.w[f"b{b}/res/kernel"][2][2:])
+            plan.copy(f"b{b}/res/b", f"b{b}/res/bias")
         sep("sep_f", "bn_f")
-        self._device_plan_head(plan, woff, region, copy, fold)
-        plan["desc"] = torch.tensor(plan["desc"], dtype=torch.int32)
-        plan["lstm"] = torch.tensor(plan["lstm"], dtype=torch.int32) if plan["lstm"] else None
+        self._device_plan_head(plan)
         self._plan = plan
         return plan
 
-    def _device_plan_head(self, plan, woff, region, copy, fold) -> None:
-        u = self.lstm_units
+    def _device_plan_head(self, plan: PreparePlan) -> None:
+        u, w = self.lstm_units, plan.layout.w
         for layer in (1, 2):
-            fin = self.weights[f"lstm{layer}/fwd/kernel"].shape[0]
-            W, bvec, U = region(fin * 8 * u), region(8 * u), region(2 * u * 4 * u)
+            fin = w[f"lstm{layer}/fwd/kernel"][2][0]
+            W, bvec, U = plan.region(fin * 8 * u), plan.region(8 * u), plan.region(2 * u * 4 * u)
             for d, name in enumerate(("fwd", "bwd")):  # _prepare_head's permuted columns, concatenation and stack: orcai_pack_lstm, mode 0
-                plan["lstm"].append([woff[f"lstm{layer}/{name}/kernel"], W, fin, u, 8 * u, d * 4 * u, 0])
-                plan["lstm"].append([woff[f"lstm{layer}/{name}/bias"], bvec, 1, u, 8 * u, d * 4 * u, 0])
-                plan["lstm"].append([woff[f"lstm{layer}/{name}/recurrent"], U + d * u * 4 * u, u, u, 4 * u, 0, 0])
-            plan["views"].update({f"lstm{layer}/W": (W, (fin, 8 * u)), f"lstm{layer}/b": (bvec, (8 * u,)), f"lstm{layer}/U": (U, (2, u, 4 * u))})
-        copy("dense1/W", "dense1/kernel", self.weights["dense1/kernel"].shape)
-        copy("dense1/b", "dense1/bias", self.weights["dense1/bias"].shape)
-        fold("dense1", "bn_d")
-        copy("dense2/W", "dense2/kernel", self.weights["dense2/kernel"].shape)
-        copy("dense2/b", "dense2/bias", self.weights["dense2/bias"].shape)
+                plan.lstm.append([w[f"lstm{layer}/{name}/kernel"][0], W, fin, u, 8 * u, d * 4 * u, 0])
+                plan.lstm.append([w[f"lstm{layer}/{name}/bias"][0], bvec, 1, u, 8 * u, d * 4 * u, 0])
+                plan.lstm.append([w[f"lstm{layer}/{name}/recurrent"][0], U + d * u * 4 * u, u, u, 4 * u, 0, 0])
+            plan.views.update({f"lstm{layer}/W": (W, (fin, 8 * u)), f"lstm{layer}/b": (bvec, (8 * u,)), f"lstm{layer}/U": (U, (2, u, 4 * u))})
+        plan.copy("dense1/W", "dense1/kernel")
+        plan.copy("dense1/b", "dense1/bias")
+        plan.fold("dense1", "bn_d")
+        plan.copy("dense2/W", "dense2/kernel")
+        plan.copy("dense2/b", "dense2/bias")
 
     def prepare_device(self, wflat: torch.Tensor, sflat: torch.Tensor) -> dict:
         """prepare()'s tensors, bit for bit, built on the device from f32 cuda tensors wflat = the trainable variables and sflat = the BatchNorm
         moving statistics, each flattened and concatenated in variable_spec() order: no host round trip.  Views of one fresh buffer; the model's
         own cache (prepare()) is not touched."""
-        plan = self._device_plan()
-        dev = wflat.device
         if not (wflat.is_cuda and wflat.dtype == torch.float32 and wflat.is_contiguous() and sflat.is_cuda and sflat.dtype == torch.float32 and sflat.is_contiguous()):
             raise ValueError("prepare_device: wflat / sflat must be contiguous f32 cuda tensors")
-        n_w = sum(int(np.prod(s)) for _, s, _, t in self.variable_spec() if t)
-        n_s = sum(int(np.prod(s)) for _, s, _, t in self.variable_spec() if not t)
-        if wflat.numel() != n_w or sflat.numel() != n_s:
-            raise ValueError(f"prepare_device: expected {n_w} weights and {n_s} statistics, got {wflat.numel()} and {sflat.numel()}")
-        if plan.get("dev") != dev:  # the descriptor tables on this device (uploaded once)
-            plan["desc_dev"] = plan["desc"].to(dev)
-            plan["lstm_dev"] = None if plan["lstm"] is None else plan["lstm"].to(dev)
-            plan["dev"] = dev
-        lib, st = N.lib(), N.stream_ptr()
-        out = torch.empty(plan["size"], dtype=torch.float32, device=dev)
-        N.check(lib.orcai_prepare_inference(wflat.data_ptr(), sflat.data_ptr(), plan["desc_dev"].data_ptr(), int(plan["desc"].shape[0]), BN_EPS, out.data_ptr(), st),
-                "orcai_prepare_inference")
-        if plan["lstm_dev"] is not None:
-            N.check(lib.orcai_pack_lstm(wflat.data_ptr(), plan["lstm_dev"].data_ptr(), int(plan["lstm"].shape[0]), out.data_ptr(), None, st), "orcai_pack_lstm")
-        return {key: out[o : o + int(np.prod(shape))].view(shape) for key, (o, shape) in plan["views"].items()}
+        lay = self.layout()
+        if wflat.numel() != lay.n_w or sflat.numel() != lay.n_s:
+            raise ValueError(f"prepare_device: expected {lay.n_w} weights and {lay.n_s} statistics, got {wflat.numel()} and {sflat.numel()}")
+        return self._device_plan().run(wflat, sflat)
+
+    @contextlib.contextmanager
+    def bound(self, prepared: dict):
+        """Run the enclosed calls on `prepared` (prepare_device's tensors) instead of the model's own weights; the previous binding returns afterwards."""
+        previous, self._dev = self._dev, prepared
+        try:
+            yield self
+        finally:
+            self._dev = previous
 
     def padded_width(self, w: int) -> int:
         return (w + self.kernel_size // 2 + 3) & ~3
+
+    def plane_shape(self, c: int, h: int, w: int) -> tuple:
+        """One image's zero-padded f32 planes [channel quad][HP][WP][4] ("Padded plane layout" in csrc/model_fwd.hip)."""
+        return ((c + 3) // 4, h + 2 * (self.kernel_size // 2), self.padded_width(w), 4)
 
     def _buffers(self, B: int, first: int = 1, last: int | None = None, need_input: bool = True, height: int | None = None) -> dict:
         """Zero-padded activation planes of residual blocks first..last for a trunk chunk of B snippets (see "Padded plane
@@ -393,10 +444,9 @@ class ResNetLSTM:
             return have[1]
         shapes = self.stage_shapes(height)
         dev = torch.device("cuda", torch.cuda.current_device())
-        R = self.kernel_size // 2
 
-        def planes(c, h, w):  # [B][channel quad][HP][WP][4]
-            return torch.zeros((B, (c + 3) // 4, h + 2 * R, self.padded_width(w), 4), dtype=torch.float32, device=dev)
+        def planes(c, h, w):
+            return torch.zeros((B, *self.plane_shape(c, h, w)), dtype=torch.float32, device=dev)
 
         ws = {}
         if need_input:
@@ -814,9 +864,9 @@ class ResNet1DConv(ResNetLSTM):
         k1 = FINAL_FILTERS  # k_size = x.shape[2] after the frequency mean = the channel count (architectures.py:108)
         return [("conv1d/kernel", (k1, FINAL_FILTERS, self.num_labels), self.conv_kind, True), ("conv1d/bias", (self.num_labels,), "zeros", True)]
 
-    def _device_plan_head(self, plan, woff, region, copy, fold) -> None:
-        copy("conv1d/W", "conv1d/kernel", self.weights["conv1d/kernel"].shape)
-        copy("conv1d/b", "conv1d/bias", self.weights["conv1d/bias"].shape)
+    def _device_plan_head(self, plan: PreparePlan) -> None:
+        plan.copy("conv1d/W", "conv1d/kernel")
+        plan.copy("conv1d/b", "conv1d/bias")
 
     def _prepare_head(self, d: dict) -> None:
         d["conv1d/W"] = self._upload(self.weights["conv1d/kernel"])

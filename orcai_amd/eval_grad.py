@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from orcai_amd import _native as N
-from orcai_amd.architectures import BN_EPS, DENSE_UNITS, ENTRY_FILTERS, FINAL_FILTERS
+from orcai_amd.architectures import BN_EPS, DENSE_UNITS, ENTRY_FILTERS, FINAL_FILTERS, PreparePlan
 
 Tensor = torch.Tensor
 
@@ -54,14 +54,9 @@ def compose_dgrad(lib, g: Tensor, y_gate, x_gate, B: int, Cin: int, Cout: int, H
 def saved_layout(model) -> tuple[list, int]:
     """[(name, offset, shape)] per snippet and the floats per snippet of ``saved``: tensor `name` of a batch of B snippets is
     saved[B * offset : B * (offset + prod(shape))] viewed as [B, *shape].  Host arithmetic only (the fake implementations use it)."""
-    k = model.kernel_size
-    R = k // 2
+    planes = model.plane_shape
     shapes = model.stage_shapes()
     H, W = model.input_hw
-
-    def planes(c, h, w):
-        return ((c + 3) // 4, h + 2 * R, model.padded_width(w), 4)
-
     items = [("y0", planes(ENTRY_FILTERS, H, W))]
     for b, f in enumerate(model.filters, start=1):
         h, w, _ = shapes[b - 1]
@@ -111,88 +106,52 @@ class EvalGrad:
             self.lib = N.lib()
         return self.lib
 
-    def _offsets(self):
-        woff, soff, o1, o2 = {}, {}, 0, 0
-        for name, shape, _, trainable in self.model.variable_spec():
-            n = int(np.prod(shape))
-            if trainable:
-                woff[name], o1 = (o1, tuple(shape)), o1 + n
-            else:
-                soff[name], o2 = (o2, tuple(shape)), o2 + n
-        return woff, soff
-
-    def _extra_plan(self):
-        """Descriptors of the backward's own operands for orcai_prepare_inference (kinds 3, 4, 5): per separable conv wts = scale (.) pointwise^T
+    def _extra_plan(self) -> PreparePlan:
+        """The backward's own operands from flat device weights (orcai_prepare_inference kinds 3, 4, 5): per separable conv wts = scale (.) pointwise^T
         and the reversed taps, per block the transposed residual kernel."""
         if self._plan is not None:
             return self._plan
-        m, k = self.model, self.model.kernel_size
-        woff, soff = self._offsets()
-        desc, views, size = [], {}, 0
-
-        def region(numel):
-            nonlocal size
-            off = size
-            size += (numel + 63) // 64 * 64
-            return off
-
+        m, lay = self.model, self.model.layout()
+        plan = PreparePlan(lay)
         convs, c = [], ENTRY_FILTERS
         for b, f in enumerate(m.filters, start=1):
             convs += [(f"b{b}/sep_a", f"b{b}/bn_a", c, f), (f"b{b}/sep_b", f"b{b}/bn_b", f, f)]
-            off = region(c * f)
-            desc.append([5, off, c * f, woff[f"b{b}/res/kernel"][0], c, f, 0, 0])
-            views[f"b{b}/res/wT"] = (off, (f, c))
+            plan.add(5, f"b{b}/res/wT", (f, c), c * f, lay.w[f"b{b}/res/kernel"][0], c, f)
             c = f
         convs.append(("sep_f", "bn_f", c, FINAL_FILTERS))
         for name, bn, cin, cout in convs:
-            off = region(cin * cout)
-            desc.append([3, off, cout, woff[bn + "/gamma"][0], soff[bn + "/var"][0], woff[name + "/pointwise"][0], cin, 0])
-            views[name + "/wts"] = (off, (cout, cin))
-            cq = (cin + 3) // 4
-            off = region(cq * k * k * 4)
-            desc.append([4, off, cin, woff[name + "/depthwise"][0], k, 0, 0, 0])
-            views[name + "/dw_rev"] = (off, (cq, k * k, 4))
-        self._plan = {"desc": torch.tensor(desc, dtype=torch.int32), "views": views, "size": size, "convs": convs, "dev": None}
-        return self._plan
+            plan.add(3, name + "/wts", (cout, cin), cout, lay.w[bn + "/gamma"][0], lay.s[bn + "/var"][0], lay.w[name + "/pointwise"][0], cin)
+            plan.dw(name + "/dw_rev", name + "/depthwise", kind=4)
+        self._plan = plan
+        return plan
 
     def bind(self, wflat: Tensor, sflat: Tensor) -> dict:
         """Everything forward and backward read, from flat device weights: prepare_device's folded inference tensors, the backward's operands
         (one more orcai_prepare_inference launch) and views of the raw entry-conv variables."""
-        m, plan = self.model, self._extra_plan()
-        d = dict(m.prepare_device(wflat, sflat))
-        dev = wflat.device
-        if plan["dev"] != dev:
-            plan["desc_dev"], plan["dev"] = plan["desc"].to(dev), dev
-        out = torch.empty(plan["size"], dtype=torch.float32, device=dev)
-        N.check(self._lib().orcai_prepare_inference(wflat.data_ptr(), sflat.data_ptr(), plan["desc_dev"].data_ptr(), int(plan["desc"].shape[0]), BN_EPS, out.data_ptr(),
-                                                    N.stream_ptr()), "orcai_prepare_inference")
-        for key, (o, shape) in plan["views"].items():
-            d[key] = out[o : o + int(np.prod(shape))].view(shape)
+        d = dict(self.model.prepare_device(wflat, sflat))
+        d.update(self._extra_plan().run(wflat, sflat))
         # the heads' data-gradient GEMMs run on the forward GEMM kernel with transposed operands: orcai_gemm_strided splits K with float atomics
         # for these shapes, and this gradient is bit-reproducible
         for key in ("dense2/W", "dense1/W", "lstm1/W", "lstm2/W"):
             if key in d:
                 d[key + "T"] = d[key].t().contiguous()
-        woff, soff = self._offsets()
-        for name in ("conv0/kernel", "conv0/bias", "bn0/gamma", "bn0/beta"):
-            o, shape = woff[name]
-            d["raw/" + name] = wflat[o : o + int(np.prod(shape))]
-        for name in ("bn0/mean", "bn0/var"):
-            o, shape = soff[name]
-            d["raw/" + name] = sflat[o : o + int(np.prod(shape))]
+        lay = self.model.layout()
+        for flat, table, names in ((wflat, lay.w, ("conv0/kernel", "conv0/bias", "bn0/gamma", "bn0/beta")), (sflat, lay.s, ("bn0/mean", "bn0/var"))):
+            for name in names:
+                o, n, _ = table[name]
+                d["raw/" + name] = flat[o : o + n]
         return d
 
     def _params(self, params, device) -> dict:
         if params is not None:
             return self.bind(*params)
-        if self._own is None or self._own[0] != device:
-            spec = self.model.variable_spec()
-            flat = lambda tr: torch.from_numpy(np.concatenate([self.model.weights[n].reshape(-1) for n, _, _, t in spec if t == tr]).astype(np.float32)).to(device)  # noqa: E731
-            self._own = (device, self.bind(flat(True), flat(False)))
+        m = self.model
+        if self._own is None or self._own[0] != (device, m.weights_version):  # set_weights_dict bumps the version: never the old network
+            self._own = ((device, m.weights_version), self.bind(*m.layout().flatten(m.weights, device)))
         return self._own[1]
 
     def invalidate(self) -> None:
-        """Forget the device copies of the model's own weights (after model.set_weights_dict)."""
+        """Forget the device copies of the model's own weights (set_weights_dict does it too; this is for weights edited in place)."""
         self._own = None
 
     # ------------------------------------------------------------------ saved
@@ -267,11 +226,10 @@ class EvalGrad:
         if ws is not None:
             return ws
         m = self.model
-        R = m.kernel_size // 2
         shapes = m.stage_shapes()
 
         def planes(c, h, w):
-            return torch.zeros((B, (c + 3) // 4, h + 2 * R, m.padded_width(w), 4), dtype=torch.float32, device=device)
+            return torch.zeros((B, *m.plane_shape(c, h, w)), dtype=torch.float32, device=device)
 
         ws = {"sums0": torch.zeros(32, dtype=torch.float64, device=device), "ones": torch.ones(64, device=device), "zeros": torch.zeros(64, device=device)}
         c = ENTRY_FILTERS

@@ -37,7 +37,6 @@ from __future__ import annotations
 
 import functools
 import json
-import math
 import os
 import weakref
 from pathlib import Path
@@ -97,13 +96,9 @@ def _out_steps(config: str) -> int:
     return h
 
 
-def _spec_split(config: str):
-    spec = _skeleton(config).variable_spec()
-    return [tuple(s) for _, s, _, t in spec if t], [tuple(s) for _, s, _, t in spec if not t]
-
-
 def _check_vars(config: str, weights, stats) -> None:
-    ws, ss = _spec_split(config)
+    lay = _skeleton(config).layout()
+    ws, ss = [v[2] for v in lay.w.values()], [v[2] for v in lay.s.values()]
     got_w, got_s = [tuple(w.shape) for w in weights], [tuple(s.shape) for s in stats]
     if got_w != ws or got_s != ss:
         raise ValueError(f"orcai torch ops: weights / stats do not follow variable_spec() of the config ({len(ws)} weights, {len(ss)} statistics expected, "
@@ -111,6 +106,39 @@ def _check_vars(config: str, weights, stats) -> None:
     for t in list(weights) + list(stats):
         if t.dtype != torch.float32 or not t.is_cuda:
             raise ValueError("orcai torch ops: weights and stats must be f32 cuda tensors")
+
+
+def _check_x(config: str, x: Tensor, who: str) -> None:
+    H, W = (int(v) for v in _parse(config)["input_shape"][:2])
+    if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32:
+        raise ValueError(f"{who}: x must be f32 [B, {H}, {W}], got {x.dtype} {tuple(x.shape)}")
+
+
+def _check_pcm(pcm: Tensor, who: str) -> None:
+    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
+        raise ValueError(f"{who}: pcm must be a 1-d f32 cuda tensor")
+
+
+def _probs_fake(x, weights, stats, config, training=None, dropout_seed=None):
+    return x.new_empty((x.shape[0], _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
+
+
+def _flat_grad_fake(grad, config):
+    return grad.new_empty((_skeleton(config).layout().n_w,), dtype=torch.float32)
+
+
+_LIB = torch.library.Library("orcai", "FRAGMENT")
+
+
+def _register(name: str, schema: str, impl, fake, autograd) -> None:
+    """An op on _LIB: torch.library.custom_op registers no autograd formula for an op that mutates an argument (orcai::forward's moving statistics) and
+    none around an inner op, so these are defined with torch.library directly: the CUDA kernel (the CPU one refuses: its checks name the missing
+    GPU), the fake implementation, and an Autograd kernel around a torch.autograd.Function that redispatches below autograd."""
+    _LIB.define(name + schema)
+    _LIB.impl(name, impl, "CUDA")
+    _LIB.impl(name, impl, "CPU")
+    torch.library.register_fake("orcai::" + name, fake, lib=_LIB)
+    _LIB.impl(name, autograd, "Autograd")
 
 
 # ---------------------------------------------------------------------------------------------------------------- per (config, device) state
@@ -137,7 +165,8 @@ class _Engine:
         return self._trainer
 
     def flat(self, weights, stats):
-        return torch.cat([w.detach().reshape(-1) for w in weights]), torch.cat([s.detach().reshape(-1) for s in stats])
+        lay = self.model.layout()
+        return lay.flatten(dict(zip(lay.w_names + lay.s_names, [*weights, *stats])), self.device)
 
     def eval_forward(self, x: Tensor, weights, stats) -> Tensor:
         m = self.model
@@ -146,20 +175,14 @@ class _Engine:
         out = torch.empty((B, m.out_steps, m.num_labels), dtype=torch.float32, device=x.device)
         if B == 0:
             return out
-        m._dev = m.prepare_device(*self.flat(weights, stats))
-        try:
+        with m.bound(m.prepare_device(*self.flat(weights, stats))):
             m.forward_device(x.detach().contiguous().view(-1), H * W, B, out)
-        finally:
-            m._dev = None
         return out
 
     def predict(self, spec: Tensor, weights, stats) -> Tensor:
         m = self.model
-        m._dev = m.prepare_device(*self.flat(weights, stats))
-        try:
+        with m.bound(m.prepare_device(*self.flat(weights, stats))):
             return m.predict_spectrogram(spec.detach().contiguous())
-        finally:
-            m._dev = None
 
     def train_forward(self, x: Tensor, weights, stats, dropout_seed: int) -> Tensor:
         from orcai_amd.training import BN_MOMENTUM
@@ -175,13 +198,11 @@ class _Engine:
         m, P = self.model, tr.P
         H, W = m.input_hw
         torch.cat([w.detach().reshape(-1) for w in weights], out=P.w)
-        n_s = sum(k for _, k in P.stat_offsets.values())
-        torch.cat([s.detach().reshape(-1) for s in stats], out=P.stats_flat[:n_s])
+        torch.cat([s.detach().reshape(-1) for s in stats], out=P.stats_flat)
         tr.seed = int(dropout_seed)  # the masks Trainer(seed=dropout_seed) draws at its step 0 (the counter is never advanced here)
         probs = tr.forward_train(x.detach().contiguous().view(-1), H * W, int(x.shape[0]))
         P.ema_all(BN_MOMENTUM)  # batch statistics -> moving statistics, the kernel Trainer.apply runs
-        names = [n for n, _, t in P.spec if not t]
-        for s, n in zip(stats, names):
+        for s, n in zip(stats, P.layout.s_names):
             s.copy_(P.stats[n].view(s.shape))
         return probs
 
@@ -227,16 +248,18 @@ def _bins(sampling_rate: int, nfft: int, freq_hi: float) -> int:
     return crop_indices(fft_frequencies(sampling_rate, nfft), [0, freq_hi])[1]
 
 
+def _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo=0.0, q_hi=1.0) -> dict:
+    return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
+
+
 @torch.library.custom_op("orcai::spectrogram", mutates_args=())
 def spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
     """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate): frequencies 0 .. freq_hi, quantile normalisation (q_lo, q_hi)."""
     from orcai_amd.frontend import get_frontend
 
-    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
-        raise ValueError("orcai::spectrogram: pcm must be a 1-d f32 cuda tensor")
-    sp = {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
+    _check_pcm(pcm, "orcai::spectrogram")
     with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(pcm, sp)
+        return get_frontend(pcm.device).make_spectrogram(pcm, _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi))
 
 
 @spectrogram.register_fake
@@ -245,12 +268,13 @@ def _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
     return pcm.new_empty((T, _bins(sampling_rate, nfft, freq_hi)), dtype=torch.float32)
 
 
-# ---------------------------------------------------------------------------------------------------------------- orcai::forward
-# torch.library.custom_op registers no autograd formula for an op that mutates an argument (the moving statistics), so orcai::forward is
-# defined with torch.library directly: a CUDA kernel, the fake implementation, and an Autograd kernel around a torch.autograd.Function that
-# redispatches below autograd.  Its backward is the functional op orcai::forward_backward.
-_LIB = torch.library.Library("orcai", "FRAGMENT")
-_LIB.define("forward(Tensor x, Tensor[] weights, Tensor(a!)[] stats, str config, bool training, SymInt dropout_seed) -> Tensor")
+# ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
+# forward_wrt_input is orcai::forward with the gradient w.r.t. the snippets as well: for something trainable or differentiable IN FRONT of the
+# detector (a learnable gain / equaliser / denoiser on the spectrogram, differentiable augmentation, adversarial or gradient-penalty training,
+# saliency of a training loss).  Its own op, because orcai::forward's refusal of x.requires_grad is part of that op's contract; the CUDA / CPU /
+# fake implementations are shared, and so are the per-(config, device) engine and its one open step.  The backwards are the functional ops
+# orcai::forward_backward and orcai::forward_wrt_input_backward.  Training mode only: the eval-mode forward (moving statistics) has no backward.
+_FORWARD_SCHEMA = "(Tensor x, Tensor[] weights, Tensor(a!)[] stats, str config, bool training, SymInt dropout_seed) -> Tensor"
 
 
 def forward(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, training: bool, dropout_seed: int) -> Tensor:
@@ -260,11 +284,13 @@ def forward(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, 
     return torch.ops.orcai.forward(x, weights, stats, config, training, dropout_seed)
 
 
+def forward_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, training: bool, dropout_seed: int) -> Tensor:
+    """orcai::forward whose training-mode backward also returns dL/dx (f32 [B, H, W]) when x requires grad."""
+    return torch.ops.orcai.forward_wrt_input(x, weights, stats, config, training, dropout_seed)
+
+
 def _forward_impl(x, weights, stats, config, training, dropout_seed):
-    cfg = _parse(config)
-    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
-    if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32:
-        raise ValueError(f"orcai::forward: x must be f32 [B, {H}, {W}], got {x.dtype} {tuple(x.shape)}")
+    _check_x(config, x, "orcai::forward")
     _check_vars(config, weights, stats)
     eng = _engine(config, x.device)
     with torch.cuda.device(x.device):
@@ -273,16 +299,6 @@ def _forward_impl(x, weights, stats, config, training, dropout_seed):
                 raise ValueError("orcai::forward(training=True): empty batch")
             return eng.train_forward(x, weights, stats, dropout_seed)
         return eng.eval_forward(x, weights, stats)
-
-
-_LIB.impl("forward", _forward_impl, "CUDA")
-_LIB.impl("forward", _forward_impl, "CPU")  # (refuses: the checks name the missing GPU)
-
-
-@torch.library.register_fake("orcai::forward", lib=_LIB)
-def _forward_fake(x, weights, stats, config, training, dropout_seed):
-    _parse(config)
-    return x.new_empty((x.shape[0], _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
 
 
 @torch.library.custom_op("orcai::forward_backward", mutates_args=())
@@ -294,67 +310,7 @@ def forward_backward(grad: Tensor, probs: Tensor, config: str) -> Tensor:
 
 @forward_backward.register_fake
 def _forward_backward_fake(grad, probs, config):
-    return grad.new_empty((sum(math.prod(s) for s in _spec_split(config)[0]),), dtype=torch.float32)
-
-
-class _GraphToken:
-    """Lives on the autograd node of a training forward: while it does, that forward's backward may still come."""
-
-
-class _ForwardFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, stats, config, training, dropout_seed, *weights):
-        with torch._C._AutoDispatchBelowAutograd():
-            out = torch.ops.orcai.forward(x, list(weights), stats, config, training, dropout_seed)
-        ctx.training, ctx.config = bool(training), config
-        ctx.shapes = [tuple(w.shape) for w in weights]
-        ctx.save_for_backward(out)
-        if training and not torch._subclasses.fake_tensor.is_fake(out):
-            ctx.token = _GraphToken()
-            eng = _ENGINES.get(_key(config, out.device))
-            if eng is not None:
-                eng.token = weakref.ref(ctx.token)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad):
-        if not ctx.training:
-            raise RuntimeError("orcai::forward(training=False) has no backward (BatchNorm with moving statistics); run the forward with training=True to train")
-        (probs,) = ctx.saved_tensors
-        flat = torch.ops.orcai.forward_backward(grad, probs, ctx.config)
-        sizes = [math.prod(s) for s in ctx.shapes]
-        return (None, None, None, None, None, *[t.view(s) for t, s in zip(torch.split(flat, sizes), ctx.shapes)])
-
-
-def _forward_autograd(x, weights, stats, config, training, dropout_seed):
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise NotImplementedError("orcai::forward computes no gradient w.r.t. its input x (only w.r.t. the weights): pass x with requires_grad=False")
-    if torch.is_grad_enabled() and any(w.requires_grad for w in weights):
-        return _ForwardFunction.apply(x, stats, config, training, dropout_seed, *weights)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.forward(x, weights, stats, config, training, dropout_seed)
-
-
-_LIB.impl("forward", _forward_autograd, "Autograd")
-
-
-# ---------------------------------------------------------------------------------------------------------------- orcai::forward_wrt_input
-# orcai::forward with the gradient w.r.t. the snippets as well: for something trainable or differentiable IN FRONT of the detector (a learnable
-# gain / equaliser / denoiser on the spectrogram, differentiable augmentation, adversarial or gradient-penalty training, saliency of a training
-# loss).  Its own op, because orcai::forward's refusal of x.requires_grad is part of that op's contract; the CUDA / CPU / fake implementations
-# are orcai::forward's, and both share the per-(config, device) engine and its one open step.  Training mode only: the eval-mode forward
-# (moving statistics) has no backward at all.
-_LIB.define("forward_wrt_input(Tensor x, Tensor[] weights, Tensor(a!)[] stats, str config, bool training, SymInt dropout_seed) -> Tensor")
-
-
-def forward_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, training: bool, dropout_seed: int) -> Tensor:
-    """orcai::forward whose training-mode backward also returns dL/dx (f32 [B, H, W]) when x requires grad."""
-    return torch.ops.orcai.forward_wrt_input(x, weights, stats, config, training, dropout_seed)
-
-
-_LIB.impl("forward_wrt_input", _forward_impl, "CUDA")
-_LIB.impl("forward_wrt_input", _forward_impl, "CPU")  # (refuses: the checks name the missing GPU)
-torch.library.register_fake("orcai::forward_wrt_input", _forward_fake, lib=_LIB)
+    return _flat_grad_fake(grad, config)
 
 
 @torch.library.custom_op("orcai::forward_wrt_input_backward", mutates_args=())
@@ -368,46 +324,64 @@ def forward_wrt_input_backward(grad: Tensor, probs: Tensor, config: str) -> tupl
 @forward_wrt_input_backward.register_fake
 def _forward_wrt_input_backward_fake(grad, probs, config):
     H, W = (int(v) for v in _parse(config)["input_shape"][:2])
-    flat = grad.new_empty((sum(math.prod(s) for s in _spec_split(config)[0]),), dtype=torch.float32)
-    return flat, grad.new_empty((probs.shape[0], H, W), dtype=torch.float32)
+    return _flat_grad_fake(grad, config), grad.new_empty((probs.shape[0], H, W), dtype=torch.float32)
 
 
-class _ForwardWrtInputFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, stats, config, training, dropout_seed, *weights):
+class _GraphToken:
+    """Lives on the autograd node of a training forward: while it does, that forward's backward may still come."""
+
+
+def _training_autograd(name: str, backward_name: str, returns_dx: bool, eval_refusal: str, x_refusal: str | None = None):
+    """The Autograd kernel of orcai::<name>: a Function whose backward is orcai::<backward_name> (the flat weight gradient, with returns_dx also dL/dx).
+    eval_refusal: what a backward through training=False raises; x_refusal: what an x that requires grad raises (None: it gets dx)."""
+
+    class Function(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, stats, config, training, dropout_seed, *weights):
+            with torch._C._AutoDispatchBelowAutograd():
+                out = getattr(torch.ops.orcai, name)(x, list(weights), stats, config, training, dropout_seed)
+            ctx.training, ctx.config = bool(training), config
+            ctx.save_for_backward(out)
+            if training and not torch._subclasses.fake_tensor.is_fake(out):
+                ctx.token = _GraphToken()
+                eng = _ENGINES.get(_key(config, out.device))
+                if eng is not None:
+                    eng.token = weakref.ref(ctx.token)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad):
+            if not ctx.training:
+                raise RuntimeError(eval_refusal)
+            (probs,) = ctx.saved_tensors
+            res = getattr(torch.ops.orcai, backward_name)(grad, probs, ctx.config)
+            flat, dx = res if returns_dx else (res, None)
+            need = ctx.needs_input_grad
+            wgrads = [g if n else None for g, n in zip(_skeleton(ctx.config).layout().split_w(flat), need[5:])]
+            return (dx if need[0] else None, None, None, None, None, *wgrads)
+
+    Function.__name__ = Function.__qualname__ = "_" + "".join(part.capitalize() for part in name.split("_")) + "Function"  # the node's name in traces
+
+    def autograd(x, weights, stats, config, training, dropout_seed):
+        if torch.is_grad_enabled():
+            if x.requires_grad and x_refusal is not None:
+                raise NotImplementedError(x_refusal)
+            if x.requires_grad or any(w.requires_grad for w in weights):
+                return Function.apply(x, stats, config, training, dropout_seed, *weights)
         with torch._C._AutoDispatchBelowAutograd():
-            out = torch.ops.orcai.forward_wrt_input(x, list(weights), stats, config, training, dropout_seed)
-        ctx.training, ctx.config = bool(training), config
-        ctx.shapes = [tuple(w.shape) for w in weights]
-        ctx.save_for_backward(out)
-        if training and not torch._subclasses.fake_tensor.is_fake(out):
-            ctx.token = _GraphToken()
-            eng = _ENGINES.get(_key(config, out.device))
-            if eng is not None:
-                eng.token = weakref.ref(ctx.token)
-        return out
+            return getattr(torch.ops.orcai, name)(x, weights, stats, config, training, dropout_seed)
 
-    @staticmethod
-    def backward(ctx, grad):
-        if not ctx.training:
-            raise RuntimeError("orcai::forward_wrt_input(training=False) has no backward (BatchNorm with moving statistics): the gradient w.r.t. the "
-                               "input, too, needs the forward with training=True")
-        (probs,) = ctx.saved_tensors
-        flat, dx = torch.ops.orcai.forward_wrt_input_backward(grad, probs, ctx.config)
-        sizes = [math.prod(s) for s in ctx.shapes]
-        need = ctx.needs_input_grad
-        wgrads = [t.view(s) if n else None for t, s, n in zip(torch.split(flat, sizes), ctx.shapes, need[5:])]
-        return (dx if need[0] else None, None, None, None, None, *wgrads)
+    return autograd
 
 
-def _forward_wrt_input_autograd(x, weights, stats, config, training, dropout_seed):
-    if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
-        return _ForwardWrtInputFunction.apply(x, stats, config, training, dropout_seed, *weights)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.forward_wrt_input(x, weights, stats, config, training, dropout_seed)
-
-
-_LIB.impl("forward_wrt_input", _forward_wrt_input_autograd, "Autograd")
+_register("forward", _FORWARD_SCHEMA, _forward_impl, _probs_fake, _training_autograd(
+    "forward", "forward_backward", False,
+    "orcai::forward(training=False) has no backward (BatchNorm with moving statistics); run the forward with training=True to train",
+    "orcai::forward computes no gradient w.r.t. its input x (only w.r.t. the weights): pass x with requires_grad=False"))
+_register("forward_wrt_input", _FORWARD_SCHEMA, _forward_impl, _probs_fake, _training_autograd(
+    "forward_wrt_input", "forward_wrt_input_backward", True,
+    "orcai::forward_wrt_input(training=False) has no backward (BatchNorm with moving statistics): the gradient w.r.t. the "
+    "input, too, needs the forward with training=True"))
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::spectrogram_wrt_pcm
@@ -416,17 +390,12 @@ _LIB.impl("forward_wrt_input", _forward_wrt_input_autograd, "Autograd")
 # recording).  Its own op, as forward_wrt_input is: orcai::spectrogram's schema and behaviour stay what they are.  The forward is the same launch
 # sequence (same bits); with a pcm that requires grad it also keeps the run's six statistics (orcai_frontend_stats_dev), and the backward is the
 # functional op orcai::spectrogram_backward (orcai_spectrogram_bwd), which holds ref_db, p_lo and p_hi constant (include/orcai_hip.h).
-def _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo=0.0, q_hi=1.0) -> dict:
-    return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
-
-
 @torch.library.custom_op("orcai::spectrogram_with_stats", mutates_args=())
 def spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> tuple[Tensor, Tensor]:
     """orcai::spectrogram and the f32[6] statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the run, on the device."""
     from orcai_amd.frontend import get_frontend
 
-    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
-        raise ValueError("orcai::spectrogram_with_stats: pcm must be a 1-d f32 cuda tensor")
+    _check_pcm(pcm, "orcai::spectrogram_with_stats")
     with torch.cuda.device(pcm.device):
         return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi), return_stats=True)
 
@@ -441,8 +410,7 @@ def spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate
     """dL/dpcm f32[n] from grad = dL/dspectrogram f32[T, K], the pcm of the forward and the statistics orcai::spectrogram_with_stats returned."""
     from orcai_amd.frontend import get_frontend
 
-    if pcm.dim() != 1 or pcm.dtype != torch.float32 or not pcm.is_cuda:
-        raise ValueError("orcai::spectrogram_backward: pcm must be a 1-d f32 cuda tensor")
+    _check_pcm(pcm, "orcai::spectrogram_backward")
     with torch.cuda.device(pcm.device):
         return get_frontend(pcm.device).spectrogram_backward(pcm.detach(), grad.contiguous(), stats, _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi))
 
@@ -452,9 +420,6 @@ def _spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, freq_
     return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
 
 
-_LIB.define("spectrogram_wrt_pcm(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi) -> Tensor")
-
-
 def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
     """orcai::spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 to 4096."""
     return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
@@ -462,11 +427,6 @@ def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, fr
 
 def _spectrogram_wrt_pcm_impl(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
     return torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-
-
-_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_impl, "CUDA")
-_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_impl, "CPU")  # (refuses: the check names the missing GPU)
-torch.library.register_fake("orcai::spectrogram_wrt_pcm", _spectrogram_fake, lib=_LIB)
 
 
 class _SpectrogramFunction(torch.autograd.Function):
@@ -494,7 +454,8 @@ def _spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, 
         return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
 
 
-_LIB.impl("spectrogram_wrt_pcm", _spectrogram_wrt_pcm_autograd, "Autograd")
+_register("spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi) -> Tensor",
+          _spectrogram_wrt_pcm_impl, _spectrogram_fake, _spectrogram_wrt_pcm_autograd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::detect_wrt_input
@@ -520,23 +481,18 @@ def _saved_per_snippet(config: str) -> int:
 @torch.library.custom_op("orcai::detect_with_saved", mutates_args=())
 def detect_with_saved(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> tuple[Tensor, Tensor]:
     """EvalGrad.forward: the eval-mode probabilities f32[B, steps, labels] and the flat f32 tensor of stored activations its backward reads."""
-    cfg = _parse(config)
-    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
-    if x.dim() != 3 or tuple(x.shape[1:]) != (H, W) or x.dtype != torch.float32:
-        raise ValueError(f"orcai::detect_wrt_input: x must be f32 [B, {H}, {W}], got {x.dtype} {tuple(x.shape)}")
+    _check_x(config, x, "orcai::detect_wrt_input")
     _check_vars(config, weights, stats)
     eng, eg = _eval_grad(config, x.device)
     if x.shape[0] == 0:
-        return x.new_empty((0, _out_steps(config), cfg["num_labels"])), x.new_empty((0,))
+        return _probs_fake(x, weights, stats, config), x.new_empty((0,))
     with torch.cuda.device(x.device):
         return eg.forward(x.detach().contiguous(), params=eng.flat(weights, stats))
 
 
 @detect_with_saved.register_fake
 def _detect_with_saved_fake(x, weights, stats, config):
-    cfg = _parse(config)
-    return (x.new_empty((x.shape[0], _out_steps(config), cfg["num_labels"]), dtype=torch.float32),
-            x.new_empty((x.shape[0] * _saved_per_snippet(config),), dtype=torch.float32))
+    return _probs_fake(x, weights, stats, config), x.new_empty((x.shape[0] * _saved_per_snippet(config),), dtype=torch.float32)
 
 
 @torch.library.custom_op("orcai::detect_backward", mutates_args=())
@@ -558,9 +514,6 @@ def _detect_backward_fake(grad, saved, weights, stats, config):
     return grad.new_empty((grad.shape[0], H, W), dtype=torch.float32)
 
 
-_LIB.define("detect_wrt_input(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor")
-
-
 def detect_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
     """The model in eval mode on snippets x[B][H][W]; its backward returns dL/dx when x requires grad (never a weight gradient)."""
     return torch.ops.orcai.detect_wrt_input(x, weights, stats, config)
@@ -568,15 +521,6 @@ def detect_wrt_input(x: Tensor, weights: list[Tensor], stats: list[Tensor], conf
 
 def _detect_impl(x, weights, stats, config):
     return torch.ops.orcai.detect_with_saved(x, weights, stats, config)[0]
-
-
-def _detect_fake(x, weights, stats, config):
-    return x.new_empty((x.shape[0], _out_steps(config), _parse(config)["num_labels"]), dtype=torch.float32)
-
-
-_LIB.impl("detect_wrt_input", _detect_impl, "CUDA")
-_LIB.impl("detect_wrt_input", _detect_impl, "CPU")  # (refuses: the checks name the missing GPU)
-torch.library.register_fake("orcai::detect_wrt_input", _detect_fake, lib=_LIB)
 
 
 class _DetectFunction(torch.autograd.Function):
@@ -604,7 +548,7 @@ def _detect_autograd(x, weights, stats, config):
         return torch.ops.orcai.detect_wrt_input(x, weights, stats, config)
 
 
-_LIB.impl("detect_wrt_input", _detect_autograd, "Autograd")
+_register("detect_wrt_input", "(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor", _detect_impl, _probs_fake, _detect_autograd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram

@@ -24,35 +24,16 @@ class FlatParams:
     """Named views into flat device buffers (weights, gradients, Adam m / v)."""
 
     def __init__(self, model: ResNetLSTM, device):
+        lay = self.layout = model.layout()
         self.spec = [(n, tuple(s), t) for n, s, _, t in model.variable_spec()]
-        self.offsets = {}
-        off = 0
-        for n, s, t in self.spec:
-            if t:
-                self.offsets[n] = (off, int(np.prod(s)), s)
-                off += int(np.prod(s))
-        self.n_trainable = off
-        self.w = torch.empty(off, dtype=torch.float32, device=device)
-        self.g = torch.zeros(off, dtype=torch.float32, device=device)
-        self.m = torch.zeros(off, dtype=torch.float32, device=device)
-        self.v = torch.zeros(off, dtype=torch.float32, device=device)
+        self.offsets, self.n_trainable = lay.w, lay.n_w
+        self.stat_offsets = {n: v[:2] for n, v in lay.s.items()}
         # BN moving mean / var (non-trainable): views into ONE flat buffer, mirrored by a flat buffer of the current step's batch
         # statistics in the same order, so that the moving-average update of every BatchNorm is one launch (orcai_ema_update)
-        self.stat_offsets, soff = {}, 0
-        for n, s, t in self.spec:
-            if not t:
-                self.stat_offsets[n] = (soff, int(np.prod(s)))
-                soff += int(np.prod(s))
-        self.stats_flat = torch.zeros(max(soff, 1), dtype=torch.float32, device=device)
-        self.batch_flat = torch.zeros(max(soff, 1), dtype=torch.float32, device=device)
+        self.w, self.stats_flat = lay.flatten(model.weights, device)
+        self.g, self.m, self.v = (torch.zeros_like(self.w) for _ in range(3))
         self.stats = {n: self.stats_flat[o : o + k] for n, (o, k) in self.stat_offsets.items()}
-        for n, s, t in self.spec:
-            a = torch.from_numpy(np.ascontiguousarray(model.weights[n])).to(device)
-            if t:
-                self.W(n).copy_(a)
-            else:
-                self.stats[n].copy_(a)
-        self.batch_flat.copy_(self.stats_flat)  # a BatchNorm that does not run this step leaves its moving statistics unchanged
+        self.batch_flat = self.stats_flat.clone()  # a BatchNorm that does not run this step leaves its moving statistics unchanged
 
     def W(self, name) -> torch.Tensor:
         o, n, s = self.offsets[name]
@@ -446,7 +427,8 @@ class TrunkTrainer:
 
     def _planes(self, B, c, h, w):
         G = self.G
-        return torch.zeros((B, (c + G - 1) // G, h + 2 * self.R, self.model.padded_width(w), G), dtype=self.adt, device=self.dev)
+        shape = ((c + G - 1) // G, h + 2 * self.R, self.model.padded_width(w), G) if self.half else self.model.plane_shape(c, h, w)
+        return torch.zeros((B, *shape), dtype=self.adt, device=self.dev)
 
     def _fn(self, name):
         """C-ABI launcher `orcai_<name>` (f32 quad planes) or its f16 octet-plane twin `orcai_h_<name>` (same argument list)."""

@@ -233,6 +233,30 @@ def test_two_forwards_alive_at_once():
     assert torch.equal(_bits(xb.grad), _bits(xb2.grad)) and not torch.equal(xa.grad, xb.grad)
 
 
+def test_new_weights_reach_evalgrad_without_invalidate():
+    """set_weights_dict on the model an EvalGrad(params=None) already ran on, and no invalidate(): the next forward and backward are, bit for bit,
+    those of an EvalGrad built after the change -- never the old network's."""
+    from orcai_amd.architectures import ResNetLSTM
+    from orcai_amd.eval_grad import EvalGrad
+
+    c = _e2e("k3")
+    cfg = c["cfg"]
+    make = lambda seed: ResNetLSTM(cfg["input_shape"], cfg["num_labels"], list(cfg["filters"]), cfg["kernel_size"], 0.5, cfg["lstm_units"], seed=seed)  # noqa: E731
+    model = make(1)
+    eg = EvalGrad(model)
+    old, _ = eg.forward(c["x"])
+    model.set_weights_dict(make(2).weights)
+    probs, saved = eg.forward(c["x"])
+    dx = eg.backward(c["r"], saved)
+    fresh = EvalGrad(model)
+    want, want_saved = fresh.forward(c["x"])
+    assert not torch.equal(want, old)  # the two networks differ on this input
+    assert torch.equal(_bits(probs), _bits(want))
+    assert torch.equal(_bits(dx), _bits(fresh.backward(c["r"], want_saved)))
+    eg.invalidate()  # still there, still harmless
+    assert torch.equal(_bits(eg.forward(c["x"])[0]), _bits(want))
+
+
 def test_saliency_helper():
     from orcai_amd.eval_grad import saliency
 
