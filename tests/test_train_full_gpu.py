@@ -52,6 +52,8 @@ def _run(cfg, B, seed, rate=0.5, record=False):
         (dict(input_shape=(32, 16, 1), filters=(10, 20), kernel_size=5, lstm_units=64, num_labels=2), 2),
         # a first block wide enough for the strip-tile kernels (BatchNorm statistics reduced in the separable convs' epilogue)
         (dict(input_shape=(16, 120, 1), filters=(20, 24), kernel_size=3, lstm_units=64, num_labels=3), 2),
+        # B * 8 = 320 rows in the head's weight-gradient GEMMs: split-K, its zero fill meeting the Trainer's pre-cleared accumulator arena
+        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 40),
     ],
 )
 def test_full_step_gradients_vs_autograd(cfg, B):

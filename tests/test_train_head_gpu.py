@@ -57,7 +57,8 @@ def _oracle_head(p, featv, y, masks, rate, W):
     return probs.detach().numpy(), float(bce.detach()), float(loss.detach()), grads, f.grad.numpy(), {k: v.detach().numpy() for k, v in stats.items()}
 
 
-@pytest.mark.parametrize("n,units,use_dropout", [(5, 64, True), (18, 128, True), (3, 64, False)])
+# n = 40 and 45: the weight-gradient GEMMs contract over n * 8 = 320 and 360 rows, where orcai_gemm_strided splits K in two (160 + 160, 192 + 168)
+@pytest.mark.parametrize("n,units,use_dropout", [(5, 64, True), (18, 128, True), (3, 64, False), (40, 64, True), (45, 128, False)])
 def test_head_forward_backward_vs_autograd(n, units, use_dropout):
     model, p, P, head, rng = _setup(3 + n, n, units)
     Tn, W, C = 8, 3, 36
