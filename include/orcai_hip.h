@@ -54,6 +54,16 @@ int orcai_frontend_reset(void* workspace, void* stream);
  *   out[n] = sum_j x[floor(n*M/L) - ntaps/2 + 1 + j] * table[(n*M) mod L][j]; table f32[L][ntaps], ntaps % 4 == 0. */
 int orcai_resample_polyphase(const float* x, int64_t n_in, float* out, int64_t n_out, int L, int M, const float* table, int ntaps, void* stream);
 
+/* The adjoint of orcai_resample_polyphase with the same table: the gradient w.r.t. the audio at its native rate (the resampler is linear,
+ * so this is its whole backward; the reference has no counterpart, it never differentiates librosa.load).
+ *   dx[k] = sum_n dout[n] * table[(n*M) mod L][k - (floor(n*M/L) - ntaps/2 + 1)]
+ * over the outputs n in [0, n_out) whose window holds k: n in [ceil((k - ntaps/2)*L/M), ceil((k + ntaps/2)*L/M)).
+ *   dout f32[n_out], dx f32[n_in]: EVERY element of dx is written (the caller does not zero it); n_out is the forward's output length.
+ * Gather form, one owner per dx[k] adding in ascending n, no float atomics: two launches give the same bits.  Every (L, M, ntaps) the forward
+ * accepts runs (nothing is staged in LDS, so no table is too large); ORCAI_E_BADARG for what the forward rejects (null pointer, non-positive
+ * size, ntaps % 4 != 0).  Index arithmetic is 64-bit. */
+int orcai_resample_polyphase_bwd(const float* dout, int64_t n_out, float* dx, int64_t n_in, int L, int M, const float* table, int ntaps, void* stream);
+
 /* librosa.stft(n_fft=512, hop_length=hop, window="hann", center=True, pad_mode="constant")
  * followed by the first half of amplitude_to_db (spectrogram.py:34-39, :51-53):
  *   out_db[t*k_crop + k] = 10*log10(max(|X[k,t]|^2, 1e-10))          k in [0, k_crop)

@@ -5,6 +5,7 @@ known without a GPU.
 
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.detect_wrt_input(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
@@ -21,7 +22,11 @@ still alive raises instead of overwriting what that graph's backward needs (``fo
 whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
 detector.  ``spectrogram_wrt_pcm`` is ``spectrogram`` (same bits) whose backward delivers dL/dpcm (``orcai_spectrogram_bwd``; the three
 normalisation statistics are held constant), so the chain pcm -> spectrogram -> snippets -> probabilities is differentiable down to the
-waveform.
+waveform.  ``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
+same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
+sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
+``WaveformFrontEnd(spectrogram_parameter, native_rate)`` is the two stages as one ``torch.nn.Module``: the waveform at the rate it was recorded
+at -> the [T, K] spectrogram, differentiable down to those samples.
 
 ``detect_wrt_input`` is the PREDICT-TIME network (BatchNorm with the moving statistics, no Dropout, nothing written to ``stats``) with
 autograd w.r.t. ``x`` only: saliency, robustness probes, training something in front of the detector that will be deployed
@@ -30,7 +35,7 @@ reads in a tensor of its own, so any number of forwards may be alive at once.  `
 refusing a backward: they run the fused inference path, which stores nothing.
 
 What does not exist: a gradient w.r.t. the weights in eval mode, any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
-itself has no backward, and the resampler is not differentiated.
+itself has no backward, and ``orcai::resample`` / ``orcai::resample_backward`` have no second derivative.
 """
 
 from __future__ import annotations
@@ -456,6 +461,107 @@ def _spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, 
 
 _register("spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi) -> Tensor",
           _spectrogram_wrt_pcm_impl, _spectrogram_fake, _spectrogram_wrt_pcm_autograd)
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::resample
+# The project's polyphase resampler (orcai_amd/resample.py, what `orcai predict` runs on a recording that is not at the model's rate) as an op with
+# autograd w.r.t. the audio.  It is linear, so its backward is its adjoint with the same table: the functional op orcai::resample_backward
+# (orcai_resample_polyphase_bwd).  Nothing is saved for the backward but the input's length.  Equal rates: both ops copy (an op may not alias its input).
+def _check_rates(sr_in, sr_out, who: str) -> None:
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError(f"{who}: sr_in and sr_out must be positive, got {sr_in} and {sr_out}")
+
+
+def _resampled_length(n, sr_in: int, sr_out: int):
+    """ceil(n * sr_out / sr_in) in integers (n may be symbolic); resample.output_length for every length a recording has."""
+    return (n * sr_out + sr_in - 1) // sr_in
+
+
+def resample(pcm: Tensor, sr_in: int, sr_out: int) -> Tensor:
+    """resample_device (same bits) of f32 pcm[n] at sr_in -> f32[ceil(n * sr_out / sr_in)] at sr_out; its backward returns dL/dpcm when pcm requires grad."""
+    return torch.ops.orcai.resample(pcm, sr_in, sr_out)
+
+
+def _resample_impl(pcm, sr_in, sr_out):
+    from orcai_amd.resample import resample_device
+
+    _check_pcm(pcm, "orcai::resample")
+    _check_rates(sr_in, sr_out, "orcai::resample")
+    if sr_in == sr_out:
+        return pcm.detach().clone()
+    return resample_device(pcm.detach(), sr_in, sr_out)
+
+
+def _resample_fake(pcm, sr_in, sr_out):
+    return pcm.new_empty((pcm.shape[0] if sr_in == sr_out else _resampled_length(pcm.shape[0], sr_in, sr_out),), dtype=torch.float32)
+
+
+@torch.library.custom_op("orcai::resample_backward", mutates_args=())
+def resample_backward(grad: Tensor, n_in: int, sr_in: int, sr_out: int) -> Tensor:
+    """dL/dpcm f32[n_in] from grad = dL/d(resampled) f32[ceil(n_in * sr_out / sr_in)]: the adjoint of orcai::resample."""
+    from orcai_amd.resample import resample_backward_device
+
+    if grad.dim() != 1 or grad.dtype != torch.float32 or not grad.is_cuda:
+        raise ValueError("orcai::resample_backward: grad must be a 1-d f32 cuda tensor")
+    _check_rates(sr_in, sr_out, "orcai::resample_backward")
+    if sr_in == sr_out:
+        if grad.shape[0] != n_in:
+            raise ValueError(f"orcai::resample_backward: grad has {grad.shape[0]} samples, n_in is {n_in}")
+        return grad.detach().clone()
+    return resample_backward_device(grad.detach(), n_in, sr_in, sr_out)
+
+
+@resample_backward.register_fake
+def _resample_backward_fake(grad, n_in, sr_in, sr_out):
+    return grad.new_empty((n_in,), dtype=torch.float32)
+
+
+class _ResampleFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, sr_in, sr_out):
+        with torch._C._AutoDispatchBelowAutograd():
+            out = torch.ops.orcai.resample(pcm, sr_in, sr_out)
+        ctx.args = (pcm.shape[0], sr_in, sr_out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        return torch.ops.orcai.resample_backward(grad, *ctx.args), None, None
+
+
+def _resample_autograd(pcm, sr_in, sr_out):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _ResampleFunction.apply(pcm, sr_in, sr_out)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.resample(pcm, sr_in, sr_out)
+
+
+_register("resample", "(Tensor pcm, SymInt sr_in, SymInt sr_out) -> Tensor", _resample_impl, _resample_fake, _resample_autograd)
+
+
+class WaveformFrontEnd(torch.nn.Module):
+    """A recording at the rate it was made at -> the [T, K] spectrogram the detector reads, differentiable down to those samples:
+    forward(pcm f32[n] at native_rate) = spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...), the two stages `orcai predict` runs in
+    front of the model (same bits).  spectrogram_parameter is the "spectrogram" section of a model's parameter file (sampling_rate, nfft,
+    n_overlap = the hop, freq_range = [0, freq_hi], quantiles).  The three normalisation statistics are held constant in the backward."""
+
+    def __init__(self, spectrogram_parameter: dict, native_rate: int):
+        super().__init__()
+        sp = spectrogram_parameter
+        if float(sp["freq_range"][0]) != 0.0:
+            raise ValueError(f"WaveformFrontEnd: freq_range must start at 0 (orcai::spectrogram keeps the leading bins), got {sp['freq_range']}")
+        self.native_rate = int(native_rate)
+        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
+        self.freq_hi = float(sp["freq_range"][1])
+        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
+        _check_rates(self.native_rate, self.sampling_rate, "WaveformFrontEnd")
+
+    def forward(self, pcm: Tensor) -> Tensor:
+        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
+        return torch.ops.orcai.spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, self.freq_hi, self.q_lo, self.q_hi)
+
+    def extra_repr(self) -> str:
+        return f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, freq_hi={self.freq_hi}"
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::detect_wrt_input
