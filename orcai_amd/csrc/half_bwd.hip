@@ -1381,7 +1381,7 @@ int orcai_h_outer_reduce(const void* A, int Ca, const void* Bq, int Cb, int B, i
 }
 
 int orcai_h_dw_wgrad(const void* x, const void* du, int B, int C, int H, int W, int ksize_planes, int ktap, int relu_in, float* dW, void* stream) {
-  if (!x || !du || !dW || B <= 0 || C <= 0 || C > 64 || B > 65535) return ORCAI_E_BADARG;
+  if (!x || !du || !dW || B <= 0 || C <= 0 || C > 64 || B > 65535 || H <= 0 || W <= 0 || ktap > ksize_planes) return ORCAI_E_BADARG;  // as orcai_dw_wgrad
   const int WP = orcai_padded_width(W, ksize_planes), RP = ksize_planes / 2;
   const int VAL = 64 - 2 * (ktap / 2);
   const int tasks = (H * WP + VAL - 1) / VAL;

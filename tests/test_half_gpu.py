@@ -397,6 +397,9 @@ def _check_half_step(cfg, B, ref, tr, out, seed, probs_bar=5e-3):
             continue
         gm = matched["grads"][name]
         gn, gmn = float(np.linalg.norm(g)), float(np.linalg.norm(gm))
+        if gn == 0.0 and gmn == 0.0:  # an identically zero gradient (the recurrent LSTM kernels of a one-step sequence): no direction to compare, it must be zero here too
+            assert not got.any(), name
+            continue
         rel[name] = float(np.linalg.norm(got - g)) / max(gn, 1e-12)
         relm[name] = float(np.linalg.norm(got - gm)) / max(gmn, 1e-12)
         cos[name] = float((got * g).sum() / max(np.linalg.norm(got) * gn, 1e-30))
@@ -436,6 +439,36 @@ def test_half_training_step_at_the_benchmarked_shapes(filters):
     blk1 = [rc for n, rc, a in rec.calls if n == "orcai_h_bn_bwd_pointwise_wgrad" and (a[5], a[6]) == (736, 171)]
     assert blk1 == [0, 0], blk1
     assert rec.rcs("orcai_h_pool_bwd_bn_bias") == [0] * 4 and not rec.rcs("orcai_h_planes_sum")
+
+
+@pytest.mark.parametrize(
+    "cfg,B",
+    [
+        # stage widths 171 / 86 / 43 at k = 5: several 64-pixel windows per row of the flat padded plane
+        (dict(input_shape=(16, 171, 1), filters=(12, 30), kernel_size=5, lstm_units=64, num_labels=3), 2),
+        # k = 7 at the sweep's width: row pitch 176
+        (dict(input_shape=(16, 171, 1), filters=(20, 24), kernel_size=7, lstm_units=64, num_labels=3), 2),
+        # four blocks, widths 130 / 65 / 33 / 17 / 9, up to eight channel octets
+        (dict(input_shape=(16, 130, 1), filters=(30, 40, 50, 60), kernel_size=5, lstm_units=64, num_labels=3), 2),
+    ],
+    ids=["k5_171", "k7_171", "k5_130x4"],
+)
+def test_half_training_step_wide_kernels(cfg, B):
+    """Kernel sizes 5 and 7 on planes wider than one window, f16 path: the separate orcai_h_* launchers TrunkTrainer falls back to for k != 3,
+    at the bars of test_half_training_step_gradients_vs_autograd (branch-matched float64 oracle), with the record of the launchers that ran."""
+    from orcai_amd import _native as N
+
+    ref, tr, out = _train_setup(cfg, B, seed=5, rate=0.5, precision="f16", record=True)
+    rec = tr.trunk.lib
+    tr.trunk.lib = rec._lib
+    names = sorted({n for n, _, _ in rec.calls})
+    print(f"launchers of the f16 training step k = {cfg['kernel_size']} {cfg['filters']}:", {n: (len(rec.rcs(n)), sum(rc == N.E_UNSUPPORTED for rc in rec.rcs(n))) for n in names})
+    _check_half_step(cfg, B, ref, tr, out, seed=5)
+    for name in ("orcai_h_dw_wgrad", "orcai_h_sepconv", "orcai_h_bn_planes_stats", "orcai_h_bn_planes_apply", "orcai_h_outer_reduce", "orcai_h_pool_bwd_bn_bias",
+                 "orcai_h_conv0_affine", "orcai_h_conv0_bn_bwd"):
+        assert rec.rcs(name) and not any(rec.rcs(name)), (name, rec.rcs(name))
+    marching = [n for n in names if n.startswith(("orcai_h_dw_bwd_fused", "orcai_h_sepconv_stats")) or n in ("orcai_conv0_stats_march", "orcai_h_conv0_affine_bn")]
+    assert not [n for n in marching if 0 in rec.rcs(n)], marching
 
 
 def _branch_matched_reference(cfg, B, tr, seed, rate):

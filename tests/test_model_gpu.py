@@ -69,6 +69,40 @@ def test_forward_intermediates_orcai_v1():
     assert np.abs(o - ref64).max() <= 1e-5
 
 
+@pytest.mark.parametrize("kernel_size", [5, 7])
+def test_forward_intermediates_wide_kernels(kernel_size):
+    """test_forward_intermediates_orcai_v1 for kernel sizes 5 and 7 at the sweep's width (171 columns: several 64-pixel windows per row of the
+    flat padded planes, row pitch 176): every intermediate of the inference trunk, the pads, and the probabilities at the same bars."""
+    H, W, B = 32, 171, 3
+    model, p = make_model(3, input_shape=(H, W, 1), filters=(30, 40), kernel_size=kernel_size, lstm_units=64, num_labels=7)
+    rng = np.random.default_rng(0)
+    x = rng.random((B, H, W, 1), dtype=np.float32)
+    ref, inter = M.forward_ref(p, x, return_intermediates=True)
+    xd = torch.from_numpy(x[..., 0].copy()).cuda()
+    out = torch.empty((B, H // 4, 7), dtype=torch.float32, device="cuda")
+    keep = {}
+    model.forward_device(xd.view(-1), H * W, B, out, keep=keep)
+    got = {k: v.cpu().numpy() for k, v in keep.items()}
+    close(got["prev0"], inter["conv0"])
+    for b in range(1, 3):
+        close(got[f"a{b}"], inter[f"b{b}/a"])
+        bref = inter[f"b{b}/b"]  # the kernel stores max over column pairs (2j, 2j+1), the first half of the (3,2) max-pool
+        wx = (bref.shape[3] + 1) // 2
+        pairs = np.full(bref.shape[:3] + (2 * wx,), -np.inf, dtype=np.float32)
+        pairs[..., : bref.shape[3]] = bref
+        close(got[f"b{b}"], pairs.reshape(bref.shape[:3] + (wx, 2)).max(axis=4))
+        close(got[f"prev{b}"], inter[f"b{b}"])
+    close(got["feat"], inter["features"])
+    close(got["h1"], inter["lstm1"])
+    close(got["h2"], inter["lstm2"])
+    for name in ("prev0", "a1", "prev1", "a2", "prev2"):  # pad rows/columns/channels of the layout stay zero
+        assert not got[name + "/pads"].any(), name
+    o = out.cpu().numpy()
+    assert np.abs(o - ref).max() <= 1e-5, np.abs(o - ref).max()
+    ref64 = M.forward_ref(p, x, dtype=torch.float64)
+    assert np.abs(o - ref64).max() <= 1e-5
+
+
 def test_predict_api_and_chunking():
     model, p = make_model(4)
     rng = np.random.default_rng(1)

@@ -76,3 +76,53 @@ def test_random_training_configs(seed):
         if err > (5e-4 if not zero_mean_bias else 1e-4):
             bad[name] = err
     assert not bad, (cfg, B, bad)
+
+
+def _random_cfg_wide(rng):
+    """What _random_cfg cannot draw for training: kernel sizes 5 and 7 (7 never, 5 only up to W = 65) at widths up to the sweep's 171, where the
+    separate launchers of the k != 3 training step need several 64-pixel windows per row of the flat padded plane."""
+    nb = int(rng.integers(1, 4))
+    k = int(rng.choice([5, 7]))
+    H = int(rng.integers(2, 5)) * 2**nb
+    W = int(rng.choice([59, 62, 64, 65, 86, 121, 124, 171]))
+    filters = tuple(int(rng.integers(3, 64)) for _ in range(nb))
+    return dict(input_shape=(H, W, 1), filters=filters, kernel_size=k, lstm_units=int(rng.choice([64, 128])), num_labels=int(rng.integers(1, 9)))
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_training_configs_wide(seed):
+    """test_random_training_configs with _random_cfg_wide: the same checks at the same bars (free-running float64 oracle)."""
+    from orcai_amd.architectures import ResNetLSTM
+    from orcai_amd.training import Trainer
+
+    rng = np.random.default_rng(3000 + seed)
+    cfg = _random_cfg_wide(rng)
+    p = M.calibrated_params(seed=seed, **cfg)
+    for k in p:
+        if k.endswith(("gamma", "beta")):
+            p[k] = (p[k] + 0.2 * rng.standard_normal(p[k].shape)).astype(np.float32)
+    H, W, _ = cfg["input_shape"]
+    steps = H // 2 ** len(cfg["filters"])
+    L, u = cfg["num_labels"], cfg["lstm_units"]
+    B = int(rng.choice([2, 3]))
+    x = rng.random((B, H, W, 1), dtype=np.float32)
+    y = (rng.random((B, steps, L)) > 0.5).astype(np.float32)
+    y[0, :, 0] = -1.0
+    ref = T.loss_and_grads(p, x, y, None, 0.0)
+    model = ResNetLSTM(cfg["input_shape"], L, list(cfg["filters"]), cfg["kernel_size"], 0.0, u)
+    model.set_weights_dict(p)
+    tr = Trainer(model, learning_rate=1e-3)
+    out = tr.forward_backward(torch.from_numpy(np.ascontiguousarray(x[..., 0])).cuda().view(-1), H * W, B, torch.from_numpy(y).cuda(), masks=None)
+    acc = out["acc"].cpu().numpy()
+    print(f"seed {seed}: {cfg}, B = {B}")
+    assert np.abs(out["probs"].cpu().numpy() - ref["probs"]).max() <= 5e-6, cfg
+    assert abs(acc[0] / acc[1] + acc[3] - ref["loss"]) <= 2e-6 * max(1.0, abs(ref["loss"])), cfg
+    bad = {}
+    for name, g in ref["grads"].items():
+        got = tr.P.G(name).cpu().numpy()
+        zero_mean_bias = name.endswith("/bias") and not name.startswith(("dense2", "lstm", "dense1")) and "res" not in name
+        scale = max(1e-3, float(np.abs(g).max())) if not zero_mean_bias else 1.0
+        err = float(np.abs(got - g).max()) / scale
+        if err > (5e-4 if not zero_mean_bias else 1e-4):
+            bad[name] = err
+    assert not bad, (cfg, B, bad)

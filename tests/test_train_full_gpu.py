@@ -16,7 +16,7 @@ from oracle import train_ref as T  # noqa: E402
 from recording_lib import RecordingLib  # noqa: E402
 
 
-def _run(cfg, B, seed, rate=0.5, record=False):
+def _run(cfg, B, seed, rate=0.5, record=False, dx=None):
     from orcai_amd.architectures import ResNetLSTM
     from orcai_amd.training import Trainer
 
@@ -39,7 +39,8 @@ def _run(cfg, B, seed, rate=0.5, record=False):
     if record:
         tr.trunk.lib = RecordingLib(tr.trunk.lib)
     xd = torch.from_numpy(np.ascontiguousarray(x[..., 0])).cuda().view(-1)
-    out = tr.forward_backward(xd, H * W, B, torch.from_numpy(y).cuda(), masks={k: torch.from_numpy(v).cuda() for k, v in masks.items()})
+    extra = {} if dx is None else {"dx": dx}
+    out = tr.forward_backward(xd, H * W, B, torch.from_numpy(y).cuda(), masks={k: torch.from_numpy(v).cuda() for k, v in masks.items()}, **extra)
     tr._test_inputs = (p, x, y, masks, rate)
     return ref, tr, out, p
 
@@ -77,6 +78,12 @@ def _branch_matched_reference(tr):
     block outputs, bn_f's and dense1's rectified tensors; bn_a's from y_a, materialised here by the orcai_bn_planes_apply launch whose value
     the on-load BatchNorm of the fused kernels reproduces bit for bit (tests/test_train_fused_gpu.py); pooling selections from v_b
     (first maximal element of sign(gamma) * v in window scan order, the kernels' rule)."""
+    p, x, y, masks, rate = tr._test_inputs
+    return T.loss_and_grads(p, x, y, masks, rate, forced_np=_forced_branches(tr))
+
+
+def _forced_branches(tr):
+    """The ReLU masks and pooling selections of the step `tr` just ran, in the form oracle.train_ref takes as `forced_np`."""
     from oracle.model_ref import same_pad
 
     p, x, y, masks, rate = tr._test_inputs
@@ -107,7 +114,7 @@ def _branch_matched_reference(tr):
     hl, wl, _ = shapes[-1]
     forced["relu/bn_f"] = (hc["x1"].cpu().numpy().reshape(B, hl, wl, -1).transpose(0, 3, 1, 2) > 0).astype(np.float64)
     forced["relu/dense1"] = (hc["pre1"].cpu().numpy() > 0).astype(np.float64)
-    return T.loss_and_grads(p, x, y, masks, rate, forced_np=forced)
+    return forced
 
 
 def _check_step(ref, tr, out):
@@ -162,6 +169,62 @@ def test_full_step_gradients_at_the_benchmarked_shape():
     blk1 = [rc for n, rc, a in rec.calls if n == "orcai_bn_bwd_pointwise_wgrad" and (a[5], a[6]) == (736, 171)]
     assert blk1 == [0, 0], blk1
     assert rec.rcs("orcai_pool_bwd_bn_bias") == [0] * 4
+
+
+WIDE_KERNEL_CONFIGS = [
+    # stage widths 171 / 86 / 43: four, two and one 60-column window per row at k = 5; one and two 16-channel output tiles
+    (dict(input_shape=(16, 171, 1), filters=(12, 30), kernel_size=5, lstm_units=64, num_labels=3), 2),
+    # k = 7 at the sweep's width: row pitch 176, 58 valid columns per 64-pixel window
+    (dict(input_shape=(16, 171, 1), filters=(20, 24), kernel_size=7, lstm_units=64, num_labels=3), 2),
+    # widths 130 / 65 / 33 / 17 at k = 7, two / three / four output tiles, a final stage of 3 rows
+    (dict(input_shape=(24, 130, 1), filters=(30, 40, 50), kernel_size=7, lstm_units=64, num_labels=7), 2),
+    # one very wide block, a ragged channel quad (17 = 4 * 4 + 1)
+    (dict(input_shape=(8, 300, 1), filters=(17,), kernel_size=5, lstm_units=64, num_labels=2), 3),
+]
+
+
+@pytest.mark.parametrize("cfg,B", WIDE_KERNEL_CONFIGS, ids=["k5_171", "k7_171", "k7_130x3", "k5_300"])
+def test_full_step_gradients_wide_kernels(cfg, B):
+    """Kernel sizes 5 and 7 -- which the hyper-parameter sweep trains at 736 x 171 (defaults/default_hps_parameter.json) -- on planes
+    wider than one 64-pixel window, where the separate launchers TrunkTrainer falls back to for k != 3 need several windows per row:
+    window tails, windows crossing a row edge with a 2 / 3 pixel halo, the last window hanging over the row pitch.  Checked as
+    test_full_step_gradients_at_the_benchmarked_shape is: probabilities against the free-running float64 oracle, everything else against
+    the oracle on the branches the f32 forward took, at _check_step's bars; the free-running deviation is printed.  The launcher record
+    shows that the fall-back launchers, and none of the k = 3 marching entry points, produced the result.  For the two (16, 171) shapes
+    the step also returns the input gradient, held to test_step_input_gradient_vs_autograd's bar (5e-4 of max|ref|) against the
+    free-running oracle's (as that test does) and the branch-matched oracle's."""
+    from orcai_amd import _native as N
+    from test_input_grad_gpu import _oracle_dx
+
+    H, W, _ = cfg["input_shape"]
+    with_dx = (H, W) == (16, 171)
+    dx = torch.full((B, H, W), float("nan"), device="cuda") if with_dx else None
+    ref, tr, out, p = _run(cfg, B, seed=5, record=True, dx=dx)
+    rec = tr.trunk.lib
+    tr.trunk.lib = rec._lib  # (the launches below are the test's own)
+    free = {n: float(np.abs(tr.P.G(n).cpu().numpy() - g).max()) / max(1e-3, float(np.abs(g).max())) for n, g in ref["grads"].items()}
+    worst = sorted(free.items(), key=lambda kv: -kv[1])[:3]
+    print(f"k = {cfg['kernel_size']} {cfg['input_shape'][:2]} {cfg['filters']} step vs the free-running float64 oracle: worst {[(n, f'{v:.1e}') for n, v in worst]}")
+    names = sorted({n for n, _, _ in rec.calls})
+    print("launchers of the training step:", {n: (len(rec.rcs(n)), sum(rc == N.E_UNSUPPORTED for rc in rec.rcs(n))) for n in names})
+    matched = _branch_matched_reference(tr)
+    assert np.abs(out["probs"].cpu().numpy() - ref["probs"]).max() <= 5e-6  # the forward itself agrees with the free-running oracle
+    _check_step(matched, tr, out)
+    for name in ("orcai_dw_wgrad", "orcai_sepconv_planes_u", "orcai_bn_planes_stats", "orcai_bn_planes_apply", "orcai_outer_reduce", "orcai_pool_bwd_bn_bias",
+                 "orcai_conv0_bn_bwd_x"):
+        assert rec.rcs(name) and not any(rec.rcs(name)), (name, rec.rcs(name))
+    marching = [n for n in names if n.startswith(("orcai_dw_bwd_fused", "orcai_sepconv_planes_stats")) or n == "orcai_conv0_stats_march"]
+    assert not [n for n in marching if 0 in rec.rcs(n)], marching
+    if with_dx:
+        _, x, y, masks, rate = tr._test_inputs
+        free_dx = _oracle_dx(p, x, y, masks, rate)
+        want = _oracle_dx(p, x, y, masks, rate, forced_np=_forced_branches(tr))
+        got = dx.cpu().numpy().astype(np.float64)
+        scale = float(np.abs(want).max())
+        err = float(np.abs(got - want).max()) / scale
+        free_err = float(np.abs(got - free_dx).max()) / float(np.abs(free_dx).max())
+        print(f"k {cfg['kernel_size']} {cfg['input_shape'][:2]}: max|dx - ref| / max|ref| = {err:.2e} (free-running oracle: {free_err:.2e}), max|ref| = {scale:.2e}")
+        assert np.isfinite(got).all() and err <= 5e-4 and free_err <= 5e-4, (err, free_err)  # no branch flip at these shapes: the free-running oracle, as in the cited test, holds too
 
 
 def test_training_reduces_loss_and_roundtrips_weights():

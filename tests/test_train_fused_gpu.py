@@ -225,6 +225,10 @@ def test_batchnorm_applied_on_load_equals_the_materialised_tensor(Cin, Cout, H, 
 
 @pytest.mark.parametrize("H,W,B,k", [(37, 171, 2, 3), (16, 12, 5, 3), (9, 33, 3, 5), (8, 7, 2, 7)])
 def test_entry_conv_in_two_passes_without_v0(H, W, B, k):
+    _entry_conv_two_passes_case(H, W, B, k)
+
+
+def _entry_conv_two_passes_case(H, W, B, k):
     """orcai_conv0_stats + orcai_bn_finish_sharded + orcai_conv0_affine_bn against orcai_conv0_affine + orcai_bn_planes_stats +
     orcai_bn_planes_apply: y0 bit for bit, batch statistics to summation order; orcai_conv0_bn_bwd_x (v0 rebuilt from the input taps)
     against orcai_conv0_bn_bwd on the stored v0: gradients to float-atomic reordering."""
