@@ -753,6 +753,49 @@ int orcai_sepconv_dgrad(const float* g, const float* y_gate, const float* x_gate
 int orcai_rows_affine(const float* x, int64_t M, int cols, int C, const float* scale, const float* shift, int relu, float* y, void* stream);
 int orcai_rows_affine_relu_bwd(const float* dy, const float* ref, int64_t M, int cols, int C, const float* scale, float* dx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weight gradients of the INFERENCE network (EvalGrad.backward(wgrad=True); csrc/eval_grad.hip): fine-tuning with BatchNorm frozen on its moving
+ * statistics and no Dropout -- what Keras forms for model(x, training=False) with trainable variables (architectures.py:162-241, training=False).
+ * The moving statistics get no gradient.  The reductions themselves are the training step's launchers (orcai_outer_reduce, orcai_planes_sum,
+ * orcai_dw_wgrad, orcai_conv0_bn_bwd_x[_ready], the head's GEMMs); orcai_sepconv_wgrad_frozen replaces the first three in one pass where it is faster.
+ * ------------------------------------------------------------------------------------------ */
+
+/* A layer z = W . u + bias in front of a frozen BatchNorm, y = scale (.) z + shift with inv = 1 / sqrt(var + eps), scale = gamma * inv,
+ * shift = beta - mean * scale (architectures.py:162-241, training=False), from the two reductions over snippets and pixels of gg = the gradient at y:
+ *   sums[co]    = sum_p gg[co][p]                      (orcai_planes_sum)
+ *   G[co][ci]   = sum_p gg[co][p] * u[ci][p]           (orcai_outer_reduce(gg, u); f32[Cout][Cin])
+ *   dbeta[co]   = sums[co]
+ *   dbias[co]   = scale[co] * sums[co]
+ *   dWpw[ci][co] = scale[co] * G[co][ci]               (Keras pointwise layout (1, 1, Cin, Cout))
+ *   dgamma[co]  = inv[co] * (sum_ci pw[ci][co] * G[co][ci] + (bias[co] - mean[co]) * sums[co])     (sum_p gg * z = sum_ci pw * G + bias * sums: neither
+ *                                                                                                    z nor u is stored, nothing is divided by gamma)
+ * pw: the layer's kernel f32[Cin][Cout]; bias may be NULL (none).  G == NULL (the entry conv, whose dgamma / dbeta / dW orcai_conv0_bn_bwd_x[_ready]
+ * deliver): only dbias and dbeta are written, pw / mean / dWpw / dgamma are not read or written.  dbias and dbeta may each be NULL (not wanted); no output
+ * may alias an input.  Every output element is written (nothing accumulated) by one thread of ONE workgroup, plain f32: bit-reproducible.
+ * ORCAI_E_BADARG: null sums / gamma / var, G without pw / mean / dWpw / dgamma, no output at all, channel counts outside 1 .. 4096. */
+int orcai_frozen_bn_finish(const float* G, const float* sums, const float* pw, const float* bias, const float* gamma, const float* mean, const float* var, float eps,
+                           int Cin, int Cout, float* dWpw, float* dbias, float* dgamma, float* dbeta, void* stream);
+/* The three reductions of a folded separable conv's weight gradients (k = 3) in ONE pass over (x, g) -- what compose_wgrad forms with six launches
+ * (architectures.py:162-241, training=False; the formulae above):
+ *   gg = g where y_gate > 0 (everywhere when y_gate is NULL),  r = relu_in ? relu(x) : x,  u = dw(r) with the FORWARD taps,  du = wts^T gg
+ *   G[co][ci] = sum gg[co][p] * u[ci][p]     dbeta[co] = sum gg[co][p]     dWdw[t][ci] = sum r[ci][p + off(t)] * du[ci][p]   (Keras layout (3, 3, Cin, 1))
+ *   x: planes of Cin channels; g, y_gate: planes of Cout channels (only interiors are read: pads may hold anything); taps f32[ceil(Cin/4)][9][4], the layout
+ *   orcai_sepconv_bn reads (orcai_prepare_inference kind 1); wts f32[Cout][Cin] = scale[co] * pw[ci][co] (kind 3).
+ * u and du never reach memory.  Every element of G, dbeta and dWdw is WRITTEN (nothing accumulated).  Each workgroup leaves its partial sums in a slot of
+ * `workspace`; a second launch adds the slots in index order: no float atomics, two launches give the same bits.
+ * workspace_floats >= min(B * ceil(H/4) * ceil(W/16), 1024) * (Cout*Cin + Cout + 9*Cin); 1024 * 4736 floats serve every supported shape.
+ * ORCAI_E_UNSUPPORTED before anything is touched: ksize 5 or 7, Cin or Cout > 64, B > 65535, a smaller workspace -- the caller runs compose_wgrad.
+ * ORCAI_E_BADARG: null x / g / taps / wts / G / dbeta / dWdw / workspace, planes or taps not 16-byte aligned, non-positive sizes, ksize not in {3, 5, 7}. */
+int orcai_sepconv_wgrad_frozen(const float* x, const float* g, const float* y_gate, int relu_in, int B, int Cin, int Cout, int H, int W, int ksize, const float* taps,
+                               const float* wts, float* G, float* dbeta, float* dWdw, float* workspace, int64_t workspace_floats, void* stream);
+/* dbeta / dgamma of a frozen BatchNorm on a row tensor f32[M][cols], channel = column % C (Dense(128, relu) -> BatchNormalization with moving statistics,
+ * architectures.py:231-237, training=False): dy = the gradient at the BatchNorm's OUTPUT, x = its input (the ReLU output the eval-mode forward keeps),
+ *   dbeta[c] = sum dy,   dgamma[c] = rsqrt(var[c] + eps) * sum dy * (x - mean[c]).
+ * workspace: 2 * cols floats.  Column sums in a fixed order, no atomics: two launches give the same bits.
+ * ORCAI_E_BADARG: a null pointer, non-positive sizes, cols not a multiple of C. */
+int orcai_rows_bn_frozen_wgrad(const float* dy, const float* x, int64_t M, int cols, int C, const float* mean, const float* var, float eps, float* dbeta, float* dgamma,
+                               float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

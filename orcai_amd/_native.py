@@ -174,6 +174,9 @@ _SIGNATURES = {
     "orcai_sepconv_dgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4),
     "orcai_rows_affine": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_rows_affine_relu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_sepconv_wgrad_frozen": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p] * 6 + [c_i64, C.c_void_p]),
+    "orcai_frozen_bn_finish": (C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "orcai_rows_bn_frozen_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
 }
 
 

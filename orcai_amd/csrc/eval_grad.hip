@@ -7,6 +7,11 @@
 //   orcai_rows_affine            y = [relu](x * scale[col % C] + shift[col % C]) on a row tensor (Dense-128's folded BatchNorm, kept apart from the
 //                                GEMM so that the ReLU output in front of it stays available to the backward)
 //   orcai_rows_affine_relu_bwd   its backward: dx = ref > 0 ? dy * scale[col % C] : 0
+//   orcai_sepconv_wgrad_frozen   the reductions of a folded separable conv's weight gradients (G = sum gg (x) u, sum gg, the depthwise gradient) in ONE pass over
+//                                (x, g): u and du never reach HBM; per-workgroup partials added in a fixed order
+//   orcai_frozen_bn_finish       weight gradients of a layer in front of a FROZEN BatchNorm from two reductions (G = sum gg (x) u, sum gg): the
+//                                pointwise kernel, the bias, gamma and beta (EvalGrad.backward(wgrad=True))
+//   orcai_rows_bn_frozen_wgrad   dbeta / dgamma of a frozen BatchNorm on a row tensor (Dense-128's)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -177,6 +182,243 @@ __global__ __launch_bounds__(256) void rows_affine_relu_bwd_kernel(const float* 
   dx[i] = on ? dy[i] * scale[c] : 0.0f;
 }
 
+// =========================================================================================
+// sepconv_wgrad_frozen_kernel (k = 3).  A workgroup of 4 waves walks over tiles of 4 image rows x 16 columns (tile = blockIdx.x, + gridDim.x, ...: a fixed
+// assignment) and keeps its sums in registers until the end.  Per tile
+//   load     x with its one-pixel halo (6 x 18, zero outside the image, ReLU'd when relu_in) as xs[ci][halo pixel]; gg = g gated by y_gate > 0 (zero outside the
+//            image) as gs[co][pixel]: LDS images [channel][pixel], pitch 66 (bn_bwd_pw_wgrad_kernel's pattern).  The pads of the planes are never read.
+//   u, du    u[ci][p] = 9 fma on the x tile (vector ALU) -> us; du = wts^T gg by v_mfma_f32_16x16x4_f32 with k = output channel (A = wts from LDS, row = ci;
+//            B = gs, column = pixel; wave w owns tile row w) -> ds.  Neither reaches HBM.
+//   sums     G[co][ci] += gg u^T by the same MFMA with k = pixel (A = gs, B = us; the up to 16 output tiles are dealt round-robin to the waves, 4 accumulator
+//            registers each); dWdw[t][ci] += sum_p xs[ci][p + off(t)] * ds[ci][p] and dbeta[co] += sum_p gs[co][p] on the vector ALU.
+// At the end every workgroup writes its Cout*Cin + Cout + 9*Cin partial sums to its own slot of the workspace; wgrad_frozen_fold_kernel adds the slots in
+// index order in double.  No atomics: two launches give the same bits.
+// =========================================================================================
+constexpr int WF_ROWS = 4, WF_COLS = 16, WF_PIX = WF_ROWS * WF_COLS, WF_HW = WF_COLS + 2, WF_HALO = (WF_ROWS + 2) * WF_HW, WF_PITCH = WF_PIX + 2, WF_MAX_WG = 1024;
+
+__global__ __launch_bounds__(256) void sepconv_wgrad_frozen_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ y_gate,
+                                                                   const float* __restrict__ taps /*[CQi][9][4]*/, const float* __restrict__ wts /*[Cout][Cin]*/,
+                                                                   int Cin, int Cout, int H, int W, int WP, int relu_in, int TY, int TX, int ntiles,
+                                                                   float* __restrict__ part /*[gridDim.x][Cout*Cin + Cout + 9*Cin]*/) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int CQi = (Cin + 3) >> 2, CQo = (Cout + 3) >> 2;
+  const int MTI = (Cin + 15) >> 4, MTO = (Cout + 15) >> 4, CiP = MTI * 16, CoP = MTO * 16;
+  float* xs = smem;                  // [CiP][WF_HALO]
+  float* gs = xs + CiP * WF_HALO;    // [CoP][WF_PITCH]
+  float* us = gs + CoP * WF_PITCH;   // [CiP][WF_PITCH]
+  float* ds = us + CiP * WF_PITCH;   // [CiP][WF_PITCH]
+  float* wl = ds + CiP * WF_PITCH;   // [CoP][CiP]   wts, zero-padded
+  const int lds_floats = CiP * WF_HALO + (CoP + 2 * CiP) * WF_PITCH + CoP * CiP;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lk = lane >> 4, lj = lane & 15;
+  for (int i = tid; i < lds_floats; i += 256) smem[i] = 0.0f;  // the rows of the channels that pad a 16-tile stay zero
+  __syncthreads();
+  for (int i = tid; i < Cout * Cin; i += 256) {
+    const int co = i / Cin, ci = i - co * Cin;
+    wl[co * CiP + ci] = wts[i];
+  }
+  const int64_t plane = (int64_t)(H + 2) * WP;  // float4 pixels of one channel quad of one snippet
+  f32x4 accG[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) accG[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float accW[3] = {0.f, 0.f, 0.f};
+  float accB = 0.f;
+  const int ntileG = MTO * MTI;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int b = tile / (TY * TX);
+    const int rem = tile - b * (TY * TX);
+    const int y0 = (rem / TX) * WF_ROWS, x0 = (rem % TX) * WF_COLS;
+    // ---- load: x tile with halo, gated g tile
+    for (int i = tid; i < CQi * WF_HALO; i += 256) {
+      const int q = i / WF_HALO, hp = i - q * WF_HALO;
+      const int iy = y0 - 1 + hp / WF_HW, ix = x0 - 1 + hp % WF_HW;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = reinterpret_cast<const float4*>(x)[((int64_t)b * CQi + q) * plane + (int64_t)(iy + 1) * WP + ix];
+      float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * q + j;
+        float t = c < Cin ? e[j] : 0.0f;
+        if (relu_in) t = fmaxf(t, 0.0f);
+        xs[c * WF_HALO + hp] = t;
+      }
+    }
+    for (int i = tid; i < CQo * WF_PIX; i += 256) {
+      const int q = i / WF_PIX, p = i - q * WF_PIX;
+      const int iy = y0 + p / WF_COLS, ix = x0 + p % WF_COLS;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (iy < H && ix < W) {
+        const int64_t at = ((int64_t)b * CQo + q) * plane + (int64_t)(iy + 1) * WP + ix;
+        v = reinterpret_cast<const float4*>(g)[at];
+        if (y_gate) {
+          const float4 yv = reinterpret_cast<const float4*>(y_gate)[at];
+          v.x = yv.x > 0.0f ? v.x : 0.0f;
+          v.y = yv.y > 0.0f ? v.y : 0.0f;
+          v.z = yv.z > 0.0f ? v.z : 0.0f;
+          v.w = yv.w > 0.0f ? v.w : 0.0f;
+        }
+      }
+      float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gs[(4 * q + j) * WF_PITCH + p] = (4 * q + j) < Cout ? e[j] : 0.0f;
+    }
+    __syncthreads();
+    // ---- u on the vector ALU
+    for (int i = tid; i < CQi * 4 * WF_PIX; i += 256) {
+      const int c = i / WF_PIX, p = i - c * WF_PIX;
+      const float* tp = taps + (c >> 2) * 36 + (c & 3);
+      const float* xp = xs + c * WF_HALO + (p / WF_COLS) * WF_HW + (p % WF_COLS);
+      float a = 0.0f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) a = fmaf(tp[4 * t], xp[(t / 3) * WF_HW + (t % 3)], a);
+      us[c * WF_PITCH + p] = a;
+    }
+    // ---- du = wts^T gg: wave w owns the 16 pixels of tile row w
+    for (int mt = 0; mt < MTI; ++mt) {
+      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int k0 = 0; k0 < CoP; k0 += 4) acc = mfma16(wl[(k0 + lk) * CiP + mt * 16 + lj], gs[(k0 + lk) * WF_PITCH + wave * 16 + lj], acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ds[(mt * 16 + 4 * lk + r) * WF_PITCH + wave * 16 + lj] = acc[r];
+    }
+    __syncthreads();
+    // ---- G += gg u^T (k = pixel)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = wave + 4 * j;
+      if (t < ntileG) {
+        const int mo = t / MTI, mi = t - mo * MTI;
+        const float* ap = gs + (mo * 16 + lj) * WF_PITCH + lk;
+        const float* bp = us + (mi * 16 + lj) * WF_PITCH + lk;
+#pragma unroll 4
+        for (int p0 = 0; p0 < WF_PIX; p0 += 4) accG[j] = mfma16(ap[p0], bp[p0], accG[j]);
+      }
+    }
+    // ---- dWdw and dbeta on the vector ALU
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int q = tid + 256 * j;
+      const int c = q / 9, t = q - 9 * c;
+      if (c < Cin) {
+        const float* xp = xs + c * WF_HALO + (t / 3) * WF_HW + (t % 3);
+        const float* dp = ds + c * WF_PITCH;
+        float a = accW[j];
+        for (int p = 0; p < WF_PIX; ++p) a = fmaf(xp[(p / WF_COLS) * WF_HW + (p % WF_COLS)], dp[p], a);
+        accW[j] = a;
+      }
+    }
+    if (tid < Cout) {
+      const float* gp = gs + tid * WF_PITCH;
+      float a = accB;
+      for (int p = 0; p < WF_PIX; ++p) a += gp[p];
+      accB = a;
+    }
+    __syncthreads();  // the next tile's loads overwrite xs / gs
+  }
+  // ---- this workgroup's partial sums
+  const int S = Cout * Cin + Cout + 9 * Cin;
+  float* mine = part + (size_t)blockIdx.x * S;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int t = wave + 4 * j;
+    if (t < ntileG) {
+      const int mo = t / MTI, mi = t - mo * MTI;
+      const int ci = mi * 16 + lj;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int co = mo * 16 + 4 * lk + r;
+        if (co < Cout && ci < Cin) mine[co * Cin + ci] = accG[j][r];
+      }
+    }
+  }
+  if (tid < Cout) mine[Cout * Cin + tid] = accB;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int q = tid + 256 * j;
+    const int c = q / 9, t = q - 9 * c;
+    if (c < Cin) mine[Cout * Cin + Cout + t * Cin + c] = accW[j];  // Keras (3, 3, Cin, 1)
+  }
+}
+
+__global__ __launch_bounds__(256) void wgrad_frozen_fold_kernel(const float* __restrict__ part, int nwg, int Cin, int Cout, float* __restrict__ G, float* __restrict__ dbeta,
+                                                                float* __restrict__ dWdw) {
+  const int S = Cout * Cin + Cout + 9 * Cin;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= S) return;
+  double a = 0.0;
+  for (int w = 0; w < nwg; ++w) a += (double)part[(size_t)w * S + e];
+  const float v = (float)a;
+  if (e < Cout * Cin) G[e] = v;
+  else if (e < Cout * Cin + Cout) dbeta[e - Cout * Cin] = v;
+  else dWdw[e - Cout * Cin - Cout] = v;
+}
+
+// One workgroup per layer, plain f32: a few KB of arithmetic behind orcai_outer_reduce / orcai_planes_sum.  inv is 1 / sqrtf (correctly rounded division
+// and square root); every output element is written by exactly one thread.
+__global__ __launch_bounds__(256) void frozen_bn_finish_kernel(const float* __restrict__ G, const float* __restrict__ sums, const float* __restrict__ pw,
+                                                               const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                               const float* __restrict__ var, float eps, int Cin, int Cout, float* __restrict__ dWpw,
+                                                               float* __restrict__ dbias, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  __shared__ float scale_s[4096];  // gamma * inv per channel, formed once: dWpw and dbias see the same rounding
+  for (int co = threadIdx.x; co < Cout; co += 256) {
+    const float inv = 1.0f / sqrtf(var[co] + eps);
+    const float sc = gamma[co] * inv;
+    scale_s[co] = sc;
+    const float db = sums[co];
+    if (dbeta) dbeta[co] = db;
+    if (dbias) dbias[co] = sc * db;
+    if (G) {
+      float acc = 0.0f;  // sum over pixels of gg * (pw . u) = sum_ci pw[ci][co] * G[co][ci]
+      for (int ci = 0; ci < Cin; ++ci) acc = fmaf(pw[(size_t)ci * Cout + co], G[(size_t)co * Cin + ci], acc);
+      const float z0 = (bias ? bias[co] : 0.0f) - mean[co];  // the conv's own bias and the moving mean are constants of the pre-normalisation tensor
+      dgamma[co] = inv * fmaf(z0, db, acc);
+    }
+  }
+  if (!G) return;
+  __syncthreads();
+  for (int ci = 0; ci < Cin; ++ci)
+    for (int co = threadIdx.x; co < Cout; co += 256) dWpw[(size_t)ci * Cout + co] = scale_s[co] * G[(size_t)co * Cin + ci];
+}
+
+// A workgroup owns 64 columns: thread (ry, cx) adds rows ry, ry + 4, ... of column cx (coalesced over cx), the four partial sums are added in a fixed
+// order through LDS: no atomics, two launches give the same bits.
+__global__ __launch_bounds__(256) void rows_bn_frozen_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t M, int cols, int C,
+                                                                   const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                                   float* __restrict__ part /*[2][cols]*/) {
+  __shared__ float sb[4][64], sg[4][64];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + cx;
+  float b = 0.0f, g = 0.0f;
+  if (col < cols) {
+    const float mu = mean[col % C];
+    for (int64_t r = ry; r < M; r += 4) {
+      const float d = dy[r * cols + col];
+      b += d;
+      g = fmaf(d, x[r * cols + col] - mu, g);
+    }
+  }
+  sb[ry][cx] = b;
+  sg[ry][cx] = g;
+  __syncthreads();
+  if (ry == 0 && col < cols) {
+    part[col] = (sb[0][cx] + sb[1][cx]) + (sb[2][cx] + sb[3][cx]);
+    part[cols + col] = (sg[0][cx] + sg[1][cx]) + (sg[2][cx] + sg[3][cx]);
+  }
+}
+
+// channel c of a row tensor with cols = W * C columns: the W columns c, c + C, ... added in order
+__global__ __launch_bounds__(256) void rows_bn_frozen_fold_kernel(const float* __restrict__ part, int cols, int C, const float* __restrict__ var, float eps,
+                                                                  float* __restrict__ dbeta, float* __restrict__ dgamma) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  float b = 0.0f, g = 0.0f;
+  for (int col = c; col < cols; col += C) {
+    b += part[col];
+    g += part[cols + col];
+  }
+  dbeta[c] = b;
+  dgamma[c] = g * (1.0f / sqrtf(var[c] + eps));
+}
+
 template <int MTI>
 int launch_dgrad(const float* g, const float* y_gate, const float* x_gate, int B, int Cin, int Cout, int H, int W, const float* wts, const float* dw_rev, float* dr,
                  hipStream_t st) {
@@ -233,6 +475,54 @@ int orcai_rows_affine_relu_bwd(const float* dy, const float* ref, int64_t M, int
   const int64_t n = M * cols;
   if ((n + 255) / 256 >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
   hipLaunchKernelGGL(rows_affine_relu_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, ref, n, cols, C, scale, dx);
+  return (int)hipGetLastError();
+}
+
+int orcai_sepconv_wgrad_frozen(const float* x, const float* g, const float* y_gate, int relu_in, int B, int Cin, int Cout, int H, int W, int ksize, const float* taps,
+                               const float* wts, float* G, float* dbeta, float* dWdw, float* workspace, int64_t workspace_floats, void* stream) {
+  if (!x || !g || !taps || !wts || !G || !dbeta || !dWdw || !workspace || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return ORCAI_E_BADARG;
+  if (ksize != 3 && ksize != 5 && ksize != 7) return ORCAI_E_BADARG;
+  if ((((uintptr_t)x | (uintptr_t)g | (uintptr_t)y_gate | (uintptr_t)taps) & 15) || (((uintptr_t)wts | (uintptr_t)G | (uintptr_t)dbeta | (uintptr_t)dWdw | (uintptr_t)workspace) & 3))
+    return ORCAI_E_BADARG;
+  if (ksize != 3 || Cin > 64 || Cout > 64 || B > 65535) return ORCAI_E_UNSUPPORTED;  // k = 5, 7: the caller runs compose_wgrad
+  const int WP = orcai_padded_width(W, 3);
+  const int64_t plane = (int64_t)(H + 2) * WP;
+  if (16 * plane >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  const int TY = (H + WF_ROWS - 1) / WF_ROWS, TX = (W + WF_COLS - 1) / WF_COLS;
+  const int64_t ntiles = (int64_t)B * TY * TX;
+  if (ntiles >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  const int64_t S = (int64_t)Cout * Cin + Cout + 9 * Cin;
+  const int nwg = (int)(ntiles < WF_MAX_WG ? ntiles : WF_MAX_WG);
+  if (workspace_floats < nwg * S) return ORCAI_E_UNSUPPORTED;  // the size the header states
+  const int CiP = (Cin + 15) / 16 * 16, CoP = (Cout + 15) / 16 * 16;
+  const size_t lds = sizeof(float) * ((size_t)CiP * WF_HALO + (size_t)(CoP + 2 * CiP) * WF_PITCH + (size_t)CoP * CiP);
+  static size_t lds_set = 0;  // dynamic LDS beyond the 64 KiB default needs the opt-in
+  if (lds > lds_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)sepconv_wgrad_frozen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    lds_set = lds;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sepconv_wgrad_frozen_kernel, dim3((unsigned)nwg), dim3(256), lds, st, x, g, y_gate, taps, wts, Cin, Cout, H, W, WP, relu_in, TY, TX, (int)ntiles, workspace);
+  hipLaunchKernelGGL(wgrad_frozen_fold_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, workspace, nwg, Cin, Cout, G, dbeta, dWdw);
+  return (int)hipGetLastError();
+}
+
+int orcai_frozen_bn_finish(const float* G, const float* sums, const float* pw, const float* bias, const float* gamma, const float* mean, const float* var, float eps,
+                           int Cin, int Cout, float* dWpw, float* dbias, float* dgamma, float* dbeta, void* stream) {
+  if (!sums || !gamma || !var || Cout <= 0 || Cout > 4096) return ORCAI_E_BADARG;
+  if (G && (!pw || !mean || !dWpw || !dgamma || Cin <= 0 || Cin > 4096)) return ORCAI_E_BADARG;
+  if (!G && !dbias && !dbeta) return ORCAI_E_BADARG;
+  hipLaunchKernelGGL(frozen_bn_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, sums, pw, bias, gamma, mean, var, eps, Cin, Cout, dWpw, dbias, dgamma, dbeta);
+  return (int)hipGetLastError();
+}
+
+int orcai_rows_bn_frozen_wgrad(const float* dy, const float* x, int64_t M, int cols, int C, const float* mean, const float* var, float eps, float* dbeta, float* dgamma,
+                               float* workspace, void* stream) {
+  if (!dy || !x || !mean || !var || !dbeta || !dgamma || !workspace || M <= 0 || cols <= 0 || C <= 0 || cols % C) return ORCAI_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rows_bn_frozen_wgrad_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(256), 0, st, dy, x, M, cols, C, mean, var, eps, workspace);
+  hipLaunchKernelGGL(rows_bn_frozen_fold_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, workspace, cols, C, var, eps, dbeta, dgamma);
   return (int)hipGetLastError();
 }
 

@@ -17,6 +17,14 @@ the pooling is orcai_pool_bwd, the residual 1x1 stride-2 gradient is scatter-add
 training kernels' data-gradient halves (orcai_lstm_bwd, orcai_conv1d_bwd into a scratch weight gradient) and dgrad GEMMs on the forward GEMM
 kernel (no split-K atomics: two runs give the same bits).
 
+    dx, dwflat = eg.backward(dprobs, saved, wgrad=True)    # + f32 [layout().n_w]: the gradient w.r.t. every trainable variable, ParamLayout order
+
+adds the weight gradients of that same network -- fine-tuning with BatchNorm FROZEN on its moving statistics (OrcaiModule(frozen_bn=True)):
+per separable conv ONE orcai_sepconv_wgrad_frozen (k = 3; it refuses k = 5 / 7, and ``compose_wgrad`` -- the training step's reduction launchers on a
+recomputed depthwise output -- runs instead, as it does where the fused kernel measured slower: EvalGrad.fused_wgrad), finished by orcai_frozen_bn_finish, the residual convs by orcai_outer_reduce(a_stride2) / orcai_planes_sum, the entry conv by orcai_conv0_bn_bwd_x[_ready] with
+the moving statistics, the heads by the training step's weight-gradient GEMMs on LSTM outputs rebuilt from the features.  dx keeps its launches and bits;
+the weight gradients go through float atomics (orcai_dw_wgrad, split-K GEMMs) and are reproducible to rounding only.
+
 The entry conv REUSES orcai_conv0_bn_bwd_dx: called with the moving statistics and zeroed sums it evaluates the eval-mode formula
 (dv = gamma * rsqrt(var + eps) * dy where the ReLU fired).  Its ReLU decision is formed from the unfolded BatchNorm, the forward's from the folded
 one; the two can only differ for a pre-activation within rounding of zero, and dr1 is already zero where the stored y0 is (x_gate of block 1's
@@ -49,6 +57,37 @@ def compose_dgrad(lib, g: Tensor, y_gate, x_gate, B: int, Cin: int, Cout: int, H
                                      dr.data_ptr(), st), "orcai_sepconv_planes")
     if x_gate is not None:
         N.check(lib.orcai_planes_relu_bwd(dr.data_ptr(), x_gate.data_ptr(), dr.numel(), dr.data_ptr(), st), "orcai_planes_relu_bwd")
+
+
+
+def compose_wgrad(lib, g: Tensor, y_gate, x: Tensor, relu_in: int, B: int, Cin: int, Cout: int, H: int, W: int, k: int, dw: Tensor, wts: Tensor, pw: Tensor, bias, gamma: Tensor,
+                  mean: Tensor, var: Tensor, u: Tensor, du: Tensor, G: Tensor, sums: Tensor, scratch: Tensor, partials: Tensor, dWdw: Tensor, dWpw: Tensor, dbias, dgamma: Tensor,
+                  dbeta: Tensor, st, consts: dict | None = None) -> None:
+    """The weight gradients of one folded separable conv y = [relu](scale (.) (pw . u + bias) + shift), u = dw(relu_in ? relu(x) : x), of the eval path from the
+    launchers of the training step: ReLU gate of g IN PLACE (idempotent: compose_dgrad and orcai_sepconv_dgrad form the same gg), u recomputed by the
+    forward taps with an identity pointwise factor, G = sum gg (x) u (orcai_outer_reduce), sum gg (orcai_planes_sum), du = wts^T gg, the depthwise gradient
+    sum r (.) du accumulated in Keras layout into dWdw (orcai_dw_wgrad), and orcai_frozen_bn_finish for dWpw / dbias / dgamma / dbeta.  g, x, u, du (planes of Cin
+    channels, scratch) need zero pads; G [Cout][Cin] and dWdw must be zero on entry (both launchers accumulate); scratch: f64[64]; partials: orcai_outer_reduce's
+    workspace.  dw: the forward taps [ceil(Cin/4)][k*k][4]; pw / bias / gamma / mean / var: the layer's variables (Keras layouts).  consts (optional): a dict
+    that keeps the constant operands ("ones", "zeros", ("eye", Cin)) between calls."""
+    dev = g.device
+    consts = {} if consts is None else consts
+    for key, make in (("ones", lambda: torch.ones(64, device=dev)), ("zeros", lambda: torch.zeros(64, device=dev)), (("eye", Cin), lambda: torch.eye(Cin, device=dev).contiguous())):
+        if key not in consts:
+            consts[key] = make()
+    ones, zeros, eye = consts["ones"], consts["zeros"], consts[("eye", Cin)]
+    if y_gate is not None:
+        N.check(lib.orcai_planes_relu_bwd(g.data_ptr(), y_gate.data_ptr(), g.numel(), g.data_ptr(), st), "orcai_planes_relu_bwd")
+    N.check(lib.orcai_sepconv_planes(x.data_ptr(), B, Cin, H, W, k, k, relu_in, dw.data_ptr(), eye.data_ptr(), ones.data_ptr(), zeros.data_ptr(), Cin, 0, 0, 0, 0,
+                                     u.data_ptr(), st), "orcai_sepconv_planes")
+    N.check(lib.orcai_outer_reduce(g.data_ptr(), Cout, u.data_ptr(), Cin, B, H, W, k, 0, 0, 0, G.data_ptr(), partials.data_ptr(), partials.numel(), st), "orcai_outer_reduce")
+    N.check(lib.orcai_planes_sum(g.data_ptr(), B, Cout, H, W, k, scratch.data_ptr(), sums.data_ptr(), 0, st), "orcai_planes_sum")
+    N.check(lib.orcai_sepconv_planes(g.data_ptr(), B, Cout, H, W, k, 1, 0, ones.data_ptr(), wts.data_ptr(), ones.data_ptr(), zeros.data_ptr(), Cin, 0, 0, 0, 0,
+                                     du.data_ptr(), st), "orcai_sepconv_planes")
+    N.check(lib.orcai_dw_wgrad(x.data_ptr(), du.data_ptr(), B, Cin, H, W, k, k, relu_in, dWdw.data_ptr(), st), "orcai_dw_wgrad")
+    N.check(lib.orcai_frozen_bn_finish(G.data_ptr(), sums.data_ptr(), pw.data_ptr(), None if bias is None else bias.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                       var.data_ptr(), BN_EPS, Cin, Cout, dWpw.data_ptr(), None if dbias is None else dbias.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), st),
+            "orcai_frozen_bn_finish")
 
 
 def saved_layout(model) -> tuple[list, int]:
@@ -140,6 +179,7 @@ class EvalGrad:
             for name in names:
                 o, n, _ = table[name]
                 d["raw/" + name] = flat[o : o + n]
+        d["flat/w"], d["flat/s"] = wflat, sflat  # the weight gradient reads the variables themselves (Keras layouts)
         return d
 
     def _params(self, params, device) -> dict:
@@ -264,14 +304,88 @@ class EvalGrad:
         """C[M][Nn] = A[M][K] BT[K][Nn] (a dgrad GEMM: BT = the layer's weight matrix transposed)."""
         N.check(self._lib().orcai_gemm_bias_act(A.data_ptr(), BT.data_ptr(), None, None, None, C.data_ptr(), M, Nn, K, 0, N.stream_ptr()), "orcai_gemm_bias_act")
 
-    def backward(self, dprobs: Tensor, saved: Tensor, params=None) -> Tensor:
+    def backward(self, dprobs: Tensor, saved: Tensor, params=None, wgrad: bool = False):
+        """dx f32 [B, H, W]; with wgrad=True (dx, dwflat): dwflat f32 [layout().n_w], the gradient w.r.t. every trainable variable of the PREDICT-TIME network
+        (BatchNorm frozen on its moving statistics, which get no gradient) in ParamLayout order -- the flat order of Trainer and torch_ops.  dx is the same
+        launches and the same bits either way."""
         v = self.views(saved)
         if tuple(dprobs.shape) != tuple(v["probs"].shape) or dprobs.dtype != torch.float32 or dprobs.device != saved.device:
             raise ValueError(f"EvalGrad.backward: dprobs must be f32 {tuple(v['probs'].shape)} on {saved.device}, got {dprobs.dtype} {tuple(dprobs.shape)} on {dprobs.device}")
         with torch.cuda.device(saved.device):
-            return self._backward(dprobs.detach().contiguous(), v, params)
+            return self._backward(dprobs.detach().contiguous(), v, params, wgrad)
 
-    def _backward(self, dprobs, v, params):
+    # ------------------------------------------------------------------ weight gradients (wgrad=True)
+    def _wgrad_buffers(self, ws: dict, dev) -> None:
+        if "partials" not in ws:
+            ws["partials"] = torch.empty(512 * 64 * 64, dtype=torch.float32, device=dev)  # per-workgroup partial products (orcai_outer_reduce, orcai_conv0_bn_bwd_x)
+            ws["sum_scratch"] = torch.zeros(64, dtype=torch.float64, device=dev)
+            ws["sums_c0"] = torch.zeros(1024, dtype=torch.float64, device=dev)
+
+    def _scratch_planes(self, ws: dict, key: str, like: Tensor) -> Tensor:
+        """Zero-padded scratch planes shared by the layers of one shape (only interiors are ever written)."""
+        t = ws.get((key, tuple(like.shape)))
+        if t is None:
+            t = ws[(key, tuple(like.shape))] = torch.zeros_like(like)
+        return t
+
+    # Where orcai_sepconv_wgrad_frozen beats compose_wgrad (tools/time_frozen_grad.py, DESIGN 4.8: 1.30 x at 16 input channels, 0.41-0.66 x from 30 on -- its
+    # tile of 64 pixels leaves the G contraction 16 MFMAs per output tile between barriers, and the LDS images of wider layers leave one or two workgroups per
+    # compute unit); elsewhere, and where the launcher refuses (k = 5 / 7), the composition runs.
+    WGRAD_FUSED_MAX_CHANNELS = 16
+    WGRAD_WORKSPACE_FLOATS = 1024 * (64 * 64 + 64 + 9 * 64)  # serves every shape the launcher supports (include/orcai_hip.h)
+
+    def fused_wgrad(self, B: int, Cin: int, h: int, w: int) -> bool:
+        """Whether this separable conv's weight gradient asks orcai_sepconv_wgrad_frozen (k = 5 / 7 ask too: the launcher answers ORCAI_E_UNSUPPORTED)."""
+        return self.model.kernel_size != 3 or Cin <= self.WGRAD_FUSED_MAX_CHANNELS
+
+    def _wgrad_sep(self, d, ws, dw, name, bn, g, y_gate, x, relu_in, B, Cin, Cout, h, w):
+        """The gradients of separable conv `name` and the frozen BatchNorm `bn` behind it into the flat gradient dw: the reductions by orcai_sepconv_wgrad_frozen
+        where fused_wgrad() names the layer and the launcher accepts it, finished by orcai_frozen_bn_finish; otherwise compose_wgrad (g gated in place)."""
+        lib, st, lay, wf, sf = self._lib(), N.stream_ptr(), self.model.layout(), d["flat/w"], d["flat/s"]
+        W = lambda flat, n: flat[lay.w[n][0] : lay.w[n][0] + lay.w[n][1]]  # noqa: E731
+        S = lambda n: sf[lay.s[n][0] : lay.s[n][0] + lay.s[n][1]]  # noqa: E731
+        if ("wg/G", Cout, Cin) not in ws:
+            ws[("wg/G", Cout, Cin)] = (torch.zeros(Cout * Cin, dtype=torch.float32, device=g.device), torch.empty(Cout, dtype=torch.float32, device=g.device))
+        G, sums = ws[("wg/G", Cout, Cin)]
+        pw, bias, gamma, mean, var = W(wf, name + "/pointwise"), W(wf, name + "/bias"), W(wf, bn + "/gamma"), S(bn + "/mean"), S(bn + "/var")
+        if self.fused_wgrad(B, Cin, h, w):
+            if "wg/partials" not in ws:
+                ws["wg/partials"] = torch.empty(self.WGRAD_WORKSPACE_FLOATS, dtype=torch.float32, device=g.device)
+            rc = lib.orcai_sepconv_wgrad_frozen(x.data_ptr(), g.data_ptr(), None if y_gate is None else y_gate.data_ptr(), relu_in, B, Cin, Cout, h, w, self.model.kernel_size,
+                                                d[name + "/dw"].data_ptr(), d[name + "/wts"].data_ptr(), G.data_ptr(), sums.data_ptr(), W(dw, name + "/depthwise").data_ptr(),
+                                                ws["wg/partials"].data_ptr(), ws["wg/partials"].numel(), st)
+            if rc != N.E_UNSUPPORTED:
+                N.check(rc, "orcai_sepconv_wgrad_frozen")
+                N.check(lib.orcai_frozen_bn_finish(G.data_ptr(), sums.data_ptr(), pw.data_ptr(), bias.data_ptr(), gamma.data_ptr(), mean.data_ptr(), var.data_ptr(), BN_EPS, Cin,
+                                                   Cout, W(dw, name + "/pointwise").data_ptr(), W(dw, name + "/bias").data_ptr(), W(dw, bn + "/gamma").data_ptr(),
+                                                   W(dw, bn + "/beta").data_ptr(), st), "orcai_frozen_bn_finish")
+                return
+        G.zero_()  # orcai_outer_reduce accumulates
+        compose_wgrad(lib, g, y_gate, x, relu_in, B, Cin, Cout, h, w, self.model.kernel_size, d[name + "/dw"], d[name + "/wts"], pw, bias, gamma, mean, var,
+                      self._scratch_planes(ws, "wg/u", x), self._scratch_planes(ws, "wg/du", x), G, sums, ws["sum_scratch"], ws["partials"], W(dw, name + "/depthwise"),
+                      W(dw, name + "/pointwise"), W(dw, name + "/bias"), W(dw, bn + "/gamma"), W(dw, bn + "/beta"), st, consts=ws)
+
+    def _gemm_wgrad(self, A, lda, Bm, ldb, C, M, Nn, K):
+        """C[M][Nn] = A^T Bm with A [K][lda] (its first M columns) and Bm [K][ldb] (its first Nn columns): the training step's weight-gradient GEMM."""
+        N.check(self._lib().orcai_gemm_strided(A.data_ptr(), 1, lda, Bm.data_ptr(), ldb, 1, C.data_ptr(), M, Nn, K, 1.0, 0, None, 0.0, N.stream_ptr()), "orcai_gemm_strided")
+
+    def _recompute_lstm_outputs(self, d, v, B, T):
+        """h1, h2 [B][T][2u]: `saved` keeps the gates and cell states, not the layer outputs the weight gradients contract with -- the forward's two launches per
+        layer again (the same bits), gates and cell states into scratch."""
+        lib, st, u, p = self._lib(), N.stream_ptr(), self.model.lstm_units, N.ptr
+        f32 = dict(dtype=torch.float32, device=v["feat"].device)
+        M = B * T
+        xin, fin, out = v["feat"], v["feat"].shape[-1], []
+        xz, gates, cs = torch.empty((B, T, 2, 4 * u), **f32), torch.empty((B, T, 2, 4 * u), **f32), torch.empty((B, T, 2, u), **f32)
+        for layer in (1, 2):
+            N.check(lib.orcai_gemm_bias_act(p(xin), p(d[f"lstm{layer}/W"]), p(d[f"lstm{layer}/b"]), None, None, p(xz), M, 8 * u, fin, 0, st), "orcai_gemm_bias_act")
+            hout = torch.empty((B, T, 2 * u), **f32)
+            N.check(lib.orcai_lstm_train_fwd(p(xz), p(d[f"lstm{layer}/U"]), B, T, u, p(hout), p(gates), p(cs), st), "orcai_lstm_train_fwd")
+            out.append(hout)
+            xin, fin = hout, 2 * u
+        return out
+
+    def _backward(self, dprobs, v, params, wgrad=False):
         m, lib, st = self.model, self._lib(), N.stream_ptr()
         dev = dprobs.device
         d = self._params(params, dev)
@@ -285,33 +399,77 @@ class EvalGrad:
         f32 = dict(dtype=torch.float32, device=dev)
         ws = self._workspace(B, dev)
         p = N.ptr
+        dw = None
+        if wgrad:
+            # the flat gradient, zeroed: orcai_outer_reduce, orcai_dw_wgrad, orcai_conv1d_bwd and the entry conv's launchers accumulate
+            lay = m.layout()
+            dw = torch.zeros(lay.n_w, **f32)
+            self._wgrad_buffers(ws, dev)
+            Gw = lambda n: dw[lay.w[n][0] : lay.w[n][0] + lay.w[n][1]]  # noqa: E731
+            Sv = lambda n: d["flat/s"][lay.s[n][0] : lay.s[n][0] + lay.s[n][1]]  # noqa: E731
         dz = torch.empty((M, L), **f32)
         N.check(lib.orcai_sigmoid_bwd(p(v["probs"]), p(dprobs), M * L, p(dz), st), "orcai_sigmoid_bwd")
         if self.conv1d:
             dfm = torch.empty((B, T, FINAL_FILTERS), **f32)
-            dW = torch.zeros((FINAL_FILTERS, FINAL_FILTERS, L), **f32)  # orcai_conv1d_bwd has no data-gradient-only form: its weight gradient lands here and is dropped
+            # orcai_conv1d_bwd has no data-gradient-only form: without wgrad its weight gradient lands in a scratch tensor and is dropped
+            dW = Gw("conv1d/kernel") if wgrad else torch.zeros((FINAL_FILTERS, FINAL_FILTERS, L), **f32)
             N.check(lib.orcai_conv1d_bwd(p(v["fm"]), p(d["conv1d/W"]), p(dz), B, T, FINAL_FILTERS, FINAL_FILTERS, L, p(dW), p(dfm), st), "orcai_conv1d_bwd")
+            if wgrad:
+                N.check(lib.orcai_colsum(p(dz), M, L, p(Gw("conv1d/bias")), 0, st), "orcai_colsum")
             dfeat = torch.empty((M, cols), **f32)
             N.check(lib.orcai_freq_mean_bwd(p(dfm), M, wd, FINAL_FILTERS, p(dfeat), st), "orcai_freq_mean_bwd")
         else:
             u = m.lstm_units
             dd1 = torch.empty((M, DENSE_UNITS), **f32)
             self._gemm(dz, d["dense2/WT"], dd1, M, DENSE_UNITS, L)
+            if wgrad:
+                # Dense(labels) from the BatchNorm output d1 (recomputed from the stored ReLU output), and bn_d from the gradient at its output -- before
+                # orcai_rows_affine_relu_bwd turns dd1 into the gradient in front of the ReLU
+                d1 = torch.empty((M, DENSE_UNITS), **f32)
+                N.check(lib.orcai_rows_affine(p(v["pre1"]), M, DENSE_UNITS, DENSE_UNITS, p(d["dense1/scale"]), p(d["dense1/shift"]), 0, p(d1), st), "orcai_rows_affine")
+                self._gemm_wgrad(d1, DENSE_UNITS, dz, L, Gw("dense2/kernel"), DENSE_UNITS, L, M)
+                N.check(lib.orcai_colsum(p(dz), M, L, p(Gw("dense2/bias")), 0, st), "orcai_colsum")
+                rows_ws = torch.empty(2 * DENSE_UNITS, **f32)
+                N.check(lib.orcai_rows_bn_frozen_wgrad(p(dd1), p(v["pre1"]), M, DENSE_UNITS, DENSE_UNITS, p(Sv("bn_d/mean")), p(Sv("bn_d/var")), BN_EPS, p(Gw("bn_d/beta")),
+                                                       p(Gw("bn_d/gamma")), p(rows_ws), st), "orcai_rows_bn_frozen_wgrad")
             N.check(lib.orcai_rows_affine_relu_bwd(p(dd1), p(v["pre1"]), M, DENSE_UNITS, DENSE_UNITS, p(d["dense1/scale"]), p(dd1), st), "orcai_rows_affine_relu_bwd")
+            if wgrad:
+                h1, h2 = self._recompute_lstm_outputs(d, v, B, T)
+                self._gemm_wgrad(h2, 2 * u, dd1, DENSE_UNITS, Gw("dense1/kernel"), 2 * u, DENSE_UNITS, M)
+                N.check(lib.orcai_colsum(p(dd1), M, DENSE_UNITS, p(Gw("dense1/bias")), 0, st), "orcai_colsum")
+                unpack, alive = [], []  # kernel-order LSTM gradients -> Keras layout in the flat gradient: ONE launch for both layers at the end
             dh = torch.empty((M, 2 * u), **f32)
             self._gemm(dd1, d["dense1/WT"], dh, M, 2 * u, DENSE_UNITS)
             for layer, fin in ((2, 2 * u), (1, cols)):
                 dxz = torch.empty((B, T, 2, 4 * u), **f32)
                 N.check(lib.orcai_lstm_bwd(p(dh), p(v[f"gates{layer}"]), p(v[f"cs{layer}"]), p(d[f"lstm{layer}/U"]), B, T, u, p(dxz), st), "orcai_lstm_bwd")
+                if wgrad:  # the training step's weight-gradient GEMMs on this dxz (both directions at once, permuted columns)
+                    xin, hout = (h1, h2) if layer == 2 else (v["feat"], h1)
+                    dWc, dbc, hp = torch.empty((fin, 8 * u), **f32), torch.empty(8 * u, **f32), torch.empty((B, T, 2, u), **f32)
+                    self._gemm_wgrad(xin, fin, dxz, 8 * u, dWc, fin, 8 * u, M)
+                    N.check(lib.orcai_colsum(p(dxz), M, 8 * u, p(dbc), 0, st), "orcai_colsum")
+                    N.check(lib.orcai_lstm_hprev(p(hout), B, T, u, p(hp), st), "orcai_lstm_hprev")
+                    for di, dname in enumerate(("fwd", "bwd")):
+                        dU = torch.empty((u, 4 * u), **f32)
+                        self._gemm_wgrad(hp.view(-1)[di * u :], 2 * u, dxz.view(-1)[di * 4 * u :], 8 * u, dU, u, 4 * u, M)
+                        unpack += [N.UnpackDesc(dU.data_ptr(), 4 * u, 0, u, Gw(f"lstm{layer}/{dname}/recurrent").data_ptr(), None, 0.0),
+                                   N.UnpackDesc(dWc.data_ptr(), 8 * u, di * 4 * u, fin, Gw(f"lstm{layer}/{dname}/kernel").data_ptr(), None, 0.0),
+                                   N.UnpackDesc(dbc.data_ptr(), 8 * u, di * 4 * u, 1, Gw(f"lstm{layer}/{dname}/bias").data_ptr(), None, 0.0)]
+                        alive += [dU, dWc, dbc]
                 dxl = torch.empty((M, fin), **f32)
                 self._gemm(dxz, d[f"lstm{layer}/WT"], dxl, M, fin, 8 * u)
                 dh = dxl
+            if wgrad:
+                N.check(lib.orcai_unpack_lstm_grads((N.UnpackDesc * len(unpack))(*unpack), len(unpack), u, st), "orcai_unpack_lstm_grads")
+                del alive
             dfeat = dh
         # the ReLU behind bn_f (its scale is inside sep_f's wts), then into planes
         N.check(lib.orcai_relu_bwd(p(dfeat), p(v["feat"]), M * cols, p(dfeat), st), "orcai_relu_bwd")
         N.check(lib.orcai_feat_to_planes(p(dfeat), B, FINAL_FILTERS, T, wd, k, p(ws["dvf"]), st), "orcai_feat_to_planes")
         nb = len(m.filters)
         dprev = ws["dprev_f"]
+        if wgrad:
+            self._wgrad_sep(d, ws, dw, "sep_f", "bn_f", ws["dvf"], None, v[f"prev{nb}"], 0, B, c_last, FINAL_FILTERS, T, wd)
         self._dgrad(d, ws, "sep_f", ws["dvf"], None, None, B, c_last, FINAL_FILTERS, T, wd, dprev)
         for b in range(nb, 0, -1):
             f = m.filters[b - 1]
@@ -321,7 +479,15 @@ class EvalGrad:
             dout = dprev
             dyb, dya, dr = ws[f"dyb{b}"], ws[f"dya{b}"], ws[f"dr{b}"]
             N.check(lib.orcai_pool_bwd(p(dout), p(v[f"s{b}"]), B, f, h, w, k, p(dyb), st), "orcai_pool_bwd")
+            if wgrad:
+                # the residual 1x1 stride-2 conv reads the block input at the even pixels; dout is the gradient at its output
+                N.check(lib.orcai_outer_reduce(p(x_in), cprev, p(dout), f, B, ho, wo, k, 1, h, w, p(Gw(f"b{b}/res/kernel")), p(ws["partials"]), ws["partials"].numel(), st),
+                        "orcai_outer_reduce")
+                N.check(lib.orcai_planes_sum(p(dout), B, f, ho, wo, k, p(ws["sum_scratch"]), p(Gw(f"b{b}/res/bias")), 0, st), "orcai_planes_sum")
+                self._wgrad_sep(d, ws, dw, f"b{b}/sep_b", f"b{b}/bn_b", dyb, None, v[f"a{b}"], 0, B, f, f, h, w)
             self._dgrad(d, ws, f"b{b}/sep_b", dyb, None, None, B, f, f, h, w, dya)
+            if wgrad:
+                self._wgrad_sep(d, ws, dw, f"b{b}/sep_a", f"b{b}/bn_a", dya, v[f"a{b}"], x_in, 1, B, cprev, f, h, w)
             self._dgrad(d, ws, f"b{b}/sep_a", dya, v[f"a{b}"], x_in, B, cprev, f, h, w, dr)
             # the residual 1x1 stride-2 conv reads the block input in front of the ReLU: its gradient joins at the even pixels
             N.check(lib.orcai_sepconv_planes(p(dout), B, f, ho, wo, k, 1, 0, p(ws["ones"]), p(d[f"b{b}/res/wT"]), p(ws["ones"]), p(ws["zeros"]), cprev, 0, 3, h, w, p(dr), st),
@@ -330,7 +496,20 @@ class EvalGrad:
         dx = torch.empty((B, H, W), **f32)
         N.check(lib.orcai_conv0_bn_bwd_dx(p(v["x"]), H * W, p(dprev), B, H, W, k, p(d["raw/conv0/kernel"]), p(d["raw/conv0/bias"]), p(d["raw/bn0/mean"]), p(d["raw/bn0/var"]),
                                           p(d["raw/bn0/gamma"]), p(d["raw/bn0/beta"]), BN_EPS, p(ws["sums0"]), p(dx), st), "orcai_conv0_bn_bwd_dx")
-        return dx
+        if not wgrad:
+            return dx
+        # The entry conv.  orcai_conv0_bn_bwd_x with the MOVING statistics: its sums sum g and sum g * xhat ARE the eval-mode dbeta0 and dgamma0; its weight gradient
+        # is that of a batch-statistics BatchNorm and is dropped.  orcai_conv0_bn_bwd_x_ready on zeroed sums forms dv = gamma * inv * g exactly (the trick dx uses):
+        # its weight gradient is the eval-mode dW0, and the (zero) sums it reports are dropped.  dbias0 = sum dv = scale0 * dbeta0 (orcai_frozen_bn_finish).
+        c0 = (p(v["x"]), H * W, p(dprev), B, H, W, k, p(d["raw/conv0/kernel"]), p(d["raw/conv0/bias"]), p(d["raw/bn0/mean"]), p(d["raw/bn0/var"]), p(d["raw/bn0/gamma"]),
+              p(d["raw/bn0/beta"]), BN_EPS)
+        junk_w, junk_s = torch.zeros(k * k * ENTRY_FILTERS, **f32), torch.empty(2 * ENTRY_FILTERS, **f32)
+        N.check(lib.orcai_conv0_bn_bwd_x(*c0, p(ws["sums_c0"]), p(Gw("bn0/beta")), p(Gw("bn0/gamma")), p(junk_w), p(ws["partials"]), ws["partials"].numel(), st), "orcai_conv0_bn_bwd_x")
+        N.check(lib.orcai_conv0_bn_bwd_x_ready(*c0, p(ws["sums0"]), p(junk_s), p(junk_s[ENTRY_FILTERS:]), p(Gw("conv0/kernel")), p(ws["partials"]), ws["partials"].numel(), st),
+                "orcai_conv0_bn_bwd_x_ready")
+        N.check(lib.orcai_frozen_bn_finish(None, p(Gw("bn0/beta")), None, None, p(d["raw/bn0/gamma"]), None, p(d["raw/bn0/var"]), BN_EPS, 0, ENTRY_FILTERS, None,
+                                           p(Gw("conv0/bias")), None, None, st), "orcai_frozen_bn_finish")
+        return dx, dw
 
 
 def saliency(model, x: Tensor, label: int | None = None) -> Tensor:

@@ -9,6 +9,7 @@ known without a GPU.
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.detect_wrt_input(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
+    torch.ops.orcai.detect_wrt_params(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
     torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
 
 ``weights`` / ``stats`` are the trainable variables and the BatchNorm moving statistics in ``variable_spec()`` order (Keras layouts);
@@ -34,7 +35,13 @@ autograd w.r.t. ``x`` only: saliency, robustness probes, training something in f
 reads in a tensor of its own, so any number of forwards may be alive at once.  ``forward`` / ``forward_wrt_input`` with training=False keep
 refusing a backward: they run the fused inference path, which stores nothing.
 
-What does not exist: a gradient w.r.t. the weights in eval mode, any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
+``detect_wrt_params`` is the same predict-time network with autograd w.r.t. the weights as well (and ``x`` when it requires grad): fine-tuning with
+BatchNorm FROZEN on its moving statistics and no Dropout -- the network ``orcai predict`` runs -- through ``OrcaiModule(model, frozen_bn=True)`` and any
+``torch.optim``.  Its backward is the functional op ``orcai::detect_backward_params(grad, saved, weights, stats, config) -> (dx, dwflat)``
+(``EvalGrad.backward(wgrad=True)``); ``stats`` get no gradient and are never written.  ``detect_wrt_input`` keeps returning no weight gradient.
+
+What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``orcai train`` on the frozen network (its fused ``Trainer`` step is training mode)
+or through the shared-trunk ``predict_spectrogram`` path, any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
 itself has no backward, and ``orcai::resample`` / ``orcai::resample_backward`` have no second derivative.
 """
 
@@ -657,6 +664,66 @@ def _detect_autograd(x, weights, stats, config):
 _register("detect_wrt_input", "(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor", _detect_impl, _probs_fake, _detect_autograd)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::detect_wrt_params
+# The predict-time network with the gradient w.r.t. its weights as well: fine-tuning a pretrained detector with BatchNorm frozen on its moving
+# statistics (EvalGrad.backward(wgrad=True)).  Built as detect_wrt_input is: the same inner forward op (orcai::detect_with_saved), and a functional
+# backward op that returns dx and the flat weight gradient in ParamLayout order; the autograd kernel splits it per variable (layout().split_w, the
+# inverse of _Engine.flat).  The statistics get None; nothing is mutated.
+@torch.library.custom_op("orcai::detect_backward_params", mutates_args=())
+def detect_backward_params(grad: Tensor, saved: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> tuple[Tensor, Tensor]:
+    """EvalGrad.backward(wgrad=True): (dL/dx f32[B, H, W], the flat f32 gradient w.r.t. the trainable variables in variable_spec() order) from grad = dL/dprobs
+    and the `saved` tensor orcai::detect_with_saved returned for the same weights."""
+    cfg = _parse(config)
+    H, W = int(cfg["input_shape"][0]), int(cfg["input_shape"][1])
+    _check_vars(config, weights, stats)
+    eng, eg = _eval_grad(config, grad.device)
+    if grad.shape[0] == 0:
+        return grad.new_empty((0, H, W)), grad.new_zeros((eng.model.layout().n_w,))
+    with torch.cuda.device(grad.device):
+        return eg.backward(grad, saved, params=eng.flat(weights, stats), wgrad=True)
+
+
+@detect_backward_params.register_fake
+def _detect_backward_params_fake(grad, saved, weights, stats, config):
+    return _detect_backward_fake(grad, saved, weights, stats, config), _flat_grad_fake(grad, config)
+
+
+def detect_wrt_params(x: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
+    """The model in eval mode on snippets x[B][H][W]; its backward returns a gradient per weight (BatchNorm frozen on `stats`, which get none) and dL/dx when
+    x requires grad."""
+    return torch.ops.orcai.detect_wrt_params(x, weights, stats, config)
+
+
+class _DetectParamsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, config, n_weights, *variables):
+        weights, stats = list(variables[:n_weights]), list(variables[n_weights:])
+        with torch._C._AutoDispatchBelowAutograd():
+            probs, saved = torch.ops.orcai.detect_with_saved(x, weights, stats, config)
+        ctx.config, ctx.n_weights = config, n_weights
+        ctx.save_for_backward(saved, *[t.detach() for t in variables])
+        return probs
+
+    @staticmethod
+    def backward(ctx, grad):
+        saved, *variables = ctx.saved_tensors
+        n = ctx.n_weights
+        dx, flat = torch.ops.orcai.detect_backward_params(grad.contiguous(), saved, list(variables[:n]), list(variables[n:]), ctx.config)
+        need = ctx.needs_input_grad
+        wgrads = [g if want else None for g, want in zip(_skeleton(ctx.config).layout().split_w(flat), need[3 : 3 + n])]
+        return (dx if need[0] else None, None, None, *wgrads, *([None] * (len(variables) - n)))
+
+
+def _detect_params_autograd(x, weights, stats, config):
+    if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
+        return _DetectParamsFunction.apply(x, config, len(weights), *weights, *stats)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.detect_wrt_params(x, weights, stats, config)
+
+
+_register("detect_wrt_params", "(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor", _detect_impl, _probs_fake, _detect_params_autograd)
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
 @torch.library.custom_op("orcai::predict_spectrogram", mutates_args=())
 def predict_spectrogram(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
@@ -688,11 +755,17 @@ class OrcaiModule(torch.nn.Module):
     only, and an x that requires grad raises -- unless input_grad=True: the module then calls orcai::forward_wrt_input, whose training-mode
     backward also returns dL/dx (not in eval mode, not for f16 models).  input_grad="eval": as input_grad=True in .train(); in .eval() the
     module calls orcai::detect_wrt_input, the predict-time network with a backward w.r.t. x (the parameters get no gradient, the statistics are
-    not touched).  Built from a model object or a model directory (io.load_orcai_model).  dropout_seed of the n-th training forward:
+    not touched).  frozen_bn=True: fine-tuning of the PREDICT-TIME network -- the module calls orcai::detect_wrt_params whether in .train() or .eval():
+    BatchNorm with the moving statistics (never written: bit-identical after any number of steps), no Dropout, gradients for every parameter and
+    for an x that requires grad; input_grad="eval" is implied, input_grad=True (the training-mode input gradient) contradicts it and raises.
+    Built from a model object or a model directory (io.load_orcai_model).  dropout_seed of the n-th training forward:
     seed * 1000003 + n."""
 
-    def __init__(self, model, seed: int = 0, input_grad: bool | str = False):
+    def __init__(self, model, seed: int = 0, input_grad: bool | str = False, frozen_bn: bool = False):
         super().__init__()
+        if frozen_bn and input_grad is not False and input_grad != "eval":
+            raise ValueError("OrcaiModule: frozen_bn=True runs the eval-mode network, whose input gradient is input_grad='eval' (implied); "
+                             f"input_grad={input_grad!r} asks for the training-mode one")
         if isinstance(model, (str, os.PathLike)):
             from orcai_amd.io import load_orcai_model
 
@@ -712,6 +785,9 @@ class OrcaiModule(torch.nn.Module):
         if isinstance(input_grad, str) and input_grad != "eval":
             raise ValueError(f"OrcaiModule: input_grad must be False, True or 'eval', got {input_grad!r}")
         self.input_grad = input_grad if input_grad == "eval" else bool(input_grad)
+        self.frozen_bn = bool(frozen_bn)
+        if self.frozen_bn:
+            self.input_grad = "eval"
         self.dropout_draws = 0
 
     def weights_list(self) -> list:
@@ -721,6 +797,8 @@ class OrcaiModule(torch.nn.Module):
         return [getattr(self, param_name(n)) for n in self._stats]
 
     def forward(self, x: Tensor) -> Tensor:
+        if self.frozen_bn:
+            return torch.ops.orcai.detect_wrt_params(x, self.weights_list(), self.stats_list(), self.config)
         if self.input_grad == "eval" and not self.training:
             return torch.ops.orcai.detect_wrt_input(x, self.weights_list(), self.stats_list(), self.config)
         seed = 0
