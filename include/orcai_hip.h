@@ -645,6 +645,26 @@ int orcai_h_sepconv(const void* in, int B, int Cin, int H, int W, int ksize_plan
 int orcai_h_pool_res_add(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, void* out, int xpooled,
                          const float* bn_mean, const float* bn_var, const float* bn_gamma, const float* bn_beta, float bn_eps, void* stream);
 
+/* orcai_h_pool_res_add(xpooled = 1, no BatchNorm) over B windows of one recording, every output row stored into the per-snippet planes that hold
+ * it: the f16 twin of orcai_pool_res_add_scatter, with its row semantics (window b's output row r is recording row base + b * img_step + r; stored
+ * for r_lo <= r < r_hi, also r < r_lo for a window starting at recording row 0, into rows keep_lo <= y < keep_hi of snippets 0 <= k < nsnip).
+ *   out f16[nsnip][ceil(C/8)][Hd + 2*(k/2)][orcai_padded_width(ceil(W/2), k)][8] octet planes (pads untouched), Hd = 2 * period.
+ * Bit for bit the values orcai_h_pool_res_add stores for the same window (one kernel body).  ORCAI_E_UNSUPPORTED, before anything is launched: a shape
+ * orcai_h_pool_res_add does not take on its x-pooled path (C or Cp > 64, k not 3 / 5 / 7), keep_hi - keep_lo > 2 * period, more than 65535 windows,
+ * or a plane / recording-row offset past the kernel's 32-bit indices.  ORCAI_E_BADARG: null or misaligned pointers, non-positive sizes. */
+int orcai_h_pool_res_add_scatter(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, void* out, int Hd,
+                                 int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo, int keep_hi, void* stream);
+/* The same with up to ORCAI_ROW_FAMILIES destination families (orcai_pool_res_add_scatter_families): recording row R goes to row
+ * y = R - offset - j * period of image j of every family, 0 <= j < count, keep_lo <= y < keep_hi; out f16[count][ceil(C/8)][Hd + 2*(k/2)][...][8].
+ * `fams` is a HOST array, read during the call.  Also ORCAI_E_UNSUPPORTED: more than ORCAI_ROW_FAMILIES families, or a family with
+ * keep_hi - keep_lo > 2 * period (a row in more than two of its images). */
+typedef struct {
+  void* out;
+  int Hd, period, offset, count, keep_lo, keep_hi;
+} orcai_h_row_family;
+int orcai_h_pool_res_add_scatter_families(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, int base,
+                                          int img_step, int r_lo, int r_hi, const orcai_h_row_family* fams /* host */, int n_fams, void* stream);
+
 /* C[M][N] = act(A[M][K] Wt^T + bias) [* scale + shift]: A f32 (converted to f16 on load), Wt f16[N][roundup32(K)], f32 accumulate and
  * output; act 1 = ReLU.  LSTM input projections and Dense-128 (architectures.py:210-237).  K % 4 == 0. */
 int orcai_h_gemm_bias_act(const float* A, const void* Wt, const float* bias, const float* scale, const float* shift, float* C, int64_t M, int N, int K, int act,

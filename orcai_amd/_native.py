@@ -24,7 +24,7 @@ class UnpackDesc(C.Structure):
 
 
 class RowFamily(C.Structure):
-    """orcai_row_family of include/orcai_hip.h."""
+    """orcai_row_family / orcai_h_row_family of include/orcai_hip.h (one layout)."""
 
     _fields_ = [("out", C.c_void_p), ("Hd", C.c_int), ("period", C.c_int), ("offset", C.c_int), ("count", C.c_int), ("keep_lo", C.c_int), ("keep_hi", C.c_int)]
 
@@ -133,6 +133,8 @@ _SIGNATURES = {
     "orcai_h_conv0_affine_bn": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "orcai_h_sepconv": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "orcai_h_pool_res_add": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p]),
+    "orcai_h_pool_res_add_scatter": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
+    "orcai_h_pool_res_add_scatter_families": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
     "orcai_h_gemm_bias_act": (C.c_int, [C.c_void_p] * 6 + [c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "orcai_h_bn_planes_stats": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),
     "orcai_h_planes_sum": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -286,13 +286,32 @@ __global__ __launch_bounds__(256) void sepconv_h_kernel(const h16* __restrict__ 
 // operands as 16-byte vectors, takes the maximum in f16, adds the residual in f32 and stores 16 bytes.
 // bn_mean != NULL (training forward): s holds the PRE-BatchNorm tensor and the pooling runs on BN(s) = fma(s, sc, sh) without
 // materialising it: fma is monotone per channel, so the maximum (minimum for sc < 0) is transformed once.
+// The per-pixel code lives in pool_res_add_h_body; a kernel passes the store: store(b, oq, i, j, flat, v) receives the finished octet oq of output
+// pixel (row i, column j; flat = (i + R) * WPo + j) of image b.
+// SCATTER (pool_res_scatter_h_kernel: orcai_h_pool_res_add_scatter, orcai_h_pool_res_add_scatter_families): the images of the launch are windows of one
+// recording, not snippets, and every output row is stored into every destination image that holds it -- the row map of the f32 path's
+// pool_res_add_x_kernel (model_fwd.hip, "SCATTER"), on octet planes.  Image b's output row r is recording row Rr = base + b * img_step + r; a row is
+// stored only for r in [r_lo, r_hi) (a window that starts at recording row 0 also stores its rows above r_lo).  Each of up to kRowFamiliesH families is
+// `count` images of Hd rows, image j holding recording rows [offset + j * period, + Hd); Rr goes to row y = Rr - offset - j * period of every image j in
+// [0, count) with y in [keep_lo, keep_hi).  keep_hi - keep_lo <= 2 * period (checked by the launchers): at most two images of a family hold a kept row,
+// both written by the lane that owns the value -- plain 16-byte stores, no atomics.
 // =========================================================================================
-template <int MT>
-__global__ __launch_bounds__(256) void pool_res_add_h_kernel(const h16* __restrict__ s, const h16* __restrict__ prev, int C, int Cp, int H, int W, int WP, int R,
-                                                              int Ho, int Wo, int WPo, int pad_top, int pad_left, const h16* __restrict__ wrf /*[KGp][MT][64][8]*/,
-                                                              const float* __restrict__ br, h16* __restrict__ out /*[B][CO][Ho+2R][WPo][8]*/, int xpooled,
-                                                              int tasks, uint32_t magic_WPo, const float* __restrict__ bn_mean, const float* __restrict__ bn_var,
-                                                              const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta, float bn_eps) {
+constexpr int kRowFamiliesH = ORCAI_ROW_FAMILIES;
+struct RowFamilyH {
+  h16* out;  // [count][CO][Hd + 2R][WPo][8] padded planes, pads untouched
+  int Hd, period, offset, count, keep_lo, keep_hi;
+};
+struct RowMapH {
+  int base, img_step, r_lo, r_hi, nfam;
+  RowFamilyH f[kRowFamiliesH];
+};
+
+template <int MT, typename Store>
+__device__ __forceinline__ void pool_res_add_h_body(const h16* __restrict__ s, const h16* __restrict__ prev, int C, int Cp, int H, int W, int WP, int R, int Ho, int Wo,
+                                                    int WPo, int pad_top, int pad_left, const h16* __restrict__ wrf /*[KGp][MT][64][8]*/,
+                                                    const float* __restrict__ br, int xpooled, int tasks, uint32_t magic_WPo, const float* __restrict__ bn_mean,
+                                                    const float* __restrict__ bn_var, const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
+                                                    float bn_eps, Store store) {
   const int lane = threadIdx.x & 63;
   int bx, b;
   xcd_remap(bx, b);
@@ -300,7 +319,7 @@ __global__ __launch_bounds__(256) void pool_res_add_h_kernel(const h16* __restri
   if (task >= tasks) return;
   const int lk = lane >> 4, lj = lane & 15;
   const int CO = (C + 7) >> 3, COp = (Cp + 7) >> 3, KGp = (COp + 3) >> 2;
-  const int plane = (H + 2 * R) * WP, plane_o = (Ho + 2 * R) * WPo;
+  const int plane = (H + 2 * R) * WP;
   const int qbase = R * WPo + task * 64;
   const int q = qbase + lane;
   const int prow = (int)__umulhi((uint32_t)q, magic_WPo);
@@ -409,9 +428,47 @@ __global__ __launch_bounds__(256) void pool_res_add_h_kernel(const h16* __restri
         if (bn_mean) pooled = fmaf(bsc[m][e] >= 0.0f ? pm[e] : pn[e], bsc[m][e], bsh[m][e]);
         o8[e] = c < C ? pooled + res[e] : 0.0f;
       }
-      reinterpret_cast<h16x8*>(out)[((int64_t)b * CO + oq) * plane_o + flat] = pack8(o8);
+      store(b, oq, i, j, flat, pack8(o8));
     }
   }
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void pool_res_add_h_kernel(const h16* __restrict__ s, const h16* __restrict__ prev, int C, int Cp, int H, int W, int WP, int R,
+                                                              int Ho, int Wo, int WPo, int pad_top, int pad_left, const h16* __restrict__ wrf /*[KGp][MT][64][8]*/,
+                                                              const float* __restrict__ br, h16* __restrict__ out /*[B][CO][Ho+2R][WPo][8]*/, int xpooled,
+                                                              int tasks, uint32_t magic_WPo, const float* __restrict__ bn_mean, const float* __restrict__ bn_var,
+                                                              const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta, float bn_eps) {
+  const int CO = (C + 7) >> 3, plane_o = (Ho + 2 * R) * WPo;
+  pool_res_add_h_body<MT>(s, prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, pad_top, pad_left, wrf, br, xpooled, tasks, magic_WPo, bn_mean, bn_var, bn_gamma, bn_beta, bn_eps,
+                          [=](int b, int oq, int, int, int flat, h16x8 v) { reinterpret_cast<h16x8*>(out)[((int64_t)b * CO + oq) * plane_o + flat] = v; });
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void pool_res_scatter_h_kernel(const h16* __restrict__ s /*x-pooled*/, const h16* __restrict__ prev, int C, int Cp, int H, int W, int WP,
+                                                                  int R, int Ho, int Wo, int WPo, int pad_top, const h16* __restrict__ wrf,
+                                                                  const float* __restrict__ br, int tasks, uint32_t magic_WPo, RowMapH rm) {
+  const int CO = (C + 7) >> 3;
+  pool_res_add_h_body<MT>(s, prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, pad_top, 0, wrf, br, 1, tasks, magic_WPo, nullptr, nullptr, nullptr, nullptr, 0.0f,
+                          [&](int b, int oq, int orow, int ocol, int, h16x8 v) {
+                            const int rr = rm.base + b * rm.img_step + orow;
+                            if ((orow < rm.r_lo && rr != orow) || orow >= rm.r_hi) return;  // rr == orow: the window starts at the first snippet's own top edge
+#pragma unroll
+                            for (int fi = 0; fi < kRowFamiliesH; ++fi) {
+                              if (fi >= rm.nfam) break;  // uniform: the family count is a kernel argument
+                              const RowFamilyH& fm = rm.f[fi];
+                              const int rel = rr - fm.offset - fm.keep_lo;
+                              if (rel < 0) continue;
+                              const int jhi = rel / fm.period;
+                              const int64_t plane_d = (int64_t)(fm.Hd + 2 * R) * WPo;
+#pragma unroll
+                              for (int d = 0; d < 2; ++d) {
+                                const int j = jhi - d, y = rr - fm.offset - j * fm.period;
+                                if (j >= 0 && j < fm.count && y < fm.keep_hi)
+                                  reinterpret_cast<h16x8*>(fm.out)[((int64_t)j * CO + oq) * plane_d + (int64_t)(y + R) * WPo + ocol] = v;
+                              }
+                            }
+                          });
 }
 
 // =========================================================================================
@@ -877,6 +934,80 @@ int orcai_h_pool_res_add(const void* s, const void* prev, int B, int C, int Cp, 
   }
 #undef ORCAI_HPOOL
   return (int)hipGetLastError();
+}
+
+// the x-pooled pooling tail stored through a row map: ORCAI_E_UNSUPPORTED, before anything is launched, for every shape orcai_h_pool_res_add does not run on its
+// x-pooled path and wherever an offset would leave the kernels' index width
+static int h_pool_res_scatter_launch(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, RowMapH rm,
+                                     void* stream) {
+  if (ksize != 3 && ksize != 5 && ksize != 7) return ORCAI_E_UNSUPPORTED;
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  int tot_h = (Ho - 1) * 2 + 3 - H, tot_w = (Wo - 1) * 2 + 2 - W;
+  if (tot_h < 0) tot_h = 0;
+  if (tot_w < 0) tot_w = 0;
+  if (tot_w / 2 != 0 || C > 64 || Cp > 64 || B > 65535) return ORCAI_E_UNSUPPORTED;
+  const int WP = orcai_padded_width(W, ksize), WPo = orcai_padded_width(Wo, ksize), R = ksize / 2;
+  // 32-bit pixel offsets inside one plane of prev; flat output pixel * WPo below 2^32 (the row / column split by multiplication, magic_for)
+  if ((int64_t)(H + 2 * R) * WP >= (1ll << 31) || ((int64_t)(Ho + R) * WPo + 64) * WPo >= (1ll << 32)) return ORCAI_E_UNSUPPORTED;
+  if ((int64_t)rm.base + (int64_t)(B - 1) * rm.img_step + Ho >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;  // recording rows stay 32-bit
+  rm.r_lo = rm.r_lo < 0 ? 0 : rm.r_lo;
+  rm.r_hi = rm.r_hi > Ho ? Ho : rm.r_hi;
+  const int tasks = (Ho * WPo + 63) / 64;
+  dim3 grid((tasks + 3) / 4, B);
+  hipStream_t st = (hipStream_t)stream;
+#define ORCAI_HSCATTER(MT)                                                                                                                                     \
+  hipLaunchKernelGGL(pool_res_scatter_h_kernel<MT>, grid, dim3(256), 0, st, (const h16*)s, (const h16*)prev, C, Cp, H, W, WP, R, Ho, Wo, WPo, tot_h / 2, (const h16*)wrf, \
+                     br, tasks, magic_for(WPo), rm)
+  switch ((C + 15) / 16) {
+    case 1: ORCAI_HSCATTER(1); break;
+    case 2: ORCAI_HSCATTER(2); break;
+    case 3: ORCAI_HSCATTER(3); break;
+    case 4: ORCAI_HSCATTER(4); break;
+    default: return ORCAI_E_UNSUPPORTED;
+  }
+#undef ORCAI_HSCATTER
+  return (int)hipGetLastError();
+}
+
+int orcai_h_pool_res_add_scatter(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, void* out, int Hd,
+                                 int nsnip, int period, int base, int img_step, int r_lo, int r_hi, int keep_lo, int keep_hi, void* stream) {
+  if (!s || !prev || !wrf || !br || !out || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || nsnip <= 0 || period <= 0) return ORCAI_E_BADARG;
+  if ((((uintptr_t)s | (uintptr_t)prev | (uintptr_t)wrf | (uintptr_t)out) & 15) || ((uintptr_t)br & 3)) return ORCAI_E_BADARG;
+  if ((int64_t)keep_hi - keep_lo > 2 * (int64_t)period) return ORCAI_E_UNSUPPORTED;  // a row in more than two snippets
+  if (keep_lo < 0 || keep_hi > Hd || keep_lo >= keep_hi || Hd != 2 * period || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+  // one family: the snippets themselves (snippet k = rows [k * period, k * period + Hd) of the recording)
+  if ((int64_t)(nsnip - 1) * period + Hd >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  RowMapH rm{};
+  rm.base = base;
+  rm.img_step = img_step;
+  rm.r_lo = r_lo;
+  rm.r_hi = r_hi;
+  rm.nfam = 1;
+  rm.f[0] = RowFamilyH{(h16*)out, Hd, period, 0, nsnip, keep_lo, keep_hi};
+  return h_pool_res_scatter_launch(s, prev, B, C, Cp, H, W, ksize, wrf, br, rm, stream);
+}
+
+int orcai_h_pool_res_add_scatter_families(const void* s, const void* prev, int B, int C, int Cp, int H, int W, int ksize, const void* wrf, const float* br, int base,
+                                          int img_step, int r_lo, int r_hi, const orcai_h_row_family* fams, int n_fams, void* stream) {
+  if (!s || !prev || !wrf || !br || !fams || B <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0 || n_fams <= 0 || base < 0 || img_step < 0) return ORCAI_E_BADARG;
+  if ((((uintptr_t)s | (uintptr_t)prev | (uintptr_t)wrf) & 15) || ((uintptr_t)br & 3)) return ORCAI_E_BADARG;
+  if (n_fams > kRowFamiliesH) return ORCAI_E_UNSUPPORTED;
+  RowMapH rm{};
+  rm.base = base;
+  rm.img_step = img_step;
+  rm.r_lo = r_lo;
+  rm.r_hi = r_hi;
+  rm.nfam = n_fams;
+  for (int i = 0; i < n_fams; ++i) {
+    const orcai_h_row_family& f = fams[i];
+    if (!f.out || ((uintptr_t)f.out & 15) || f.Hd <= 0 || f.period <= 0 || f.count <= 0 || f.offset < 0 || f.keep_lo < 0 || f.keep_hi > f.Hd || f.keep_lo >= f.keep_hi)
+      return ORCAI_E_BADARG;
+    // the kernel visits the two images whose kept rows can hold a row: a family whose kept rows overlap more is not run
+    if (f.keep_hi - f.keep_lo > 2 * f.period) return ORCAI_E_UNSUPPORTED;
+    if ((int64_t)f.offset + (int64_t)(f.count - 1) * f.period + f.Hd >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+    rm.f[i] = RowFamilyH{(h16*)f.out, f.Hd, f.period, f.offset, f.count, f.keep_lo, f.keep_hi};
+  }
+  return h_pool_res_scatter_launch(s, prev, B, C, Cp, H, W, ksize, wrf, br, rm, stream);
 }
 
 int orcai_h_gemm_bias_act(const float* A, const void* Wt, const float* bias, const float* scale, const float* shift, float* C, int64_t M, int N, int K, int act,
