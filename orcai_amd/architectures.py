@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from orcai_amd import _native as N
+from orcai_amd import shared_trunk
 from orcai_amd.auxiliary import MASK_VALUE, Messenger  # noqa: F401  (re-exported like the reference)
 
 BN_EPS = 1e-3  # keras BatchNormalization default epsilon
@@ -52,6 +53,31 @@ def depthwise_kernel_layout(dwk: np.ndarray) -> np.ndarray:
     out = np.zeros((cq * 4, k * k), dtype=np.float32)
     out[:c] = dwk[:, :, :, 0].transpose(2, 0, 1).reshape(c, k * k)
     return np.ascontiguousarray(out.reshape(cq, 4, k * k).transpose(0, 2, 1))
+
+
+def keep_planes(model, ws: dict, B: int, lanes: int, shapes, keep: dict) -> None:
+    """The trunks' test hook: the workspace planes of the first B images back to f32 [B][C][H][W] in keep[name], what sits outside the image
+    in keep[name + "/pads"].  lanes: channels per pixel vector (4 in the f32 quad planes, 8 in the f16 octet planes)."""
+    R = model.kernel_size // 2
+    chans = {"prev0": ENTRY_FILTERS}
+    widths = {"prev0": shapes[0][1]}
+    for i, f in enumerate(model.filters, start=1):
+        chans.update({f"a{i}": f, f"b{i}": f, f"prev{i}": f})
+        widths.update({f"a{i}": shapes[i - 1][1], f"b{i}": shapes[i - 1][1], f"prev{i}": shapes[i][1]})
+    for name, t in ws.items():
+        if name == "prev0s":  # only written by the fused entry path, which the keep hook does not use
+            continue
+        t = t[:B].float()  # the workspace may be larger than this chunk
+        Bq, CV, hp, wp, _ = t.shape
+        full = t.permute(0, 1, 4, 2, 3).reshape(Bq, CV * lanes, hp, wp)
+        if name.startswith("b"):  # x-pooled (unpadded rows): [B][CV][H][WPx][lanes] -> [B][C][H][ceil(W/2)]
+            keep[name] = full[:, : chans[name], :, : (widths[name] + 1) // 2].clone()
+            continue
+        hh = hp - 2 * R
+        keep[name] = full[:, : chans[name], R : R + hh, : widths[name]].clone()
+        pads = full.clone()
+        pads[:, : chans[name], R : R + hh, : widths[name]] = 0
+        keep[name + "/pads"] = pads
 
 
 class ParamLayout:
@@ -438,7 +464,7 @@ class ResNetLSTM:
         layout" in csrc/model_fwd.hip), or of B images `height` rows tall.  Allocated ZEROED once for the largest chunk seen; the
         kernels never write the pads.  `prev{first-1}` (the input of block `first`) is included when need_input."""
         last = len(self.filters) if last is None else last
-        key = (first, last) if height is None else (first, last, height)
+        key = (first, last, need_input, height)
         have = self._ws.get(key)
         if have is not None and have[0] >= B:  # planes are snippet-major: a smaller chunk uses the head of a larger workspace
             return have[1]
@@ -505,10 +531,9 @@ class ResNetLSTM:
         """Convolutional trunk for one chunk of B snippets, stages first..last: stage 0 = entry conv, b = residual block b,
         len(filters)+1 = final separable conv (writes the LSTM input features feat[B][steps][W_last*36]).  Returns the workspace
         (its `prev{last}` planes are the input of stage last+1).
-        height: the B images are `height` rows tall instead of snippets.  scatter = [(b0, count, C entry, arguments before xpooled,
-        arguments after it)]: block `last`'s tail runs as one launch of orcai_pool_res_add_scatter or orcai_pool_res_add_scatter_families
-        per segment of images b0 .. b0 + count - 1, storing through its row map instead of into ws[prev{last}] (the shared stages of
-        overlapping snippets, forward_device)."""
+        height: the B images are `height` rows tall instead of snippets.  scatter = [(b0, count, shared_trunk.RowMap | Families)]: block
+        `last`'s tail runs as one launch of orcai_pool_res_add_scatter or orcai_pool_res_add_scatter_families per segment of images
+        b0 .. b0 + count - 1, storing through its row map instead of into ws[prev{last}] (the shared stages of overlapping snippets)."""
         lib = N.lib()
         d = self.prepare()
         nb = len(self.filters)
@@ -549,9 +574,14 @@ class ResNetLSTM:
             self._launch(pb, "orcai_sepconv_bn", lib.orcai_sepconv_bn, N.ptr(a), B, f, h, wd, k, 0, N.ptr(d[pb + "/dw"]), N.ptr(d[pb + "/pw"]),
                          N.ptr(d[pb + "/scale"]), N.ptr(d[pb + "/shift"]), f, 0, 2, N.ptr(bb), st)
             if scattered:
-                for b0, cnt, what, pre, post in scatter:
+                mode = 3 if entry else 1  # the residual input: the entry activation's compact subsample or the block's input planes
+                for b0, cnt, dst in scatter:
+                    if isinstance(dst, shared_trunk.RowMap):
+                        what, rowmap = "orcai_pool_res_add_scatter", (N.ptr(dst.planes), mode, *dst[1:])
+                    else:
+                        what, rowmap = "orcai_pool_res_add_scatter_families", (mode, *dst[:4], ctypes.addressof(dst.array), len(dst.array))
                     self._launch(f"b{b}/pool_res", what, getattr(lib, what), N.ptr(bb[b0:]), N.ptr(prev[b0:]), cnt, f, c, h, wd, k,
-                                 N.ptr(d[f"b{b}/res/w"]), N.ptr(d[f"b{b}/res/b"]), *pre, 3 if entry else 1, *post, st)
+                                 N.ptr(d[f"b{b}/res/w"]), N.ptr(d[f"b{b}/res/b"]), *rowmap, st)
                 continue
             self._launch(f"b{b}/pool_res", "orcai_pool_res_add", lib.orcai_pool_res_add, N.ptr(bb), N.ptr(prev), B, f, c, h, wd, k, N.ptr(d[f"b{b}/res/w"]),
                          N.ptr(d[f"b{b}/res/b"]), N.ptr(nxt), 3 if entry else 1, st)
@@ -559,30 +589,8 @@ class ResNetLSTM:
             h, wd, c = shapes[-1]
             self._launch("sep_f", "orcai_sepconv_bn", lib.orcai_sepconv_bn, N.ptr(ws[f"prev{nb}"]), B, c, h, wd, k, 0, N.ptr(d["sep_f/dw"]), N.ptr(d["sep_f/pw"]),
                          N.ptr(d["sep_f/scale"]), N.ptr(d["sep_f/shift"]), FINAL_FILTERS, 1, 1, feat.data_ptr(), st)
-        if keep is not None:  # test hook: planes back to [B][C][H][W]
-            R = k // 2
-            chans = {"prev0": ENTRY_FILTERS}
-            widths = {"prev0": shapes[0][1]}
-            for i, f in enumerate(self.filters, start=1):
-                chans.update({f"a{i}": f, f"b{i}": f, f"prev{i}": f})
-                widths.update({f"a{i}": shapes[i - 1][1], f"b{i}": shapes[i - 1][1], f"prev{i}": shapes[i][1]})
-            for name, t in ws.items():
-                if name == "prev0s":  # only written by the fused entry path, which the keep hook does not use
-                    continue
-                if name.startswith("b"):  # x-pooled (unpadded rows): [B][CQ][H][WPx][4] -> [B][C][H][ceil(W/2)]
-                    t = t[:B]  # the workspace may be larger than this chunk
-                    Bq, CQ, hh, WPx, _ = t.shape
-                    full = t.permute(0, 1, 4, 2, 3).reshape(Bq, CQ * 4, hh, WPx)
-                    keep[name] = full[:, : chans[name], :, : (widths[name] + 1) // 2].clone()
-                    continue
-                t = t[:B]
-                Bq, CQ, HPp, WPp, _ = t.shape
-                hh = HPp - 2 * R
-                full = t.permute(0, 1, 4, 2, 3).reshape(Bq, CQ * 4, HPp, WPp)
-                keep[name] = full[:, : chans[name], R : R + hh, : widths[name]].clone()
-                pads = full.clone()
-                pads[:, : chans[name], R : R + hh, : widths[name]] = 0
-                keep[name + "/pads"] = pads
+        if keep is not None:
+            keep_planes(self, ws, B, 4, shapes, keep)
         return ws
 
     def head_device(self, feat: torch.Tensor, out: torch.Tensor, keep: dict | None = None) -> None:
@@ -614,157 +622,34 @@ class ResNetLSTM:
 
     def forward_device(self, src: torch.Tensor, snippet_stride: int, n: int, out: torch.Tensor, chunk: int = 128, keep: dict | None = None) -> None:
         """n snippets starting at ``src`` (f32 cuda), snippet i at element offset i*snippet_stride, each [H][W] row-major
-        (unpadded).  Writes probabilities into out[n][steps][labels].  The trunk runs in chunks of `chunk` snippets
-        (bounds activation memory); the recurrent head runs once over all n."""
-        if self.precision == "f16":
-            return self.half_engine().forward_device(src, snippet_stride, n, out, chunk=chunk, keep=keep)
-        steps, wd, _ = self.stage_shapes()[-1]
-        feat = torch.empty((n, steps, wd * FINAL_FILTERS), dtype=torch.float32, device=src.device)
-        nb = len(self.filters)
-        split = self.tail_from_block  # blocks >= split (small planes) run over `tail_chunk` snippets per launch to fill the chip
-        geo = self.shared_geometry(snippet_stride) if keep is None and 2 <= split <= nb else None  # decided before anything is launched
-        geo2 = self.tail_geometry(snippet_stride) if geo is not None else None
-        if geo2 is not None:  # two levels: blocks split .. nb once per recording row too, only the final conv and the head per snippet
-            big = min(n, self.tail_chunk)
-            tail = self._buffers(big, nb + 1, nb, need_input=True)
-            carry = tail[f"prev{nb}"]  # level 2 stores every snippet's rows straight into the final conv's input planes
-            for t0 in range(0, n, big):  # tail chunks stay independent: each computes its own first and last stride
-                nt = min(big, n - t0)
-                self._two_level_stage(src[t0 * snippet_stride :], nt, carry, geo, geo2, chunk)
-                self.trunk_device(None, snippet_stride, nt, feat[t0:], first=nb + 1, last=nb + 1, ws=tail)
-        elif geo is not None:
-            big = min(n, self.tail_chunk)
-            tail = self._buffers(big, split, nb, need_input=True)
-            carry = tail[f"prev{split - 1}"]  # the shared stage stores every snippet's rows straight into the tail's input planes
-            for t0 in range(0, n, big):  # tail chunks stay independent: each computes its own first and last stride
-                nt = min(big, n - t0)
-                self._shared_stage(src[t0 * snippet_stride :], nt, carry, geo, chunk)
-                self.trunk_device(None, snippet_stride, nt, feat[t0:], first=split, last=nb + 1, ws=tail)
-        elif keep is not None or split > nb or n <= chunk:
-            for s in range(0, n, chunk):
-                B = min(chunk, n - s)
-                self.trunk_device(src[s * snippet_stride :], snippet_stride, B, feat[s:], keep=keep if s == 0 else None)
-        else:
-            big = min(n, self.tail_chunk)
-            tail = self._buffers(big, split, nb, need_input=True)  # its prev{split-1} planes receive the head stages' output
-            carry = tail[f"prev{split - 1}"]
-            for t0 in range(0, n, big):
-                nt = min(big, n - t0)
-                for s in range(t0, t0 + nt, chunk):
-                    B = min(chunk, t0 + nt - s)
-                    head = dict(self._buffers(B, 1, split - 1))
-                    head[f"prev{split - 1}"] = carry[s - t0 :]  # the last head stage writes straight into the tail's input planes
-                    self.trunk_device(src[s * snippet_stride :], snippet_stride, B, None, first=0, last=split - 1, ws=head)
-                self.trunk_device(None, snippet_stride, nt, feat[t0:], first=split, last=nb + 1, ws=tail)
-        self.head_device(feat, out, keep=keep)
+        (unpadded).  Writes probabilities into out[n][steps][labels].  The route and its chunking: shared_trunk.forward_device."""
+        engine = self.half_engine() if self.precision == "f16" else self
+        shared_trunk.forward_device(engine, src, snippet_stride, n, out, chunk=chunk, keep=keep)
 
+    # ------------------------------------------------------------------ what the shared-trunk driver asks of an engine (shared_trunk.py)
     shared_strides = 8  # snippet strides a super-snippet keeps (its halo adds ~1 %)
+    model = property(lambda self: self)  # the f32 engine is the model itself
+    # n > chunk snippets that share nothing: blocks < tail_from_block in chunks of `chunk`, the later blocks over tail_chunk snippets
+    two_phase_unshared = True
+
+    def fits(self, shapes, blocks) -> bool:
+        """The f32 launchers' own 32-bit offset checks for `blocks` of images with these stage shapes: every input plane of a separable conv,
+        and the x-pooled tensor that the last block's row-map tail (orcai_pool_res_add_scatter[_families]) reads."""
+        R = self.kernel_size // 2
+        for b in blocks:
+            h, wd, _ = shapes[b - 1]
+            if 16 * (h + 2 * R) * self.padded_width(wd) >= 1 << 27:
+                return False
+        last = blocks[-1]
+        h, wd, _ = shapes[last - 1]
+        return (self.filters[last - 1] + 3) // 4 * h * (((wd + 1) // 2 + 3) & ~3) < 1 << 28
 
     def shared_geometry(self, snippet_stride: int):
-        """overlap.SharedStage for the blocks before tail_from_block when the snippets overlap by half (predict_spectrogram), None
-        for every layout or shape that takes the per-snippet path.  Refuses what orcai_pool_res_add_scatter would refuse."""
-        from orcai_amd.overlap import shared_stage
-
-        H, W = self.input_hw
-        S = self.tail_from_block - 1
-        if self.precision != "f32" or not 1 <= S <= len(self.filters) or not self.share_overlap:
-            return None
-        geo = shared_stage(H, W, self.kernel_size, S, snippet_stride)
-        if geo is None:
-            return None
-        hi = self.shared_strides * (H // 2) + 2 * geo.halo  # the tallest image: every plane stays inside the kernels' 32-bit offset checks
-        for h, wd, _ in self.stage_shapes(hi)[:S]:
-            if 16 * (h + 2 * (self.kernel_size // 2)) * self.padded_width(wd) >= 1 << 27:
-                return None
-        h, wd, _ = self.stage_shapes(hi)[S - 1]
-        if (self.filters[S - 1] + 3) // 4 * h * (((wd + 1) // 2 + 3) & ~3) >= 1 << 28:
-            return None
-        return geo
-
-    def _shared_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, chunk: int) -> None:
-        """Entry conv and blocks 1 .. geo.blocks of nt consecutive 50 %-overlapping snippets (snippet 0 at src), computed once per
-        recording row: super-snippets for the rows away from snippet edges, crops of every snippet's first / last rows for its
-        edge patches (orcai_amd/overlap.py).  Every row of every snippet lands in carry[0:nt] exactly once.  Activation memory
-        stays within what `chunk` snippets use on the per-snippet path."""
-        from orcai_amd.overlap import plan_windows
-
-        H, W = self.input_hw
-        S = geo.blocks
-        supers, crops = plan_windows(geo, H, nt, self.shared_strides)
-        budget = chunk * H  # image rows per launch group, as on the per-snippet path
-        n_crop = max(1, min(nt, budget // (4 * geo.crop)))
-        n_super = max(1, (budget - n_crop * geo.crop) // max(w.height for w in supers))
-        for group, per in ((supers, n_super), (crops, n_crop)):
-            for w in group:
-                for b0 in range(0, w.count, per):
-                    B = min(per, w.count - b0)
-                    ws = self._buffers(min(per, w.count), 1, S, height=w.height)
-                    rowmap = (geo.rows, nt, geo.period, w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)
-                    self.trunk_device(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=S, ws=ws, height=w.height,
-                                      scatter=[(0, B, "orcai_pool_res_add_scatter", (N.ptr(carry),), rowmap)])
+        """shared_trunk.shared_geometry of the f32 engine; None for a model of another precision (its engine answers for itself)."""
+        return shared_trunk.shared_geometry(self, snippet_stride) if self.precision == "f32" else None
 
     def tail_geometry(self, snippet_stride: int):
-        """overlap.tail_stage for blocks tail_from_block .. last (level 2 of the shared trunk) where shared_geometry applies, None
-        where only blocks before tail_from_block are shared.  Refuses what the launchers would refuse at the level-2 image heights."""
-        from orcai_amd.overlap import tail_stage
-
-        if self.shared_geometry(snippet_stride) is None:
-            return None
-        H, W = self.input_hw
-        nb, split = len(self.filters), self.tail_from_block
-        geo2 = tail_stage(H, W, self.kernel_size, split, nb, snippet_stride)
-        if geo2 is None:
-            return None
-        P2 = H // 2 // 2 ** (split - 1)  # level-1 output rows per snippet stride
-        m2 = max(self.shared_strides, -(-2 * geo2.halo // P2))
-        hi = (m2 * P2 + 2 * geo2.halo) * 2 ** (split - 1)  # the tallest level-2 image, in spectrogram rows
-        shapes = self.stage_shapes(hi)
-        for h, wd, _ in shapes[split - 1 : nb]:
-            if 16 * (h + 2 * (self.kernel_size // 2)) * self.padded_width(wd) >= 1 << 27:
-                return None
-        h, wd, _ = shapes[nb - 1]
-        if (self.filters[nb - 1] + 3) // 4 * h * (((wd + 1) // 2 + 3) & ~3) >= 1 << 28:
-            return None
-        return geo2
-
-    def _two_level_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, geo2, chunk: int) -> None:
-        """Entry conv and blocks 1 .. nb of nt consecutive 50 %-overlapping snippets (snippet 0 at src), computed once per recording
-        row in two levels (orcai_amd/overlap.py, plan_two_level).  Level 1 (blocks 1 .. geo.blocks) runs as _shared_stage, its last
-        tail storing into the level-2 images: super-images of level-1 output rows and crops of every snippet's first / last rows.
-        Level 2 runs the remaining blocks on those images, its last tail storing every snippet's rows into carry[0:nt] exactly once."""
-        from orcai_amd.overlap import plan_two_level
-
-        H, W = self.input_hw
-        S, nb = geo.blocks, len(self.filters)
-        plan = plan_two_level(geo, geo2, H, nt, self.shared_strides)
-        up = geo.scale  # spectrogram rows per level-1 output row
-        planes = {"super": self._buffers(plan.super_images, S + 1, S, height=plan.super_height * up)[f"prev{S}"],
-                  "crop": self._buffers(2 * nt, S + 1, S, height=plan.crop_height * up)[f"prev{S}"]}
-        img_bytes = {key: t[0].numel() * t.element_size() for key, t in planes.items()}
-
-        # level 1: as _shared_stage; the families are host arrays read during each launch call
-        budget = chunk * H
-        n_crop = max(1, min(nt, budget // (4 * geo.crop)))
-        n_super = max(1, (budget - n_crop * geo.crop) // max(w.height for w, _ in plan.level1[:-2]))
-        for i, (w, fams) in enumerate(plan.level1):
-            per = n_super if i < len(plan.level1) - 2 else n_crop
-            arr = (N.RowFamily * len(fams))(*[N.RowFamily(N.ptr(planes[f.planes]) + f.image * img_bytes[f.planes], f.height, f.period, f.offset, f.count,
-                                                          f.keep_lo, f.keep_hi) for f in fams])
-            for b0 in range(0, w.count, per):
-                B = min(per, w.count - b0)
-                ws = self._buffers(min(per, w.count), 1, S, height=w.height)
-                post = (w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, ctypes.addressof(arr), len(fams))
-                self.trunk_device(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=S, ws=ws, height=w.height,
-                                  scatter=[(0, B, "orcai_pool_res_add_scatter_families", (), post)])
-
-        # level 2: all super-images in one launch group, all crops in another; the last tail once per window
-        for key, windows, height in (("super", plan.supers, plan.super_height), ("crop", plan.crops, plan.crop_height)):
-            count = sum(w.count for w, _ in windows)
-            ws = dict(self._buffers(count, S + 1, nb, need_input=False, height=height * up))
-            ws[f"prev{S}"] = planes[key]
-            segs = [(j, w.count, "orcai_pool_res_add_scatter", (N.ptr(carry),),
-                     (geo2.rows, nt, geo2.period, w.base, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)) for w, j in windows]
-            self.trunk_device(None, 0, count, None, first=S + 1, last=nb, ws=ws, height=height * up, scatter=segs)
+        return shared_trunk.tail_geometry(self, snippet_stride) if self.precision == "f32" else None
 
     def half_engine(self):
         if self._half_engine is None:

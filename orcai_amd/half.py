@@ -12,11 +12,14 @@ reference computes in f32, and the predict headline is measured in f32.  No CPU 
 
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
 from orcai_amd import _native as N
-from orcai_amd.architectures import DENSE_UNITS, ENTRY_FILTERS, FINAL_FILTERS, lstm_column_permutation
+from orcai_amd import shared_trunk
+from orcai_amd.architectures import DENSE_UNITS, ENTRY_FILTERS, FINAL_FILTERS, keep_planes, lstm_column_permutation
 
 LOSS_SCALE = 1024.0  # static loss scale of the f16 backward pass (gradients of O(1e-4) activations stay normal f16 numbers)
 
@@ -60,7 +63,7 @@ class HalfEngine:
         arch = getattr(model, "architecture", "")
         if arch not in ("ResNetLSTM", "ResNet1DConv"):
             raise NotImplementedError(f"the f16 path implements ResNetLSTM and ResNet1DConv, not {arch!r}")
-        self.m = model
+        self.m = self.model = model
         self.conv1d = arch == "ResNet1DConv"  # the head: frequency mean + Conv1D on the f32 kernels, no LSTM / Dense weights to pack
         self._dev = None
         self._ws = {}
@@ -144,9 +147,9 @@ class HalfEngine:
     def trunk(self, src: torch.Tensor, snippet_stride: int, B: int, feat: torch.Tensor, keep: dict | None = None, first: int = 0, last: int | None = None,
               ws: dict | None = None, height: int | None = None, scatter: list | None = None) -> dict:
         """Stages first..last for B snippets, as ResNetLSTM.trunk_device: 0 = entry conv, b = residual block b, len(filters) + 1 = final separable
-        conv (writes feat).  height: the B images are `height` rows tall instead of snippets.  scatter = [(b0, count, launcher, arguments after br)]:
+        conv (writes feat).  height: the B images are `height` rows tall instead of snippets.  scatter = [(b0, count, shared_trunk.RowMap | Families)]:
         block `last`'s tail runs as one orcai_h_pool_res_add_scatter[_families] launch per segment of images b0 .. b0 + count - 1, storing through
-        its row map instead of into ws[prev{last}] (the shared stages of overlapping snippets, forward_device)."""
+        its row map instead of into ws[prev{last}] (the shared stages of overlapping snippets)."""
         m, lib, d, st = self.m, N.lib(), self.prepare(), N.stream_ptr()
         nb = len(m.filters)
         last = nb + 1 if last is None else last
@@ -170,7 +173,11 @@ class HalfEngine:
             launch("h/" + pb, "orcai_h_sepconv", lib.orcai_h_sepconv, N.ptr(a), B, f, h, wd, k, k, 0, N.ptr(d[pb + "/dw"]), N.ptr(d[pb + "/pw"]),
                    N.ptr(d[pb + "/scale"]), N.ptr(d[pb + "/shift"]), f, 0, 2, 0, 0, N.ptr(bb), None, st)
             if scatter is not None and b == last:
-                for b0, cnt, what, rowmap in scatter:
+                for b0, cnt, dst in scatter:
+                    if isinstance(dst, shared_trunk.RowMap):
+                        what, rowmap = "orcai_h_pool_res_add_scatter", (N.ptr(dst.planes), *dst[1:])
+                    else:
+                        what, rowmap = "orcai_h_pool_res_add_scatter_families", (*dst[:4], ctypes.addressof(dst.array), len(dst.array))
                     launch(f"h/b{b}/pool_res", what, getattr(lib, what), N.ptr(bb[b0:]), N.ptr(prev[b0:]), cnt, f, c, h, wd, k, N.ptr(d[f"b{b}/res/w"]),
                            N.ptr(d[f"b{b}/res/b"]), *rowmap, st)
                 continue
@@ -181,27 +188,8 @@ class HalfEngine:
         h, wd, c = shapes[-1]
         launch("h/sep_f", "orcai_h_sepconv", lib.orcai_h_sepconv, N.ptr(ws[f"prev{len(m.filters)}"]), B, c, h, wd, k, k, 0, N.ptr(d["sep_f/dw"]), N.ptr(d["sep_f/pw"]),
                N.ptr(d["sep_f/scale"]), N.ptr(d["sep_f/shift"]), FINAL_FILTERS, 1, 1, 0, 0, feat.data_ptr(), None, st)
-        if keep is not None:  # test hook: planes back to f32 [B][C][H][W]
-            R = k // 2
-            chans = {"prev0": ENTRY_FILTERS}
-            widths = {"prev0": shapes[0][1]}
-            for i, f in enumerate(m.filters, start=1):
-                chans.update({f"a{i}": f, f"b{i}": f, f"prev{i}": f})
-                widths.update({f"a{i}": shapes[i - 1][1], f"b{i}": shapes[i - 1][1], f"prev{i}": shapes[i][1]})
-            for name, t in ws.items():
-                t = t[:B].float()
-                if name.startswith("b"):  # x-pooled: [B][CO][H][WPx][8]
-                    Bq, CO, hh, WPx, _ = t.shape
-                    full = t.permute(0, 1, 4, 2, 3).reshape(Bq, CO * 8, hh, WPx)
-                    keep[name] = full[:, : chans[name], :, : (widths[name] + 1) // 2].clone()
-                    continue
-                Bq, CO, HPp, WPp, _ = t.shape
-                hh = HPp - 2 * R
-                full = t.permute(0, 1, 4, 2, 3).reshape(Bq, CO * 8, HPp, WPp)
-                keep[name] = full[:, : chans[name], R : R + hh, : widths[name]].clone()
-                pads = full.clone()
-                pads[:, : chans[name], R : R + hh, : widths[name]] = 0
-                keep[name + "/pads"] = pads
+        if keep is not None:
+            keep_planes(m, ws, B, 8, shapes, keep)
         return ws
 
     def head(self, feat: torch.Tensor, out: torch.Tensor, keep: dict | None = None) -> None:
@@ -237,35 +225,14 @@ class HalfEngine:
             keep.update({"feat": feat.clone(), "h1": h1.clone(), "h2": h2.clone()})
 
     def forward_device(self, src: torch.Tensor, snippet_stride: int, n: int, out: torch.Tensor, chunk: int = 128, keep: dict | None = None) -> None:
-        """Same contract as ResNetLSTM.forward_device (f32 spectrogram snippets in, f32 probabilities out).  Snippets that overlap by half
-        (predict_spectrogram) share the trunk as on the f32 path: two levels where both geometries exist, one where only the first
-        does, the per-snippet loop otherwise and under the keep hook.  The same bits on every route."""
-        m = self.m
-        steps, wd, _ = m.stage_shapes()[-1]
-        feat = torch.empty((n, steps, wd * FINAL_FILTERS), dtype=torch.float32, device=src.device)
-        nb, split = len(m.filters), m.tail_from_block
-        geo = self.shared_geometry(snippet_stride) if keep is None and 2 <= split <= nb else None  # decided before anything is launched
-        geo2 = self.tail_geometry(snippet_stride) if geo is not None else None
-        if geo is not None:
-            first = nb + 1 if geo2 is not None else split  # the first stage that still runs per snippet
-            big = min(n, m.tail_chunk)
-            tail = self._buffers(big, first, nb, need_input=True)
-            carry = tail[f"prev{first - 1}"]  # the shared stages store every snippet's rows straight into these planes
-            for t0 in range(0, n, big):  # tail chunks stay independent: each computes its own first and last stride
-                nt = min(big, n - t0)
-                if geo2 is not None:
-                    self._two_level_stage(src[t0 * snippet_stride :], nt, carry, geo, geo2, chunk)
-                else:
-                    self._shared_stage(src[t0 * snippet_stride :], nt, carry, geo, chunk)
-                self.trunk(None, snippet_stride, nt, feat[t0:], first=first, last=nb + 1, ws=tail)
-        else:
-            for s in range(0, n, chunk):
-                B = min(chunk, n - s)
-                self.trunk(src[s * snippet_stride :], snippet_stride, B, feat[s:], keep=keep if s == 0 else None)
-        self.head(feat, out, keep=keep)
+        """Same contract as ResNetLSTM.forward_device (f32 spectrogram snippets in, f32 probabilities out), same routes: shared_trunk.forward_device."""
+        shared_trunk.forward_device(self, src, snippet_stride, n, out, chunk=chunk, keep=keep)
 
-    # ------------------------------------------------------------------ shared rows of overlapping snippets (DESIGN 4.1)
-    def _fits(self, shapes, blocks) -> bool:
+    # ------------------------------------------------------------------ what the shared-trunk driver asks of an engine (shared_trunk.py)
+    trunk_device, head_device = trunk, head
+    two_phase_unshared = False  # snippets that share nothing run the whole trunk in chunks of `chunk`, however many there are
+
+    def fits(self, shapes, blocks) -> bool:
         """The f16 launchers' own index checks for `blocks` of images with these stage shapes: orcai_h_sepconv's plane bound and the
         scatter launchers' bounds on the source plane and on the row / column split of a flat output pixel."""
         m = self.m
@@ -279,93 +246,7 @@ class HalfEngine:
         return ((h + R) * wpo + 64) * wpo < 1 << 32
 
     def shared_geometry(self, snippet_stride: int):
-        """overlap.SharedStage for the blocks before tail_from_block when the snippets overlap by half, None for every layout or shape that takes
-        the per-snippet path (ResNetLSTM.shared_geometry for f16).  Refuses what the f16 launchers would refuse at the tallest image."""
-        from orcai_amd.overlap import shared_stage
-
-        m = self.m
-        H, W = m.input_hw
-        S = m.tail_from_block - 1
-        if not 1 <= S <= len(m.filters) or not m.share_overlap or max(m.filters) > 64:
-            return None
-        geo = shared_stage(H, W, m.kernel_size, S, snippet_stride)
-        if geo is None:
-            return None
-        hi = m.shared_strides * (H // 2) + 2 * geo.halo
-        return geo if self._fits(m.stage_shapes(hi), range(1, S + 1)) else None
+        return shared_trunk.shared_geometry(self, snippet_stride)
 
     def tail_geometry(self, snippet_stride: int):
-        """overlap.tail_stage for blocks tail_from_block .. last (level 2) where shared_geometry applies, None where only level 1 is shared."""
-        from orcai_amd.overlap import tail_stage
-
-        m = self.m
-        if self.shared_geometry(snippet_stride) is None:
-            return None
-        H, W = m.input_hw
-        nb, split = len(m.filters), m.tail_from_block
-        geo2 = tail_stage(H, W, m.kernel_size, split, nb, snippet_stride)
-        if geo2 is None:
-            return None
-        P2 = H // 2 // 2 ** (split - 1)  # level-1 output rows per snippet stride
-        m2 = max(m.shared_strides, -(-2 * geo2.halo // P2))
-        hi = (m2 * P2 + 2 * geo2.halo) * 2 ** (split - 1)  # the tallest level-2 image, in spectrogram rows
-        return geo2 if self._fits(m.stage_shapes(hi), range(split, nb + 1)) else None
-
-    def _level1(self, src: torch.Tensor, nt: int, geo, chunk: int, groups) -> None:
-        """The entry conv and blocks 1 .. geo.blocks on the level-1 windows, in launch groups of at most `chunk` snippets' worth of rows (as
-        ResNetLSTM._shared_stage).  groups = [(window, is_crop, launcher, arguments(window, first image of the group))]."""
-        H, W = self.m.input_hw
-        budget = chunk * H
-        n_crop = max(1, min(nt, budget // (4 * geo.crop)))
-        n_super = max(1, (budget - n_crop * geo.crop) // max(w.height for w, crop, _, _ in groups if not crop))
-        for w, crop, what, args in groups:
-            per = n_crop if crop else n_super
-            for b0 in range(0, w.count, per):
-                B = min(per, w.count - b0)
-                ws = self._buffers(min(per, w.count), 1, geo.blocks, height=w.height)
-                self.trunk(src[(w.start + b0 * w.step) * W :], w.step * W, B, None, first=0, last=geo.blocks, ws=ws, height=w.height,
-                           scatter=[(0, B, what, args(w, b0))])
-
-    def _shared_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, chunk: int) -> None:
-        """Entry conv and blocks 1 .. geo.blocks of nt consecutive 50 %-overlapping snippets, once per recording row (overlap.plan_windows):
-        every row of every snippet lands in carry[0:nt] exactly once."""
-        from orcai_amd.overlap import plan_windows
-
-        supers, crops = plan_windows(geo, self.m.input_hw[0], nt, self.m.shared_strides)
-
-        def rowmap(w, b0):
-            return (N.ptr(carry), geo.rows, nt, geo.period, w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)
-
-        self._level1(src, nt, geo, chunk, [(w, False, "orcai_h_pool_res_add_scatter", rowmap) for w in supers] +
-                     [(w, True, "orcai_h_pool_res_add_scatter", rowmap) for w in crops])
-
-    def _two_level_stage(self, src: torch.Tensor, nt: int, carry: torch.Tensor, geo, geo2, chunk: int) -> None:
-        """Entry conv and blocks 1 .. nb of nt consecutive 50 %-overlapping snippets, once per recording row in two levels
-        (overlap.plan_two_level, ResNetLSTM._two_level_stage): level 1 stores into the level-2 images, level 2 into carry[0:nt]."""
-        import ctypes
-
-        from orcai_amd.overlap import plan_two_level
-
-        m = self.m
-        S, nb = geo.blocks, len(m.filters)
-        plan = plan_two_level(geo, geo2, m.input_hw[0], nt, m.shared_strides)
-        up = geo.scale  # spectrogram rows per level-1 output row
-        planes = {"super": self._buffers(plan.super_images, S + 1, S, height=plan.super_height * up)[f"prev{S}"],
-                  "crop": self._buffers(2 * nt, S + 1, S, height=plan.crop_height * up)[f"prev{S}"]}
-        img_bytes = {key: t[0].numel() * t.element_size() for key, t in planes.items()}
-        groups = []
-        for i, (w, fams) in enumerate(plan.level1):  # the families are host arrays read during each launch call
-            arr = (N.RowFamily * len(fams))(*[N.RowFamily(N.ptr(planes[f.planes]) + f.image * img_bytes[f.planes], f.height, f.period, f.offset, f.count,
-                                                          f.keep_lo, f.keep_hi) for f in fams])
-            groups.append((w, i >= len(plan.level1) - 2, "orcai_h_pool_res_add_scatter_families",
-                           lambda w, b0, arr=arr: (w.base + b0 * w.img_step, w.img_step, w.r_lo, w.r_hi, ctypes.addressof(arr), len(arr))))
-        self._level1(src, nt, geo, chunk, groups)
-
-        # level 2: all super-images in one launch group, all crops in another; the last tail once per window
-        for key, windows, height in (("super", plan.supers, plan.super_height), ("crop", plan.crops, plan.crop_height)):
-            count = sum(w.count for w, _ in windows)
-            ws = dict(self._buffers(count, S + 1, nb, need_input=False, height=height * up))
-            ws[f"prev{S}"] = planes[key]
-            segs = [(j, w.count, "orcai_h_pool_res_add_scatter",
-                     (N.ptr(carry), geo2.rows, nt, geo2.period, w.base, w.img_step, w.r_lo, w.r_hi, w.keep_lo, w.keep_hi)) for w, j in windows]
-            self.trunk(None, 0, count, None, first=S + 1, last=nb, ws=ws, height=height * up, scatter=segs)
+        return shared_trunk.tail_geometry(self, snippet_stride)

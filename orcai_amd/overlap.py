@@ -7,8 +7,8 @@ each snippet edge, where the snippet's zero padding (or the pooling's -inf paddi
 Blocks 1 .. S can therefore be computed once per recording row on tall windows ("super-snippets") and the few edge rows of each
 snippet ("patches") on short crops of its own first and last rows, whose other edge is wrong by construction but far enough away.
 
-Everything here is exact integer geometry, no device code: ``shared_stage`` says whether a layout qualifies and how, the model
-(``ResNetLSTM.forward_device``) plans its launches from the answer.
+Everything here is exact integer geometry, no device code: ``shared_stage`` says whether a layout qualifies and how, the driver of
+both precisions (``orcai_amd/shared_trunk.py``) plans its launches from the answer.
 """
 
 from __future__ import annotations
