@@ -816,6 +816,33 @@ int orcai_sepconv_wgrad_frozen(const float* x, const float* g, const float* y_ga
 int orcai_rows_bn_frozen_wgrad(const float* dy, const float* x, int64_t M, int cols, int C, const float* mean, const float* var, float eps, float* dbeta, float* dgamma,
                                float* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The recording-level gradient (orcai_amd/eval_grad.py: RecordingGrad; csrc/eval_grad.hip): the adjoints of the two linear steps around the detector in
+ * `orcai predict` -- slicing the spectrogram [T][W] into snippets i = rows [i * shift, i * shift + H) (predict.py:244-261) and the 50 %-overlap average
+ * of their predictions (predict.py:276-293, orcai_overlap_average).  Both work on a CHUNK of consecutive snippets i0 .. i0 + nb - 1, so the caller
+ * recomputes the detector chunk by chunk.  Gathers, one thread per output element, no atomics: two launches give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+
+/* dpred[i - i0][off][l] = dagg[i * step + off][l] / c(i * step + off) for the snippets i0 <= i < i0 + nb of a recording of n snippets:
+ *   dagg f32[S][L] the gradient w.r.t. the averaged probabilities; dpred f32[nb][P][L] w.r.t. the chunk's per-snippet predictions;
+ *   c(s) = the number of snippets 0 .. n-1 that cover output step s, as orcai_overlap_average counts it (1 or 2 with step = P / 2).
+ * Rows of dagg no snippet covers (the forward writes 0 there) are not read.  Every element of dpred is written.
+ * ORCAI_E_BADARG: a null pointer, non-positive n / P / L / step / nb, i0 < 0, i0 + nb > n, (n - 1) * step + P > S.
+ * ORCAI_E_UNSUPPORTED (nothing launched): nb * P * L needs 2^31 or more workgroups of 256 threads. */
+int orcai_overlap_average_bwd(const float* dagg, int n, int P, int L, int step, int64_t S, int i0, int nb, float* dpred, void* stream);
+/* dspec[t][w] += sum over the chunk's snippets i (ascending) that cover row t of dx[i - i0][t - i * shift][w], for the rows
+ * [i0 * shift, (i0 + nb - 1) * shift + H) of dspec f32[T][W]; dx f32[nb][H][W].  One read-add-write per element of that row range; the other rows are not
+ * touched.  The caller zeroes dspec once (orcai_zero_fill) and runs the chunks on one stream: the result does not depend on how the snippets are chunked
+ * beyond the order of f32 additions, and is deterministic.  ORCAI_E_BADARG: a null pointer, non-positive nb / H / W / shift, i0 < 0,
+ * (i0 + nb - 1) * shift + H > T.  ORCAI_E_UNSUPPORTED (nothing launched): the chunk's row range times W needs 2^31 or more workgroups of 256 threads
+ * (use smaller chunks). */
+int orcai_snippets_overlap_add(const float* dx, int i0, int nb, int H, int W, int shift, int64_t T, float* dspec, void* stream);
+/* Stream-ordered zero fill of `bytes` (a multiple of 4) at the 4-byte aligned p by a KERNEL (csrc/zero_fill.h: the fill every accumulator of this
+ * library gets).  For buffers the CALLER owns (RecordingGrad's dspec): like every fill of the library it asks orcai_arena_take first, so a pointer to a
+ * fresh slot of a registered orcai_scratch_arena would be counted as taken and left to the arena's own clear -- do not pass memory of that arena.
+ * ORCAI_E_BADARG: null or misaligned p, bytes negative or not a multiple of 4. */
+int orcai_zero_fill(void* p, int64_t bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,9 @@ _SIGNATURES = {
     "orcai_sepconv_wgrad_frozen": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p] * 6 + [c_i64, C.c_void_p]),
     "orcai_frozen_bn_finish": (C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "orcai_rows_bn_frozen_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4),
+    "orcai_overlap_average_bwd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "orcai_snippets_overlap_add": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [c_i64, C.c_void_p, C.c_void_p]),
+    "orcai_zero_fill": (C.c_int, [C.c_void_p, c_i64, C.c_void_p]),
 }
 
 

@@ -12,11 +12,15 @@
 //   orcai_frozen_bn_finish       weight gradients of a layer in front of a FROZEN BatchNorm from two reductions (G = sum gg (x) u, sum gg): the
 //                                pointwise kernel, the bias, gamma and beta (EvalGrad.backward(wgrad=True))
 //   orcai_rows_bn_frozen_wgrad   dbeta / dgamma of a frozen BatchNorm on a row tensor (Dense-128's)
+//   orcai_overlap_average_bwd    the adjoint of orcai_overlap_average for a chunk of snippets: dpred = dagg / cover count (RecordingGrad.backward)
+//   orcai_snippets_overlap_add   the adjoint of slicing a spectrogram into 50 %-overlapping snippets: a chunk's dx gathered and added into dspec
+//   orcai_zero_fill              zero_fill.h's stream-ordered kernel fill for a caller's accumulator (dspec)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "orcai_hip.h"
+#include "zero_fill.h"
 
 namespace {
 
@@ -419,6 +423,50 @@ __global__ __launch_bounds__(256) void rows_bn_frozen_fold_kernel(const float* _
   dgamma[c] = g * (1.0f / sqrtf(var[c] + eps));
 }
 
+// =========================================================================================
+// The two adjoints of the recording-level function (predict.py:244-261 slices, predict.py:276-293 averages; the forward kernel is model_fwd.hip's
+// overlap_average_kernel).  Both are gathers with one thread per OUTPUT element: no atomics, two launches give the same bits.  Consecutive threads walk
+// the innermost index (label / frequency bin), so reads and writes are coalesced; every index is int64_t (T * W passes 2^30 for long recordings).
+// =========================================================================================
+// dpred[i - i0][off][l] = dagg[i * step + off][l] / c(i * step + off), c(s) = the number of snippets 0 .. n-1 that cover step s, counted by the forward's loop
+__global__ __launch_bounds__(256) void overlap_average_bwd_kernel(const float* __restrict__ dagg /*[S][L]*/, int n, int P, int L, int step, int i0, int64_t total,
+                                                                   float* __restrict__ dpred /*[nb][P][L]*/) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int l = (int)(idx % L);
+  const int64_t r = idx / L;
+  const int off = (int)(r % P);
+  const int64_t i = i0 + r / P;
+  const int64_t s = i * step + off;
+  int64_t i_hi = s / step;
+  if (i_hi > n - 1) i_hi = n - 1;
+  int64_t i_lo = (s - P + step) / step;  // ceil((s - P + 1)/step)
+  if (s - P + 1 <= 0) i_lo = 0;
+  int c = 0;
+  for (int64_t j = i_lo; j <= i_hi; ++j) {
+    const int64_t o = s - j * step;
+    if (o >= 0 && o < P) ++c;
+  }
+  dpred[idx] = dagg[s * L + l] / (float)c;  // c >= 1: snippet i itself covers s
+}
+
+// dspec[t][w] += sum over the chunk's snippets i that cover row t, in ascending i, of dx[i - i0][t - i * shift][w]; thread <-> (t, w) of rows [t0, t0 + rows)
+__global__ __launch_bounds__(256) void snippets_overlap_add_kernel(const float* __restrict__ dx /*[nb][H][W]*/, int i0, int nb, int H, int W, int shift, int64_t t0,
+                                                                    int64_t total, float* __restrict__ dspec /*[T][W]*/) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t t = t0 + idx / W;
+  const int w = (int)(idx % W);
+  int64_t i_hi = t / shift;
+  if (i_hi > (int64_t)i0 + nb - 1) i_hi = (int64_t)i0 + nb - 1;
+  int64_t i_lo = t - H + 1 <= 0 ? 0 : (t - H + shift) / shift;  // ceil((t - H + 1)/shift)
+  if (i_lo < i0) i_lo = i0;
+  float sum = 0.0f;
+  for (int64_t i = i_lo; i <= i_hi; ++i) sum += dx[((i - i0) * H + (t - i * shift)) * W + w];
+  const int64_t at = t * W + w;
+  dspec[at] = dspec[at] + sum;
+}
+
 template <int MTI>
 int launch_dgrad(const float* g, const float* y_gate, const float* x_gate, int B, int Cin, int Cout, int H, int W, const float* wts, const float* dw_rev, float* dr,
                  hipStream_t st) {
@@ -524,6 +572,30 @@ int orcai_rows_bn_frozen_wgrad(const float* dy, const float* x, int64_t M, int c
   hipLaunchKernelGGL(rows_bn_frozen_wgrad_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(256), 0, st, dy, x, M, cols, C, mean, var, eps, workspace);
   hipLaunchKernelGGL(rows_bn_frozen_fold_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, workspace, cols, C, var, eps, dbeta, dgamma);
   return (int)hipGetLastError();
+}
+
+int orcai_overlap_average_bwd(const float* dagg, int n, int P, int L, int step, int64_t S, int i0, int nb, float* dpred, void* stream) {
+  if (!dagg || !dpred || n <= 0 || P <= 0 || L <= 0 || step <= 0 || i0 < 0 || nb <= 0 || (int64_t)i0 + nb > n) return ORCAI_E_BADARG;
+  if ((int64_t)(n - 1) * step + P > S) return ORCAI_E_BADARG;  // every step of every snippet is a row of dagg
+  const int64_t total = (int64_t)nb * P * L;
+  if ((total + 255) / 256 >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  hipLaunchKernelGGL(overlap_average_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dagg, n, P, L, step, i0, total, dpred);
+  return (int)hipGetLastError();
+}
+
+int orcai_snippets_overlap_add(const float* dx, int i0, int nb, int H, int W, int shift, int64_t T, float* dspec, void* stream) {
+  if (!dx || !dspec || nb <= 0 || i0 < 0 || H <= 0 || W <= 0 || shift <= 0 || (int64_t)i0 + nb > (1ll << 31) - 1) return ORCAI_E_BADARG;
+  const int64_t t0 = (int64_t)i0 * shift, t1 = ((int64_t)i0 + nb - 1) * shift + H;
+  if (t1 > T) return ORCAI_E_BADARG;
+  const int64_t total = (t1 - t0) * W;
+  if ((total + 255) / 256 >= (1ll << 31)) return ORCAI_E_UNSUPPORTED;
+  hipLaunchKernelGGL(snippets_overlap_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dx, i0, nb, H, W, shift, t0, total, dspec);
+  return (int)hipGetLastError();
+}
+
+int orcai_zero_fill(void* p, int64_t bytes, void* stream) {
+  if (!p || bytes < 0 || (bytes & 3) || ((uintptr_t)p & 3)) return ORCAI_E_BADARG;
+  return (int)orcai_zero::zero_async(p, (size_t)bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -25,6 +25,14 @@ recomputed depthwise output -- runs instead, as it does where the fused kernel m
 the moving statistics, the heads by the training step's weight-gradient GEMMs on LSTM outputs rebuilt from the features.  dx keeps its launches and bits;
 the weight gradients go through float atomics (orcai_dw_wgrad, split-K GEMMs) and are reproducible to rounding only.
 
+RecordingGrad is the same gradient for a whole RECORDING: the function `orcai predict` reports, spectrogram [T, W] -> the 50 %-overlap average [T // tpo, labels]
+of the snippets' probabilities, differentiated w.r.t. the spectrogram (and the weights) in chunks of snippets, so that the stored activations do not grow with T
+(DESIGN 4.9):
+
+    rg = RecordingGrad(model, chunk=64)
+    avg = rg.forward(spec)                # f32 [T // tpo, L]: predict_spectrogram + orcai_overlap_average, bit for bit what `orcai predict` averages
+    dspec = rg.backward(spec, davg)       # f32 [T, W]; with wgrad=True (dspec, dwflat)
+
 The entry conv REUSES orcai_conv0_bn_bwd_dx: called with the moving statistics and zeroed sums it evaluates the eval-mode formula
 (dv = gamma * rsqrt(var + eps) * dy where the ReLU fired).  Its ReLU decision is formed from the unfolded BatchNorm, the forward's from the folded
 one; the two can only differ for a pre-activation within rounding of zero, and dr1 is already zero where the stored y0 is (x_gate of block 1's
@@ -183,6 +191,8 @@ class EvalGrad:
         return d
 
     def _params(self, params, device) -> dict:
+        if isinstance(params, dict):  # already bound (RecordingGrad binds once for all its chunks)
+            return params
         if params is not None:
             return self.bind(*params)
         m = self.model
@@ -260,10 +270,18 @@ class EvalGrad:
 
     # ------------------------------------------------------------------ backward
     def _workspace(self, B: int, device) -> dict:
-        """Gradient planes (zero pads; only interiors are ever written, so they persist) for a batch of B snippets."""
+        """Gradient planes (zero pads; only interiors are ever written, so they persist) for a batch of B snippets.  One set is kept, sized for the largest
+        batch seen on the device: planes are snippet-major, so a smaller batch (the ragged last chunk of RecordingGrad) works in the head of it."""
         key = (B, device)
         ws = self._ws.get(key)
         if ws is not None:
+            return ws
+        full = next((w for (b, dev), w in self._ws.items() if dev == device and b > B and "_parent" not in w), None)
+        if full is not None:
+            batched = full["_batched"]
+            ws = {name: (t[:B] if name in batched else t) for name, t in full.items() if name not in ("_batched", "_B")}
+            ws["_parent"] = full
+            self._ws[key] = ws
             return ws
         m = self.model
         shapes = m.stage_shapes()
@@ -279,8 +297,29 @@ class EvalGrad:
             c = f
         T, wd, _ = shapes[-1]
         ws["dvf"], ws["dprev_f"] = planes(FINAL_FILTERS, T, wd), planes(c, T, wd)
-        self._ws = {key: ws}  # one batch size at a time
+        ws["_B"], ws["_batched"] = B, {name for name in ws if name.startswith(("dy", "dr", "dvf", "dprev"))}
+        self._ws = {key: ws}  # a larger batch replaces the set (and the heads taken from it)
         return ws
+
+    @staticmethod
+    def _lazy_planes(ws: dict, key, like: Tensor) -> Tensor:
+        """Zero-padded scratch planes shaped like `like`, made on first use (only interiors are ever written); in a workspace that is the head of a larger one
+        they are the head of the larger one's."""
+        t = ws.get(key)
+        if t is None:
+            parent = ws.get("_parent")
+            if parent is None:
+                t = torch.zeros_like(like)
+                if "_batched" in ws:
+                    ws["_batched"].add(key)
+            else:
+                full = parent.get(key)
+                if full is None:
+                    full = parent[key] = torch.zeros((parent["_B"], *like.shape[1:]), dtype=like.dtype, device=like.device)
+                    parent["_batched"].add(key)
+                t = full[: like.shape[0]]
+            ws[key] = t
+        return t
 
     def fused(self, B: int, Cin: int, h: int, w: int) -> bool:
         """Whether this separable conv's backward asks orcai_sepconv_dgrad (k = 5 / 7 ask too: the launcher answers ORCAI_E_UNSUPPORTED)."""
@@ -295,9 +334,7 @@ class EvalGrad:
             if rc != N.E_UNSUPPORTED:
                 N.check(rc, "orcai_sepconv_dgrad")
                 return
-        du = ws.get("du/" + name)  # the pointwise product of the composed path (zero pads, interior rewritten by every call)
-        if du is None:
-            du = ws["du/" + name] = torch.zeros_like(dr)
+        du = self._lazy_planes(ws, "du/" + name, dr)  # the pointwise product of the composed path (zero pads, interior rewritten by every call)
         compose_dgrad(lib, g, y_gate, x_gate, B, Cin, Cout, h, w, k, wts, dw_rev, dr, du, st)
 
     def _gemm(self, A, BT, C, M, Nn, K):
@@ -323,10 +360,7 @@ class EvalGrad:
 
     def _scratch_planes(self, ws: dict, key: str, like: Tensor) -> Tensor:
         """Zero-padded scratch planes shared by the layers of one shape (only interiors are ever written)."""
-        t = ws.get((key, tuple(like.shape)))
-        if t is None:
-            t = ws[(key, tuple(like.shape))] = torch.zeros_like(like)
-        return t
+        return self._lazy_planes(ws, (key, tuple(like.shape[1:])), like)
 
     # Where orcai_sepconv_wgrad_frozen beats compose_wgrad (tools/time_frozen_grad.py, DESIGN 4.8: 1.30 x at 16 input channels, 0.41-0.66 x from 30 on -- its
     # tile of 64 pixels leaves the G contraction 16 MFMAs per output tile between barriers, and the LDS images of wider layers leave one or two workgroups per
@@ -522,3 +556,110 @@ def saliency(model, x: Tensor, label: int | None = None) -> Tensor:
     else:
         g[:, :, label] = 1.0
     return eg.backward(g, saved)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the whole recording
+def recording_geometry(H: int, n_filters: int, T: int) -> dict:
+    """The snippet geometry of a recording of T spectrogram frames for snippets of H frames and a trunk of n_filters blocks (predict.py:244-293;
+    aggregate_predictions_device): shift, tpo (time steps per output step), P (output steps per snippet), step (output steps between snippets), n (snippets,
+    0 when the recording is shorter than one), S (output steps of the recording) and rows = (first, one past the last) spectrogram row a snippet covers --
+    the frames from rows[1] on reach no snippet and get no gradient.  Host arithmetic only."""
+    shift, tpo = H // 2, 2**n_filters
+    n = max((T - H) // shift + 1, 0) if shift > 0 else 0
+    return dict(H=H, shift=shift, tpo=tpo, P=H // tpo, step=shift // tpo, n=n, S=T // tpo, rows=(0, (n - 1) * shift + H if n > 0 else 0))
+
+
+class RecordingGrad:
+    """The recording-level function of `orcai predict` and its gradient (module docstring).  forward runs the shared-trunk predict path and
+    keeps nothing; backward recomputes the per-snippet EvalGrad forward in chunks of at most `chunk` consecutive snippets -- chunk x EvalGrad.per_snippet
+    floats of stored activations at a time, whatever T is -- and carries each chunk's gradient through the two adjoints orcai_overlap_average_bwd and
+    orcai_snippets_overlap_add.  The gradient is therefore that of the per-snippet forward, whose probabilities lie within 5e-6 of the shared-trunk
+    path's (tests/test_eval_grad_gpu.py), not bit-equal to them.  `params` as for EvalGrad.  chunk: 64 is the batch EvalGrad was timed at
+    (profiles/eval_grad_mi355x.json)."""
+
+    def __init__(self, model, chunk: int = 64, eval_grad: EvalGrad | None = None):
+        """eval_grad: an EvalGrad of `model` to run the chunks on (its workspaces are then shared with its other callers); None: one of its own."""
+        if int(chunk) <= 0:
+            raise ValueError(f"RecordingGrad: chunk must be positive, got {chunk}")
+        if eval_grad is not None and eval_grad.model is not model:
+            raise ValueError("RecordingGrad: eval_grad belongs to another model")
+        self.eg = EvalGrad(model) if eval_grad is None else eval_grad  # EvalGrad raises for f16 models
+        self.model, self.chunk = model, int(chunk)
+
+    def geometry(self, T: int) -> dict:
+        H, _ = self.model.input_hw
+        g = recording_geometry(H, len(self.model.filters), int(T))
+        if g["P"] != self.model.out_steps or g["step"] * g["tpo"] != g["shift"]:
+            raise NotImplementedError(f"RecordingGrad: snippets of {H} frames do not tile into output steps of {g['tpo']} frames (the overlap average assumes they do)")
+        return g
+
+    def _check_spec(self, spec: Tensor, who: str) -> dict:
+        W = self.model.input_hw[1]
+        if spec.dim() != 2 or spec.shape[1] != W or spec.dtype != torch.float32 or not spec.is_cuda:
+            raise ValueError(f"RecordingGrad.{who}: spec must be an f32 cuda tensor [T, {W}], got {spec.dtype} {tuple(spec.shape)} on {spec.device}")
+        g = self.geometry(spec.shape[0])
+        if g["n"] <= 0:
+            raise ValueError(f"recording too short: {int(spec.shape[0])} spectrogram frames, one snippet needs {g['H']}")
+        return g
+
+    def forward(self, spec: Tensor, params=None) -> Tensor:
+        """avg f32 [T // tpo, L]: model.predict_spectrogram (the shared-trunk path) and orcai_overlap_average, rounded to f32 -- the bits of
+        aggregate_predictions_device(...)[0].astype(np.float32).  Nothing is kept for the backward: it reads `spec` again."""
+        g = self._check_spec(spec, "forward")
+        m, lib = self.model, self.eg._lib()
+        with torch.cuda.device(spec.device):
+            x = spec.detach().contiguous()
+            if params is None:
+                pred = m.predict_spectrogram(x)
+            else:
+                with m.bound(m.prepare_device(*params)):
+                    pred = m.predict_spectrogram(x)
+            agg = torch.empty((g["S"], m.num_labels), dtype=torch.float64, device=spec.device)
+            cnt = torch.empty((g["S"],), dtype=torch.float64, device=spec.device)
+            N.check(lib.orcai_overlap_average(N.ptr(pred), g["n"], g["P"], m.num_labels, g["step"], g["S"], N.ptr(agg), N.ptr(cnt), N.stream_ptr()), "orcai_overlap_average")
+            return agg.to(torch.float32)
+
+    def backward(self, spec: Tensor, davg: Tensor, params=None, wgrad: bool = False):
+        """dspec f32 [T, W] from davg = dL/davg f32 [T // tpo, L]; with wgrad=True (dspec, dwflat), dwflat as EvalGrad.backward's, added over the chunks in
+        chunk order.  Frames behind the last full snippet get zero."""
+        g = self._check_spec(spec, "backward")
+        m, eg, lib = self.model, self.eg, self.eg._lib()
+        H, W = m.input_hw
+        T, L, n, shift = int(spec.shape[0]), m.num_labels, g["n"], g["shift"]
+        if tuple(davg.shape) != (g["S"], L) or davg.dtype != torch.float32 or davg.device != spec.device:
+            raise ValueError(f"RecordingGrad.backward: davg must be f32 {(g['S'], L)} on {spec.device}, got {davg.dtype} {tuple(davg.shape)} on {davg.device}")
+        f32 = dict(dtype=torch.float32, device=spec.device)
+        with torch.cuda.device(spec.device):
+            st = N.stream_ptr()
+            x, davg = spec.detach().contiguous(), davg.detach().contiguous()
+            d = eg._params(params, spec.device)  # bound once: every chunk reads the same operands
+            dspec = torch.empty((T, W), **f32)
+            N.check(lib.orcai_zero_fill(N.ptr(dspec), 4 * dspec.numel(), st), "orcai_zero_fill")
+            dw = torch.zeros(m.layout().n_w, **f32) if wgrad else None
+            for i0 in range(0, n, self.chunk):
+                nb = min(self.chunk, n - i0)
+                snippets = torch.as_strided(x[i0 * shift :], (nb, H, W), (shift * W, W, 1)).contiguous()  # the row slice carries spec's own storage offset
+                _, saved = eg.forward(snippets, params=d)
+                del snippets  # `saved` holds its own copy
+                dpred = torch.empty((nb, g["P"], L), **f32)
+                N.check(lib.orcai_overlap_average_bwd(N.ptr(davg), n, g["P"], L, g["step"], g["S"], i0, nb, N.ptr(dpred), st), "orcai_overlap_average_bwd")
+                res = eg.backward(dpred, saved, params=d, wgrad=wgrad)
+                del saved, dpred
+                dx = res[0] if wgrad else res
+                N.check(lib.orcai_snippets_overlap_add(N.ptr(dx), i0, nb, H, W, shift, T, N.ptr(dspec), st), "orcai_snippets_overlap_add")
+                if wgrad:
+                    dw.add_(res[1])
+                del res, dx
+        return (dspec, dw) if wgrad else dspec
+
+
+def recording_saliency(model, spec: Tensor, label: int | None = None, chunk: int = 64) -> Tensor:
+    """d(sum over the recording's output steps of avg[:, label]) / dspec of the predict-time network, f32 [T, W]; label=None sums over all labels."""
+    rg = RecordingGrad(model, chunk)
+    g = rg._check_spec(spec, "forward")
+    davg = torch.zeros((g["S"], model.num_labels), dtype=torch.float32, device=spec.device)
+    if label is None:
+        davg.fill_(1.0)
+    else:
+        davg[:, label] = 1.0
+    return rg.backward(spec, davg)

@@ -11,6 +11,8 @@ known without a GPU.
     torch.ops.orcai.detect_wrt_input(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
     torch.ops.orcai.detect_wrt_params(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
     torch.ops.orcai.predict_spectrogram(spec f32[T, W], weights, stats, config) -> f32[n, steps, labels]
+    torch.ops.orcai.detect_recording(spec f32[T, W], weights, stats, config, chunk) -> f32[T // tpo, labels]
+    torch.ops.orcai.detect_recording_wrt_params(spec f32[T, W], weights, stats, config, chunk) -> f32[T // tpo, labels]
 
 ``weights`` / ``stats`` are the trainable variables and the BatchNorm moving statistics in ``variable_spec()`` order (Keras layouts);
 ``config`` is the JSON string ``model_config`` makes.  ``OrcaiModule`` wraps all of it as a ``torch.nn.Module``.
@@ -40,8 +42,17 @@ BatchNorm FROZEN on its moving statistics and no Dropout -- the network ``orcai 
 ``torch.optim``.  Its backward is the functional op ``orcai::detect_backward_params(grad, saved, weights, stats, config) -> (dx, dwflat)``
 (``EvalGrad.backward(wgrad=True)``); ``stats`` get no gradient and are never written.  ``detect_wrt_input`` keeps returning no weight gradient.
 
-What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``orcai train`` on the frozen network (its fused ``Trainer`` step is training mode)
-or through the shared-trunk ``predict_spectrogram`` path, any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
+``detect_recording`` is the function ``orcai predict`` reports -- every 50 %-overlapping snippet of ``spec`` through the predict-time network
+(``predict_spectrogram``, the shared-trunk path) and the overlap average of their probabilities, rounded to f32 (tpo = 2 ** len(filters)) -- with autograd
+w.r.t. ``spec``: its backward is the functional op ``orcai::detect_recording_bwd(grad, spec, weights, stats, config, chunk) -> dspec``
+(``RecordingGrad.backward``: the detector recomputed in chunks of ``chunk`` snippets, so the stored activations do not grow with T).  Nothing but
+``spec`` and the variables is saved.  ``detect_recording_wrt_params`` is the same function with autograd w.r.t. the weights as well (BatchNorm frozen on
+``stats``); its backward is ``orcai::detect_recording_bwd_params(...) -> (dspec, dwflat)``.  Behind ``WaveformFrontEnd`` the gradient reaches the samples
+at their native rate.
+
+What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``orcai train`` on the frozen network (its fused ``Trainer`` step is training mode),
+a backward of ``orcai::predict_spectrogram`` itself (the shared-trunk kernels are not differentiated: ``detect_recording`` recomputes the snippets as a batch),
+any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
 itself has no backward, and ``orcai::resample`` / ``orcai::resample_backward`` have no second derivative.
 """
 
@@ -724,6 +735,117 @@ def _detect_params_autograd(x, weights, stats, config):
 _register("detect_wrt_params", "(Tensor x, Tensor[] weights, Tensor[] stats, str config) -> Tensor", _detect_impl, _probs_fake, _detect_params_autograd)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::detect_recording
+# The recording-level function of `orcai predict` (snippets -> predict-time network -> 50 %-overlap average) with the gradient w.r.t. the spectrogram
+# (orcai_amd/eval_grad.py: RecordingGrad), wired as detect_wrt_input / detect_wrt_params are: the forward keeps nothing but its arguments, the backward is a
+# functional op that recomputes the detector in chunks of `chunk` snippets.  One EvalGrad per (config, device) serves both families of ops.
+def _recording_grad(config: str, device: torch.device, chunk: int):
+    from orcai_amd.eval_grad import RecordingGrad
+
+    eng, eg = _eval_grad(config, device)
+    return eng, RecordingGrad(eng.model, int(chunk), eval_grad=eg)  # host bookkeeping only: the engine's EvalGrad holds the workspaces
+
+
+def _check_spec(config: str, spec: Tensor, who: str) -> None:
+    W = int(_parse(config)["input_shape"][1])
+    if spec.dim() != 2 or spec.shape[1] != W or spec.dtype != torch.float32:
+        raise ValueError(f"{who}: spec must be f32 [T, {W}], got {spec.dtype} {tuple(spec.shape)}")
+
+
+def _avg_fake(spec, weights, stats, config, chunk):
+    cfg = _parse(config)
+    return spec.new_empty((spec.shape[0] // 2 ** len(cfg["filters"]), cfg["num_labels"]), dtype=torch.float32)
+
+
+def detect_recording(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, chunk: int = 64) -> Tensor:
+    """The overlap-averaged probabilities f32[T // tpo, labels] of the recording spec[T][W] (what `orcai predict` thresholds, rounded to f32); its backward
+    returns dL/dspec when spec requires grad (never a weight gradient).  A recording shorter than one snippet raises."""
+    return torch.ops.orcai.detect_recording(spec, weights, stats, config, chunk)
+
+
+def detect_recording_wrt_params(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, chunk: int = 64) -> Tensor:
+    """detect_recording whose backward also returns a gradient per weight (BatchNorm frozen on `stats`, which get none)."""
+    return torch.ops.orcai.detect_recording_wrt_params(spec, weights, stats, config, chunk)
+
+
+def _detect_recording_impl(spec, weights, stats, config, chunk):
+    _check_spec(config, spec, "orcai::detect_recording")
+    _check_vars(config, weights, stats)
+    eng, rg = _recording_grad(config, spec.device, chunk)
+    with torch.cuda.device(spec.device):
+        return rg.forward(spec.detach(), params=eng.flat(weights, stats))
+
+
+@torch.library.custom_op("orcai::detect_recording_bwd", mutates_args=())
+def detect_recording_bwd(grad: Tensor, spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, chunk: int) -> Tensor:
+    """RecordingGrad.backward: dL/dspec f32[T, W] from grad = dL/davg f32[T // tpo, labels] and the spectrogram of the forward."""
+    _check_spec(config, spec, "orcai::detect_recording_bwd")
+    _check_vars(config, weights, stats)
+    eng, rg = _recording_grad(config, spec.device, chunk)
+    with torch.cuda.device(spec.device):
+        return rg.backward(spec.detach(), grad.contiguous(), params=eng.flat(weights, stats))
+
+
+@detect_recording_bwd.register_fake
+def _detect_recording_bwd_fake(grad, spec, weights, stats, config, chunk):
+    return spec.new_empty(spec.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("orcai::detect_recording_bwd_params", mutates_args=())
+def detect_recording_bwd_params(grad: Tensor, spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str, chunk: int) -> tuple[Tensor, Tensor]:
+    """RecordingGrad.backward(wgrad=True): (dL/dspec f32[T, W], the flat f32 gradient w.r.t. the trainable variables in variable_spec() order)."""
+    _check_spec(config, spec, "orcai::detect_recording_bwd_params")
+    _check_vars(config, weights, stats)
+    eng, rg = _recording_grad(config, spec.device, chunk)
+    with torch.cuda.device(spec.device):
+        return rg.backward(spec.detach(), grad.contiguous(), params=eng.flat(weights, stats), wgrad=True)
+
+
+@detect_recording_bwd_params.register_fake
+def _detect_recording_bwd_params_fake(grad, spec, weights, stats, config, chunk):
+    return spec.new_empty(spec.shape, dtype=torch.float32), _flat_grad_fake(grad, config)
+
+
+def _recording_autograd(name: str, with_params: bool):
+    """The Autograd kernel of orcai::<name>: spec and the variables are all the backward needs (it recomputes); with_params: the weights get gradients too."""
+
+    class Function(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, spec, config, chunk, n_weights, *variables):
+            with torch._C._AutoDispatchBelowAutograd():
+                avg = getattr(torch.ops.orcai, name)(spec, list(variables[:n_weights]), list(variables[n_weights:]), config, chunk)
+            ctx.config, ctx.chunk, ctx.n_weights = config, chunk, n_weights
+            ctx.save_for_backward(spec.detach(), *[t.detach() for t in variables])
+            return avg
+
+        @staticmethod
+        def backward(ctx, grad):
+            spec, *variables = ctx.saved_tensors
+            n = ctx.n_weights
+            args = (grad.contiguous(), spec, list(variables[:n]), list(variables[n:]), ctx.config, ctx.chunk)
+            need = ctx.needs_input_grad
+            if not with_params:
+                return (torch.ops.orcai.detect_recording_bwd(*args), None, None, None, *([None] * len(variables)))
+            dspec, flat = torch.ops.orcai.detect_recording_bwd_params(*args)
+            wgrads = [g if want else None for g, want in zip(_skeleton(ctx.config).layout().split_w(flat), need[4 : 4 + n])]
+            return (dspec if need[0] else None, None, None, None, *wgrads, *([None] * (len(variables) - n)))
+
+    Function.__name__ = Function.__qualname__ = "_" + "".join(part.capitalize() for part in name.split("_")) + "Function"
+
+    def autograd(spec, weights, stats, config, chunk):
+        if torch.is_grad_enabled() and (spec.requires_grad or (with_params and any(w.requires_grad for w in weights))):
+            return Function.apply(spec, config, chunk, len(weights), *weights, *stats)
+        with torch._C._AutoDispatchBelowAutograd():
+            return getattr(torch.ops.orcai, name)(spec, weights, stats, config, chunk)
+
+    return autograd
+
+
+_RECORDING_SCHEMA = "(Tensor spec, Tensor[] weights, Tensor[] stats, str config, SymInt chunk) -> Tensor"
+_register("detect_recording", _RECORDING_SCHEMA, _detect_recording_impl, _avg_fake, _recording_autograd("detect_recording", False))
+_register("detect_recording_wrt_params", _RECORDING_SCHEMA, _detect_recording_impl, _avg_fake, _recording_autograd("detect_recording_wrt_params", True))
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::predict_spectrogram
 @torch.library.custom_op("orcai::predict_spectrogram", mutates_args=())
 def predict_spectrogram(spec: Tensor, weights: list[Tensor], stats: list[Tensor], config: str) -> Tensor:
@@ -810,6 +932,17 @@ class OrcaiModule(torch.nn.Module):
 
     def predict_spectrogram(self, spec: Tensor) -> Tensor:
         return torch.ops.orcai.predict_spectrogram(spec, self.weights_list(), self.stats_list(), self.config)
+
+    def detect_recording(self, spec: Tensor, chunk: int = 64) -> Tensor:
+        """The overlap-averaged probabilities f32[T // tpo, labels] of the recording spec f32[T, W] -- always the PREDICT-TIME network, whatever
+        self.training says (orcai::detect_recording).  input_grad="eval": a spec that requires grad gets dL/dspec; frozen_bn=True: so does every parameter
+        (orcai::detect_recording_wrt_params); otherwise a spec that requires grad raises.  The backward recomputes the detector `chunk` snippets at a time."""
+        if self.frozen_bn:
+            return torch.ops.orcai.detect_recording_wrt_params(spec, self.weights_list(), self.stats_list(), self.config, chunk)
+        if self.input_grad != "eval" and torch.is_grad_enabled() and spec.requires_grad:
+            raise NotImplementedError("OrcaiModule.detect_recording: the gradient w.r.t. the spectrogram is that of the predict-time network: build the module with "
+                                      "input_grad='eval' (or frozen_bn=True for the weight gradients as well)")
+        return torch.ops.orcai.detect_recording(spec, self.weights_list(), self.stats_list(), self.config, chunk)
 
     def to_model(self):
         """Writes the parameters and buffers back into the model object (for .save, predict, `orcai predict`) and returns it."""
