@@ -49,6 +49,21 @@ size_t orcai_frontend_workspace_bytes(void);
  * recording's orcai_stft_db / orcai_hist_level1. */
 int orcai_frontend_reset(void* workspace, void* stream);
 
+/* Sample decode: the data chunk of a RIFF/WAVE file as it lies in the file (interleaved little-endian frames), on the device -> the samples of ONE
+ * channel as f32, with libsndfile's float scaling (the soundfile half of librosa.load(mono=False) + the channel pick, spectrogram.py:23-31).
+ *   format     0 U8   (x - 128) / 128          3 S32  x * 2^-31, rounded once (round to nearest even)
+ *              1 S16  x * 2^-15                4 F32  the bits, untouched (NaN payloads and signed zeros included)
+ *              2 S24  x * 2^-23 (sign-extended) 5 F64  one round-to-nearest-even cast: overflow -> +-inf, f32 subnormals kept
+ *   frames     n_frames frames of `channels` samples; 16-byte aligned, and READABLE up to n_frames * frame_bytes ROUNDED UP TO 16
+ *              (frame_bytes = channels * bytes per sample): every load is an aligned 16-byte word, the last one may reach past the last
+ *              frame (those bytes are read and ignored; they need not be initialised)
+ *   channels   1..64;  channel  0-based, in [0, channels)
+ *   out        f32[n_frames], 16-byte aligned; exactly n_frames floats are written
+ * Every conversion is exact or rounds once, so out equals the host decode (orcai_amd.wavio.read_wav) bit for bit.  One lane decodes 16 consecutive
+ * frames: their bytes start at a multiple of 16 for every format and channel count, the stores are 16 bytes wide, no LDS.  Byte offsets are 64-bit.
+ * ORCAI_E_BADARG: null or misaligned pointer, n_frames <= 0, channels outside 1..64, channel outside [0, channels), unknown format. */
+int orcai_pcm_decode(const void* frames, int64_t n_frames, int channels, int channel, int format, float* out, void* stream);
+
 /* Rational polyphase resampler (the resampling half of librosa.load(sr=...), spectrogram.py:23-27; libsoxr itself
  * is absent, so this stage cannot be bit-compared: parity unpinned).
  *   out[n] = sum_j x[floor(n*M/L) - ntaps/2 + 1 + j] * table[(n*M) mod L][j]; table f32[L][ntaps], ntaps % 4 == 0. */

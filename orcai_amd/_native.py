@@ -182,6 +182,7 @@ _SIGNATURES = {
     "orcai_overlap_average_bwd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_snippets_overlap_add": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [c_i64, C.c_void_p, C.c_void_p]),
     "orcai_zero_fill": (C.c_int, [C.c_void_p, c_i64, C.c_void_p]),
+    "orcai_pcm_decode": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

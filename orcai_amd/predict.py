@@ -339,9 +339,10 @@ def predict(recording_path: str | Path, channel: int = 1, model_dir: str | Path 
     progressbar = tqdm(recording_table.index, desc="Starting ...", unit="file", disable=verbosity < 1)
     from orcai_amd import wavio
 
-    # decode the next recordings on background threads while the GPU works on the current one (the GPU needs ~60 ms per hour of audio)
+    # read the next recordings into page-locked memory on background threads while the GPU works on the current one (the samples are decoded on the
+    # device: load_wav)
     wavio.set_prefetcher(wavio.WavPrefetcher([Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"])
-                                              for i in recording_table.index]))
+                                              for i in recording_table.index], raw=True))
     # one recording deep: the GPU half of recording i is queued before the host half of recording i - 1 (threshold, label table, files) runs
     quiet = Messenger(verbosity=0)
     in_flight = None  # (table index, state)

@@ -18,21 +18,27 @@ from tqdm import tqdm
 from orcai_amd import frontend as fe
 from orcai_amd.auxiliary import Messenger
 from orcai_amd.io import read_json, save_array, write_vector_to_json
-from orcai_amd.wavio import read_wav_prefetched
+from orcai_amd import wavio
 
 DEFAULT_ORCAI_PARAMETER = files("orcai_amd.defaults").joinpath("default_orcai_parameter.json")
 
 
 def load_wav(wav_file_path: Path | str, sampling_rate: int, channel: int, msgr: Messenger) -> torch.Tensor:
     """``librosa.load(path, sr=sampling_rate, mono=False)`` + channel pick (spectrogram.py:23-31),
-    returning the mono signal as a float32 tensor on the GPU at `sampling_rate`."""
-    wav, native_sr = read_wav_prefetched(wav_file_path)  # [channels, frames]; decoded ahead of time in table mode
-    if wav.shape[0] > 1:
+    returning the mono signal as a float32 tensor on the GPU at `sampling_rate`.  The data chunk goes to the device as the bytes of the file and
+    ``orcai_pcm_decode`` makes the one channel's samples there (the same bits as ``wavio.read_wav``'s)."""
+    raw = wavio.read_wav_raw_prefetched(wav_file_path)  # read ahead of time, into page-locked memory, in table mode
+    channels, native_sr = raw.channels, raw.rate
+    if channels > 1:
         msgr.warning(f"Multiple channels found, using channel {channel}")
-        mono = wav[channel - 1]
+        index = range(channels)[channel - 1]  # Python's indexing, as wav[channel - 1]: 0 picks the last channel, out of range raises IndexError
     else:
-        mono = wav[0]
-    pcm = torch.from_numpy(np.ascontiguousarray(mono)).cuda()
+        index = 0
+    if channels > wavio.MAX_DEVICE_CHANNELS:  # wider than the device decode takes: the host decode
+        raw.release()
+        pcm = torch.from_numpy(np.ascontiguousarray(wavio.read_wav(wav_file_path)[0][index])).cuda()
+    else:
+        pcm = wavio.upload_and_decode(raw, index)
     if native_sr != sampling_rate:
         from orcai_amd.resample import resample_device
 

@@ -6,6 +6,7 @@ known without a GPU.
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
+    torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.forward_wrt_input(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
     torch.ops.orcai.detect_wrt_input(x f32[B, H, W], weights, stats, config) -> f32[B, steps, labels]
@@ -28,6 +29,9 @@ normalisation statistics are held constant), so the chain pcm -> spectrogram -> 
 waveform.  ``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
 same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
 sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
+``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
+of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
+bytes, so it has no autograd.
 ``WaveformFrontEnd(spectrogram_parameter, native_rate)`` is the two stages as one ``torch.nn.Module``: the waveform at the rate it was recorded
 at -> the [T, K] spectrogram, differentiable down to those samples.
 
@@ -555,6 +559,56 @@ def _resample_autograd(pcm, sr_in, sr_out):
 
 
 _register("resample", "(Tensor pcm, SymInt sr_in, SymInt sr_out) -> Tensor", _resample_impl, _resample_fake, _resample_autograd)
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::decode_pcm
+# The sample decode `orcai predict` runs on the bytes of a recording's data chunk (orcai_amd/wavio.py: decode_device).  The kernel reads aligned 16-byte
+# words, so the bytes it is given are padded to a multiple of 16 when they are not one (a copy; wavio.upload_and_decode allocates padded and makes none).
+# Integer input: nothing to differentiate, the Autograd key runs the kernel.
+def _pcm_frames(nbytes, channels: int, sample_format: int, who: str):
+    from orcai_amd.wavio import BYTES_PER_SAMPLE, MAX_DEVICE_CHANNELS
+
+    if not 0 <= sample_format < len(BYTES_PER_SAMPLE):
+        raise ValueError(f"{who}: format must be 0 U8, 1 S16, 2 S24, 3 S32, 4 F32 or 5 F64, got {sample_format}")
+    if not 1 <= channels <= MAX_DEVICE_CHANNELS:
+        raise ValueError(f"{who}: channels must be 1 .. {MAX_DEVICE_CHANNELS}, got {channels}")
+    return nbytes // (channels * BYTES_PER_SAMPLE[sample_format])
+
+
+def decode_pcm(frames: Tensor, channels: int, channel: int, format: int) -> Tensor:
+    """The f32 samples of 0-based `channel` from uint8 frames[nbytes], the interleaved little-endian frames of a WAV data chunk (whole frames are
+    decoded, trailing bytes ignored)."""
+    return torch.ops.orcai.decode_pcm(frames, channels, channel, format)
+
+
+def _decode_pcm_impl(frames, channels, channel, format):
+    from orcai_amd.wavio import BYTES_PER_SAMPLE, decode_device
+
+    if frames.dim() != 1 or frames.dtype != torch.uint8 or not frames.is_cuda:
+        raise ValueError("orcai::decode_pcm: frames must be a 1-d uint8 cuda tensor")
+    n = _pcm_frames(frames.shape[0], channels, format, "orcai::decode_pcm")
+    if not 0 <= channel < channels:
+        raise ValueError(f"orcai::decode_pcm: channel must be in [0, {channels}), got {channel}")
+    if n == 0:
+        return frames.new_empty((0,), dtype=torch.float32)
+    need = -(-n * channels * BYTES_PER_SAMPLE[format] // 16) * 16
+    if frames.shape[0] < need or frames.data_ptr() % 16 or not frames.is_contiguous():
+        padded = frames.new_empty((need,))
+        padded[: min(need, frames.shape[0])].copy_(frames[:need])
+        frames = padded
+    return decode_device(frames, n, channels, channel, format)
+
+
+def _decode_pcm_fake(frames, channels, channel, format):
+    return frames.new_empty((_pcm_frames(frames.shape[0], channels, format, "orcai::decode_pcm"),), dtype=torch.float32)
+
+
+def _decode_pcm_autograd(frames, channels, channel, format):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.decode_pcm(frames, channels, channel, format)
+
+
+_register("decode_pcm", "(Tensor frames, SymInt channels, SymInt channel, SymInt format) -> Tensor", _decode_pcm_impl, _decode_pcm_fake, _decode_pcm_autograd)
 
 
 class WaveformFrontEnd(torch.nn.Module):
