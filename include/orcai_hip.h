@@ -64,6 +64,15 @@ int orcai_frontend_reset(void* workspace, void* stream);
  * ORCAI_E_BADARG: null or misaligned pointer, n_frames <= 0, channels outside 1..64, channel outside [0, channels), unknown format. */
 int orcai_pcm_decode(const void* frames, int64_t n_frames, int channels, int channel, int format, float* out, void* stream);
 
+/* The same decode for EVERY channel from one read of the bytes: frames, n_frames, channels, format as orcai_pcm_decode.
+ *   out        f32[channels][stride], 16-byte aligned: plane c holds the n_frames samples of channel c, bit for bit what
+ *              orcai_pcm_decode(..., channel = c, ...) writes; the stride - n_frames floats behind them are not written
+ *   stride     floats between planes: >= n_frames and a multiple of 4, so that every plane starts 16-byte aligned (roundup(n_frames, 4))
+ * A workgroup copies a tile of frames (a multiple of 16 frames, at most 32 KiB) to LDS with aligned 16-byte loads, every word of the file once, and
+ * converts it plane after plane with consecutive lanes storing consecutive floats of a plane.
+ * ORCAI_E_BADARG: null or misaligned pointer, n_frames <= 0, channels outside 1..64, unknown format, stride < n_frames or not a multiple of 4. */
+int orcai_pcm_decode_planar(const void* frames, int64_t n_frames, int channels, int format, float* out, int64_t stride, void* stream);
+
 /* Rational polyphase resampler (the resampling half of librosa.load(sr=...), spectrogram.py:23-27; libsoxr itself
  * is absent, so this stage cannot be bit-compared: parity unpinned).
  *   out[n] = sum_j x[floor(n*M/L) - ntaps/2 + 1 + j] * table[(n*M) mod L][j]; table f32[L][ntaps], ntaps % 4 == 0. */
@@ -291,6 +300,16 @@ int orcai_dense_sigmoid(const float* x, const float* w, const float* bias, int64
 /* predict.py:276-293: overlay the n snippet predictions [n][P][L] at offsets i*step, count overlaps, divide.
  *   agg f64[S][L], cnt f64[S];  float64 accumulation in snippet order (bit-exact with the numpy loop). */
 int orcai_overlap_average(const float* pred, int n, int P, int L, int step, int64_t S, double* agg, double* cnt, void* stream);
+
+/* orcai_overlap_average over a table of R recordings in one launch (several recordings through one detector pass: orcai_amd/batch.py).
+ *   pred  f32[n_total][P][L]: the snippets of all recordings, recording r's at pred[first_r .. first_r + n_r)
+ *   table int64[R][4] ON THE DEVICE, row r = {first_r, n_r, S_r, row_r}: row_0 = 0, row_{r+1} = row_r + S_r, S_total = the sum of S_r
+ *   agg   f64[S_total][L], cnt f64[S_total]: rows row_r .. row_r + S_r are, bit for bit, what orcai_overlap_average(pred + first_r*P*L, n_r, P, L,
+ *         step, S_r, ...) writes for recording r alone, the zero-count steps behind its last snippet included.
+ * One thread per output element (binary search of its recording on row_r), no atomics: deterministic.  The table's contents are not checked.
+ * ORCAI_E_BADARG: a null pointer, R < 1, non-positive P / L / step / S_total.  ORCAI_E_UNSUPPORTED: S_total * L needs 2^31 or more workgroups. */
+int orcai_overlap_average_ragged(const float* pred, int P, int L, int step, const int64_t* table, int R, int64_t S_total, double* agg, double* cnt,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training (train.py:155-219: Adam(lr) + MaskedBinaryCrossentropy + MaskedBinaryAccuracy; architectures.py:210-286)

@@ -183,6 +183,8 @@ _SIGNATURES = {
     "orcai_snippets_overlap_add": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [c_i64, C.c_void_p, C.c_void_p]),
     "orcai_zero_fill": (C.c_int, [C.c_void_p, c_i64, C.c_void_p]),
     "orcai_pcm_decode": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "orcai_pcm_decode_planar": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p]),
+    "orcai_overlap_average_ragged": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

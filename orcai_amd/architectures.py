@@ -23,6 +23,7 @@ import torch
 from orcai_amd import _native as N
 from orcai_amd import shared_trunk
 from orcai_amd.auxiliary import MASK_VALUE, Messenger  # noqa: F401  (re-exported like the reference)
+from orcai_amd.batch import DEFAULT_MAX_FRAMES, plan_batches, short_recordings
 
 BN_EPS = 1e-3  # keras BatchNormalization default epsilon
 ENTRY_FILTERS = 16  # architectures.py:164
@@ -683,6 +684,49 @@ class ResNetLSTM:
         if n > 0:
             self.forward_device(spectrogram.view(-1), shift * W, n, out, chunk=chunk)
         return out
+
+    # ------------------------------------------------------------------ several recordings in one detector pass (orcai_amd/batch.py)
+    def batch_buffer(self, layout) -> torch.Tensor:
+        """The f32 cuda buffer [layout.rows][W] of a batch.Batch, with the rows between one recording's end and the next one's start zero-filled
+        (orcai_zero_fill); the caller writes recording r into rows [offsets[r], offsets[r] + frames[r])."""
+        W = self.input_hw[1]
+        buf = torch.empty((layout.rows, W), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+        st = N.stream_ptr()
+        for row, rows in layout.gaps():
+            N.check(N.lib().orcai_zero_fill(buf[row:].data_ptr(), 4 * rows * W, st), "orcai_zero_fill")
+        return buf
+
+    def predict_batch(self, buf: torch.Tensor, layout, chunk: int = 128) -> tuple:
+        """ONE forward_device over a filled batch buffer.  Returns (predictions of all layout.n_total batch snippets f32 cuda [n_total][steps][labels],
+        [view of recording r's [n_r][steps][labels]]).  The snippets that straddle two recordings are computed and never read."""
+        H, W = self.input_hw
+        assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and tuple(buf.shape) == (layout.rows, W)
+        out = torch.empty((layout.n_total, self.out_steps, self.num_labels), dtype=torch.float32, device=buf.device)
+        self.forward_device(buf.view(-1), (H // 2) * W, layout.n_total, out, chunk=chunk)
+        return out, [out[first : first + n] for first, n in layout.snippets]
+
+    def predict_spectrograms(self, specs, max_frames: int = DEFAULT_MAX_FRAMES, chunk: int = 128) -> list:
+        """predict_spectrogram for a list of device spectrograms [T_r][W] in as few detector passes as max_frames buffer rows allow
+        (batch.plan_batches): consecutive recordings are copied end to end into one buffer, each at a multiple of H/2 rows, and one
+        forward_device runs over it.  Element r is f32 cuda [n_r][steps][labels] (a view of its pass's output), bit for bit
+        predict_spectrogram(specs[r]) -- a snippet's probabilities depend on its own rows only; [0][steps][labels] for a T_r < H."""
+        H, W = self.input_hw
+        for spec in specs:
+            assert spec.is_cuda and spec.dtype == torch.float32 and spec.is_contiguous() and spec.dim() == 2 and spec.shape[1] == W
+        results = [None] * len(specs)
+        frames = [int(spec.shape[0]) for spec in specs]
+        for r in short_recordings(frames, H):
+            results[r] = torch.empty((0, self.out_steps, self.num_labels), dtype=torch.float32, device=specs[r].device)
+        for layout in plan_batches(frames, H, max_frames, self.time_reduction):
+            if len(layout.items) == 1:  # nothing to lay out: the recording is read in place
+                buf = specs[layout.items[0]]
+            else:
+                buf = self.batch_buffer(layout)
+                for r, o, T in zip(layout.items, layout.offsets, layout.frames):
+                    buf[o : o + T].copy_(specs[r])
+            for r, view in zip(layout.items, self.predict_batch(buf, layout, chunk=chunk)[1]):
+                results[r] = view
+        return results
 
     # ------------------------------------------------------------------ keras-shaped training API (train.py:155-219)
     def compile(self, optimizer=None, loss=None, metrics=None, learning_rate: float | None = None, seed: int = 0) -> None:

@@ -23,6 +23,23 @@ DEFAULT_HPS = files("orcai_amd.defaults").joinpath("default_hps_parameter.json")
 EPILOG = "MI355X-native implementation of the orcAI hot path (https://github.com/ethz-tb/orcAI)"
 
 
+class ChannelType(click.ParamType):
+    """A channel number or 'all'."""
+
+    name = "channel"
+
+    def convert(self, value, param, ctx):
+        if isinstance(value, int) or value == "all":
+            return value
+        try:
+            return int(value)
+        except ValueError:
+            self.fail(f"{value!r} is neither a channel number nor 'all'", param, ctx)
+
+
+CHANNEL = ChannelType()
+
+
 @click.group(help="orcAI on MI355X: detect acoustic signals in spectrograms generated from audio recordings.", epilog=EPILOG)
 @click.version_option(package_name=None, version=__import__("orcai_amd").__version__)
 def cli():
@@ -32,7 +49,11 @@ def cli():
 @cli.command(name="predict", short_help="Predicts call annotations.", no_args_is_help=True, epilog=EPILOG,
              help="Predicts call annotations from RECORDING_PATH: a wav file or a recording table (.csv).")
 @click.argument("recording_path", type=FileR)
-@click.option("--channel", "-c", type=int, default=1, show_default=True, help="Channel to use for prediction if running predictions for a single file.")
+@click.option("--channel", "-c", type=CHANNEL, default="1", show_default=True,
+              help="Channel to use for prediction if running predictions for a single file; 'all': every channel, one output file each.")
+@click.option("--batch-frames", "batch_frames", type=click.IntRange(min=0), default=0, show_default=True,
+              help="Recording table only: run consecutive recordings through the detector in batches of at most this many spectrogram frames "
+                   "(675000 is an hour's worth); 0: one detector pass per recording.")
 @click.option("--model", "-m", type=click.Choice(INCLUDED_MODELS, case_sensitive=False), default="orcai-V1", show_default=True,
               help="Builtin model to use for prediction. Overridden if model_dir is given.")
 @click.option("--model_dir", "-md", "model_dir", type=DirR, default=None, show_default="use builtin model", help="Path to a model directory.")

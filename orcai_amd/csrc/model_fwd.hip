@@ -2319,6 +2319,45 @@ __global__ __launch_bounds__(256) void overlap_average_kernel(const float* __res
   if (l == 0) cnt[s] = (double)c;
 }
 
+// overlap_average over a table of recordings in one launch (orcai_overlap_average_ragged): recording r's snippets are pred[first_r .. first_r + n_r),
+// its S_r output steps are rows row_r .. row_r + S_r of agg / cnt.  One thread per output element finds its recording by binary search on the first
+// output rows (ascending), then does overlap_average_kernel's arithmetic on that recording alone: the same f64 sum in snippet order, one division.
+__global__ __launch_bounds__(256) void overlap_average_ragged_kernel(const float* __restrict__ pred /*[n_total][P][L]*/, int P, int L, int step,
+                                                                      const int64_t* __restrict__ table /*[R][4]: first snippet, n, S, first row*/, int R,
+                                                                      int64_t S_total, double* __restrict__ agg /*[S_total][L]*/,
+                                                                      double* __restrict__ cnt /*[S_total]*/) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= S_total * L) return;
+  const int64_t row = idx / L;
+  const int l = (int)(idx % L);
+  int lo = 0, hi = R - 1;  // the last recording whose first output row is <= row
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[4 * mid + 3] <= row) lo = mid; else hi = mid - 1;
+  }
+  const int64_t first = table[4 * lo], n = table[4 * lo + 1];
+  const int64_t s = row - table[4 * lo + 3];
+  double sum = 0.0;
+  int c = 0;
+  if (s < table[4 * lo + 2]) {  // always, for a table whose rows tile [0, S_total)
+    int64_t i_hi = s / step;
+    if (i_hi > n - 1) i_hi = n - 1;
+    int64_t i_lo = (s - P + step) / step;
+    if (s - P + 1 <= 0) i_lo = 0;
+    const float* p = pred + first * P * L;
+    for (int64_t i = i_lo; i <= i_hi; ++i) {
+      const int64_t off = s - i * step;
+      if (off >= 0 && off < P) {
+        sum += (double)p[(i * P + off) * L + l];
+        ++c;
+      }
+    }
+  }
+  if (c > 0) sum /= (double)c;
+  agg[idx] = sum;
+  if (l == 0) cnt[row] = (double)c;
+}
+
 inline uint32_t magic_for(uint32_t d) { return (uint32_t)((0x100000000ull + d - 1) / d); }  // __umulhi(n, magic) == n / d while n*d < 2^32
 
 // ---------------------------------------------------------------- ResNet1DConv head (architectures.py:10-15, 107-115)
@@ -2954,6 +2993,15 @@ int orcai_dense_sigmoid(const float* x, const float* w, const float* bias, int64
 int orcai_overlap_average(const float* pred, int n, int P, int L, int step, int64_t S, double* agg, double* cnt, void* stream) {
   if (!pred || !agg || !cnt || n < 0 || P <= 0 || L <= 0 || step <= 0 || S <= 0) return ORCAI_E_BADARG;
   hipLaunchKernelGGL(overlap_average_kernel, dim3((unsigned)((S * L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred, n, P, L, step, S, agg, cnt);
+  return (int)hipGetLastError();
+}
+
+int orcai_overlap_average_ragged(const float* pred, int P, int L, int step, const int64_t* table, int R, int64_t S_total, double* agg, double* cnt,
+                                 void* stream) {
+  if (!pred || !table || !agg || !cnt || R < 1 || P <= 0 || L <= 0 || step <= 0 || S_total <= 0) return ORCAI_E_BADARG;
+  const int64_t blocks = (S_total * L + 255) / 256;
+  if (blocks > 0x7fffffff) return ORCAI_E_UNSUPPORTED;
+  hipLaunchKernelGGL(overlap_average_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pred, P, L, step, table, R, S_total, agg, cnt);
   return (int)hipGetLastError();
 }
 

@@ -62,23 +62,38 @@ class FrontEnd:
                                       "need the reference's CPU path")
 
     # -- the whole of make_spectrogram after decode (spectrogram.py:90-147) -----------------
-    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False):
-        """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
-        Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
-        sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which spectrogram_backward needs -- the
-        workspace itself is overwritten by the next recording."""
+    def _kept_bins(self, spectrogram_parameter: dict) -> int:
+        """K of make_spectrogram's [T, K]; the parameter's own refusals."""
         n_fft = int(spectrogram_parameter["nfft"])
-        hop = int(spectrogram_parameter["n_overlap"])
         self._check_nfft(n_fft)
         freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
         f_lo, f_hi = crop_indices(freqs, spectrogram_parameter["freq_range"])
         if f_lo != 0:
             raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
+        return f_hi
+
+    def spectrogram_shape(self, n_samples: int, spectrogram_parameter: dict) -> tuple[int, int]:
+        """(T, K) of make_spectrogram's result for a signal of n_samples at the parameter's rate: host arithmetic only."""
+        K = self._kept_bins(spectrogram_parameter)
+        n_fft, hop = int(spectrogram_parameter["nfft"]), int(spectrogram_parameter["n_overlap"])
+        return 1 + (n_samples - (n_fft & 1)) // hop, K  # librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop
+
+    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False, out: torch.Tensor | None = None):
+        """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
+        Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
+        sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which spectrogram_backward needs -- the
+        workspace itself is overwritten by the next recording.  out: a contiguous f32[T, K] of this device to write into (a recording's rows of a
+        batch buffer, predict.predict_wavs) instead of a new tensor."""
+        n_fft = int(spectrogram_parameter["nfft"])
+        hop = int(spectrogram_parameter["n_overlap"])
+        K = self._kept_bins(spectrogram_parameter)
         pcm = self._check_pcm(pcm)
         n = pcm.numel()
         T = 1 + (n - (n_fft & 1)) // hop  # librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop
-        K = f_hi
-        out = torch.empty((T, K), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((T, K), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, K) and out.is_contiguous()):
+            raise ValueError(f"make_spectrogram: out must be a contiguous float32 CUDA tensor [{T}, {K}]")
         total = T * K
         r_lo = nearest_rank_index(total, spectrogram_parameter["quantiles"][0])
         r_hi = nearest_rank_index(total, spectrogram_parameter["quantiles"][1])

@@ -84,17 +84,23 @@ def filter_predictions_file(predicted_labels: Path | str, output_file: Path | st
 
 
 class PendingAggregate:
-    """Averaged probabilities of one recording on their way from the GPU to pinned host memory.  `result()` waits for the copy (an
-    event on the launch stream, not a device-wide synchronisation) and returns the two host arrays."""
+    """Averaged probabilities of one recording, or of every recording of a batch, on their way from the GPU to pinned host memory.  `result()` waits
+    for the copy (an event on the launch stream, not a device-wide synchronisation) and returns the two host arrays; for a batch (`slices` =
+    [(first output row, rows)] per recording) `results()` returns one (aggregated, count) pair per recording, views of the one host buffer."""
 
-    def __init__(self, agg_host: torch.Tensor, cnt_host: torch.Tensor, event, keep=()):
-        self._agg, self._cnt, self._event, self._keep = agg_host, cnt_host, event, keep
+    def __init__(self, agg_host: torch.Tensor, cnt_host: torch.Tensor, event, keep=(), slices=None):
+        self._agg, self._cnt, self._event, self._keep, self._slices = agg_host, cnt_host, event, keep, slices
 
     def result(self) -> tuple[np.ndarray, np.ndarray]:
         if self._event is not None:
             self._event.synchronize()
             self._event, self._keep = None, ()
         return self._agg.numpy(), self._cnt.numpy()
+
+    def results(self) -> list[tuple[np.ndarray, np.ndarray]]:
+        agg, cnt = self.result()
+        slices = self._slices if self._slices is not None else [(0, len(cnt))]
+        return [(agg[row : row + rows], cnt[row : row + rows]) for row, rows in slices]
 
 
 def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snippet_length: int, n_filters: int, wait: bool = True):
@@ -122,6 +128,27 @@ def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snipp
     event = torch.cuda.Event()
     event.record()
     return PendingAggregate(agg_host, cnt_host, event, keep=(agg, cnt, predictions))
+
+
+def aggregate_batch_device(predictions: torch.Tensor, layout, snippet_length: int, n_filters: int) -> PendingAggregate:
+    """aggregate_predictions_device for every recording of a batch (batch.Batch) in one launch of orcai_overlap_average_ragged; the averaged
+    probabilities and counts of the whole batch go to the host in ONE pinned copy behind one event.  predictions: f32 cuda [layout.n_total, P, L]
+    (model.predict_batch).  Per recording the same bits as aggregate_predictions_device on its own snippets."""
+    tpo = 2**n_filters
+    P = snippet_length // tpo
+    step = (snippet_length // 2) // tpo
+    L = int(predictions.shape[2])
+    S = layout.out_rows
+    pred = predictions.contiguous()
+    table = torch.tensor(layout.table, dtype=torch.int64).pin_memory().to(pred.device, non_blocking=True)
+    both = torch.empty(S * (L + 1), dtype=torch.float64, device=pred.device)  # agg [S][L], then cnt [S]
+    N.check(N.lib().orcai_overlap_average_ragged(N.ptr(pred), P, L, step, N.ptr(table), len(layout.table), S, both.data_ptr(), both[S * L :].data_ptr(),
+                                                 N.stream_ptr()), "orcai_overlap_average_ragged")
+    host = torch.empty(S * (L + 1), dtype=torch.float64, pin_memory=True)
+    host.copy_(both, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    return PendingAggregate(host[: S * L].view(S, L), host[S * L :], event, keep=(both, table, pred), slices=[(row, rows) for _, _, rows, row in layout.table])
 
 
 def compute_aggregated_predictions(recording_path: Path, spectrogram, model, orcai_parameter: dict, shape: dict,
@@ -244,6 +271,124 @@ def predict_wav(recording_path: Path | str, channel: int, model, orcai_parameter
     return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
 
 
+def _too_short(n_frames: int, snippet_length: int) -> ValueError:
+    return ValueError(f"recording too short: {n_frames} spectrogram frames, one snippet needs {snippet_length}")
+
+
+def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_frames: int, msgr: Messenger = Messenger(verbosity=0)):
+    """The GPU half of several recordings per detector pass (batch.py), as a generator of batch states.  sources: an iterable of (key, thunk),
+    thunk() -> the recording's f32 cuda samples at the model's sampling rate (spectrogram.load_wav), called one by one as the batches fill.  A
+    batch closes before the recording that would take its buffer past max_frames spectrogram frames; a state is yielded once the work of its batch is
+    QUEUED: the front end of every recording into its rows of the batch buffer, one forward pass, one orcai_overlap_average_ragged, one copy to
+    pinned memory.  state["members"] = [(key, delta_t)] in buffer order, state["failed"] = [(key, exception)]: the recordings met since the last
+    state that raised (thunk errors, a spectrogram of the wrong width, too short for one snippet) and are in no batch."""
+    from orcai_amd import frontend as fe
+    from orcai_amd.batch import Grouper, layout as batch_layout
+
+    sp = orcai_parameter["spectrogram"]
+    H, W = shape["input_shape"][0], shape["input_shape"][1]
+    n_filters = len(orcai_parameter["model"]["filters"])
+    grouper = Grouper(H, max_frames)
+    members, failed = [], []  # members: (key, pcm, T, delta_t)
+
+    def queue():
+        state = {"members": [(key, delta_t) for key, _, _, delta_t in members], "failed": list(failed), "pending": None, "orcai_parameter": orcai_parameter}
+        if members:
+            lay = batch_layout([T for _, _, T, _ in members], H, 2**n_filters)
+            buf = model.batch_buffer(lay)
+            front = fe.get_frontend()
+            for (_, pcm, T, _), o in zip(members, lay.offsets):
+                front.make_spectrogram(pcm, sp, out=buf[o : o + T])
+            predictions, _ = model.predict_batch(buf, lay)
+            state["pending"] = aggregate_batch_device(predictions, lay, H, n_filters)
+            state["junk_snippets"], state["snippets"] = lay.junk, lay.n_total
+            msgr.info(f"batch of {len(members)} recordings: {lay.n_total} snippets in one pass ({lay.junk} of them between recordings)")
+        members.clear()
+        failed.clear()
+        grouper.close()
+        return state
+
+    for key, thunk in sources:
+        try:
+            pcm = thunk()
+            T, K = fe.get_frontend().spectrogram_shape(pcm.numel(), sp)
+            times = fe.frames_to_time(min(T, 2), sp["sampling_rate"], sp["n_overlap"])
+            delta_t = times[1] - times[0]
+            if K != W:
+                raise ValueError(f"Spectrogram shape ({K}) for {getattr(key, 'stem', key)} not equal to input shape ({W})")
+            if T < H:
+                raise _too_short(T, H)
+        except Exception as e:  # this recording alone; the batch goes on
+            failed.append((key, e))
+            continue
+        if not grouper.fits(T):
+            yield queue()
+        grouper.add(T)
+        members.append((key, pcm, T, delta_t))
+    if members or failed:
+        yield queue()
+
+
+def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> list:
+    """The host half of one batch state: [(key, predict_wav's triple or the exception the recording raised)], the failed ones first."""
+    out = list(state["failed"])
+    if state["pending"] is not None:
+        for (key, delta_t), pair in zip(state["members"], state["pending"].results()):
+            out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"]}, label_suffix=label_suffix, msgr=msgr)))
+    return out
+
+
+def _run_batches(states, finish) -> None:
+    """One batch deep: the GPU half of batch b + 1 is queued (the next state is drawn from the generator) before finish(state of batch b) runs."""
+    in_flight = None
+    for state in states:
+        if in_flight is not None:
+            finish(in_flight)
+        in_flight = state
+    if in_flight is not None:
+        finish(in_flight)
+
+
+def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_frames: int | None = None, msgr: Messenger = Messenger(verbosity=0)):
+    """First half of predict_wavs: a generator of batch states (_launch_batches) whose keys are the indices into `items`."""
+    from orcai_amd.batch import DEFAULT_MAX_FRAMES
+    from orcai_amd.spectrogram import load_wav
+
+    sr = orcai_parameter["spectrogram"]["sampling_rate"]
+    sources = ((i, lambda path=path, channel=channel: load_wav(Path(path), sr, channel, msgr)) for i, (path, channel) in enumerate(items))
+    return _launch_batches(sources, model, orcai_parameter, shape, DEFAULT_MAX_FRAMES if max_frames is None else max_frames, msgr=msgr)
+
+
+def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> list:
+    """Second half (host): [(index into items, (predicted_labels, aggregated_predictions, delta_t) or the exception that item raised)]."""
+    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr)
+
+
+def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*", max_frames: int | None = None,
+                 msgr: Messenger = Messenger(verbosity=0)) -> list:
+    """predict_wav for every (path, channel) of `items`, several recordings per detector pass: batches of at most max_frames spectrogram frames
+    (batch.DEFAULT_MAX_FRAMES: an hour's worth) go through ONE forward pass and ONE overlap average, the host half of a batch runs beside the GPU
+    half of the next.  Returns, per item, what predict_wav returns for it -- the same label table, the same f64 probabilities, the same delta_t --
+    or the exception it raised (a missing file, a recording shorter than one snippet); the other items are unaffected.
+    A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item."""
+    items = list(items)
+    results = [None] * len(items)
+    if not hasattr(model, "predict_batch"):
+        for i, (path, channel) in enumerate(items):
+            try:
+                results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr)
+            except Exception as e:
+                results[i] = e
+        return results
+
+    def finish(state):
+        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr):
+            results[i] = result
+
+    _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr), finish)
+    return results
+
+
 def save_predictions(predicted_labels: pd.DataFrame, output_path: Path | str, delta_t: float, msgr: Messenger = Messenger(verbosity=0)) -> None:
     """Tab-separated start/stop/label with header, seconds rounded to 4 places (predict.py:474-499)."""
     predicted_labels = _convert_times_to_seconds(predicted_labels, delta_t)
@@ -261,10 +406,9 @@ def save_prediction_probabilities(aggregated_predictions: np.ndarray, orcai_para
     msgr.info(f"Prediction probabilities saved to {predictions_path}")
 
 
-def _launch_recording(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
-                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None) -> dict:
-    """predict.py:534-575: output path and overwrite check, then the GPU half of the recording (queued, not waited for)."""
-    recording_path = Path(recording_path)
+def _checked_output_path(recording_path: Path, channel: int, orcai_parameter: dict, output_path: Path | str = "default", overwrite: bool = False,
+                         msgr: Messenger = Messenger(verbosity=0)):
+    """predict.py:534-575: the output path of one recording and the overwrite check."""
     if output_path is not None:
         if output_path == "default":
             filename = f"{recording_path.stem}_c{channel}_{orcai_parameter['name']}_predicted.txt"
@@ -277,22 +421,37 @@ def _launch_recording(recording_path: Path | str, channel: int, model, orcai_par
                 msgr.warning(f"Output file {output_path} already exists. Overwriting.")
             else:
                 raise FileExistsError(f"Annotation file already exists: {output_path}")
+    return output_path
+
+
+def _launch_recording(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
+                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None) -> dict:
+    """predict.py:534-575: output path and overwrite check, then the GPU half of the recording (queued, not waited for)."""
+    recording_path = Path(recording_path)
+    output_path = _checked_output_path(recording_path, channel, orcai_parameter, output_path, overwrite, msgr)
     state = predict_wav_launch(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape, msgr=msgr,
                                progressbar=progressbar)
     state["output_path"] = output_path
     return state
 
 
-def _finish_recording(state: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                      msgr: Messenger = Messenger(verbosity=0)) -> None:
-    """predict.py:576-632: the host half -- labels, optional duration filter, files."""
-    predicted_labels, aggregated_predictions, delta_t = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
-    output_path, orcai_parameter = state["output_path"], state["orcai_parameter"]
+def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
+                    label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> None:
+    """predict.py:576-632 after the labels: optional duration filter, files."""
+    predicted_labels, aggregated_predictions, delta_t = result
     if call_duration_limits is not None:
         predicted_labels = filter_predictions(predicted_labels, delta_t=delta_t, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
     save_predictions(predicted_labels=predicted_labels, output_path=output_path, delta_t=delta_t, msgr=msgr)
     if save_probabilities:
         save_prediction_probabilities(aggregated_predictions=aggregated_predictions, orcai_parameter=orcai_parameter, delta_t=delta_t, output_path=output_path, msgr=msgr)
+
+
+def _finish_recording(state: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
+                      msgr: Messenger = Messenger(verbosity=0)) -> None:
+    """predict.py:576-632: the host half -- labels, optional duration filter, files."""
+    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
+    _save_recording(result, state["output_path"], state["orcai_parameter"], save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
+                    label_suffix=label_suffix, msgr=msgr)
 
 
 def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
@@ -304,16 +463,90 @@ def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_par
     _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
 
 
-def predict(recording_path: str | Path, channel: int = 1, model_dir: str | Path = DEFAULT_MODEL_DIR, output_path: str | Path = "default",
+def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default", overwrite: bool = False,
+                          save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
+                          msgr: Messenger = Messenger(verbosity=0)) -> None:
+    """predict(channel="all"): one read and one upload of the file, every channel decoded by orcai_pcm_decode_planar, the channels as ONE batch through
+    the detector.  One output file per channel, under the name -- and with the bytes -- predict(channel=c) gives it."""
+    from orcai_amd.spectrogram import load_wav_all
+
+    if output_path is not None and output_path != "default":
+        raise ValueError("channel='all' writes one file per channel next to the recording: output_path must be 'default' (or None)")
+    pcms = load_wav_all(recording_path, orcai_parameter["spectrogram"]["sampling_rate"], msgr)
+    paths = {c: _checked_output_path(recording_path, c, orcai_parameter, output_path, overwrite, msgr) for c in range(1, len(pcms) + 1)}
+    sources = ((c, lambda pcm=pcm: pcm) for c, pcm in enumerate(pcms, start=1))
+    errors = []
+
+    def finish(state):
+        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr):
+            if isinstance(result, Exception):
+                errors.append(result)
+                continue
+            _save_recording(result, paths[c], orcai_parameter, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
+                            label_suffix=label_suffix, msgr=msgr)
+
+    total = sum(int(pcm.numel()) for pcm in pcms) // orcai_parameter["spectrogram"]["n_overlap"] + (shape["input_shape"][0] + 1) * len(pcms)
+    _run_batches(_launch_batches(sources, model, orcai_parameter, shape, max_frames=total, msgr=msgr), finish)  # max_frames: all channels in one batch
+    if errors:
+        raise errors[0]  # every channel has the same length: the single-channel call's error
+
+
+def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter: dict, shape: dict, batch_frames: int, overwrite: bool,
+                           save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm) -> None:
+    """Table mode with batch_frames > 0: the rows of the table in order, grouped into detector passes of at most batch_frames spectrogram frames.
+    Per recording the output path, the overwrite check, the files and the error line are those of the one-by-one loop; one batch deep, so the host
+    half of a batch (labels, files) runs beside the GPU half of the next."""
+    from orcai_amd.spectrogram import load_wav
+
+    quiet = Messenger(verbosity=0)
+    sr = orcai_parameter["spectrogram"]["sampling_rate"]
+    outputs = {}
+
+    def error(i, e):
+        msgr.error(f"Error predicting {recording_table.loc[i, 'recording']}: {e.args[0] if e.args else e}")  # predict.py:752-755: log and continue
+
+    def sources():
+        for i in progressbar:
+            path = Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"])
+            channel = recording_table.loc[i, "channel"]
+            try:
+                outputs[i] = _checked_output_path(path, channel, orcai_parameter, recording_table.loc[i, "output_path"], overwrite, quiet)
+            except Exception as e:
+                error(i, e)
+                continue
+            yield i, lambda path=path, channel=channel: load_wav(path, sr, channel, quiet)
+
+    def finish(state):
+        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet):
+            try:
+                if isinstance(result, Exception):
+                    raise result
+                _save_recording(result, outputs[i], orcai_parameter, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
+                                label_suffix=label_suffix, msgr=quiet)
+            except Exception as e:
+                error(i, e)
+
+    _run_batches(_launch_batches(sources(), model, orcai_parameter, shape, batch_frames, msgr=quiet), finish)
+
+
+def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str | Path = DEFAULT_MODEL_DIR, output_path: str | Path = "default",
             overwrite: bool = False, save_probabilities: bool = False, base_dir_recording: str | Path | None = None,
-            call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None) -> None:
-    """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757)."""
+            call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None,
+            batch_frames: int = 0) -> None:
+    """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757).
+    channel="all" (a wav file): every channel of the file from one read of its bytes, one output file per channel.
+    batch_frames > 0 (a table): consecutive recordings go through the detector in batches of at most batch_frames spectrogram frames
+    (predict_wavs' path: many short clips fill the GPU that one of them cannot); 0, the default, is one detector pass per recording.  The files
+    are the same bytes either way."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Predicting calls")
     model_dir = Path(model_dir)
     recording_path = Path(recording_path)
     msgr.part(f"Loading model: {model_dir.stem}")
     model, orcai_parameter, shape = load_orcai_model(model_dir)
+    if recording_path.suffix == ".wav" and channel == "all" and hasattr(model, "predict_batch"):
+        return _predict_all_channels(recording_path, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite,
+                                     save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
     if recording_path.suffix == ".wav":
         return _predict_and_save(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape,
                                  output_path=output_path, overwrite=overwrite, save_probabilities=save_probabilities,
@@ -343,8 +576,14 @@ def predict(recording_path: str | Path, channel: int = 1, model_dir: str | Path 
     # device: load_wav)
     wavio.set_prefetcher(wavio.WavPrefetcher([Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"])
                                               for i in recording_table.index], raw=True))
-    # one recording deep: the GPU half of recording i is queued before the host half of recording i - 1 (threshold, label table, files) runs
     quiet = Messenger(verbosity=0)
+    if batch_frames > 0 and hasattr(model, "predict_batch"):
+        _predict_table_batched(recording_table, model, orcai_parameter, shape, batch_frames, overwrite=overwrite, save_probabilities=save_probabilities,
+                               call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar)
+        wavio.set_prefetcher(None)
+        msgr.success("Predictions finished.")
+        return
+    # one recording deep: the GPU half of recording i is queued before the host half of recording i - 1 (threshold, label table, files) runs
     in_flight = None  # (table index, state)
 
     def finish(entry):

@@ -46,6 +46,24 @@ def load_wav(wav_file_path: Path | str, sampling_rate: int, channel: int, msgr: 
     return pcm
 
 
+def load_wav_all(wav_file_path: Path | str, sampling_rate: int, msgr: Messenger) -> list:
+    """load_wav for every channel of the file from ONE read and ONE upload of its bytes: ``orcai_pcm_decode_planar`` makes all channels' samples on the
+    device, the resampler then runs per channel.  Element c equals ``load_wav(..., channel=c + 1)`` bit for bit."""
+    raw = wavio.read_wav_raw_prefetched(wav_file_path)
+    channels, native_sr = raw.channels, raw.rate
+    if channels > wavio.MAX_DEVICE_CHANNELS:  # wider than the device decode takes: the host decode, as load_wav
+        raw.release()
+        planes = torch.from_numpy(wavio.read_wav(wav_file_path)[0]).cuda()
+    else:
+        planes = wavio.upload_and_decode_all(raw)
+    pcms = [planes[c] for c in range(channels)]
+    if native_sr != sampling_rate:
+        from orcai_amd.resample import resample_device
+
+        pcms = [resample_device(pcm, native_sr, sampling_rate) for pcm in pcms]
+    return pcms
+
+
 def calculate_spectrogram(wav_file_path: Path, channel: int, spectrogram_parameter: dict, msgr: Messenger = Messenger(verbosity=0)):
     """dB spectrogram [257, T] (float32), frequencies [257], times [T] (spectrogram.py:15-55)."""
     sr = spectrogram_parameter["sampling_rate"]

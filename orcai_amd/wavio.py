@@ -6,7 +6,8 @@ unsigned 8-bit (x - 128) / 2**7, IEEE float passed through.
 
 Two routes.  ``read_wav`` decodes every channel on the host (numpy only).  ``read_wav_raw`` parses the container the same way but leaves the data
 chunk as the bytes of the file, read straight into a (page-locked) buffer; ``decode_device`` turns those bytes, uploaded, into one channel's f32
-samples with ``orcai_pcm_decode`` (csrc/wav_decode.hip), bit for bit what ``read_wav`` gives.  The predict path takes the second route.
+samples with ``orcai_pcm_decode`` (csrc/wav_decode.hip), ``decode_device_planar`` into every channel's with ``orcai_pcm_decode_planar``, bit for bit what
+``read_wav`` gives.  The predict path takes the second route.
 """
 
 from __future__ import annotations
@@ -238,15 +239,12 @@ def decode_device(frames, n_frames: int, channels: int, channel: int, sample_for
     return out
 
 
-def upload_and_decode(raw: RawWav, channel: int):
-    """The samples of 0-based `channel` of a RawWav as f32 on the current device: non-blocking upload of the payload bytes, then orcai_pcm_decode.
-    A pinned payload goes back to the pool, gated by the event recorded after its copy."""
+def _upload(raw: RawWav):
+    """The payload bytes of a RawWav on the current device, padded to a multiple of 16: a non-blocking copy when the payload is page-locked.  A pinned
+    payload goes back to the pool, gated by the event recorded after its copy."""
     import torch
 
     nbytes = raw.n_frames * raw.channels * BYTES_PER_SAMPLE[raw.format]
-    if raw.n_frames == 0:
-        raw.release()
-        return torch.empty(0, dtype=torch.float32, device="cuda")
     frames = torch.empty(-(-nbytes // 16) * 16, dtype=torch.uint8, device="cuda")
     if raw._pinned is not None:
         frames[:nbytes].copy_(raw.payload, non_blocking=True)
@@ -255,7 +253,48 @@ def upload_and_decode(raw: RawWav, channel: int):
         raw.release(event)
     else:
         frames[:nbytes].copy_(torch.from_numpy(raw.payload))
-    return decode_device(frames, raw.n_frames, raw.channels, channel, raw.format)
+    return frames
+
+
+def upload_and_decode(raw: RawWav, channel: int):
+    """The samples of 0-based `channel` of a RawWav as f32 on the current device: non-blocking upload of the payload bytes, then orcai_pcm_decode."""
+    import torch
+
+    if raw.n_frames == 0:
+        raw.release()
+        return torch.empty(0, dtype=torch.float32, device="cuda")
+    return decode_device(_upload(raw), raw.n_frames, raw.channels, channel, raw.format)
+
+
+def decode_device_planar(frames, n_frames: int, channels: int, sample_format: int):
+    """orcai_pcm_decode_planar: uint8 cuda `frames` (the data chunk, padded to a multiple of 16 bytes) -> f32 cuda [channels][n_frames], a view of
+    planes roundup(n_frames, 4) floats apart (each starts 16-byte aligned and is contiguous); plane c equals decode_device(..., channel=c, ...)."""
+    import torch
+
+    from orcai_amd import _native as N
+
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 1 and frames.is_contiguous()):
+        raise TypeError("frames must be a contiguous 1-D uint8 CUDA tensor")
+    if not 0 <= sample_format < len(BYTES_PER_SAMPLE):
+        raise ValueError(f"unknown sample format {sample_format}")
+    need = -(-n_frames * channels * BYTES_PER_SAMPLE[sample_format] // 16) * 16
+    if frames.numel() < need:
+        raise ValueError(f"frames holds {frames.numel()} bytes; {n_frames} frames need {need} (rounded up to 16)")
+    stride = -(-n_frames // 4) * 4
+    out = torch.empty((channels, stride), dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        N.check(N.lib().orcai_pcm_decode_planar(N.ptr(frames), n_frames, channels, sample_format, N.ptr(out), stride, N.stream_ptr()), "orcai_pcm_decode_planar")
+    return out[:, :n_frames]
+
+
+def upload_and_decode_all(raw: RawWav):
+    """Every channel of a RawWav as f32 [channels][n_frames] on the current device from ONE upload of the payload bytes and one orcai_pcm_decode_planar."""
+    import torch
+
+    if raw.n_frames == 0:
+        raw.release()
+        return torch.empty((raw.channels, 0), dtype=torch.float32, device="cuda")
+    return decode_device_planar(_upload(raw), raw.n_frames, raw.channels, raw.format)
 
 
 def write_wav_pcm16(path: str | Path, samples: np.ndarray, rate: int) -> None:
