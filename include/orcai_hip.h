@@ -311,6 +311,30 @@ int orcai_overlap_average(const float* pred, int n, int P, int L, int step, int6
 int orcai_overlap_average_ragged(const float* pred, int P, int L, int step, const int64_t* table, int R, int64_t S_total, double* agg, double* cnt,
                                  void* stream);
 
+/* predict.py:298-340 and the duration filter of :14-159: label intervals from the averaged probabilities of R recordings, in the order of the
+ * label file (compute_binary_predictions + compute_labels, with _check_duration's verdict per interval).
+ *   agg, cnt   f64[S_total][L], f64[S_total]: what orcai_overlap_average (R = 1, table = {0, n, S, 0}) or orcai_overlap_average_ragged writes
+ *   table      int64[R][4] ON THE DEVICE, the ragged launcher's; only S_r and row_r are read.  1 <= L <= 64.
+ *   per recording r, over rows row_r .. row_r + S_r:  thr_r = threshold / max(cnt) (one f64 division; no rows or a zero maximum: no runs);
+ *              b[s][l] = agg[s][l] > thr_r (strict, NaN is false); a run is a maximal stretch of ones of one column INSIDE the recording
+ *   runs       int32[capacity][4] = {start_row, stop_row (inclusive), label, status}, rows counted from row_r, 16-byte aligned.  Recording r's runs
+ *              are runs[offsets[r] .. offsets[r + 1]), ascending by (start_row, stop_row, label_rank[label], label): the order of the stable
+ *              sort_values(by=["start", "stop", "label"]) when label_rank int[L] is the string order of the label names.
+ *   status     limits f64[L][2] = {min, max} seconds per label, NULL: every status 0.  d = (double)((stop_row - start_row) * tpo) * frame_seconds;
+ *              1 (too short) if d < min, else 2 (too long) if d > max, else 0.
+ *   offsets    int64[R + 1]; offsets[R], the number of runs found, is always written.  Runs at positions >= capacity are counted and not stored
+ *              (the caller retries with a larger buffer); capacity = L * ceil(S_total / 2) + R always suffices.
+ *   workspace  orcai_extract_labels_workspace_bytes(L, R, S_total) bytes, 256-byte aligned (0 for sizes the call refuses).
+ * Six launches on `stream` (labels.hip: row tile 256 rows, scan tile 64 row tiles); none iterates over the length of a run.  Output positions are
+ * computed by scans, not claimed: no atomics, two calls write the same bytes.  The table's contents are not checked (rows tile [0, S_total) in
+ * ascending order, as the ragged launcher wants them).
+ * ORCAI_E_BADARG: a null agg / cnt / table / label_rank / runs / offsets / workspace, L outside 1..64, R < 1, S_total < 1, capacity < 0, tpo < 1,
+ * a workspace smaller than the size function answers, misaligned runs or workspace.  ORCAI_E_UNSUPPORTED (nothing launched): 2^31 or more row tiles. */
+int orcai_extract_labels(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, double threshold,
+                         const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity, int64_t* offsets,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total);
+
 /* ------------------------------------------------------------------------------------------
  * Training (train.py:155-219: Adam(lr) + MaskedBinaryCrossentropy + MaskedBinaryAccuracy; architectures.py:210-286)
  * "Row tensors" are f32[M][cols] row-major, M = snippets * time steps.

@@ -185,6 +185,9 @@ _SIGNATURES = {
     "orcai_pcm_decode": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_pcm_decode_planar": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p]),
     "orcai_overlap_average_ragged": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_extract_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_i64, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                       C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "orcai_extract_labels_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
 }
 
 

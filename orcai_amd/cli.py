@@ -54,6 +54,8 @@ def cli():
 @click.option("--batch-frames", "batch_frames", type=click.IntRange(min=0), default=0, show_default=True,
               help="Recording table only: run consecutive recordings through the detector in batches of at most this many spectrogram frames "
                    "(675000 is an hour's worth); 0: one detector pass per recording.")
+@click.option("--device-labels", "device_labels", is_flag=True,
+              help="Threshold, run detection, sort and duration filter on the GPU; only the label intervals return to the host. Same files.")
 @click.option("--model", "-m", type=click.Choice(INCLUDED_MODELS, case_sensitive=False), default="orcai-V1", show_default=True,
               help="Builtin model to use for prediction. Overridden if model_dir is given.")
 @click.option("--model_dir", "-md", "model_dir", type=DirR, default=None, show_default="use builtin model", help="Path to a model directory.")

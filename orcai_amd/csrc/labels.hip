@@ -1,0 +1,368 @@
+// labels.hip -- label extraction of the predict path for gfx950 (orcai_extract_labels): the averaged probabilities of one recording or of a batch of
+// recordings -> the label intervals, in the order of the label file, with the verdict of the duration filter.
+//
+// Replaces the host arithmetic behind the overlap average (reference src/orcAI/predict.py:298-340 compute_binary_predictions + compute_labels, and
+// the per-interval _check_duration of :14-66): threshold / max(count), the strict comparison, find_consecutive_ones per label, the stable
+// sort_values(by=["start", "stop", "label"]) and the too short / too long decision.  Everything compared and written is an integer, so the
+// output equals the host route exactly.
+//
+// Tiles.  ROW_TILE = 256 rows per workgroup (one lane per row, four waves); SCAN_TILE = 64 row tiles (16384 rows) per pass of the scan
+// (one wave per sequence, one lane per row tile, a carry between passes).
+//
+// Launches, all on the caller's stream, none of them walks a run:
+//   1 threshold  one workgroup per recording: max of its counts (NaN kept, as np.max), thr_r = threshold / max as one f64 division
+//                (+inf, "nothing is a one", for no rows or a zero maximum).
+//   2 mask       one lane per row: the L doubles of the row are contiguous, b[l] = agg > thr_r (strict, NaN false) -> one 64-bit word per row.
+//   3 count      per row tile: start = m & ~m[row - 1], stop = m & ~m[row + 1] (neighbours inside the recording only).  Column counts come from
+//                L ballots per wave (the 64 x 64 bit transpose), summed over the four waves: 2 L + 1 counts per tile (starts of all columns,
+//                starts per column, stops per column), stored sequence-major.
+//   4 scan       exclusive scan of every sequence over the row tiles, in place; the total of sequence 0 is offsets[R].
+//   5 stops      the k-th stop of column l writes its row to stops[l][k] (k = scanned tile count + waves before + lanes below in the ballot).
+//   6 emit       the k-th start of column l reads stops[l][k]: a run.  Its output position is the scanned start count of the rows before
+//                it plus its rank among the at most 64 runs that start in its row, by (stop, label_rank, label): the wave takes its rows that
+//                start something one by one, lane = column, and compares through readlane -- n^2 / 64 steps for a row of n starts.  One 16-byte
+//                store per run.  The lane of a recording's first row writes offsets[r].
+// The output position of every run is computed, never claimed: no atomics, two calls give the same bytes.  Recordings tile [0, S_total) in
+// ascending row order (the ragged overlap average's table), so the global order (row, stop, rank, label) is the per-recording order.
+//
+// Worst cases this was laid out against: one run as long as the recording (two edges in the whole matrix: nothing iterates over its length) and
+// all 64 columns alternating every row (every second row starts 64 runs: 64 readlane steps per such row, spread over all waves).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "orcai_hip.h"
+
+namespace {
+
+constexpr int ROW_TILE = 256;  // rows per workgroup
+constexpr int SCAN_TILE = 64;  // row tiles per scan pass (one wave)
+constexpr int WAVES = ROW_TILE / 64;
+
+typedef unsigned long long u64;
+
+struct Layout {
+  size_t thr, mask, counts, stops, total;  // byte offsets into the workspace
+  int64_t tiles, colcap;
+};
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+inline Layout layout(int L, int R, int64_t S_total) {
+  Layout a;
+  a.tiles = (S_total + ROW_TILE - 1) / ROW_TILE;
+  a.colcap = S_total / 2 + R;  // runs one column can hold: the sum of ceil(S_r / 2)
+  a.thr = 0;                                                          // f64 [R]
+  a.mask = a.thr + up256((size_t)R * 8);                              // u64 [S_total]
+  a.counts = a.mask + up256((size_t)S_total * 8);                     // i64 [2 L + 1][tiles]
+  a.stops = a.counts + up256((size_t)(2 * L + 1) * a.tiles * 8);      // i32 [L][colcap]
+  a.total = a.stops + up256((size_t)L * (size_t)a.colcap * 4);
+  return a;
+}
+
+// the last recording whose first output row is <= row (overlap_average_ragged_kernel's search)
+__device__ __forceinline__ int locate(const int64_t* __restrict__ table, int R, int64_t row) {
+  int lo = 0, hi = R - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[4 * mid + 3] <= row) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+__device__ __forceinline__ int read_lane(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
+__device__ __forceinline__ u64 read_lane64(u64 v, int i) {
+  return ((u64)(uint32_t)read_lane((int)(v >> 32), i) << 32) | (uint32_t)read_lane((int)(uint32_t)v, i);
+}
+__device__ __forceinline__ u64 lanes_below(int i) { return i >= 64 ? ~0ull : ((1ull << i) - 1); }
+
+struct Edges {
+  u64 start, stop;  // columns in which a run starts / ends (inclusive) in this row
+  int rel;          // the row, counted from its recording's first
+};
+
+__device__ __forceinline__ Edges row_edges(const u64* __restrict__ mask, const int64_t* __restrict__ table, int R, int64_t S_total, int64_t row) {
+  Edges e = {0, 0, 0};
+  if (row >= S_total) return e;
+  const u64 m = mask[row];
+  if (m == 0) return e;
+  const int r = locate(table, R, row);  // m != 0: the row lies inside recording r (mask kernel)
+  const int64_t s = row - table[4 * r + 3], S = table[4 * r + 2];
+  const u64 prev = (s > 0 && row > 0) ? mask[row - 1] : 0;
+  const u64 next = (s + 1 < S && row + 1 < S_total) ? mask[row + 1] : 0;
+  e.start = m & ~prev;
+  e.stop = m & ~next;
+  e.rel = (int)s;
+  return e;
+}
+
+// ---------------------------------------------------------------- 1 threshold
+__global__ __launch_bounds__(256) void labels_threshold_kernel(const double* __restrict__ cnt, const int64_t* __restrict__ table, int64_t S_total,
+                                                                double threshold, double* __restrict__ thr) {
+  __shared__ double part[WAVES];
+  __shared__ int part_nan[WAVES];
+  const int r = blockIdx.x;
+  int64_t lo = table[4 * r + 3], hi = lo + table[4 * r + 2];
+  if (lo < 0) lo = 0;
+  if (hi > S_total) hi = S_total;
+  double m = -__builtin_inf();
+  int nan = 0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+    const double c = cnt[i];
+    nan |= (c != c);
+    m = c > m ? c : m;
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double o = __shfl_xor(m, d);
+    nan |= __shfl_xor(nan, d);
+    m = o > m ? o : m;
+  }
+  if (lane_id() == 0) {
+    part[threadIdx.x >> 6] = m;
+    part_nan[threadIdx.x >> 6] = nan;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < WAVES; ++w) {
+      m = part[w] > m ? part[w] : m;
+      nan |= part_nan[w];
+    }
+    double t = __builtin_inf();  // no rows, or a zero maximum: nothing is a one
+    if (hi > lo) {
+      if (nan) t = __builtin_nan("");  // np.max keeps a NaN: every comparison is false
+      else if (m != 0.0) t = threshold / m;
+    }
+    thr[r] = t;
+  }
+}
+
+// ---------------------------------------------------------------- 2 mask
+__global__ __launch_bounds__(256) void labels_mask_kernel(const double* __restrict__ agg, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                           const double* __restrict__ thr, u64* __restrict__ mask) {
+  const int64_t row = (int64_t)blockIdx.x * ROW_TILE + threadIdx.x;
+  if (row >= S_total) return;
+  const int r = locate(table, R, row);
+  const int64_t s = row - table[4 * r + 3];
+  u64 m = 0;
+  if (s >= 0 && s < table[4 * r + 2]) {
+    const double t = thr[r];
+    const double* __restrict__ p = agg + row * L;
+    for (int l = 0; l < L; ++l) m |= (u64)(p[l] > t) << l;
+  }
+  mask[row] = m;
+}
+
+// ---------------------------------------------------------------- 3 count
+__global__ __launch_bounds__(256) void labels_count_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                            int64_t tiles, int64_t* __restrict__ counts) {
+  __shared__ int wc[WAVES][2][64];
+  __shared__ int wr[WAVES];
+  const int64_t tile = blockIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const Edges e = row_edges(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
+  int cs = 0, ce = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1);
+    if (lane == l) {
+      cs = __popcll(bs);
+      ce = __popcll(be);
+    }
+  }
+  wc[wave][0][lane] = cs;
+  wc[wave][1][lane] = ce;
+  int n = __popcll(e.start);
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
+  if (lane == 0) wr[wave] = n;
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 128) {
+    const int which = t >> 6, l = t & 63;
+    if (l < L) {
+      int sum = 0;
+      for (int w = 0; w < WAVES; ++w) sum += wc[w][which][l];
+      counts[(int64_t)(1 + which * L + l) * tiles + tile] = sum;
+    }
+  } else if (t == 128) {
+    int sum = 0;
+    for (int w = 0; w < WAVES; ++w) sum += wr[w];
+    counts[tile] = sum;
+  }
+}
+
+// ---------------------------------------------------------------- 4 scan
+__global__ __launch_bounds__(256) void labels_scan_kernel(int64_t* __restrict__ counts, int sequences, int64_t tiles, int64_t* __restrict__ total) {
+  const int q = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (q >= sequences) return;  // a whole wave
+  const int lane = lane_id();
+  int64_t* __restrict__ seq = counts + (int64_t)q * tiles;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < tiles; base += SCAN_TILE) {
+    const int64_t i = base + lane;
+    const int64_t v = i < tiles ? seq[i] : 0;
+    int64_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t o = __shfl_up(incl, d);
+      if (lane >= d) incl += o;
+    }
+    if (i < tiles) seq[i] = carry + incl - v;
+    carry += __shfl(incl, 63);
+  }
+  if (q == 0 && lane == 0) *total = carry;
+}
+
+// ---------------------------------------------------------------- 5 stops
+__global__ __launch_bounds__(256) void labels_stops_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                            int64_t tiles, const int64_t* __restrict__ counts, int64_t colcap, int* __restrict__ stops) {
+  __shared__ int wc[WAVES][64];
+  __shared__ int64_t colbase[WAVES][64];
+  const int64_t tile = blockIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const Edges e = row_edges(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
+  int ce = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 be = __ballot((e.stop >> l) & 1);
+    if (lane == l) ce = __popcll(be);
+  }
+  wc[wave][lane] = ce;
+  __syncthreads();
+  int64_t b = 0;
+  if (lane < L) {
+    b = counts[(int64_t)(1 + L + lane) * tiles + tile];
+    for (int w = 0; w < wave; ++w) b += wc[w][lane];
+  }
+  colbase[wave][lane] = b;
+  __syncthreads();
+  for (int l = 0; l < L; ++l) {
+    const u64 be = __ballot((e.stop >> l) & 1);
+    if (be == 0) continue;
+    if ((e.stop >> l) & 1) {
+      const int64_t k = colbase[wave][l] + __popcll(be & lanes_below(lane));
+      if (k < colcap) stops[(int64_t)l * colcap + k] = e.rel;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- 6 emit
+__global__ __launch_bounds__(256) void labels_emit_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                           int64_t tiles, const int64_t* __restrict__ counts, int64_t colcap,
+                                                           const int* __restrict__ stops, const int* __restrict__ label_rank,
+                                                           const double* __restrict__ limits, double frame_seconds, int tpo, int4* __restrict__ runs,
+                                                           int64_t capacity, int64_t* __restrict__ offsets) {
+  __shared__ int wc[WAVES][64];
+  __shared__ int wr[WAVES];
+  const int64_t tile = blockIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int64_t row = tile * ROW_TILE + threadIdx.x;
+  const Edges e = row_edges(mask, table, R, S_total, row);
+  u64 mycol = 0;  // lane = column: the rows of this wave that start a run in it
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1);
+    if (lane == l) mycol = bs;
+  }
+  wc[wave][lane] = __popcll(mycol);
+  const int n = __popcll(e.start);
+  int incl = n;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(incl, d);
+    if (lane >= d) incl += o;
+  }
+  if (lane == 63) wr[wave] = incl;
+  __syncthreads();
+  int64_t cb = 0;  // lane = column: runs of the column that start before this wave's rows
+  int rk = 0;
+  double mn = 0.0, mx = __builtin_inf();
+  if (lane < L) {
+    cb = counts[(int64_t)(1 + lane) * tiles + tile];
+    for (int w = 0; w < wave; ++w) cb += wc[w][lane];
+    rk = label_rank[lane];
+    if (limits) {
+      mn = limits[2 * lane];
+      mx = limits[2 * lane + 1];
+    }
+  }
+  int64_t rb = counts[tile] + (incl - n);  // lane = row: runs that start before this row
+  for (int w = 0; w < wave; ++w) rb += wr[w];
+
+  // offsets: the first row of a recording knows how many runs lie before it; recordings without rows share the next one's first row
+  if (row < S_total) {
+    const int r = locate(table, R, row);
+    if (table[4 * r + 3] == row)
+      for (int q = r; q >= 0 && table[4 * q + 3] == row; --q) offsets[q] = rb;
+  }
+  if (tile == 0) {  // recordings without rows behind the last row (offsets[R], the total, is the scan's)
+    const int64_t total = offsets[R];
+    for (int q = threadIdx.x; q < R; q += 256)
+      if (table[4 * q + 3] >= S_total) offsets[q] = total;
+  }
+
+  u64 ne = __ballot(e.start != 0);
+  while (ne) {
+    const int i = __builtin_ctzll(ne);  // wave-uniform: the next row of this wave that starts a run
+    ne &= ne - 1;
+    const u64 m = read_lane64(e.start, i);
+    const int srel = read_lane(e.rel, i);
+    const int64_t base = (int64_t)read_lane64((u64)rb, i);
+    const bool act = (m >> lane) & 1;
+    int stop = srel;
+    if (act) {
+      const int64_t k = cb + __popcll(mycol & lanes_below(i));
+      if (k < colcap) stop = stops[(int64_t)lane * colcap + k];
+    }
+    int c = 0;  // runs of this row that sort before this lane's
+    for (u64 mm = m; mm; mm &= mm - 1) {
+      const int j = __builtin_ctzll(mm);
+      const int sj = read_lane(stop, j), rj = read_lane(rk, j);
+      c += (sj < stop) || (sj == stop && (rj < rk || (rj == rk && j < lane)));
+    }
+    if (act) {
+      const int64_t pos = base + c;
+      if (pos < capacity) {
+        int status = 0;
+        if (limits) {
+          const double d = (double)((int64_t)(stop - srel) * tpo) * frame_seconds;
+          status = d < mn ? 1 : (d > mx ? 2 : 0);
+        }
+        runs[pos] = make_int4(srel, stop, lane, status);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total) {
+  if (L < 1 || L > 64 || R < 1 || S_total < 1) return 0;
+  return layout(L, R, S_total).total;
+}
+
+int orcai_extract_labels(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, double threshold,
+                         const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity, int64_t* offsets,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  if (!agg || !cnt || !table || !label_rank || !runs || !offsets || !workspace) return ORCAI_E_BADARG;
+  if (L < 1 || L > 64 || R < 1 || S_total < 1 || capacity < 0 || tpo < 1) return ORCAI_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(runs) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return ORCAI_E_BADARG;
+  const Layout a = layout(L, R, S_total);
+  if (workspace_bytes < a.total) return ORCAI_E_BADARG;
+  if (a.tiles > 0x7fffffff) return ORCAI_E_UNSUPPORTED;
+  char* ws = static_cast<char*>(workspace);
+  double* thr = reinterpret_cast<double*>(ws + a.thr);
+  u64* mask = reinterpret_cast<u64*>(ws + a.mask);
+  int64_t* counts = reinterpret_cast<int64_t*>(ws + a.counts);
+  int* stops = reinterpret_cast<int*>(ws + a.stops);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)a.tiles), block(ROW_TILE);
+  const int sequences = 2 * L + 1;
+  hipLaunchKernelGGL(labels_threshold_kernel, dim3((unsigned)R), block, 0, st, cnt, table, S_total, threshold, thr);
+  hipLaunchKernelGGL(labels_mask_kernel, grid, block, 0, st, agg, L, table, R, S_total, thr, mask);
+  hipLaunchKernelGGL(labels_count_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts);
+  hipLaunchKernelGGL(labels_scan_kernel, dim3((unsigned)((sequences + WAVES - 1) / WAVES)), block, 0, st, counts, sequences, a.tiles, offsets + R);
+  hipLaunchKernelGGL(labels_stops_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops);
+  hipLaunchKernelGGL(labels_emit_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops, label_rank, limits,
+                     frame_seconds, tpo, reinterpret_cast<int4*>(runs), capacity, offsets);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,0 +1,161 @@
+"""Label extraction on the GPU: the host half of orcai_extract_labels.
+
+The kernel (csrc/labels.hip) thresholds the averaged probabilities, finds the runs of ones per label, orders them as the label file orders them and
+judges each against the duration limits; it hands back four integers per run.  What is left here is resolved ONCE per call, not per interval: the
+string order of the label names (`label_rank`), the {min, max} limits per label (`resolve_limits`, _check_duration's lookup), and wrapping the
+integer columns in the DataFrame the host route (predict.compute_labels, predict.filter_predictions) builds.
+"""
+
+from __future__ import annotations
+
+
+import numpy as np
+import pandas as pd
+import torch
+
+from orcai_amd import _native as N
+
+EAGER_RUNS = 4096  # runs that travel to the host with the offsets in the one eager copy (64 KiB); a recording-hour of orca calls is a few thousand
+STATUS_NAMES = np.array(["keep", "too short", "too long"], dtype=object)  # _check_duration's verdicts, by the kernel's status
+
+
+def suffixed_names(calls, label_suffix: str | None) -> list[str]:
+    """The label column's strings (compute_labels)."""
+    if (label_suffix is not None) & (label_suffix != ""):
+        return [label + label_suffix for label in calls]
+    return list(calls)
+
+
+def label_rank(calls, label_suffix: str | None) -> np.ndarray:
+    """int32 [L]: the position of every label in the stable string sort of the suffixed names -- the third key of compute_labels'
+    sort_values(by=["start", "stop", "label"]).  Equal names get consecutive ranks in label index order, which is the order the stable sort leaves
+    them in (the table is built label by label)."""
+    names = suffixed_names(calls, label_suffix)
+    rank = np.empty(len(names), dtype=np.int32)
+    rank[sorted(range(len(names)), key=lambda i: names[i])] = np.arange(len(names), dtype=np.int32)
+    return rank
+
+
+def resolve_limits(calls, label_suffix: str | None, call_duration_limits) -> np.ndarray:
+    """f64 [L][2] = {min, max} seconds per label, as _check_duration finds them for a row of that label: the suffixed name with every occurrence of
+    the suffix removed is looked up, else "default", else (0, inf); None is 0 / inf."""
+    if not isinstance(call_duration_limits, dict):
+        from orcai_amd.io import read_json
+
+        call_duration_limits = read_json(call_duration_limits)
+    out = np.empty((len(calls), 2), dtype=np.float64)
+    for i, name in enumerate(suffixed_names(calls, label_suffix)):
+        label = name.replace(f"{label_suffix}", "")
+        if label in call_duration_limits:
+            lo, hi = call_duration_limits[label]
+        elif "default" in call_duration_limits:
+            lo, hi = call_duration_limits["default"]
+        else:
+            lo, hi = 0, np.inf
+        out[i] = (0 if lo is None else lo, np.inf if hi is None else hi)
+    return out
+
+
+def labels_frame(runs: np.ndarray, calls, label_suffix: str | None, time_steps_per_output_step: int, filtered: bool):
+    """(predicted_labels, n_too_short, n_too_long) from the kernel's rows of one recording, int32 [n][4] = {start_row, stop_row, label, status} in
+    file order.  filtered=False: compute_labels' table.  filtered=True: what filter_predictions returns for that table (the kept rows under their
+    original index, with `duration` and `duration_ok`).  Column arithmetic only; nothing runs per interval."""
+    from orcai_amd.predict import compute_labels
+
+    if len(runs) == 0:  # the empty table's dtypes are those of empty lists: let the host route make it
+        frame = compute_labels([], [], [], time_steps_per_output_step, label_suffix)
+        if filtered:
+            frame["duration"] = frame["stop"] - frame["start"]
+            frame["duration_ok"] = []
+        return frame, 0, 0
+    runs = runs.astype(np.int64)
+    names = np.array(suffixed_names(calls, label_suffix), dtype=object)
+    frame = pd.DataFrame({"start": runs[:, 0] * time_steps_per_output_step, "stop": runs[:, 1] * time_steps_per_output_step, "label": names[runs[:, 2]]})
+    if not filtered:
+        return frame, 0, 0
+    status = runs[:, 3]
+    frame["duration"] = frame["stop"] - frame["start"]
+    frame["duration_ok"] = STATUS_NAMES[status]
+    return frame[status == 0], int((status == 1).sum()), int((status == 2).sum())
+
+
+_constants = {}  # (device, names, suffix, limits) -> (label_rank, limits) on the device
+
+
+def _device_constants(device, calls, label_suffix, call_duration_limits):
+    limits = None if call_duration_limits is None else resolve_limits(calls, label_suffix, call_duration_limits)
+    key = (str(device), tuple(calls), label_suffix, None if limits is None else limits.tobytes())
+    if key not in _constants:
+        if len(_constants) > 64:
+            _constants.clear()
+        rank = torch.from_numpy(label_rank(calls, label_suffix)).to(device)
+        _constants[key] = (rank, None if limits is None else torch.from_numpy(limits).to(device))
+    return _constants[key]
+
+
+class PendingLabels:
+    """The label intervals of one recording, or of every recording of a batch, on their way from the GPU to pinned host memory.  `results()` waits
+    for the copy (an event on the launch stream, not a device-wide synchronisation) and returns, per recording, (predicted_labels, n_too_short,
+    n_too_long) -- labels_frame's triple."""
+
+    def __init__(self, R, calls, label_suffix, tpo, filtered, host=None, device=None, header=0, event=None, keep=()):
+        self._R, self._calls, self._suffix, self._tpo, self.filtered = R, calls, label_suffix, tpo, filtered
+        self._host, self._device, self._header, self._event, self._keep = host, device, header, event, keep
+        self._results = None
+
+    def runs(self) -> list[np.ndarray]:
+        """Per recording the kernel's rows, int32 [n_r][4]."""
+        if self._host is None:  # nothing was launched: recordings without output rows
+            return [np.zeros((0, 4), dtype=np.int32) for _ in range(self._R)]
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+        host = self._host.numpy()
+        offsets = host[: 2 * (self._R + 1)].view(np.int64)
+        total = int(offsets[self._R])
+        rows = host[self._header :].reshape(-1, 4)
+        if total > len(rows):  # more runs than travelled with the offsets: one more copy, of exactly the rest
+            rest = self._device[self._header + 4 * len(rows) : self._header + 4 * total].cpu().numpy().reshape(-1, 4)
+            rows = np.concatenate([rows, rest])
+        self._keep = ()
+        return [rows[int(offsets[r]) : int(offsets[r + 1])] for r in range(self._R)]
+
+    def results(self) -> list[tuple[pd.DataFrame, int, int]]:
+        if self._results is None:
+            self._results = [labels_frame(rows, self._calls, self._suffix, self._tpo, self.filtered) for rows in self.runs()]
+            self._host = self._device = None
+        return self._results
+
+
+def extract_labels_device(agg_dev: torch.Tensor, cnt_dev: torch.Tensor, table_dev: torch.Tensor, R: int, calls, label_suffix: str | None,
+                          time_steps_per_output_step: int, delta_t: float, call_duration_limits=None, threshold: float = 0.5) -> PendingLabels:
+    """Queue orcai_extract_labels on the current stream for the averaged probabilities agg_dev f64 [S_total][L] / cnt_dev f64 [S_total] of the R
+    recordings of table_dev (int64 [R][4] on the device, orcai_overlap_average_ragged's table; one recording: [[0, n, S, 0]]), and the copy of its
+    result to pinned memory behind one event.  call_duration_limits (a dict or a JSON path) makes the kernel judge every interval as
+    filter_predictions does with delta_t seconds per frame.
+
+    What travels to the host: the R + 1 offsets and the first EAGER_RUNS runs, in ONE copy whose size does not depend on S_total or L.  The device
+    buffer holds the kernel's capacity bound (L * ceil(S_total / 2) + R runs, the size of agg itself), so nothing is ever dropped; when more than
+    EAGER_RUNS runs were found, results() fetches exactly the remaining ones in a second copy.  The bytes copied are 16 per run found."""
+    S_total, L = int(agg_dev.shape[0]), int(agg_dev.shape[1])
+    filtered = call_duration_limits is not None
+    if S_total < 1:
+        return PendingLabels(R, calls, label_suffix, time_steps_per_output_step, filtered)
+    lib = N.lib()
+    rank, limits = _device_constants(agg_dev.device, calls, label_suffix, call_duration_limits)
+    capacity = L * ((S_total + 1) // 2) + R
+    header = -(-2 * (R + 1) // 4) * 4  # int32 words in front of the runs: the int64 offsets, padded to 16 bytes
+    out = torch.empty(header + 4 * capacity, dtype=torch.int32, device=agg_dev.device)
+    ws_bytes = int(lib.orcai_extract_labels_workspace_bytes(L, R, S_total))
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=agg_dev.device)
+    N.check(lib.orcai_extract_labels(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, float(threshold), N.ptr(rank),
+                                     None if limits is None else N.ptr(limits), float(delta_t), int(time_steps_per_output_step),
+                                     out.data_ptr() + 4 * header, capacity, out.data_ptr(), workspace.data_ptr(), ws_bytes, N.stream_ptr()),
+            "orcai_extract_labels")
+    eager = header + 4 * min(capacity, EAGER_RUNS)
+    host = torch.empty(eager, dtype=torch.int32, pin_memory=True)
+    host.copy_(out[:eager], non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    return PendingLabels(R, calls, label_suffix, time_steps_per_output_step, filtered, host=host, device=out, header=header, event=event,
+                         keep=(agg_dev, cnt_dev, table_dev, workspace, rank, limits))

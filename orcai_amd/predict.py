@@ -1,7 +1,8 @@
 """Inference driver.  Same names, arguments, return types, output files and error behaviour as the
 reference's ``src/orcAI/predict.py``; the arithmetic (front end, snippet forward passes, overlap average)
 runs in HIP kernels.  Label extraction (thresholding an [S,7] matrix, run detection, sorting, TSV) is the
-reference's thin host logic restated with numpy/pandas.
+reference's thin host logic restated with numpy/pandas.  With ``device_labels=True`` the threshold, the run detection, the sort and the duration
+filter run in one more kernel call (orcai_extract_labels, device_labels.py) and the host wraps its integer columns in the same DataFrame.
 """
 
 from __future__ import annotations
@@ -88,10 +89,13 @@ class PendingAggregate:
     for the copy (an event on the launch stream, not a device-wide synchronisation) and returns the two host arrays; for a batch (`slices` =
     [(first output row, rows)] per recording) `results()` returns one (aggregated, count) pair per recording, views of the one host buffer."""
 
-    def __init__(self, agg_host: torch.Tensor, cnt_host: torch.Tensor, event, keep=(), slices=None):
+    def __init__(self, agg_host: torch.Tensor, cnt_host: torch.Tensor, event, keep=(), slices=None, labels=None):
         self._agg, self._cnt, self._event, self._keep, self._slices = agg_host, cnt_host, event, keep, slices
+        self.labels = labels  # device_labels.PendingLabels of the same recordings, or None; with labels the probabilities may stay on the device
 
     def result(self) -> tuple[np.ndarray, np.ndarray]:
+        if self._agg is None:  # device labels, and nobody asked for the probabilities: they were not copied
+            return None, None
         if self._event is not None:
             self._event.synchronize()
             self._event, self._keep = None, ()
@@ -99,14 +103,31 @@ class PendingAggregate:
 
     def results(self) -> list[tuple[np.ndarray, np.ndarray]]:
         agg, cnt = self.result()
+        if agg is None:
+            return [(None, None)] * (len(self._slices) if self._slices is not None else 1)
         slices = self._slices if self._slices is not None else [(0, len(cnt))]
         return [(agg[row : row + rows], cnt[row : row + rows]) for row, rows in slices]
 
 
-def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snippet_length: int, n_filters: int, wait: bool = True):
+def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True) -> dict:
+    """What the launch half needs to queue orcai_extract_labels behind the overlap average (device_labels=...): the label names, the suffix, the
+    duration limits the kernel is to judge by (None: no filter) and whether the averaged probabilities are still wanted on the host."""
+    return {"calls": orcai_parameter["calls"], "label_suffix": label_suffix, "call_duration_limits": call_duration_limits, "probabilities": probabilities}
+
+
+def _queue_labels(spec: dict, agg: torch.Tensor, cnt: torch.Tensor, table: torch.Tensor, R: int, n_filters: int, delta_t: float):
+    from orcai_amd.device_labels import extract_labels_device
+
+    return extract_labels_device(agg, cnt, table, R, spec["calls"], spec["label_suffix"], 2**n_filters, delta_t, call_duration_limits=spec["call_duration_limits"])
+
+
+def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snippet_length: int, n_filters: int, wait: bool = True,
+                                 device_labels: dict | None = None, delta_t: float = 0.0):
     """Overlap-average of per-snippet predictions on the GPU (predict.py:276-293).
     predictions: f32 cuda [n, P, L].  Returns host (f64 [n_frames // 2**n_filters, L], f64 [...]); with wait=False a PendingAggregate
-    whose copy to (pinned) host memory is still in flight, so that the caller can queue the next recording's GPU work first."""
+    whose copy to (pinned) host memory is still in flight, so that the caller can queue the next recording's GPU work first.
+    device_labels (a label_spec, with wait=False): orcai_extract_labels is queued behind the average and the PendingAggregate carries its
+    PendingLabels; the probabilities are copied only if the spec wants them."""
     lib = N.lib()
     tpo = 2**n_filters
     shift = snippet_length // 2
@@ -121,19 +142,27 @@ def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snipp
                 "orcai_overlap_average")
     if wait:
         return agg.cpu().numpy(), cnt.cpu().numpy()
+    labels = None
+    if device_labels is not None:
+        table = torch.tensor([[0, n, S, 0]], dtype=torch.int64).pin_memory().to(predictions.device, non_blocking=True)
+        labels = _queue_labels(device_labels, agg, cnt, table, 1, n_filters, delta_t)
+        if not device_labels["probabilities"]:
+            return PendingAggregate(None, None, None, labels=labels)
     agg_host = torch.empty((S, L), dtype=torch.float64, pin_memory=True)
     cnt_host = torch.empty((S,), dtype=torch.float64, pin_memory=True)
     agg_host.copy_(agg, non_blocking=True)
     cnt_host.copy_(cnt, non_blocking=True)
     event = torch.cuda.Event()
     event.record()
-    return PendingAggregate(agg_host, cnt_host, event, keep=(agg, cnt, predictions))
+    return PendingAggregate(agg_host, cnt_host, event, keep=(agg, cnt, predictions), labels=labels)
 
 
-def aggregate_batch_device(predictions: torch.Tensor, layout, snippet_length: int, n_filters: int) -> PendingAggregate:
+def aggregate_batch_device(predictions: torch.Tensor, layout, snippet_length: int, n_filters: int, device_labels: dict | None = None,
+                           delta_t: float = 0.0) -> PendingAggregate:
     """aggregate_predictions_device for every recording of a batch (batch.Batch) in one launch of orcai_overlap_average_ragged; the averaged
     probabilities and counts of the whole batch go to the host in ONE pinned copy behind one event.  predictions: f32 cuda [layout.n_total, P, L]
-    (model.predict_batch).  Per recording the same bits as aggregate_predictions_device on its own snippets."""
+    (model.predict_batch).  Per recording the same bits as aggregate_predictions_device on its own snippets.  device_labels: as there, one
+    orcai_extract_labels over the whole batch."""
     tpo = 2**n_filters
     P = snippet_length // tpo
     step = (snippet_length // 2) // tpo
@@ -144,21 +173,29 @@ def aggregate_batch_device(predictions: torch.Tensor, layout, snippet_length: in
     both = torch.empty(S * (L + 1), dtype=torch.float64, device=pred.device)  # agg [S][L], then cnt [S]
     N.check(N.lib().orcai_overlap_average_ragged(N.ptr(pred), P, L, step, N.ptr(table), len(layout.table), S, both.data_ptr(), both[S * L :].data_ptr(),
                                                  N.stream_ptr()), "orcai_overlap_average_ragged")
+    slices = [(row, rows) for _, _, rows, row in layout.table]
+    labels = None
+    if device_labels is not None:
+        labels = _queue_labels(device_labels, both[: S * L].view(S, L), both[S * L :], table, len(layout.table), n_filters, delta_t)
+        if not device_labels["probabilities"]:
+            return PendingAggregate(None, None, None, slices=slices, labels=labels)
     host = torch.empty(S * (L + 1), dtype=torch.float64, pin_memory=True)
     host.copy_(both, non_blocking=True)
     event = torch.cuda.Event()
     event.record()
-    return PendingAggregate(host[: S * L].view(S, L), host[S * L :], event, keep=(both, table, pred), slices=[(row, rows) for _, _, rows, row in layout.table])
+    return PendingAggregate(host[: S * L].view(S, L), host[S * L :], event, keep=(both, table, pred), slices=slices, labels=labels)
 
 
 def compute_aggregated_predictions(recording_path: Path, spectrogram, model, orcai_parameter: dict, shape: dict,
-                                   msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, wait: bool = True):
+                                   msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, wait: bool = True,
+                                   device_labels: dict | None = None, delta_t: float = 0.0):
     """Slice into 50 %-overlapping snippets, predict, overlap-average (predict.py:235-295).
 
     ``model`` may be any object with ``.predict(ndarray[n,L,F,1], verbose=int) -> ndarray[n,P,labels]`` (the
     reference's duck-typed boundary).  A native ResNetLSTM is run without materialising the snippets; a
     ``spectrogram`` that already lives on the GPU (torch tensor) is used in place.  wait=False returns a PendingAggregate (the
-    device-to-host copy of the averaged probabilities still in flight) instead of the two host arrays.
+    device-to-host copy of the averaged probabilities still in flight) instead of the two host arrays; device_labels / delta_t: see
+    aggregate_predictions_device.
     """
     snippet_length = shape["input_shape"][0]
     shift = snippet_length // 2
@@ -187,7 +224,8 @@ def compute_aggregated_predictions(recording_path: Path, spectrogram, model, orc
         progressbar.refresh()
     if predictions.shape[0] == 0:
         predictions = predictions.reshape(0, snippet_length // 2**n_filters, shape["num_labels"])
-    return aggregate_predictions_device(predictions, n_frames, snippet_length, n_filters, wait=wait)
+    return aggregate_predictions_device(predictions, n_frames, snippet_length, n_filters, wait=wait, device_labels=None if wait else device_labels,
+                                        delta_t=delta_t)
 
 
 def compute_binary_predictions(aggregated_predictions: np.ndarray, overlap_count: np.ndarray, calls: list[str], threshold: float = 0.5):
@@ -225,10 +263,11 @@ def _convert_times_to_seconds(predicted_labels: pd.DataFrame, delta_t: float) ->
 
 
 def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, msgr: Messenger = Messenger(verbosity=0),
-                       progressbar: tqdm = None) -> dict:
+                       progressbar: tqdm = None, device_labels: dict | None = None) -> dict:
     """First half of predict_wav: spectrogram, snippets through the model and the overlap average are QUEUED on the GPU, the averaged
     probabilities are on their way to pinned host memory.  The returned state goes to predict_wav_finish; in table mode the next
-    recording is launched in between, so the host half of one recording runs beside the GPU half of the next."""
+    recording is launched in between, so the host half of one recording runs beside the GPU half of the next.  device_labels (a label_spec; ignored
+    for a model without the native path): the label extraction is queued on the GPU as well."""
     recording_path = Path(recording_path)
     if progressbar:
         progressbar.set_description(f"{recording_path.stem}: Generating spectrogram")
@@ -246,7 +285,7 @@ def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_pa
         progressbar.set_description(f"{recording_path.stem} - Predicting annotations")
         progressbar.refresh()
     pending = compute_aggregated_predictions(recording_path=recording_path, spectrogram=spectrogram, model=model, orcai_parameter=orcai_parameter, shape=shape,
-                                             msgr=msgr, progressbar=progressbar, wait=not native)
+                                             msgr=msgr, progressbar=progressbar, wait=not native, device_labels=device_labels, delta_t=delta_t)
     return {"pending": pending, "delta_t": delta_t, "orcai_parameter": orcai_parameter}
 
 
@@ -254,6 +293,12 @@ def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = M
     """Second half of predict_wav (host): threshold, runs of ones, label table (predict.py:298-340)."""
     pending, orcai_parameter = state["pending"], state["orcai_parameter"]
     aggregated_predictions, overlap_count = pending.result() if isinstance(pending, PendingAggregate) else pending
+    device_result = state.get("device_labels_result")
+    if device_result is None and isinstance(pending, PendingAggregate) and pending.labels is not None:
+        device_result = pending.labels.results()[0]
+    if device_result is not None:
+        return _finish_device_labels(device_result, pending.labels if isinstance(pending, PendingAggregate) else state["device_labels"],
+                                     aggregated_predictions, state["delta_t"], msgr)
     row_starts, row_stops, label_names = compute_binary_predictions(aggregated_predictions=aggregated_predictions, overlap_count=overlap_count,
                                                                     calls=orcai_parameter["calls"], threshold=0.5)
     msgr.info("converting binary predictions into start and stop frames")
@@ -264,10 +309,24 @@ def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = M
     return predicted_labels, aggregated_predictions, state["delta_t"]
 
 
+def _finish_device_labels(device_result: tuple, labels, aggregated_predictions, delta_t: float, msgr: Messenger):
+    """predict_wav_finish for a recording whose labels came from orcai_extract_labels.  With duration limits the table is already the filtered one
+    and carries the kernel's counts in .attrs["duration_filter"], which _save_recording reports in place of calling filter_predictions."""
+    predicted_labels, n_short, n_long = device_result
+    found = len(predicted_labels) + n_short + n_long
+    if labels.filtered:
+        predicted_labels.attrs["duration_filter"] = {"found": found, "too_short": n_short, "too_long": n_long}
+    msgr.info(f"found {found} acoustic signals")
+    msgr.success("Prediction finished.")
+    return predicted_labels, aggregated_predictions, delta_t
+
+
 def predict_wav(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*",
-                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None):
-    """(predicted_labels DataFrame, aggregated_predictions ndarray, delta_t) for one wav file (predict.py:367-471)."""
-    state = predict_wav_launch(recording_path, channel, model, orcai_parameter, shape, msgr=msgr, progressbar=progressbar)
+                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False):
+    """(predicted_labels DataFrame, aggregated_predictions ndarray, delta_t) for one wav file (predict.py:367-471).  device_labels=True: the label
+    table comes from orcai_extract_labels (the same table)."""
+    state = predict_wav_launch(recording_path, channel, model, orcai_parameter, shape, msgr=msgr, progressbar=progressbar,
+                               device_labels=label_spec(orcai_parameter, label_suffix) if device_labels else None)
     return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
 
 
@@ -275,13 +334,15 @@ def _too_short(n_frames: int, snippet_length: int) -> ValueError:
     return ValueError(f"recording too short: {n_frames} spectrogram frames, one snippet needs {snippet_length}")
 
 
-def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_frames: int, msgr: Messenger = Messenger(verbosity=0)):
+def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_frames: int, msgr: Messenger = Messenger(verbosity=0),
+                    device_labels: dict | None = None):
     """The GPU half of several recordings per detector pass (batch.py), as a generator of batch states.  sources: an iterable of (key, thunk),
     thunk() -> the recording's f32 cuda samples at the model's sampling rate (spectrogram.load_wav), called one by one as the batches fill.  A
     batch closes before the recording that would take its buffer past max_frames spectrogram frames; a state is yielded once the work of its batch is
     QUEUED: the front end of every recording into its rows of the batch buffer, one forward pass, one orcai_overlap_average_ragged, one copy to
     pinned memory.  state["members"] = [(key, delta_t)] in buffer order, state["failed"] = [(key, exception)]: the recordings met since the last
-    state that raised (thunk errors, a spectrogram of the wrong width, too short for one snippet) and are in no batch."""
+    state that raised (thunk errors, a spectrogram of the wrong width, too short for one snippet) and are in no batch.
+    device_labels (a label_spec): one orcai_extract_labels per batch behind the average."""
     from orcai_amd import frontend as fe
     from orcai_amd.batch import Grouper, layout as batch_layout
 
@@ -300,7 +361,7 @@ def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_fram
             for (_, pcm, T, _), o in zip(members, lay.offsets):
                 front.make_spectrogram(pcm, sp, out=buf[o : o + T])
             predictions, _ = model.predict_batch(buf, lay)
-            state["pending"] = aggregate_batch_device(predictions, lay, H, n_filters)
+            state["pending"] = aggregate_batch_device(predictions, lay, H, n_filters, device_labels=device_labels, delta_t=members[0][3])
             state["junk_snippets"], state["snippets"] = lay.junk, lay.n_total
             msgr.info(f"batch of {len(members)} recordings: {lay.n_total} snippets in one pass ({lay.junk} of them between recordings)")
         members.clear()
@@ -333,8 +394,11 @@ def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messen
     """The host half of one batch state: [(key, predict_wav's triple or the exception the recording raised)], the failed ones first."""
     out = list(state["failed"])
     if state["pending"] is not None:
-        for (key, delta_t), pair in zip(state["members"], state["pending"].results()):
-            out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"]}, label_suffix=label_suffix, msgr=msgr)))
+        labels = state["pending"].labels
+        label_results = labels.results() if labels is not None else [None] * len(state["members"])
+        for (key, delta_t), pair, device_result in zip(state["members"], state["pending"].results(), label_results):
+            out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"],
+                                                 "device_labels_result": device_result, "device_labels": labels}, label_suffix=label_suffix, msgr=msgr)))
     return out
 
 
@@ -349,14 +413,16 @@ def _run_batches(states, finish) -> None:
         finish(in_flight)
 
 
-def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_frames: int | None = None, msgr: Messenger = Messenger(verbosity=0)):
+def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_frames: int | None = None, msgr: Messenger = Messenger(verbosity=0),
+                        device_labels: dict | None = None):
     """First half of predict_wavs: a generator of batch states (_launch_batches) whose keys are the indices into `items`."""
     from orcai_amd.batch import DEFAULT_MAX_FRAMES
     from orcai_amd.spectrogram import load_wav
 
     sr = orcai_parameter["spectrogram"]["sampling_rate"]
     sources = ((i, lambda path=path, channel=channel: load_wav(Path(path), sr, channel, msgr)) for i, (path, channel) in enumerate(items))
-    return _launch_batches(sources, model, orcai_parameter, shape, DEFAULT_MAX_FRAMES if max_frames is None else max_frames, msgr=msgr)
+    return _launch_batches(sources, model, orcai_parameter, shape, DEFAULT_MAX_FRAMES if max_frames is None else max_frames, msgr=msgr,
+                           device_labels=device_labels)
 
 
 def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> list:
@@ -365,18 +431,19 @@ def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = 
 
 
 def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*", max_frames: int | None = None,
-                 msgr: Messenger = Messenger(verbosity=0)) -> list:
+                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False) -> list:
     """predict_wav for every (path, channel) of `items`, several recordings per detector pass: batches of at most max_frames spectrogram frames
     (batch.DEFAULT_MAX_FRAMES: an hour's worth) go through ONE forward pass and ONE overlap average, the host half of a batch runs beside the GPU
     half of the next.  Returns, per item, what predict_wav returns for it -- the same label table, the same f64 probabilities, the same delta_t --
     or the exception it raised (a missing file, a recording shorter than one snippet); the other items are unaffected.
-    A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item."""
+    A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item.
+    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables)."""
     items = list(items)
     results = [None] * len(items)
     if not hasattr(model, "predict_batch"):
         for i, (path, channel) in enumerate(items):
             try:
-                results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr)
+                results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr, device_labels=device_labels)
             except Exception as e:
                 results[i] = e
         return results
@@ -385,7 +452,8 @@ def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix:
         for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr):
             results[i] = result
 
-    _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr), finish)
+    _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr,
+                                     device_labels=label_spec(orcai_parameter, label_suffix) if device_labels else None), finish)
     return results
 
 
@@ -425,12 +493,12 @@ def _checked_output_path(recording_path: Path, channel: int, orcai_parameter: di
 
 
 def _launch_recording(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
-                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None) -> dict:
+                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None) -> dict:
     """predict.py:534-575: output path and overwrite check, then the GPU half of the recording (queued, not waited for)."""
     recording_path = Path(recording_path)
     output_path = _checked_output_path(recording_path, channel, orcai_parameter, output_path, overwrite, msgr)
     state = predict_wav_launch(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape, msgr=msgr,
-                               progressbar=progressbar)
+                               progressbar=progressbar, device_labels=device_labels)
     state["output_path"] = output_path
     return state
 
@@ -439,7 +507,14 @@ def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_prob
                     label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> None:
     """predict.py:576-632 after the labels: optional duration filter, files."""
     predicted_labels, aggregated_predictions, delta_t = result
-    if call_duration_limits is not None:
+    counts = predicted_labels.attrs.get("duration_filter")
+    if counts is not None:  # device labels: the kernel judged every interval, the table is the filtered one
+        msgr.part("Filtering predictions")
+        msgr.part("Filtering calls based on duration")
+        if counts["found"] > 0:
+            msgr.info(f"Discarding {counts['too_long'] + counts['too_short']} calls based on duration (too short: {counts['too_short']}, too long: {counts['too_long']})")
+            msgr.success("Filtering predictions finished.")
+    elif call_duration_limits is not None:
         predicted_labels = filter_predictions(predicted_labels, delta_t=delta_t, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
     save_predictions(predicted_labels=predicted_labels, output_path=output_path, delta_t=delta_t, msgr=msgr)
     if save_probabilities:
@@ -456,16 +531,16 @@ def _finish_recording(state: dict, save_probabilities: bool = False, call_durati
 
 def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
                       overwrite: bool = False, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
-                      label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None) -> None:
+                      label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None) -> None:
     """predict.py:534-632."""
     state = _launch_recording(recording_path, channel, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite, msgr=msgr,
-                              progressbar=progressbar)
+                              progressbar=progressbar, device_labels=device_labels)
     _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
 
 
 def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default", overwrite: bool = False,
                           save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                          msgr: Messenger = Messenger(verbosity=0)) -> None:
+                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None) -> None:
     """predict(channel="all"): one read and one upload of the file, every channel decoded by orcai_pcm_decode_planar, the channels as ONE batch through
     the detector.  One output file per channel, under the name -- and with the bytes -- predict(channel=c) gives it."""
     from orcai_amd.spectrogram import load_wav_all
@@ -486,13 +561,14 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
                             label_suffix=label_suffix, msgr=msgr)
 
     total = sum(int(pcm.numel()) for pcm in pcms) // orcai_parameter["spectrogram"]["n_overlap"] + (shape["input_shape"][0] + 1) * len(pcms)
-    _run_batches(_launch_batches(sources, model, orcai_parameter, shape, max_frames=total, msgr=msgr), finish)  # max_frames: all channels in one batch
+    _run_batches(_launch_batches(sources, model, orcai_parameter, shape, max_frames=total, msgr=msgr, device_labels=device_labels), finish)  # max_frames: all channels in one batch
     if errors:
         raise errors[0]  # every channel has the same length: the single-channel call's error
 
 
 def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter: dict, shape: dict, batch_frames: int, overwrite: bool,
-                           save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm) -> None:
+                           save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm,
+                           device_labels: dict | None = None) -> None:
     """Table mode with batch_frames > 0: the rows of the table in order, grouped into detector passes of at most batch_frames spectrogram frames.
     Per recording the output path, the overwrite check, the files and the error line are those of the one-by-one loop; one batch deep, so the host
     half of a batch (labels, files) runs beside the GPU half of the next."""
@@ -526,31 +602,38 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
             except Exception as e:
                 error(i, e)
 
-    _run_batches(_launch_batches(sources(), model, orcai_parameter, shape, batch_frames, msgr=quiet), finish)
+    _run_batches(_launch_batches(sources(), model, orcai_parameter, shape, batch_frames, msgr=quiet, device_labels=device_labels), finish)
 
 
 def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str | Path = DEFAULT_MODEL_DIR, output_path: str | Path = "default",
             overwrite: bool = False, save_probabilities: bool = False, base_dir_recording: str | Path | None = None,
             call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None,
-            batch_frames: int = 0) -> None:
+            batch_frames: int = 0, device_labels: bool = False) -> None:
     """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757).
     channel="all" (a wav file): every channel of the file from one read of its bytes, one output file per channel.
     batch_frames > 0 (a table): consecutive recordings go through the detector in batches of at most batch_frames spectrogram frames
     (predict_wavs' path: many short clips fill the GPU that one of them cannot); 0, the default, is one detector pass per recording.  The files
-    are the same bytes either way."""
+    are the same bytes either way.
+    device_labels=True: threshold, run detection, sort and duration filter of every route run on the GPU (orcai_extract_labels) and only the
+    intervals found come back; without save_probabilities the averaged probabilities never leave the device.  The files are the same bytes.
+    Ignored for a model without the native path."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Predicting calls")
     model_dir = Path(model_dir)
     recording_path = Path(recording_path)
     msgr.part(f"Loading model: {model_dir.stem}")
     model, orcai_parameter, shape = load_orcai_model(model_dir)
+    spec = None
+    if device_labels and hasattr(model, "predict_spectrogram"):
+        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities)
     if recording_path.suffix == ".wav" and channel == "all" and hasattr(model, "predict_batch"):
         return _predict_all_channels(recording_path, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite,
-                                     save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
+                                     save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
+                                     device_labels=spec)
     if recording_path.suffix == ".wav":
         return _predict_and_save(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape,
                                  output_path=output_path, overwrite=overwrite, save_probabilities=save_probabilities,
-                                 call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None)
+                                 call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None, device_labels=spec)
     elif recording_path.suffix == ".csv":
         recording_table = pd.read_csv(recording_path)
     else:
@@ -579,7 +662,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     quiet = Messenger(verbosity=0)
     if batch_frames > 0 and hasattr(model, "predict_batch"):
         _predict_table_batched(recording_table, model, orcai_parameter, shape, batch_frames, overwrite=overwrite, save_probabilities=save_probabilities,
-                               call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar)
+                               call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar, device_labels=spec)
         wavio.set_prefetcher(None)
         msgr.success("Predictions finished.")
         return
@@ -598,7 +681,8 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
         try:
             launched = (i, _launch_recording(recording_path=Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"]),
                                              channel=recording_table.loc[i, "channel"], model=model, orcai_parameter=orcai_parameter, shape=shape,
-                                             output_path=recording_table.loc[i, "output_path"], overwrite=overwrite, msgr=quiet, progressbar=progressbar))
+                                             output_path=recording_table.loc[i, "output_path"], overwrite=overwrite, msgr=quiet, progressbar=progressbar,
+                                             device_labels=spec))
         except Exception as e:  # predict.py:752-755
             msgr.error(f"Error predicting {recording_table.loc[i, 'recording']}: {e.args[0] if e.args else e}")
         if in_flight is not None:
