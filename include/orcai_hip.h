@@ -335,6 +335,24 @@ int orcai_extract_labels(const double* agg, const double* cnt, int L, const int6
                          void* workspace, size_t workspace_bytes, void* stream);
 size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total);
 
+/* test.py:37-225: the integer counts behind the three tables of `orcai test` (compute_confusion_table, compute_misclassification_tables) for one
+ * batch; the host forms the tables' float64 values from them (orcai_amd/device_tables.py).
+ *   p, y       f32[M][L], M = snippets * time steps: probabilities, and labels in {0, 1, mask_value = -1}.  1 <= L <= 64.
+ *   The call ADDS to conf and mis: the caller zeroes both once per dataset (orcai_zero_fill) and every batch accumulates into them.
+ *   conf       int64[L][4] = {TN, FP, FN, TP} per label over the elements with y != mask_value; predicted = p >= 0.5f (NaN: not predicted), the truth
+ *              tests are y == 0 and y == 1.
+ *   mis        int64[2][L+1][L+1][L].  Direction d = 0 (true_pred): matrix 1 = the labels truncated to int, matrix 2 = the prediction bits; d = 1
+ *              (pred_true): the roles swapped.  Per row and direction, with ones1 / ones2 the columns equal to 1 and n1 / n2 their counts:
+ *              n1 > 1: the row is skipped.  n1 == 1: src = that column a, and the row is skipped if matrix2[row][a] == -1.  n1 == 0: src = L (NOLABEL).
+ *              n2 > 0: mis[d][src][c][n2 - 1] += 1 for every c of ones2; else mis[d][src][L][0] += 1.
+ *              A table cell is sum over n of mis[d][src][c][n - 1] / n: the n2 axis keeps the 1 / n2 shares of the host route as integers.
+ * One launch on `stream` (test_tables.hip), one lane per row; no workspace, no allocation, no synchronisation.  Integer adds only, 64-bit global
+ * accumulators: the result does not depend on the order of execution and two runs from equal buffers leave the same bytes.  Counts are reduced per
+ * workgroup first -- ballots for conf and for the NOLABEL -> NOLABEL bin of both directions, an LDS histogram of the other bins for L <= 16 -- and
+ * only non-zero workgroup totals reach global memory; for L > 16 the rows outside that one bin add straight to global memory.
+ * ORCAI_E_BADARG: a null p / y / conf / mis, M < 1, L outside 1..64.  ORCAI_E_UNSUPPORTED (nothing launched): 2^31 or more workgroups. */
+int orcai_test_counts(const float* p, const float* y, int64_t M, int L, float mask_value, int64_t* conf, int64_t* mis, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training (train.py:155-219: Adam(lr) + MaskedBinaryCrossentropy + MaskedBinaryAccuracy; architectures.py:210-286)
  * "Row tensors" are f32[M][cols] row-major, M = snippets * time steps.

@@ -173,6 +173,8 @@ def cli_hpsearch(**kwargs):
 @click.option("--test_unfiltered", "-tu", is_flag=True, help="If set, the model is also tested on the unfiltered test dataset.")
 @click.option("--output_dir", "-o", type=DirWcreate, default=None, show_default="None", help="Path to the output directory. None to save in the same directory as the model.")
 @click.option("--data_compression", "-dc", type=click.Choice(["GZIP", "None"], case_sensitive=False), default="GZIP", show_default=True, help="Data compression of saved datasets")
+@click.option("--device-tables", "device_tables", is_flag=True,
+              help="One pass per dataset: metrics and the counts behind the tables are taken on the GPU; only the counts return to the host. Same files.")
 @click.option("--verbosity", "-v", type=click.IntRange(0, 3), default=2, show_default=True, help="0: Errors only, 1: Warnings, 2: Info, 3: Debug")
 def cli_test(**kwargs):
     """cli.py:680-729."""

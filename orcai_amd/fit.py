@@ -136,17 +136,32 @@ class FitLoop:
 
     def evaluate(self, dataset) -> dict:
         """Inference-mode pass (moving BN statistics, no dropout): mean masked BCE + L2 and masked binary accuracy."""
-        self.trainer.sync_model()
-        m, lib = self.model, N.lib()
-        H, W = m.input_hw
-        tot = torch.zeros(4, dtype=torch.float64, device=self.trainer.dev)
-        acc = torch.zeros(3, dtype=torch.float64, device=self.trainer.dev)
+        tot, acc = self.evaluate_begin()
         for xb, yb in dataset:
-            B = xb.shape[0]
-            probs = torch.empty((B, m.out_steps, m.num_labels), dtype=torch.float32, device=xb.device)
-            m.forward_device(xb.contiguous().view(-1), H * W, B, probs, chunk=B)
-            N.check(lib.orcai_masked_bce(probs.data_ptr(), yb.contiguous().data_ptr(), probs.numel(), MASK_VALUE, acc.data_ptr(), None, N.stream_ptr()), "masked_bce")
-            tot[:3] += acc
+            self.evaluate_batch(xb, yb, tot, acc)
+        return self.evaluate_finish(tot)
+
+    def evaluate_begin(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """The accumulators of one evaluation pass on the device: tot f64[4] = {sum of BCE, unmasked count, correct count, unused}, acc f64[3] = one
+        batch's share of the first three."""
+        self.trainer.sync_model()
+        return torch.zeros(4, dtype=torch.float64, device=self.trainer.dev), torch.zeros(3, dtype=torch.float64, device=self.trainer.dev)
+
+    def evaluate_batch(self, xb, yb, tot, acc) -> torch.Tensor:
+        """Queues the forward pass of one batch and its masked BCE / accuracy sums into tot; returns the probabilities f32 [B][T][L] (on the device;
+        nothing is copied back or synchronised)."""
+        m = self.model
+        H, W = m.input_hw
+        B = xb.shape[0]
+        probs = torch.empty((B, m.out_steps, m.num_labels), dtype=torch.float32, device=xb.device)
+        m.forward_device(xb.contiguous().view(-1), H * W, B, probs, chunk=B)
+        N.check(N.lib().orcai_masked_bce(probs.data_ptr(), yb.contiguous().data_ptr(), probs.numel(), MASK_VALUE, acc.data_ptr(), None, N.stream_ptr()), "masked_bce")
+        tot[:3] += acc
+        return probs
+
+    def evaluate_finish(self, tot) -> dict:
+        """The pass's one copy to the host, the L2 term, the sum over ranks: Keras' logs."""
+        m = self.model
         l2 = sum(float((m.weights[k].astype(np.float64) ** 2).sum()) for k in m.weights if k.endswith("/kernel") and (k.startswith("lstm") or k.startswith("dense1")))
         a = tot.cpu().numpy()
         a[3] = L2_LAMBDA * l2

@@ -3,7 +3,9 @@
 ``_save_test_results`` (:290-315), ``test_model`` (:318-420).
 
 The tables are host-side numpy / pandas (pinned bit-for-bit by golden vectors from the reference's own functions,
-``tests/golden/test_tables.*``); the forward passes behind them run on the GPU through the model's HIP kernels.
+``tests/golden/test_tables.*``); the forward passes behind them run on the GPU through the model's HIP kernels.  With ``device_tables=True``
+the metrics and the tables come from ONE pass: the integer counts behind the tables are taken on the GPU (orcai_test_counts,
+``orcai_amd/device_tables.py``) and only they return to the host.
 """
 
 from __future__ import annotations
@@ -52,6 +54,11 @@ def _compute_misclassification_table(label_matrix_1: np.ndarray, label_matrix_2:
     np.add.at(m, (src[r_idx], c_idx), 1.0 / n2[r_idx])
     none = use & (n2 == 0)
     np.add.at(m, (src[none], np.full(int(none.sum()), num_labels)), 1.0)
+    return _misclassification_frame(m, suffix_1, suffix_2, label_names)
+
+
+def _misclassification_frame(m: np.ndarray, suffix_1: str, suffix_2: str, label_names: list[str]) -> pd.DataFrame:
+    """test.py:96-110: the accumulated (L+1) x (L+1) matrix -> row fractions rounded to 3 decimals, names, ``fraction_time``."""
     row_sum = np.sum(m, axis=1, keepdims=True)
     with np.errstate(all="ignore"):
         m = np.around(m / row_sum, 3)
@@ -87,20 +94,62 @@ def compute_confusion_table(y_true_batch: np.ndarray, y_pred_batch: np.ndarray, 
         fp = int(np.sum((t == 0) & (p == 1)))
         fn = int(np.sum((t == 1) & (p == 0)))
         tp = int(np.sum((t == 1) & (p == 1)))
-        tot = tn + fp + fn + tp
-        with np.errstate(all="ignore"):
-            table[name] = {
-                "TP": float(np.float64(tp) / tot), "FN": float(np.float64(fn) / tot), "FP": float(np.float64(fp) / tot), "TN": float(np.float64(tn) / tot),
-                "PR": float(tp / (tp + fp)) if tp + fp > 0 else np.nan,
-                "RE": float(tp / (tp + fn)) if tp + fn > 0 else np.nan,
-                "F1": float(2 * tp / (2 * tp + fp + fn)) if tp + fp + fn > 0 else np.nan,
-                "Total": int(tot),
-            }
+        table[name] = _confusion_entry(tn, fp, fn, tp)
     return pd.DataFrame.from_dict(table, orient="index").sort_values(by="Total", ascending=False)
 
 
-def _test_model_on_dataset(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger) -> dict:
-    """test.py:228-287."""
+def _confusion_entry(tn: int, fp: int, fn: int, tp: int) -> dict:
+    """test.py:196-223: one label's row of the confusion table from its four counts (Python ints)."""
+    tot = tn + fp + fn + tp
+    with np.errstate(all="ignore"):
+        return {
+            "TP": float(np.float64(tp) / tot), "FN": float(np.float64(fn) / tot), "FP": float(np.float64(fp) / tot), "TN": float(np.float64(tn) / tot),
+            "PR": float(tp / (tp + fp)) if tp + fp > 0 else np.nan,
+            "RE": float(tp / (tp + fn)) if tp + fn > 0 else np.nan,
+            "F1": float(2 * tp / (2 * tp + fp + fn)) if tp + fp + fn > 0 else np.nan,
+            "Total": int(tot),
+        }
+
+
+def _test_model_on_dataset_device(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger) -> dict:
+    """``device_tables=True``: ONE pass over the dataset.  Per batch the forward pass, the masked BCE into evaluate's accumulators and
+    orcai_test_counts are queued on the stream; nothing is copied back or synchronised inside the loop.  Metrics and tables describe the same batches."""
+    import torch
+
+    from orcai_amd.device_tables import TestCounts, confusion_table_from_counts, misclassification_tables_from_counts
+
+    msgr.part(f"Testing model on {dataset_name}")
+    msgr.info(f"Evaluating model on {dataset_name} (metrics and tables in one pass)")
+    loop = model._need_loop()
+    tot, acc = loop.evaluate_begin()
+    counts = None
+    for spectrogram_batch, label_batch in dataset:
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (spectrogram_batch, label_batch)):
+            raise ValueError("device_tables=True (orcai test --device-tables) needs batches of cuda tensors, as the package's dataset classes yield them")
+        if counts is None:
+            counts = TestCounts(len(label_names), spectrogram_batch.device)
+        label_batch = label_batch.contiguous()
+        counts.add(loop.evaluate_batch(spectrogram_batch, label_batch, tot, acc), label_batch)
+    if counts is None:
+        raise ValueError(f"device_tables=True: {dataset_name} yielded no batch")
+    conf, mis = counts.result()  # the one synchronising copy of the pass
+    data_metrics = loop.evaluate_finish(tot)
+    msgr.info(data_metrics)
+    msgr.part(f"Calculating confusion table for {dataset_name}")
+    confusion_table = confusion_table_from_counts(conf, label_names)
+    msgr.info(confusion_table)
+    tables = misclassification_tables_from_counts(mis, "true", "pred", label_names)
+    msgr.part("Misclassification tables on dataset:")
+    for key, table in tables.items():
+        msgr.info("\n" + key, indent=1)
+        msgr.info(table, indent=-1)
+    return {"dataset": dataset_name, "data_metrics": data_metrics, "confusion_table": confusion_table, "misclassification_tables": tables}
+
+
+def _test_model_on_dataset(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger, device_tables: bool = False) -> dict:
+    """test.py:228-287.  device_tables=True: the same result from one pass with the tables' counts taken on the GPU."""
+    if device_tables:
+        return _test_model_on_dataset_device(model, dataset, label_names, dataset_name, msgr)
     msgr.part(f"Testing model on {dataset_name}")
     msgr.info(f"Evaluating model on {dataset_name}")
     data_metrics = model.evaluate(dataset, return_dict=True, verbose=0 if msgr.verbosity < 3 else 1)
@@ -149,8 +198,8 @@ def _save_test_results(results: dict, save_results_dir: Path, msgr: Messenger) -
 
 
 def test_model(model_dir: Path | str, data_dir: Path | str, test_unfiltered: bool = True, output_dir: None | Path | str = None,
-               data_compression: str | None = "GZIP", verbosity: int = 2, msgr: Messenger | None = None) -> None:
-    """test.py:318-420."""
+               data_compression: str | None = "GZIP", verbosity: int = 2, msgr: Messenger | None = None, device_tables: bool = False) -> None:
+    """test.py:318-420.  device_tables=True (``orcai test --device-tables``): one pass per dataset, the tables' counts taken on the GPU; same files."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Testing model")
     data_dir, model_dir = Path(data_dir), Path(model_dir)
@@ -168,7 +217,7 @@ def test_model(model_dir: Path | str, data_dir: Path | str, test_unfiltered: boo
     for folder, name, seed_id in todo:
         dataset = load_dataset(data_dir.joinpath(folder), model_parameter["batch_size"], compression=data_compression,
                                seed=[seed_id, seed] if seed is not None else None)
-        results = _test_model_on_dataset(model, dataset, trained_calls, name, msgr)
+        results = _test_model_on_dataset(model, dataset, trained_calls, name, msgr, device_tables=device_tables)
         _save_test_results(results, output_dir, msgr)
         msgr.info(f"Saved test results to {output_dir}")
     msgr.success("Model testing completed.")
