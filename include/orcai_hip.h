@@ -335,6 +335,15 @@ int orcai_extract_labels(const double* agg, const double* cnt, int L, const int6
                          void* workspace, size_t workspace_bytes, void* stream);
 size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total);
 
+/* orcai_extract_labels with one decision threshold per label (`orcai predict --thresholds`): the same arguments, thresholds f64[L] ON THE DEVICE in
+ * place of the scalar.  thr_r[l] = thresholds[l] / max(cnt) over the rows of recording r (one f64 division per label; no rows or a zero maximum: no
+ * runs), b[s][l] = agg[s][l] > thr_r[l] (strict, NaN is false); everything behind the threshold stage -- runs, order, status, offsets, workspace, the
+ * six launches -- is orcai_extract_labels' own code, so with every threshold equal to t the output is byte for byte that of the scalar call with t.
+ * ORCAI_E_BADARG / ORCAI_E_UNSUPPORTED as there, and ORCAI_E_BADARG for a null thresholds. */
+int orcai_extract_labels_per_label(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, const double* thresholds,
+                                   const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity,
+                                   int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 /* test.py:37-225: the integer counts behind the three tables of `orcai test` (compute_confusion_table, compute_misclassification_tables) for one
  * batch; the host forms the tables' float64 values from them (orcai_amd/device_tables.py).
  *   p, y       f32[M][L], M = snippets * time steps: probabilities, and labels in {0, 1, mask_value = -1}.  1 <= L <= 64.
@@ -352,6 +361,23 @@ size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total);
  * only non-zero workgroup totals reach global memory; for L > 16 the rows outside that one bin add straight to global memory.
  * ORCAI_E_BADARG: a null p / y / conf / mis, M < 1, L outside 1..64.  ORCAI_E_UNSUPPORTED (nothing launched): 2^31 or more workgroups. */
 int orcai_test_counts(const float* p, const float* y, int64_t M, int L, float mask_value, int64_t* conf, int64_t* mis, void* stream);
+
+/* The integer counts of the threshold sweep of `orcai test --threshold-sweep` for one batch (orcai_amd/threshold_sweep.py forms TP / FP / FN / TN per
+ * threshold, the ROC and PR curves and their areas from them: the MaskedAUC of reference architectures.py:289-304 as a test-time report).
+ *   p, y        f32[M][L] as for orcai_test_counts.  1 <= L <= 64.
+ *   thresholds  f32[T] ON THE DEVICE, strictly ascending (not checked; any table leaves k inside 0..T).  1 <= T <= 1024.
+ *   hist        int64[L][2][T + 1].  For every element (row, l) with y != mask_value and y == 0 or y == 1 (its class c): k = the number of j with
+ *               p > thresholds[j] -- strict, in f32, found by searching the table itself, so a probability equal to an entry lies below it; a NaN
+ *               gives k = 0 -- and hist[l][c][k] += 1.  Every other label value is ignored.
+ *   The call ADDS to hist: the caller zeroes it once per dataset (orcai_zero_fill).  Predicted positive at threshold j is k >= j + 1.
+ * One launch on `stream` (test_tables.hip); no workspace, no allocation, no synchronisation.  Integer adds only, 64-bit global accumulators: the
+ * result does not depend on the order of execution and two runs from equal buffers leave the same bytes.  grid = (row workgroups, label tiles): a
+ * workgroup keeps the u32 image [label tile][2][T + 1] of its tile in LDS beside the table (tile = min(L, 16, what fits into 64 KiB): 16 labels and
+ * 25.9 KiB at T = 200, 7 labels and 60.1 KiB at T = 1024), and only its non-zero bins reach global memory, one 64-bit atomic add each.
+ * ORCAI_E_BADARG: a null p / y / thresholds / hist, M < 1, L outside 1..64, T outside 1..1024.  ORCAI_E_UNSUPPORTED (nothing launched): 2^31 or more
+ * row workgroups. */
+int orcai_threshold_counts(const float* p, const float* y, int64_t M, int L, float mask_value, const float* thresholds, int T, int64_t* hist,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training (train.py:155-219: Adam(lr) + MaskedBinaryCrossentropy + MaskedBinaryAccuracy; architectures.py:210-286)

@@ -56,6 +56,9 @@ def cli():
                    "(675000 is an hour's worth); 0: one detector pass per recording.")
 @click.option("--device-labels", "device_labels", is_flag=True,
               help="Threshold, run detection, sort and duration filter on the GPU; only the label intervals return to the host. Same files.")
+@click.option("--thresholds", "thresholds", type=FileR, default=None, show_default="None",
+              help="JSON file {label: threshold} with one decision threshold per label (the thresholds.json of `orcai test --threshold-sweep`); "
+                   "labels it does not name keep 0.5.")
 @click.option("--model", "-m", type=click.Choice(INCLUDED_MODELS, case_sensitive=False), default="orcai-V1", show_default=True,
               help="Builtin model to use for prediction. Overridden if model_dir is given.")
 @click.option("--model_dir", "-md", "model_dir", type=DirR, default=None, show_default="use builtin model", help="Path to a model directory.")
@@ -175,6 +178,11 @@ def cli_hpsearch(**kwargs):
 @click.option("--data_compression", "-dc", type=click.Choice(["GZIP", "None"], case_sensitive=False), default="GZIP", show_default=True, help="Data compression of saved datasets")
 @click.option("--device-tables", "device_tables", is_flag=True,
               help="One pass per dataset: metrics and the counts behind the tables are taken on the GPU; only the counts return to the host. Same files.")
+@click.option("--threshold-sweep", "threshold_sweep", is_flag=True,
+              help="Also measure every decision threshold: per dataset <name>_threshold_sweep.csv, <name>_auc.json and <name>_thresholds.json "
+                   "(the threshold of maximal F1 per label, for `orcai predict --thresholds`).")
+@click.option("--num-thresholds", "num_thresholds", type=click.IntRange(2, 1024), default=200, show_default=True,
+              help="Size of the threshold table of --threshold-sweep (that of keras.metrics.AUC).")
 @click.option("--verbosity", "-v", type=click.IntRange(0, 3), default=2, show_default=True, help="0: Errors only, 1: Warnings, 2: Info, 3: Debug")
 def cli_test(**kwargs):
     """cli.py:680-729."""

@@ -13,6 +13,8 @@
 //   1 threshold  one workgroup per recording: max of its counts (NaN kept, as np.max), thr_r = threshold / max as one f64 division
 //                (+inf, "nothing is a one", for no rows or a zero maximum).
 //   2 mask       one lane per row: the L doubles of the row are contiguous, b[l] = agg > thr_r (strict, NaN false) -> one 64-bit word per row.
+//                orcai_extract_labels_per_label: launch 1 hands on max(cnt) itself and this one compares with thr_r[l] = thresholds[l] / max(cnt),
+//                the same single f64 division per label; everything behind the mask is shared.
 //   3 count      per row tile: start = m & ~m[row - 1], stop = m & ~m[row + 1] (neighbours inside the recording only).  Column counts come from
 //                L ballots per wave (the 64 x 64 bit transpose), summed over the four waves: 2 L + 1 counts per tile (starts of all columns,
 //                starts per column, stops per column), stored sequence-major.
@@ -99,7 +101,7 @@ __device__ __forceinline__ Edges row_edges(const u64* __restrict__ mask, const i
 
 // ---------------------------------------------------------------- 1 threshold
 __global__ __launch_bounds__(256) void labels_threshold_kernel(const double* __restrict__ cnt, const int64_t* __restrict__ table, int64_t S_total,
-                                                                double threshold, double* __restrict__ thr) {
+                                                                double threshold, bool per_label, double* __restrict__ thr) {
   __shared__ double part[WAVES];
   __shared__ int part_nan[WAVES];
   const int r = blockIdx.x;
@@ -133,13 +135,17 @@ __global__ __launch_bounds__(256) void labels_threshold_kernel(const double* __r
       if (nan) t = __builtin_nan("");  // np.max keeps a NaN: every comparison is false
       else if (m != 0.0) t = threshold / m;
     }
+    if (per_label) {  // the mask kernel divides per label: it gets the maximum itself, 0 standing for "nothing is a one"
+      t = 0.0;
+      if (hi > lo) t = nan ? __builtin_nan("") : m;
+    }
     thr[r] = t;
   }
 }
 
 // ---------------------------------------------------------------- 2 mask
 __global__ __launch_bounds__(256) void labels_mask_kernel(const double* __restrict__ agg, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
-                                                           const double* __restrict__ thr, u64* __restrict__ mask) {
+                                                           const double* __restrict__ thr, const double* __restrict__ thresholds, u64* __restrict__ mask) {
   const int64_t row = (int64_t)blockIdx.x * ROW_TILE + threadIdx.x;
   if (row >= S_total) return;
   const int r = locate(table, R, row);
@@ -148,7 +154,11 @@ __global__ __launch_bounds__(256) void labels_mask_kernel(const double* __restri
   if (s >= 0 && s < table[4 * r + 2]) {
     const double t = thr[r];
     const double* __restrict__ p = agg + row * L;
-    for (int l = 0; l < L; ++l) m |= (u64)(p[l] > t) << l;
+    if (!thresholds) {
+      for (int l = 0; l < L; ++l) m |= (u64)(p[l] > t) << l;
+    } else if (t != 0.0) {  // t is max(cnt) here (NaN kept: every comparison is false); thr_r[l] = thresholds[l] / max(cnt), one f64 division
+      for (int l = 0; l < L; ++l) m |= (u64)(p[l] > thresholds[l] / t) << l;
+    }
   }
   mask[row] = m;
 }
@@ -329,18 +339,10 @@ __global__ __launch_bounds__(256) void labels_emit_kernel(const u64* __restrict_
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total) {
-  if (L < 1 || L > 64 || R < 1 || S_total < 1) return 0;
-  return layout(L, R, S_total).total;
-}
-
-int orcai_extract_labels(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, double threshold,
-                         const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity, int64_t* offsets,
-                         void* workspace, size_t workspace_bytes, void* stream) {
+// Both entry points: thresholds == nullptr is the scalar call (threshold / max(cnt) once per recording), else thresholds f64[L] on the device.
+int extract_labels(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, double threshold, const double* thresholds,
+                   const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity, int64_t* offsets,
+                   void* workspace, size_t workspace_bytes, void* stream) {
   if (!agg || !cnt || !table || !label_rank || !runs || !offsets || !workspace) return ORCAI_E_BADARG;
   if (L < 1 || L > 64 || R < 1 || S_total < 1 || capacity < 0 || tpo < 1) return ORCAI_E_BADARG;
   if ((reinterpret_cast<uintptr_t>(runs) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return ORCAI_E_BADARG;
@@ -355,14 +357,38 @@ int orcai_extract_labels(const double* agg, const double* cnt, int L, const int6
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)a.tiles), block(ROW_TILE);
   const int sequences = 2 * L + 1;
-  hipLaunchKernelGGL(labels_threshold_kernel, dim3((unsigned)R), block, 0, st, cnt, table, S_total, threshold, thr);
-  hipLaunchKernelGGL(labels_mask_kernel, grid, block, 0, st, agg, L, table, R, S_total, thr, mask);
+  hipLaunchKernelGGL(labels_threshold_kernel, dim3((unsigned)R), block, 0, st, cnt, table, S_total, threshold, thresholds != nullptr, thr);
+  hipLaunchKernelGGL(labels_mask_kernel, grid, block, 0, st, agg, L, table, R, S_total, thr, thresholds, mask);
   hipLaunchKernelGGL(labels_count_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts);
   hipLaunchKernelGGL(labels_scan_kernel, dim3((unsigned)((sequences + WAVES - 1) / WAVES)), block, 0, st, counts, sequences, a.tiles, offsets + R);
   hipLaunchKernelGGL(labels_stops_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops);
   hipLaunchKernelGGL(labels_emit_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops, label_rank, limits,
                      frame_seconds, tpo, reinterpret_cast<int4*>(runs), capacity, offsets);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total) {
+  if (L < 1 || L > 64 || R < 1 || S_total < 1) return 0;
+  return layout(L, R, S_total).total;
+}
+
+int orcai_extract_labels(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, double threshold,
+                         const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity, int64_t* offsets,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  return extract_labels(agg, cnt, L, table, R, S_total, threshold, nullptr, label_rank, limits, frame_seconds, tpo, runs, capacity, offsets, workspace,
+                        workspace_bytes, stream);
+}
+
+int orcai_extract_labels_per_label(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, const double* thresholds,
+                                   const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity,
+                                   int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!thresholds) return ORCAI_E_BADARG;
+  return extract_labels(agg, cnt, L, table, R, S_total, 0.0, thresholds, label_rank, limits, frame_seconds, tpo, runs, capacity, offsets, workspace,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"

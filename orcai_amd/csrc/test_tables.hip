@@ -19,6 +19,9 @@
 //            workgroup.  Larger L (the histogram of L = 64 is 2 MiB): one 64-bit global atomic add per (row, set column) of the rows that are NOT
 //            in the hot bin -- correct for every L, and only as fast as such rows are rare.
 // A workgroup sees at most MAX_TILES_PER_WG * 256 = 2^28 rows, so its 32-bit partial counts cannot wrap; every global accumulator is 64 bits wide.
+//
+// orcai_threshold_counts (below the first kernel) takes the counts of the threshold sweep in the same way: per label and class a histogram over the
+// position of the probability in a table of thresholds, privatised per workgroup in LDS one label tile at a time.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -137,6 +140,57 @@ __global__ __launch_bounds__(256) void test_counts_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------- orcai_threshold_counts
+// The threshold sweep of `orcai test --threshold-sweep`: hist[l][c][k] counts the elements of label l and class c whose probability lies above exactly
+// k entries of the threshold table.  grid = (row workgroups, label tiles): a workgroup takes tiles_per_wg row tiles of 256 rows and `lt` consecutive
+// labels, one lane per (row, label) element -- with one label tile (L <= SWEEP_LT_MAX and the image fits) the lanes of a wave read consecutive floats.
+// LDS: the table f32[T], then the image u32[lt][2][T + 1] of the tile; k by binary search in the LDS copy of the table (strict f32 comparison, NaN
+// above nothing), one LDS atomic add per element, one 64-bit global atomic add per non-zero bin and workgroup.  A workgroup sees at most 2^28 rows, so
+// a u32 bin cannot wrap.
+constexpr int SWEEP_LT_MAX = 16;               // labels per tile at most: T = 200 -> 16 * 2 * 201 * 4 = 25 728 bytes; T = 1024 -> 7 labels, 57 400 bytes
+constexpr size_t SWEEP_LDS_MAX = 64 * 1024;    // table + image stay inside the default 64 KiB of a workgroup
+
+__global__ __launch_bounds__(256) void threshold_counts_kernel(const float* __restrict__ p, const float* __restrict__ y, int64_t M, int L, float mask_value,
+                                                                const float* __restrict__ thresholds, int T, int lt_max, int64_t tiles_per_wg,
+                                                                u64* __restrict__ out) {
+  extern __shared__ unsigned sweep_lds[];
+  float* __restrict__ table = reinterpret_cast<float*>(sweep_lds);  // f32 [T]
+  unsigned* __restrict__ image = sweep_lds + T;                     // u32 [lt][2][T + 1]
+  const int tid = threadIdx.x;
+  const int l0 = blockIdx.y * lt_max;
+  const int lt = L - l0 < lt_max ? L - l0 : lt_max;
+  const int bins = lt * 2 * (T + 1);
+  for (int i = tid; i < T; i += ROW_TILE) table[i] = thresholds[i];
+  for (int i = tid; i < bins; i += ROW_TILE) image[i] = 0;
+  __syncthreads();
+  const int64_t tile0 = (int64_t)blockIdx.x * tiles_per_wg;
+  for (int64_t t = 0; t < tiles_per_wg; ++t) {
+    const int64_t first = (tile0 + t) * ROW_TILE;
+    if (first >= M) break;  // the whole workgroup
+    const int rows = M - first < ROW_TILE ? (int)(M - first) : ROW_TILE;
+    const int n = rows * lt;  // <= 256 * 16
+    for (int e = tid; e < n; e += ROW_TILE) {
+      const int r = e / lt, j = e - r * lt;
+      const int64_t at = (first + r) * L + l0 + j;
+      const float yv = y[at];
+      if (!(yv != mask_value) || !(yv == 0.0f || yv == 1.0f)) continue;
+      const float pv = p[at];
+      int lo = 0, hi = T;  // k = the number of entries below pv: the table ascends strictly
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pv > table[mid]) lo = mid + 1; else hi = mid;
+      }
+      atomicAdd(&image[(j * 2 + (yv == 1.0f)) * (T + 1) + lo], 1u);
+    }
+  }
+  __syncthreads();
+  u64* __restrict__ dst = out + (int64_t)l0 * 2 * (T + 1);
+  for (int i = tid; i < bins; i += ROW_TILE) {
+    const unsigned v = image[i];
+    if (v) atomicAdd(&dst[i], (u64)v);
+  }
+}
+
 }  // namespace
 
 extern "C" int orcai_test_counts(const float* p, const float* y, int64_t M, int L, float mask_value, int64_t* conf, int64_t* mis, void* stream) {
@@ -155,5 +209,23 @@ extern "C" int orcai_test_counts(const float* p, const float* y, int64_t M, int 
   } else {
     hipLaunchKernelGGL(test_counts_kernel<false>, dim3((unsigned)grid), dim3(ROW_TILE), 0, st, p, y, M, L, mask_value, tiles_per_wg, c, m);
   }
+  return (int)hipGetLastError();
+}
+
+extern "C" int orcai_threshold_counts(const float* p, const float* y, int64_t M, int L, float mask_value, const float* thresholds, int T, int64_t* hist,
+                                      void* stream) {
+  if (!p || !y || !thresholds || !hist || M < 1 || L < 1 || L > 64 || T < 1 || T > 1024) return ORCAI_E_BADARG;
+  const int64_t tiles = (M - 1) / ROW_TILE + 1;
+  int64_t tiles_per_wg = (tiles - 1) / MAX_GRID + 1;
+  if (tiles_per_wg > MAX_TILES_PER_WG) tiles_per_wg = MAX_TILES_PER_WG;
+  const int64_t grid = (tiles - 1) / tiles_per_wg + 1;
+  if (grid > 0x7fffffff) return ORCAI_E_UNSUPPORTED;
+  const size_t per_label = (size_t)2 * (T + 1) * sizeof(unsigned);
+  int lt = (int)((SWEEP_LDS_MAX - (size_t)T * sizeof(float)) / per_label);  // >= 7 at T = 1024
+  if (lt > SWEEP_LT_MAX) lt = SWEEP_LT_MAX;
+  if (lt > L) lt = L;
+  const size_t lds = (size_t)T * sizeof(float) + lt * per_label;
+  hipLaunchKernelGGL(threshold_counts_kernel, dim3((unsigned)grid, (unsigned)((L + lt - 1) / lt)), dim3(ROW_TILE), lds, (hipStream_t)stream, p, y, M, L,
+                     mask_value, thresholds, T, lt, tiles_per_wg, reinterpret_cast<u64*>(hist));
   return (int)hipGetLastError();
 }

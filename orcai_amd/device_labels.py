@@ -93,6 +93,19 @@ def _device_constants(device, calls, label_suffix, call_duration_limits):
     return _constants[key]
 
 
+def _device_thresholds(device, thresholds, L: int) -> torch.Tensor:
+    """f64 [L] on the device, uploaded once per (device, values)."""
+    values = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if len(values) != L:
+        raise ValueError(f"thresholds: one per label wanted ({L}), got {len(values)}")
+    key = (str(device), "thresholds", values.tobytes())
+    if key not in _constants:
+        if len(_constants) > 64:
+            _constants.clear()
+        _constants[key] = torch.from_numpy(values).to(device)
+    return _constants[key]
+
+
 class PendingLabels:
     """The label intervals of one recording, or of every recording of a batch, on their way from the GPU to pinned host memory.  `results()` waits
     for the copy (an event on the launch stream, not a device-wide synchronisation) and returns, per recording, (predicted_labels, n_too_short,
@@ -128,11 +141,13 @@ class PendingLabels:
 
 
 def extract_labels_device(agg_dev: torch.Tensor, cnt_dev: torch.Tensor, table_dev: torch.Tensor, R: int, calls, label_suffix: str | None,
-                          time_steps_per_output_step: int, delta_t: float, call_duration_limits=None, threshold: float = 0.5) -> PendingLabels:
+                          time_steps_per_output_step: int, delta_t: float, call_duration_limits=None, threshold: float = 0.5,
+                          thresholds=None) -> PendingLabels:
     """Queue orcai_extract_labels on the current stream for the averaged probabilities agg_dev f64 [S_total][L] / cnt_dev f64 [S_total] of the R
     recordings of table_dev (int64 [R][4] on the device, orcai_overlap_average_ragged's table; one recording: [[0, n, S, 0]]), and the copy of its
     result to pinned memory behind one event.  call_duration_limits (a dict or a JSON path) makes the kernel judge every interval as
-    filter_predictions does with delta_t seconds per frame.
+    filter_predictions does with delta_t seconds per frame.  thresholds (L floats, one per label): orcai_extract_labels_per_label in place of the
+    scalar `threshold`.
 
     What travels to the host: the R + 1 offsets and the first EAGER_RUNS runs, in ONE copy whose size does not depend on S_total or L.  The device
     buffer holds the kernel's capacity bound (L * ceil(S_total / 2) + R runs, the size of agg itself), so nothing is ever dropped; when more than
@@ -148,14 +163,19 @@ def extract_labels_device(agg_dev: torch.Tensor, cnt_dev: torch.Tensor, table_de
     out = torch.empty(header + 4 * capacity, dtype=torch.int32, device=agg_dev.device)
     ws_bytes = int(lib.orcai_extract_labels_workspace_bytes(L, R, S_total))
     workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=agg_dev.device)
-    N.check(lib.orcai_extract_labels(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, float(threshold), N.ptr(rank),
-                                     None if limits is None else N.ptr(limits), float(delta_t), int(time_steps_per_output_step),
-                                     out.data_ptr() + 4 * header, capacity, out.data_ptr(), workspace.data_ptr(), ws_bytes, N.stream_ptr()),
-            "orcai_extract_labels")
+    tail = (N.ptr(rank), None if limits is None else N.ptr(limits), float(delta_t), int(time_steps_per_output_step), out.data_ptr() + 4 * header, capacity,
+            out.data_ptr(), workspace.data_ptr(), ws_bytes, N.stream_ptr())
+    per_label = None
+    if thresholds is None:
+        N.check(lib.orcai_extract_labels(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, float(threshold), *tail), "orcai_extract_labels")
+    else:
+        per_label = _device_thresholds(agg_dev.device, thresholds, L)
+        N.check(lib.orcai_extract_labels_per_label(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, N.ptr(per_label), *tail),
+                "orcai_extract_labels_per_label")
     eager = header + 4 * min(capacity, EAGER_RUNS)
     host = torch.empty(eager, dtype=torch.int32, pin_memory=True)
     host.copy_(out[:eager], non_blocking=True)
     event = torch.cuda.Event()
     event.record()
     return PendingLabels(R, calls, label_suffix, time_steps_per_output_step, filtered, host=host, device=out, header=header, event=event,
-                         keep=(agg_dev, cnt_dev, table_dev, workspace, rank, limits))
+                         keep=(agg_dev, cnt_dev, table_dev, workspace, rank, limits, per_label))

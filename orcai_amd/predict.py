@@ -109,16 +109,19 @@ class PendingAggregate:
         return [(agg[row : row + rows], cnt[row : row + rows]) for row, rows in slices]
 
 
-def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True) -> dict:
+def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True, thresholds=None) -> dict:
     """What the launch half needs to queue orcai_extract_labels behind the overlap average (device_labels=...): the label names, the suffix, the
-    duration limits the kernel is to judge by (None: no filter) and whether the averaged probabilities are still wanted on the host."""
-    return {"calls": orcai_parameter["calls"], "label_suffix": label_suffix, "call_duration_limits": call_duration_limits, "probabilities": probabilities}
+    duration limits the kernel is to judge by (None: no filter), whether the averaged probabilities are still wanted on the host, and the per-label
+    thresholds (L floats; None: 0.5 for every label through the scalar entry point)."""
+    return {"calls": orcai_parameter["calls"], "label_suffix": label_suffix, "call_duration_limits": call_duration_limits, "probabilities": probabilities,
+            "thresholds": thresholds}
 
 
 def _queue_labels(spec: dict, agg: torch.Tensor, cnt: torch.Tensor, table: torch.Tensor, R: int, n_filters: int, delta_t: float):
     from orcai_amd.device_labels import extract_labels_device
 
-    return extract_labels_device(agg, cnt, table, R, spec["calls"], spec["label_suffix"], 2**n_filters, delta_t, call_duration_limits=spec["call_duration_limits"])
+    return extract_labels_device(agg, cnt, table, R, spec["calls"], spec["label_suffix"], 2**n_filters, delta_t, call_duration_limits=spec["call_duration_limits"],
+                                 thresholds=spec.get("thresholds"))
 
 
 def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snippet_length: int, n_filters: int, wait: bool = True,
@@ -228,8 +231,12 @@ def compute_aggregated_predictions(recording_path: Path, spectrogram, model, orc
                                         delta_t=delta_t)
 
 
-def compute_binary_predictions(aggregated_predictions: np.ndarray, overlap_count: np.ndarray, calls: list[str], threshold: float = 0.5):
-    """predict.py:298-317."""
+def compute_binary_predictions(aggregated_predictions: np.ndarray, overlap_count: np.ndarray, calls: list[str], threshold=0.5):
+    """predict.py:298-317.  threshold: a float, or a sequence of one threshold per label (column l is cut at threshold[l] / max(count))."""
+    if not np.isscalar(threshold):
+        threshold = np.asarray(threshold, dtype=np.float64)
+        if threshold.shape != (len(calls),):
+            raise ValueError(f"compute_binary_predictions: one threshold per label wanted ({len(calls)}), got shape {threshold.shape}")
     adjusted_threshold = threshold / np.max(overlap_count)
     binary_prediction = (aggregated_predictions > adjusted_threshold).astype(int)
     row_starts, row_stops, label_names = [], [], []
@@ -289,8 +296,9 @@ def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_pa
     return {"pending": pending, "delta_t": delta_t, "orcai_parameter": orcai_parameter}
 
 
-def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)):
-    """Second half of predict_wav (host): threshold, runs of ones, label table (predict.py:298-340)."""
+def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None):
+    """Second half of predict_wav (host): threshold, runs of ones, label table (predict.py:298-340).  thresholds: one per label (L floats) in place
+    of 0.5 on the host route; labels that came from the device were cut by the thresholds of their label_spec."""
     pending, orcai_parameter = state["pending"], state["orcai_parameter"]
     aggregated_predictions, overlap_count = pending.result() if isinstance(pending, PendingAggregate) else pending
     device_result = state.get("device_labels_result")
@@ -300,7 +308,8 @@ def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = M
         return _finish_device_labels(device_result, pending.labels if isinstance(pending, PendingAggregate) else state["device_labels"],
                                      aggregated_predictions, state["delta_t"], msgr)
     row_starts, row_stops, label_names = compute_binary_predictions(aggregated_predictions=aggregated_predictions, overlap_count=overlap_count,
-                                                                    calls=orcai_parameter["calls"], threshold=0.5)
+                                                                    calls=orcai_parameter["calls"],
+                                                                    threshold=0.5 if thresholds is None else thresholds)
     msgr.info("converting binary predictions into start and stop frames")
     time_steps_per_output_step = 2 ** len(orcai_parameter["model"]["filters"])
     predicted_labels = compute_labels(row_starts, row_stops, label_names, time_steps_per_output_step=time_steps_per_output_step, label_suffix=label_suffix)
@@ -322,12 +331,15 @@ def _finish_device_labels(device_result: tuple, labels, aggregated_predictions, 
 
 
 def predict_wav(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*",
-                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False):
+                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False, thresholds=None):
     """(predicted_labels DataFrame, aggregated_predictions ndarray, delta_t) for one wav file (predict.py:367-471).  device_labels=True: the label
-    table comes from orcai_extract_labels (the same table)."""
+    table comes from orcai_extract_labels (the same table).  thresholds: a dict {label: threshold} or the path of a thresholds.json."""
+    from orcai_amd.threshold_sweep import resolve_thresholds
+
+    thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
     state = predict_wav_launch(recording_path, channel, model, orcai_parameter, shape, msgr=msgr, progressbar=progressbar,
-                               device_labels=label_spec(orcai_parameter, label_suffix) if device_labels else None)
-    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
+                               device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds) if device_labels else None)
+    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
 
 
 def _too_short(n_frames: int, snippet_length: int) -> ValueError:
@@ -390,7 +402,7 @@ def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_fram
         yield queue()
 
 
-def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> list:
+def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> list:
     """The host half of one batch state: [(key, predict_wav's triple or the exception the recording raised)], the failed ones first."""
     out = list(state["failed"])
     if state["pending"] is not None:
@@ -398,7 +410,8 @@ def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messen
         label_results = labels.results() if labels is not None else [None] * len(state["members"])
         for (key, delta_t), pair, device_result in zip(state["members"], state["pending"].results(), label_results):
             out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"],
-                                                 "device_labels_result": device_result, "device_labels": labels}, label_suffix=label_suffix, msgr=msgr)))
+                                                 "device_labels_result": device_result, "device_labels": labels}, label_suffix=label_suffix, msgr=msgr,
+                                                thresholds=thresholds)))
     return out
 
 
@@ -425,35 +438,40 @@ def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_fr
                            device_labels=device_labels)
 
 
-def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> list:
+def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> list:
     """Second half (host): [(index into items, (predicted_labels, aggregated_predictions, delta_t) or the exception that item raised)]."""
-    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr)
+    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
 
 
 def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*", max_frames: int | None = None,
-                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False) -> list:
+                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False, thresholds=None) -> list:
     """predict_wav for every (path, channel) of `items`, several recordings per detector pass: batches of at most max_frames spectrogram frames
     (batch.DEFAULT_MAX_FRAMES: an hour's worth) go through ONE forward pass and ONE overlap average, the host half of a batch runs beside the GPU
     half of the next.  Returns, per item, what predict_wav returns for it -- the same label table, the same f64 probabilities, the same delta_t --
     or the exception it raised (a missing file, a recording shorter than one snippet); the other items are unaffected.
     A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item.
-    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables)."""
+    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables).  thresholds: as for predict_wav."""
+    from orcai_amd.threshold_sweep import resolve_thresholds
+
+    thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
+    listed = None if thresholds is None else dict(zip(orcai_parameter["calls"], thresholds))
     items = list(items)
     results = [None] * len(items)
     if not hasattr(model, "predict_batch"):
         for i, (path, channel) in enumerate(items):
             try:
-                results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr, device_labels=device_labels)
+                results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr, device_labels=device_labels,
+                                         thresholds=listed)
             except Exception as e:
                 results[i] = e
         return results
 
     def finish(state):
-        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr):
+        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds):
             results[i] = result
 
     _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr,
-                                     device_labels=label_spec(orcai_parameter, label_suffix) if device_labels else None), finish)
+                                     device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds) if device_labels else None), finish)
     return results
 
 
@@ -522,25 +540,27 @@ def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_prob
 
 
 def _finish_recording(state: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                      msgr: Messenger = Messenger(verbosity=0)) -> None:
+                      msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> None:
     """predict.py:576-632: the host half -- labels, optional duration filter, files."""
-    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr)
+    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
     _save_recording(result, state["output_path"], state["orcai_parameter"], save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
                     label_suffix=label_suffix, msgr=msgr)
 
 
 def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
                       overwrite: bool = False, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
-                      label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None) -> None:
+                      label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None,
+                      thresholds=None) -> None:
     """predict.py:534-632."""
     state = _launch_recording(recording_path, channel, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite, msgr=msgr,
                               progressbar=progressbar, device_labels=device_labels)
-    _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
+    _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
+                      thresholds=thresholds)
 
 
 def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default", overwrite: bool = False,
                           save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None) -> None:
+                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None, thresholds=None) -> None:
     """predict(channel="all"): one read and one upload of the file, every channel decoded by orcai_pcm_decode_planar, the channels as ONE batch through
     the detector.  One output file per channel, under the name -- and with the bytes -- predict(channel=c) gives it."""
     from orcai_amd.spectrogram import load_wav_all
@@ -553,7 +573,7 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
     errors = []
 
     def finish(state):
-        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr):
+        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds):
             if isinstance(result, Exception):
                 errors.append(result)
                 continue
@@ -568,7 +588,7 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
 
 def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter: dict, shape: dict, batch_frames: int, overwrite: bool,
                            save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm,
-                           device_labels: dict | None = None) -> None:
+                           device_labels: dict | None = None, thresholds=None) -> None:
     """Table mode with batch_frames > 0: the rows of the table in order, grouped into detector passes of at most batch_frames spectrogram frames.
     Per recording the output path, the overwrite check, the files and the error line are those of the one-by-one loop; one batch deep, so the host
     half of a batch (labels, files) runs beside the GPU half of the next."""
@@ -593,7 +613,7 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
             yield i, lambda path=path, channel=channel: load_wav(path, sr, channel, quiet)
 
     def finish(state):
-        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet):
+        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet, thresholds=thresholds):
             try:
                 if isinstance(result, Exception):
                     raise result
@@ -608,7 +628,7 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
 def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str | Path = DEFAULT_MODEL_DIR, output_path: str | Path = "default",
             overwrite: bool = False, save_probabilities: bool = False, base_dir_recording: str | Path | None = None,
             call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None,
-            batch_frames: int = 0, device_labels: bool = False) -> None:
+            batch_frames: int = 0, device_labels: bool = False, thresholds: str | Path | dict | None = None) -> None:
     """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757).
     channel="all" (a wav file): every channel of the file from one read of its bytes, one output file per channel.
     batch_frames > 0 (a table): consecutive recordings go through the detector in batches of at most batch_frames spectrogram frames
@@ -616,24 +636,32 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     are the same bytes either way.
     device_labels=True: threshold, run detection, sort and duration filter of every route run on the GPU (orcai_extract_labels) and only the
     intervals found come back; without save_probabilities the averaged probabilities never leave the device.  The files are the same bytes.
-    Ignored for a model without the native path."""
+    Ignored for a model without the native path.
+    thresholds: a dict {label: threshold} or the path of such a JSON file (the thresholds.json of ``orcai test --threshold-sweep``): label l is cut at
+    thresholds[l] in place of 0.5 on every route, with device_labels or without.  Labels it does not name keep 0.5; a label the model does not have
+    raises ValueError before the model is loaded."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Predicting calls")
     model_dir = Path(model_dir)
     recording_path = Path(recording_path)
+    if thresholds is not None:
+        from orcai_amd.threshold_sweep import resolve_thresholds
+
+        thresholds = resolve_thresholds(thresholds, read_json(model_dir.joinpath("orcai_parameter.json"))["calls"])
     msgr.part(f"Loading model: {model_dir.stem}")
     model, orcai_parameter, shape = load_orcai_model(model_dir)
     spec = None
     if device_labels and hasattr(model, "predict_spectrogram"):
-        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities)
+        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities, thresholds=thresholds)
     if recording_path.suffix == ".wav" and channel == "all" and hasattr(model, "predict_batch"):
         return _predict_all_channels(recording_path, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite,
                                      save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
-                                     device_labels=spec)
+                                     device_labels=spec, thresholds=thresholds)
     if recording_path.suffix == ".wav":
         return _predict_and_save(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape,
                                  output_path=output_path, overwrite=overwrite, save_probabilities=save_probabilities,
-                                 call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None, device_labels=spec)
+                                 call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None, device_labels=spec,
+                                 thresholds=thresholds)
     elif recording_path.suffix == ".csv":
         recording_table = pd.read_csv(recording_path)
     else:
@@ -662,7 +690,8 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     quiet = Messenger(verbosity=0)
     if batch_frames > 0 and hasattr(model, "predict_batch"):
         _predict_table_batched(recording_table, model, orcai_parameter, shape, batch_frames, overwrite=overwrite, save_probabilities=save_probabilities,
-                               call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar, device_labels=spec)
+                               call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar, device_labels=spec,
+                               thresholds=thresholds)
         wavio.set_prefetcher(None)
         msgr.success("Predictions finished.")
         return
@@ -672,7 +701,8 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     def finish(entry):
         j, state = entry
         try:
-            _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=quiet)
+            _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=quiet,
+                              thresholds=thresholds)
         except Exception as e:  # predict.py:752-755: log and continue with the next recording
             msgr.error(f"Error predicting {recording_table.loc[j, 'recording']}: {e.args[0] if e.args else e}")
 

@@ -5,7 +5,8 @@
 The tables are host-side numpy / pandas (pinned bit-for-bit by golden vectors from the reference's own functions,
 ``tests/golden/test_tables.*``); the forward passes behind them run on the GPU through the model's HIP kernels.  With ``device_tables=True``
 the metrics and the tables come from ONE pass: the integer counts behind the tables are taken on the GPU (orcai_test_counts,
-``orcai_amd/device_tables.py``) and only they return to the host.
+``orcai_amd/device_tables.py``) and only they return to the host.  ``threshold_sweep=True`` adds, on either route, the counts at every
+decision threshold, the areas under the ROC and PR curves and a recommended threshold per label (``orcai_amd/threshold_sweep.py``).
 """
 
 from __future__ import annotations
@@ -111,9 +112,10 @@ def _confusion_entry(tn: int, fp: int, fn: int, tp: int) -> dict:
         }
 
 
-def _test_model_on_dataset_device(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger) -> dict:
+def _test_model_on_dataset_device(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger, thresholds=None) -> dict:
     """``device_tables=True``: ONE pass over the dataset.  Per batch the forward pass, the masked BCE into evaluate's accumulators and
-    orcai_test_counts are queued on the stream; nothing is copied back or synchronised inside the loop.  Metrics and tables describe the same batches."""
+    orcai_test_counts are queued on the stream; nothing is copied back or synchronised inside the loop.  Metrics and tables describe the same batches.
+    thresholds (f32 [T], the sweep's table): orcai_threshold_counts joins the loop in the same way."""
     import torch
 
     from orcai_amd.device_tables import TestCounts, confusion_table_from_counts, misclassification_tables_from_counts
@@ -122,17 +124,25 @@ def _test_model_on_dataset_device(model, dataset, label_names: list[str], datase
     msgr.info(f"Evaluating model on {dataset_name} (metrics and tables in one pass)")
     loop = model._need_loop()
     tot, acc = loop.evaluate_begin()
-    counts = None
+    counts = sweep_counts = None
     for spectrogram_batch, label_batch in dataset:
         if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (spectrogram_batch, label_batch)):
             raise ValueError("device_tables=True (orcai test --device-tables) needs batches of cuda tensors, as the package's dataset classes yield them")
         if counts is None:
             counts = TestCounts(len(label_names), spectrogram_batch.device)
+            if thresholds is not None:
+                from orcai_amd.threshold_sweep import ThresholdCounts
+
+                sweep_counts = ThresholdCounts(len(label_names), thresholds, spectrogram_batch.device)
         label_batch = label_batch.contiguous()
-        counts.add(loop.evaluate_batch(spectrogram_batch, label_batch, tot, acc), label_batch)
+        probs = loop.evaluate_batch(spectrogram_batch, label_batch, tot, acc)
+        counts.add(probs, label_batch)
+        if sweep_counts is not None:
+            sweep_counts.add(probs, label_batch)
     if counts is None:
         raise ValueError(f"device_tables=True: {dataset_name} yielded no batch")
     conf, mis = counts.result()  # the one synchronising copy of the pass
+    hist = sweep_counts.result() if sweep_counts is not None else None
     data_metrics = loop.evaluate_finish(tot)
     msgr.info(data_metrics)
     msgr.part(f"Calculating confusion table for {dataset_name}")
@@ -143,13 +153,35 @@ def _test_model_on_dataset_device(model, dataset, label_names: list[str], datase
     for key, table in tables.items():
         msgr.info("\n" + key, indent=1)
         msgr.info(table, indent=-1)
-    return {"dataset": dataset_name, "data_metrics": data_metrics, "confusion_table": confusion_table, "misclassification_tables": tables}
+    results = {"dataset": dataset_name, "data_metrics": data_metrics, "confusion_table": confusion_table, "misclassification_tables": tables}
+    if hist is not None:
+        results["threshold_sweep"] = _threshold_report(hist, thresholds, label_names, msgr)
+    return results
 
 
-def _test_model_on_dataset(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger, device_tables: bool = False) -> dict:
-    """test.py:228-287.  device_tables=True: the same result from one pass with the tables' counts taken on the GPU."""
+def _threshold_report(hist: np.ndarray, thresholds: np.ndarray, label_names: list[str], msgr: Messenger) -> dict:
+    """The sweep table, the areas under the curves and the recommended thresholds of one dataset from its histogram (threshold_sweep.py)."""
+    from orcai_amd.threshold_sweep import report_from_hist
+
+    msgr.part("Threshold sweep on dataset:")
+    report = report_from_hist(hist, thresholds, label_names)
+    msgr.info(f"MAUC: {report['auc']['MAUC']}")
+    msgr.info(f"Thresholds of maximal F1: {report['thresholds']}")
+    return report
+
+
+def _test_model_on_dataset(model, dataset, label_names: list[str], dataset_name: str, msgr: Messenger, device_tables: bool = False,
+                           threshold_sweep: bool = False, num_thresholds: int = 200) -> dict:
+    """test.py:228-287.  device_tables=True: the same result from one pass with the tables' counts taken on the GPU.
+    threshold_sweep=True adds results["threshold_sweep"]: the counts at every threshold of keras_thresholds(num_thresholds), the areas under the ROC and
+    PR curves and the threshold of maximal F1 per label, from the same pass or, on the host route, from the arrays it gathers anyway."""
+    thresholds = None
+    if threshold_sweep:
+        from orcai_amd.threshold_sweep import hist_from_arrays, keras_thresholds
+
+        thresholds = keras_thresholds(num_thresholds)
     if device_tables:
-        return _test_model_on_dataset_device(model, dataset, label_names, dataset_name, msgr)
+        return _test_model_on_dataset_device(model, dataset, label_names, dataset_name, msgr, thresholds=thresholds)
     msgr.part(f"Testing model on {dataset_name}")
     msgr.info(f"Evaluating model on {dataset_name}")
     data_metrics = model.evaluate(dataset, return_dict=True, verbose=0 if msgr.verbosity < 3 else 1)
@@ -168,7 +200,10 @@ def _test_model_on_dataset(model, dataset, label_names: list[str], dataset_name:
     for key, table in tables.items():
         msgr.info("\n" + key, indent=1)
         msgr.info(table, indent=-1)
-    return {"dataset": dataset_name, "data_metrics": data_metrics, "confusion_table": confusion_table, "misclassification_tables": tables}
+    results = {"dataset": dataset_name, "data_metrics": data_metrics, "confusion_table": confusion_table, "misclassification_tables": tables}
+    if thresholds is not None:
+        results["threshold_sweep"] = _threshold_report(hist_from_arrays(data_true, data_predicted, thresholds, MASK_VALUE), thresholds, label_names, msgr)
+    return results
 
 
 def _predict_batch(model, spectrogram_batch) -> np.ndarray:
@@ -195,11 +230,21 @@ def _save_test_results(results: dict, save_results_dir: Path, msgr: Messenger) -
     results["confusion_table"].to_csv(save_results_dir.joinpath(name + "_confusion_table.csv"), index_label="Label")
     for key, table in results["misclassification_tables"].items():
         table.to_csv(save_results_dir.joinpath(name + "_misclassification_table_" + key + ".csv"), index_label="Label")
+    report = results.get("threshold_sweep")
+    if report is not None:  # --threshold-sweep: three more files; thresholds.json is what `orcai predict --thresholds` reads
+        report["sweep"].to_csv(save_results_dir.joinpath(name + "_threshold_sweep.csv"), index=False)
+        with open(save_results_dir.joinpath(name + "_auc.json"), "w") as f:
+            json.dump(report["auc"], f)
+        with open(save_results_dir.joinpath(name + "_thresholds.json"), "w") as f:
+            json.dump(report["thresholds"], f)
 
 
 def test_model(model_dir: Path | str, data_dir: Path | str, test_unfiltered: bool = True, output_dir: None | Path | str = None,
-               data_compression: str | None = "GZIP", verbosity: int = 2, msgr: Messenger | None = None, device_tables: bool = False) -> None:
-    """test.py:318-420.  device_tables=True (``orcai test --device-tables``): one pass per dataset, the tables' counts taken on the GPU; same files."""
+               data_compression: str | None = "GZIP", verbosity: int = 2, msgr: Messenger | None = None, device_tables: bool = False,
+               threshold_sweep: bool = False, num_thresholds: int = 200) -> None:
+    """test.py:318-420.  device_tables=True (``orcai test --device-tables``): one pass per dataset, the tables' counts taken on the GPU; same files.
+    threshold_sweep=True (``orcai test --threshold-sweep [--num-thresholds N]``): per dataset three more files next to the tables,
+    <name>_threshold_sweep.csv, <name>_auc.json and <name>_thresholds.json; the other files do not change."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Testing model")
     data_dir, model_dir = Path(data_dir), Path(model_dir)
@@ -217,7 +262,8 @@ def test_model(model_dir: Path | str, data_dir: Path | str, test_unfiltered: boo
     for folder, name, seed_id in todo:
         dataset = load_dataset(data_dir.joinpath(folder), model_parameter["batch_size"], compression=data_compression,
                                seed=[seed_id, seed] if seed is not None else None)
-        results = _test_model_on_dataset(model, dataset, trained_calls, name, msgr, device_tables=device_tables)
+        results = _test_model_on_dataset(model, dataset, trained_calls, name, msgr, device_tables=device_tables, threshold_sweep=threshold_sweep,
+                                         num_thresholds=num_thresholds)
         _save_test_results(results, output_dir, msgr)
         msgr.info(f"Saved test results to {output_dir}")
     msgr.success("Model testing completed.")
