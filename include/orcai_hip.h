@@ -344,6 +344,24 @@ int orcai_extract_labels_per_label(const double* agg, const double* cnt, int L, 
                                    const int* label_rank, const double* limits, double frame_seconds, int tpo, int* runs, int64_t capacity,
                                    int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* orcai_extract_labels_per_label with hysteresis and gap merging (`orcai predict --high-thresholds --merge-gap`): the same arguments plus
+ * high_thresholds f64[L] and gap_rows int32[L], both ON THE DEVICE.  Per recording r and label l, with max = max(cnt) over the recording's rows:
+ *   lo[s] = agg[s][l] > thresholds[l] / max,  hi[s] = lo[s] && agg[s][l] > high_thresholds[l] / max  (one f64 division each, strict, NaN is false);
+ *   1. candidates are the maximal stretches of lo inside the recording;  2. a candidate is kept iff one of its rows has hi set;
+ *   3. kept runs of one column and recording are joined while next.start - prev.stop - 1 <= gap_rows[l] (transitively; dropped candidates in the gap
+ *      do not matter; runs of different recordings are never joined; a gap below 1 joins nothing);
+ *   4. order, status (the duration verdict on the joined run), offsets, capacity bound and output format are orcai_extract_labels' own.
+ * With high_thresholds == thresholds and every gap 0 the output is byte for byte that of orcai_extract_labels_per_label.  Twelve launches on `stream`
+ * (labels.hip): keep flags come from prefix counts of the hi rows, chain ends from nearest-set-bit scans over the kept candidates of a column; no lane
+ * walks a run, a gap or a chain, no atomics, two calls write the same bytes.
+ *   workspace  orcai_extract_labels_refined_workspace_bytes(L, R, S_total) bytes, 256-byte aligned (0 for sizes the call refuses).
+ * ORCAI_E_BADARG as orcai_extract_labels_per_label, and for a null high_thresholds or gap_rows.  ORCAI_E_UNSUPPORTED (nothing launched):
+ * S_total >= 2^31 (candidate rows are kept as int32). */
+int orcai_extract_labels_refined(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, const double* thresholds,
+                                 const double* high_thresholds, const int* gap_rows, const int* label_rank, const double* limits, double frame_seconds,
+                                 int tpo, int* runs, int64_t capacity, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+size_t orcai_extract_labels_refined_workspace_bytes(int L, int R, int64_t S_total);
+
 /* test.py:37-225: the integer counts behind the three tables of `orcai test` (compute_confusion_table, compute_misclassification_tables) for one
  * batch; the host forms the tables' float64 values from them (orcai_amd/device_tables.py).
  *   p, y       f32[M][L], M = snippets * time steps: probabilities, and labels in {0, 1, mask_value = -1}.  1 <= L <= 64.

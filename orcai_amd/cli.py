@@ -59,6 +59,12 @@ def cli():
 @click.option("--thresholds", "thresholds", type=FileR, default=None, show_default="None",
               help="JSON file {label: threshold} with one decision threshold per label (the thresholds.json of `orcai test --threshold-sweep`); "
                    "labels it does not name keep 0.5.")
+@click.option("--high-thresholds", "high_thresholds", default=None, show_default="None",
+              help="Hysteresis: a stretch above its label's threshold is an interval only if it reaches this high threshold somewhere. A number for all "
+                   "labels, or a JSON file {label: value}; labels it does not name keep high = threshold.")
+@click.option("--merge-gap", "merge_gap", default=None, show_default="None",
+              help="Gap merging: intervals of one label at most this many seconds apart are written as one. A number for all labels, or a JSON file "
+                   "{label: seconds}; labels it does not name keep 0.")
 @click.option("--model", "-m", type=click.Choice(INCLUDED_MODELS, case_sensitive=False), default="orcai-V1", show_default=True,
               help="Builtin model to use for prediction. Overridden if model_dir is given.")
 @click.option("--model_dir", "-md", "model_dir", type=DirR, default=None, show_default="use builtin model", help="Path to a model directory.")

@@ -27,6 +27,10 @@
 // The output position of every run is computed, never claimed: no atomics, two calls give the same bytes.  Recordings tile [0, S_total) in
 // ascending row order (the ragged overlap average's table), so the global order (row, stop, rank, label) is the per-recording order.
 //
+// orcai_extract_labels_refined (hysteresis thresholds and gap merging; the second half of this file) first computes, per row, in which
+// columns a FINAL run starts and stops -- candidates from the low mask, kept iff they hold a row above the high threshold, chains of kept candidates
+// at most g rows apart joined -- and then runs launches 3-6 on those two edge words (REFINED) instead of on the mask.
+//
 // Worst cases this was laid out against: one run as long as the recording (two edges in the whole matrix: nothing iterates over its length) and
 // all 64 columns alternating every row (every second row starts 64 runs: 64 readlane steps per such row, spread over all waves).
 #include <hip/hip_runtime.h>
@@ -84,9 +88,18 @@ struct Edges {
   int rel;          // the row, counted from its recording's first
 };
 
+// REFINED (orcai_extract_labels_refined's second half): `mask` holds the two edge words of every row, {starts, stops}, as refine_edges_kernel left them
+template <bool REFINED>
 __device__ __forceinline__ Edges row_edges(const u64* __restrict__ mask, const int64_t* __restrict__ table, int R, int64_t S_total, int64_t row) {
   Edges e = {0, 0, 0};
   if (row >= S_total) return e;
+  if (REFINED) {
+    e.start = mask[2 * row];
+    e.stop = mask[2 * row + 1];
+    if ((e.start | e.stop) == 0) return e;
+    e.rel = (int)(row - table[4 * locate(table, R, row) + 3]);
+    return e;
+  }
   const u64 m = mask[row];
   if (m == 0) return e;
   const int r = locate(table, R, row);  // m != 0: the row lies inside recording r (mask kernel)
@@ -164,13 +177,14 @@ __global__ __launch_bounds__(256) void labels_mask_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------- 3 count
+template <bool REFINED>
 __global__ __launch_bounds__(256) void labels_count_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
                                                             int64_t tiles, int64_t* __restrict__ counts) {
   __shared__ int wc[WAVES][2][64];
   __shared__ int wr[WAVES];
   const int64_t tile = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = lane_id();
-  const Edges e = row_edges(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
+  const Edges e = row_edges<REFINED>(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
   int cs = 0, ce = 0;
   for (int l = 0; l < L; ++l) {
     const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1);
@@ -222,13 +236,14 @@ __global__ __launch_bounds__(256) void labels_scan_kernel(int64_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- 5 stops
+template <bool REFINED>
 __global__ __launch_bounds__(256) void labels_stops_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
                                                             int64_t tiles, const int64_t* __restrict__ counts, int64_t colcap, int* __restrict__ stops) {
   __shared__ int wc[WAVES][64];
   __shared__ int64_t colbase[WAVES][64];
   const int64_t tile = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = lane_id();
-  const Edges e = row_edges(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
+  const Edges e = row_edges<REFINED>(mask, table, R, S_total, tile * ROW_TILE + threadIdx.x);
   int ce = 0;
   for (int l = 0; l < L; ++l) {
     const u64 be = __ballot((e.stop >> l) & 1);
@@ -254,6 +269,7 @@ __global__ __launch_bounds__(256) void labels_stops_kernel(const u64* __restrict
 }
 
 // ---------------------------------------------------------------- 6 emit
+template <bool REFINED>
 __global__ __launch_bounds__(256) void labels_emit_kernel(const u64* __restrict__ mask, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
                                                            int64_t tiles, const int64_t* __restrict__ counts, int64_t colcap,
                                                            const int* __restrict__ stops, const int* __restrict__ label_rank,
@@ -264,7 +280,7 @@ __global__ __launch_bounds__(256) void labels_emit_kernel(const u64* __restrict_
   const int64_t tile = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = lane_id();
   const int64_t row = tile * ROW_TILE + threadIdx.x;
-  const Edges e = row_edges(mask, table, R, S_total, row);
+  const Edges e = row_edges<REFINED>(mask, table, R, S_total, row);
   u64 mycol = 0;  // lane = column: the rows of this wave that start a run in it
   for (int l = 0; l < L; ++l) {
     const u64 bs = __ballot((e.start >> l) & 1);
@@ -359,17 +375,368 @@ int extract_labels(const double* agg, const double* cnt, int L, const int64_t* t
   const int sequences = 2 * L + 1;
   hipLaunchKernelGGL(labels_threshold_kernel, dim3((unsigned)R), block, 0, st, cnt, table, S_total, threshold, thresholds != nullptr, thr);
   hipLaunchKernelGGL(labels_mask_kernel, grid, block, 0, st, agg, L, table, R, S_total, thr, thresholds, mask);
-  hipLaunchKernelGGL(labels_count_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts);
+  hipLaunchKernelGGL(labels_count_kernel<false>, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts);
   hipLaunchKernelGGL(labels_scan_kernel, dim3((unsigned)((sequences + WAVES - 1) / WAVES)), block, 0, st, counts, sequences, a.tiles, offsets + R);
-  hipLaunchKernelGGL(labels_stops_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops);
-  hipLaunchKernelGGL(labels_emit_kernel, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops, label_rank, limits,
+  hipLaunchKernelGGL(labels_stops_kernel<false>, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops);
+  hipLaunchKernelGGL(labels_emit_kernel<false>, grid, block, 0, st, mask, L, table, R, S_total, a.tiles, counts, a.colcap, stops, label_rank, limits,
                      frame_seconds, tpo, reinterpret_cast<int4*>(runs), capacity, offsets);
   return (int)hipGetLastError();
+}
+
+// ================================================================ orcai_extract_labels_refined: hysteresis and gap merging
+// The first half works on the CANDIDATES, the maximal stretches of the low mask: launches 1-4 above with two masks (lo, and hi = above the high
+// threshold AND lo) and a third counted sequence per column, the hi rows.  Then
+//   R5 lists  the k-th start of column l writes its global row to cstart[l][k] and the number of hi rows of the column before it to hs[l][k]; the
+//             k-th stop writes cstop[l][k] and the number of hi rows up to and including it to he[l][k].  Candidate k is KEPT iff he > hs: a
+//             difference of two prefix counts, whatever the length of the candidate.
+//   R6 keep   one lane per candidate: the kept flags as 64-bit words (one ballot per wave), keepbits[l][k / 64].
+//   R7 words  one wave per column over its words, 64 per pass with a carry: the last non-zero word before every word and the first one behind it.
+//   R8 edges  one lane per row.  A kept candidate's start finds the kept candidate before it (the bits below its own in its word, else the top bit
+//             of the word R7 points to) and starts a final run unless that one lies in the same recording at most g rows away; its stop looks at
+//             the next kept candidate likewise.  Dropped candidates have no bit, so they are skipped, and a chain of any length has one start
+//             and one stop left: nothing walks it.  Two edge words per row.
+// The second half is launches 3-6 above on those edge words (REFINED): the same scans, the same order, the same 16 bytes per run.
+// Global rows are kept as int32, so S_total >= 2^31 is ORCAI_E_UNSUPPORTED here.
+struct RefineLayout {
+  size_t thr, lo, hi, cnt3, cstart, cstop, hs, he, keep, prevnz, nextnz, edges, counts, stops, dummy, total;
+  int64_t tiles, tiles1, colcap, words;
+};
+
+inline RefineLayout refine_layout(int L, int R, int64_t S_total) {
+  RefineLayout a;
+  a.tiles = (S_total + ROW_TILE - 1) / ROW_TILE;
+  a.tiles1 = a.tiles + 1;  // one slot behind the last tile: the exclusive scan leaves the column's total there
+  a.colcap = S_total / 2 + R;
+  a.words = (a.colcap + 63) / 64;
+  const size_t list = up256((size_t)L * (size_t)a.colcap * 4), word = up256((size_t)L * (size_t)a.words * 8);
+  a.thr = 0;                                                         // f64 [R]
+  a.lo = a.thr + up256((size_t)R * 8);                               // u64 [S_total]
+  a.hi = a.lo + up256((size_t)S_total * 8);                          // u64 [S_total]
+  a.cnt3 = a.hi + up256((size_t)S_total * 8);                        // i64 [3 L][tiles + 1]
+  a.cstart = a.cnt3 + up256((size_t)(3 * L) * a.tiles1 * 8);         // i32 [L][colcap], as cstop, hs, he and stops
+  a.cstop = a.cstart + list;
+  a.hs = a.cstop + list;
+  a.he = a.hs + list;
+  a.keep = a.he + list;                                              // u64 [L][words]
+  a.prevnz = a.keep + word;                                          // i32 [L][words], as nextnz
+  a.nextnz = a.prevnz + word;
+  a.edges = a.nextnz + word;                                         // u64 [S_total][2]
+  a.counts = a.edges + up256((size_t)S_total * 16);                  // i64 [2 L + 1][tiles]
+  a.stops = a.counts + up256((size_t)(2 * L + 1) * a.tiles * 8);
+  a.dummy = a.stops + list;                                          // i64: the total the first scan has no use for
+  a.total = a.dummy + 256;
+  return a;
+}
+
+// ---------------------------------------------------------------- R2 masks
+__global__ __launch_bounds__(256) void refine_mask_kernel(const double* __restrict__ agg, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                           const double* __restrict__ thr, const double* __restrict__ thresholds,
+                                                           const double* __restrict__ high, u64* __restrict__ lo, u64* __restrict__ hi) {
+  const int64_t row = (int64_t)blockIdx.x * ROW_TILE + threadIdx.x;
+  if (row >= S_total) return;
+  const int r = locate(table, R, row);
+  const int64_t s = row - table[4 * r + 3];
+  u64 a = 0, b = 0;
+  if (s >= 0 && s < table[4 * r + 2]) {
+    const double t = thr[r];  // max(cnt), NaN kept, 0: nothing is a one (labels_threshold_kernel, per_label)
+    const double* __restrict__ p = agg + row * L;
+    if (t != 0.0) {
+      for (int l = 0; l < L; ++l) {
+        const double v = p[l];
+        const bool low = v > thresholds[l] / t;
+        a |= (u64)low << l;
+        b |= (u64)(low && v > high[l] / t) << l;  // hi counts only where lo is set
+      }
+    }
+  }
+  lo[row] = a;
+  hi[row] = b;
+}
+
+// ---------------------------------------------------------------- R3 count: starts, stops and hi rows per column and tile
+__global__ __launch_bounds__(256) void refine_count_kernel(const u64* __restrict__ lo, const u64* __restrict__ hi, int L, const int64_t* __restrict__ table, int R,
+                                                            int64_t S_total, int64_t tiles, int64_t* __restrict__ cnt3) {
+  __shared__ int wc[WAVES][3][64];
+  const int64_t tile = blockIdx.x, row = tile * ROW_TILE + threadIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const Edges e = row_edges<false>(lo, table, R, S_total, row);
+  const u64 h = row < S_total ? hi[row] : 0;
+  int cs = 0, ce = 0, ch = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1), bh = __ballot((h >> l) & 1);
+    if (lane == l) {
+      cs = __popcll(bs);
+      ce = __popcll(be);
+      ch = __popcll(bh);
+    }
+  }
+  wc[wave][0][lane] = cs;
+  wc[wave][1][lane] = ce;
+  wc[wave][2][lane] = ch;
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 192) {
+    const int which = t >> 6, l = t & 63;
+    if (l < L) {
+      int sum = 0;
+      for (int w = 0; w < WAVES; ++w) sum += wc[w][which][l];
+      int64_t* __restrict__ seq = cnt3 + (int64_t)(which * L + l) * (tiles + 1);
+      seq[tile] = sum;
+      if (tile == 0) seq[tiles] = 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- R5 lists
+__global__ __launch_bounds__(256) void refine_lists_kernel(const u64* __restrict__ lo, const u64* __restrict__ hi, int L, const int64_t* __restrict__ table, int R,
+                                                            int64_t S_total, int64_t tiles, const int64_t* __restrict__ cnt3, int64_t colcap,
+                                                            int* __restrict__ cstart, int* __restrict__ cstop, int* __restrict__ hs, int* __restrict__ he) {
+  __shared__ int wc[WAVES][3][64];
+  __shared__ int64_t base[WAVES][3][64];
+  const int64_t tile = blockIdx.x, row = tile * ROW_TILE + threadIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const Edges e = row_edges<false>(lo, table, R, S_total, row);
+  const u64 h = row < S_total ? hi[row] : 0;
+  int cs = 0, ce = 0, ch = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1), bh = __ballot((h >> l) & 1);
+    if (lane == l) {
+      cs = __popcll(bs);
+      ce = __popcll(be);
+      ch = __popcll(bh);
+    }
+  }
+  wc[wave][0][lane] = cs;
+  wc[wave][1][lane] = ce;
+  wc[wave][2][lane] = ch;
+  __syncthreads();
+  for (int which = 0; which < 3; ++which) {
+    int64_t b = 0;
+    if (lane < L) {
+      b = cnt3[(int64_t)(which * L + lane) * (tiles + 1) + tile];
+      for (int w = 0; w < wave; ++w) b += wc[w][which][lane];
+    }
+    base[wave][which][lane] = b;
+  }
+  __syncthreads();
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1);
+    if ((bs | be) == 0) continue;
+    const u64 bh = __ballot((h >> l) & 1);
+    const int64_t hb = base[wave][2][l];
+    if ((e.start >> l) & 1) {
+      const int64_t k = base[wave][0][l] + __popcll(bs & lanes_below(lane));
+      if (k < colcap) {
+        cstart[(int64_t)l * colcap + k] = (int)row;
+        hs[(int64_t)l * colcap + k] = (int)(hb + __popcll(bh & lanes_below(lane)));
+      }
+    }
+    if ((e.stop >> l) & 1) {
+      const int64_t k = base[wave][1][l] + __popcll(be & lanes_below(lane));
+      if (k < colcap) {
+        cstop[(int64_t)l * colcap + k] = (int)row;
+        he[(int64_t)l * colcap + k] = (int)(hb + __popcll(bh & lanes_below(lane + 1)));
+      }
+    }
+  }
+}
+
+// candidates of column l: the total the scan left behind the last tile of its starts, never more than the lists hold
+__device__ __forceinline__ int64_t candidates(const int64_t* __restrict__ cnt3, int l, int64_t tiles, int64_t colcap) {
+  const int64_t n = cnt3[(int64_t)l * (tiles + 1) + tiles];
+  return n < colcap ? n : colcap;
+}
+
+// ---------------------------------------------------------------- R6 keep
+__global__ __launch_bounds__(256) void refine_keep_kernel(const int64_t* __restrict__ cnt3, int64_t tiles, int64_t colcap, int64_t words,
+                                                           const int* __restrict__ hs, const int* __restrict__ he, u64* __restrict__ keepbits) {
+  const int l = blockIdx.y;
+  const int64_t n = candidates(cnt3, l, tiles, colcap);
+  if ((int64_t)blockIdx.x * 256 >= n) return;  // words behind the last candidate are never read
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool kept = k < n && he[(int64_t)l * colcap + k] > hs[(int64_t)l * colcap + k];
+  const u64 b = __ballot(kept);
+  if (lane_id() == 0 && (k >> 6) < words) keepbits[(int64_t)l * words + (k >> 6)] = b;
+}
+
+// ---------------------------------------------------------------- R7 words: nearest non-zero word before and behind every word
+__global__ __launch_bounds__(256) void refine_words_kernel(const int64_t* __restrict__ cnt3, int L, int64_t tiles, int64_t colcap, int64_t words,
+                                                            const u64* __restrict__ keepbits, int* __restrict__ prevnz, int* __restrict__ nextnz) {
+  const int l = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (l >= L) return;  // a whole wave
+  const int lane = lane_id();
+  const int64_t nw = (candidates(cnt3, l, tiles, colcap) + 63) >> 6;
+  const u64* __restrict__ kb = keepbits + (int64_t)l * words;
+  const int NONE = 0x7fffffff;
+  int carry = -1;
+  for (int64_t first = 0; first < nw; first += SCAN_TILE) {
+    const int64_t w = first + lane;
+    int incl = (w < nw && kb[w] != 0) ? (int)w : -1;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(incl, d);
+      if (lane >= d) incl = o > incl ? o : incl;
+    }
+    int excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = -1;
+    excl = carry > excl ? carry : excl;
+    if (w < nw) prevnz[(int64_t)l * words + w] = excl;
+    const int last = __shfl(incl, 63);
+    carry = last > carry ? last : carry;
+  }
+  carry = NONE;
+  for (int64_t first = nw > 0 ? ((nw - 1) / SCAN_TILE) * SCAN_TILE : -1; first >= 0; first -= SCAN_TILE) {
+    const int64_t w = first + lane;
+    int incl = (w < nw && kb[w] != 0) ? (int)w : NONE;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_down(incl, d);
+      if (lane + d < 64) incl = o < incl ? o : incl;
+    }
+    int excl = __shfl_down(incl, 1);
+    if (lane == 63) excl = NONE;
+    excl = carry < excl ? carry : excl;
+    if (w < nw) nextnz[(int64_t)l * words + w] = excl == NONE ? -1 : excl;
+    const int head = __shfl(incl, 0);
+    carry = head < carry ? head : carry;
+  }
+}
+
+// ---------------------------------------------------------------- R8 edges
+__global__ __launch_bounds__(256) void refine_edges_kernel(const u64* __restrict__ lo, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                            int64_t tiles, const int64_t* __restrict__ cnt3, int64_t colcap, int64_t words,
+                                                            const int* __restrict__ cstart, const int* __restrict__ cstop, const u64* __restrict__ keepbits,
+                                                            const int* __restrict__ prevnz, const int* __restrict__ nextnz, const int* __restrict__ gap_rows,
+                                                            u64* __restrict__ edges) {
+  __shared__ int wc[WAVES][2][64];
+  __shared__ int64_t base[WAVES][2][64];
+  const int64_t tile = blockIdx.x, row = tile * ROW_TILE + threadIdx.x;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const Edges e = row_edges<false>(lo, table, R, S_total, row);
+  int cs = 0, ce = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1);
+    if (lane == l) {
+      cs = __popcll(bs);
+      ce = __popcll(be);
+    }
+  }
+  wc[wave][0][lane] = cs;
+  wc[wave][1][lane] = ce;
+  __syncthreads();
+  for (int which = 0; which < 2; ++which) {
+    int64_t b = 0;
+    if (lane < L) {
+      b = cnt3[(int64_t)(which * L + lane) * (tiles + 1) + tile];
+      for (int w = 0; w < wave; ++w) b += wc[w][which][lane];
+    }
+    base[wave][which][lane] = b;
+  }
+  __syncthreads();
+  int64_t first = 0, last = -1;  // the recording of this row
+  if (e.start | e.stop) {
+    const int r = locate(table, R, row);
+    first = table[4 * r + 3];
+    last = first + table[4 * r + 2] - 1;
+  }
+  u64 fs = 0, fe = 0;
+  for (int l = 0; l < L; ++l) {
+    const u64 bs = __ballot((e.start >> l) & 1), be = __ballot((e.stop >> l) & 1);
+    if ((bs | be) == 0) continue;
+    const u64* __restrict__ kb = keepbits + (int64_t)l * words;
+    const int64_t g = gap_rows[l];
+    if ((e.start >> l) & 1) {
+      const int64_t k = base[wave][0][l] + __popcll(bs & lanes_below(lane));
+      const u64 word = k < colcap ? kb[k >> 6] : 0;
+      if ((word >> (k & 63)) & 1) {
+        const u64 below = word & lanes_below((int)(k & 63));
+        int64_t pk = -1;  // the kept candidate before this one
+        if (below) {
+          pk = (k & ~(int64_t)63) + 63 - __builtin_clzll(below);
+        } else {
+          const int pw = prevnz[(int64_t)l * words + (k >> 6)];
+          if (pw >= 0) pk = (int64_t)pw * 64 + 63 - __builtin_clzll(kb[pw]);
+        }
+        bool join = false;
+        if (pk >= 0) {
+          const int64_t p = cstop[(int64_t)l * colcap + pk];
+          join = p >= first && row - p - 1 <= g;
+        }
+        if (!join) fs |= 1ull << l;
+      }
+    }
+    if ((e.stop >> l) & 1) {
+      const int64_t k = base[wave][1][l] + __popcll(be & lanes_below(lane));
+      const u64 word = k < colcap ? kb[k >> 6] : 0;
+      if ((word >> (k & 63)) & 1) {
+        const u64 above = word & ~lanes_below((int)(k & 63) + 1);
+        int64_t nk = -1;  // the kept candidate behind this one
+        if (above) {
+          nk = (k & ~(int64_t)63) + __builtin_ctzll(above);
+        } else {
+          const int nw = nextnz[(int64_t)l * words + (k >> 6)];
+          if (nw >= 0) nk = (int64_t)nw * 64 + __builtin_ctzll(kb[nw]);
+        }
+        bool join = false;
+        if (nk >= 0) {
+          const int64_t q = cstart[(int64_t)l * colcap + nk];
+          join = q <= last && q - row - 1 <= g;
+        }
+        if (!join) fe |= 1ull << l;
+      }
+    }
+  }
+  if (row < S_total) {
+    edges[2 * row] = fs;
+    edges[2 * row + 1] = fe;
+  }
 }
 
 }  // namespace
 
 extern "C" {
+
+size_t orcai_extract_labels_refined_workspace_bytes(int L, int R, int64_t S_total) {
+  if (L < 1 || L > 64 || R < 1 || S_total < 1 || S_total > 0x7fffffff) return 0;
+  return refine_layout(L, R, S_total).total;
+}
+
+int orcai_extract_labels_refined(const double* agg, const double* cnt, int L, const int64_t* table, int R, int64_t S_total, const double* thresholds,
+                                 const double* high_thresholds, const int* gap_rows, const int* label_rank, const double* limits, double frame_seconds,
+                                 int tpo, int* runs, int64_t capacity, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!agg || !cnt || !table || !label_rank || !runs || !offsets || !workspace || !thresholds || !high_thresholds || !gap_rows) return ORCAI_E_BADARG;
+  if (L < 1 || L > 64 || R < 1 || S_total < 1 || capacity < 0 || tpo < 1) return ORCAI_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(runs) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return ORCAI_E_BADARG;
+  if (S_total > 0x7fffffff) return ORCAI_E_UNSUPPORTED;  // global rows are int32 in the candidate lists
+  const RefineLayout a = refine_layout(L, R, S_total);
+  if (workspace_bytes < a.total) return ORCAI_E_BADARG;
+  char* ws = static_cast<char*>(workspace);
+  double* thr = reinterpret_cast<double*>(ws + a.thr);
+  u64 *lo = reinterpret_cast<u64*>(ws + a.lo), *hi = reinterpret_cast<u64*>(ws + a.hi), *keepbits = reinterpret_cast<u64*>(ws + a.keep);
+  u64* edges = reinterpret_cast<u64*>(ws + a.edges);
+  int64_t *cnt3 = reinterpret_cast<int64_t*>(ws + a.cnt3), *counts = reinterpret_cast<int64_t*>(ws + a.counts);
+  int64_t* dummy = reinterpret_cast<int64_t*>(ws + a.dummy);
+  int *cstart = reinterpret_cast<int*>(ws + a.cstart), *cstop = reinterpret_cast<int*>(ws + a.cstop), *hs = reinterpret_cast<int*>(ws + a.hs);
+  int *he = reinterpret_cast<int*>(ws + a.he), *prevnz = reinterpret_cast<int*>(ws + a.prevnz), *nextnz = reinterpret_cast<int*>(ws + a.nextnz);
+  int* stops = reinterpret_cast<int*>(ws + a.stops);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)a.tiles), block(ROW_TILE);
+  const auto waves = [](int sequences) { return dim3((unsigned)((sequences + WAVES - 1) / WAVES)); };
+  hipLaunchKernelGGL(labels_threshold_kernel, dim3((unsigned)R), block, 0, st, cnt, table, S_total, 0.0, true, thr);
+  hipLaunchKernelGGL(refine_mask_kernel, grid, block, 0, st, agg, L, table, R, S_total, thr, thresholds, high_thresholds, lo, hi);
+  hipLaunchKernelGGL(refine_count_kernel, grid, block, 0, st, lo, hi, L, table, R, S_total, a.tiles, cnt3);
+  hipLaunchKernelGGL(labels_scan_kernel, waves(3 * L), block, 0, st, cnt3, 3 * L, a.tiles1, dummy);
+  hipLaunchKernelGGL(refine_lists_kernel, grid, block, 0, st, lo, hi, L, table, R, S_total, a.tiles, cnt3, a.colcap, cstart, cstop, hs, he);
+  hipLaunchKernelGGL(refine_keep_kernel, dim3((unsigned)((a.colcap + 255) / 256), (unsigned)L), block, 0, st, cnt3, a.tiles, a.colcap, a.words, hs, he, keepbits);
+  hipLaunchKernelGGL(refine_words_kernel, waves(L), block, 0, st, cnt3, L, a.tiles, a.colcap, a.words, keepbits, prevnz, nextnz);
+  hipLaunchKernelGGL(refine_edges_kernel, grid, block, 0, st, lo, L, table, R, S_total, a.tiles, cnt3, a.colcap, a.words, cstart, cstop, keepbits, prevnz, nextnz,
+                     gap_rows, edges);
+  hipLaunchKernelGGL(labels_count_kernel<true>, grid, block, 0, st, edges, L, table, R, S_total, a.tiles, counts);
+  hipLaunchKernelGGL(labels_scan_kernel, waves(2 * L + 1), block, 0, st, counts, 2 * L + 1, a.tiles, offsets + R);
+  hipLaunchKernelGGL(labels_stops_kernel<true>, grid, block, 0, st, edges, L, table, R, S_total, a.tiles, counts, a.colcap, stops);
+  hipLaunchKernelGGL(labels_emit_kernel<true>, grid, block, 0, st, edges, L, table, R, S_total, a.tiles, counts, a.colcap, stops, label_rank, limits,
+                     frame_seconds, tpo, reinterpret_cast<int4*>(runs), capacity, offsets);
+  return (int)hipGetLastError();
+}
+
 
 size_t orcai_extract_labels_workspace_bytes(int L, int R, int64_t S_total) {
   if (L < 1 || L > 64 || R < 1 || S_total < 1) return 0;

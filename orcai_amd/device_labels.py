@@ -93,12 +93,12 @@ def _device_constants(device, calls, label_suffix, call_duration_limits):
     return _constants[key]
 
 
-def _device_thresholds(device, thresholds, L: int) -> torch.Tensor:
-    """f64 [L] on the device, uploaded once per (device, values)."""
-    values = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+def _device_thresholds(device, thresholds, L: int, dtype=np.float64, what: str = "thresholds") -> torch.Tensor:
+    """f64 [L] (or `dtype`) on the device, uploaded once per (device, values)."""
+    values = np.ascontiguousarray(thresholds, dtype=dtype).reshape(-1)
     if len(values) != L:
-        raise ValueError(f"thresholds: one per label wanted ({L}), got {len(values)}")
-    key = (str(device), "thresholds", values.tobytes())
+        raise ValueError(f"{what}: one per label wanted ({L}), got {len(values)}")
+    key = (str(device), what, values.tobytes())
     if key not in _constants:
         if len(_constants) > 64:
             _constants.clear()
@@ -142,12 +142,13 @@ class PendingLabels:
 
 def extract_labels_device(agg_dev: torch.Tensor, cnt_dev: torch.Tensor, table_dev: torch.Tensor, R: int, calls, label_suffix: str | None,
                           time_steps_per_output_step: int, delta_t: float, call_duration_limits=None, threshold: float = 0.5,
-                          thresholds=None) -> PendingLabels:
+                          thresholds=None, high_thresholds=None, gap_rows=None) -> PendingLabels:
     """Queue orcai_extract_labels on the current stream for the averaged probabilities agg_dev f64 [S_total][L] / cnt_dev f64 [S_total] of the R
     recordings of table_dev (int64 [R][4] on the device, orcai_overlap_average_ragged's table; one recording: [[0, n, S, 0]]), and the copy of its
     result to pinned memory behind one event.  call_duration_limits (a dict or a JSON path) makes the kernel judge every interval as
     filter_predictions does with delta_t seconds per frame.  thresholds (L floats, one per label): orcai_extract_labels_per_label in place of the
-    scalar `threshold`.
+    scalar `threshold`.  high_thresholds (L floats) and gap_rows (L ints, output steps; refine.gap_rows): hysteresis and gap merging, DESIGN 4.15 --
+    orcai_extract_labels_refined when either is given (the other: high = the threshold, gap 0), the calls above untouched when neither is.
 
     What travels to the host: the R + 1 offsets and the first EAGER_RUNS runs, in ONE copy whose size does not depend on S_total or L.  The device
     buffer holds the kernel's capacity bound (L * ceil(S_total / 2) + R runs, the size of agg itself), so nothing is ever dropped; when more than
@@ -161,12 +162,22 @@ def extract_labels_device(agg_dev: torch.Tensor, cnt_dev: torch.Tensor, table_de
     capacity = L * ((S_total + 1) // 2) + R
     header = -(-2 * (R + 1) // 4) * 4  # int32 words in front of the runs: the int64 offsets, padded to 16 bytes
     out = torch.empty(header + 4 * capacity, dtype=torch.int32, device=agg_dev.device)
-    ws_bytes = int(lib.orcai_extract_labels_workspace_bytes(L, R, S_total))
+    refined = high_thresholds is not None or gap_rows is not None
+    ws_bytes = int((lib.orcai_extract_labels_refined_workspace_bytes if refined else lib.orcai_extract_labels_workspace_bytes)(L, R, S_total))
+    if refined and ws_bytes == 0:
+        raise ValueError(f"label extraction: {S_total} output rows, {L} labels, {R} recordings is outside what the kernel takes")
     workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=agg_dev.device)
     tail = (N.ptr(rank), None if limits is None else N.ptr(limits), float(delta_t), int(time_steps_per_output_step), out.data_ptr() + 4 * header, capacity,
             out.data_ptr(), workspace.data_ptr(), ws_bytes, N.stream_ptr())
     per_label = None
-    if thresholds is None:
+    if refined:
+        per_label = _device_thresholds(agg_dev.device, np.full(L, float(threshold)) if thresholds is None else thresholds, L)
+        high = per_label if high_thresholds is None else _device_thresholds(agg_dev.device, high_thresholds, L, what="high_thresholds")
+        gaps = _device_thresholds(agg_dev.device, np.zeros(L) if gap_rows is None else gap_rows, L, dtype=np.int32, what="gap_rows")
+        N.check(lib.orcai_extract_labels_refined(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, N.ptr(per_label), N.ptr(high), N.ptr(gaps), *tail),
+                "orcai_extract_labels_refined")
+        per_label = (per_label, high, gaps)
+    elif thresholds is None:
         N.check(lib.orcai_extract_labels(N.ptr(agg_dev), N.ptr(cnt_dev), L, N.ptr(table_dev), R, S_total, float(threshold), *tail), "orcai_extract_labels")
     else:
         per_label = _device_thresholds(agg_dev.device, thresholds, L)

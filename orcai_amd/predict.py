@@ -109,19 +109,30 @@ class PendingAggregate:
         return [(agg[row : row + rows], cnt[row : row + rows]) for row, rows in slices]
 
 
-def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True, thresholds=None) -> dict:
+def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True, thresholds=None,
+               refine=None) -> dict:
     """What the launch half needs to queue orcai_extract_labels behind the overlap average (device_labels=...): the label names, the suffix, the
     duration limits the kernel is to judge by (None: no filter), whether the averaged probabilities are still wanted on the host, and the per-label
-    thresholds (L floats; None: 0.5 for every label through the scalar entry point)."""
+    thresholds (L floats; None: 0.5 for every label through the scalar entry point).  refine (threshold_sweep.resolve_refinement's dict, or None):
+    the high thresholds and the merge gaps in seconds, for orcai_extract_labels_refined."""
     return {"calls": orcai_parameter["calls"], "label_suffix": label_suffix, "call_duration_limits": call_duration_limits, "probabilities": probabilities,
-            "thresholds": thresholds}
+            "thresholds": thresholds, "refine": refine}
 
 
 def _queue_labels(spec: dict, agg: torch.Tensor, cnt: torch.Tensor, table: torch.Tensor, R: int, n_filters: int, delta_t: float):
     from orcai_amd.device_labels import extract_labels_device
 
     return extract_labels_device(agg, cnt, table, R, spec["calls"], spec["label_suffix"], 2**n_filters, delta_t, call_duration_limits=spec["call_duration_limits"],
-                                 thresholds=spec.get("thresholds"))
+                                 thresholds=spec.get("thresholds"), **_refine_arguments(spec.get("refine"), 2**n_filters, delta_t, "high_thresholds", "gap_rows"))
+
+
+def _refine_arguments(refine: dict | None, time_steps_per_output_step: int, delta_t: float, high_name: str, gap_name: str) -> dict:
+    """The two keyword arguments of either route for a resolved refinement (none for None): the high thresholds, and the gaps in output steps."""
+    if refine is None:
+        return {}
+    from orcai_amd.refine import gap_rows
+
+    return {high_name: refine["high"], gap_name: gap_rows(refine["gap_seconds"], time_steps_per_output_step, delta_t)}
 
 
 def aggregate_predictions_device(predictions: torch.Tensor, n_frames: int, snippet_length: int, n_filters: int, wait: bool = True,
@@ -231,18 +242,50 @@ def compute_aggregated_predictions(recording_path: Path, spectrogram, model, orc
                                         delta_t=delta_t)
 
 
-def compute_binary_predictions(aggregated_predictions: np.ndarray, overlap_count: np.ndarray, calls: list[str], threshold=0.5):
-    """predict.py:298-317.  threshold: a float, or a sequence of one threshold per label (column l is cut at threshold[l] / max(count))."""
+def compute_binary_predictions(aggregated_predictions: np.ndarray, overlap_count: np.ndarray, calls: list[str], threshold=0.5, high_threshold=None,
+                               merge_gap_rows=None):
+    """predict.py:298-317.  threshold: a float, or a sequence of one threshold per label (column l is cut at threshold[l] / max(count)).
+    high_threshold (>= threshold) and merge_gap_rows (output steps), each a scalar or one per label: hysteresis and gap merging, refine.py's contract.
+    A stretch above `threshold` counts only if it reaches high_threshold somewhere, and kept stretches of one label at most merge_gap_rows apart are
+    one interval.  Neither given: the reference's cut, untouched."""
     if not np.isscalar(threshold):
         threshold = np.asarray(threshold, dtype=np.float64)
         if threshold.shape != (len(calls),):
             raise ValueError(f"compute_binary_predictions: one threshold per label wanted ({len(calls)}), got shape {threshold.shape}")
+    if high_threshold is not None or merge_gap_rows is not None:
+        return _refined_binary_predictions(aggregated_predictions, overlap_count, calls, threshold, high_threshold, merge_gap_rows)
     adjusted_threshold = threshold / np.max(overlap_count)
     binary_prediction = (aggregated_predictions > adjusted_threshold).astype(int)
     row_starts, row_stops, label_names = [], [], []
     for i, label_name in enumerate(calls):
         if binary_prediction[:, i].sum() > 0:  # == the reference's builtin sum(), vectorised
             row_start, row_stop = find_consecutive_ones(binary_prediction[:, i])
+            row_starts += list(row_start)
+            row_stops += list(row_stop)
+            label_names += [label_name] * len(row_start)
+    return row_starts, row_stops, label_names
+
+
+def _refined_binary_predictions(aggregated_predictions, overlap_count, calls, threshold, high_threshold, merge_gap_rows):
+    """compute_binary_predictions with hysteresis and gap merging: numpy column operations per label (refine.refined_runs)."""
+    from orcai_amd.refine import per_label, refined_runs
+
+    L = len(calls)
+    low = per_label(threshold, L, "compute_binary_predictions: threshold", np.float64)
+    high = low if high_threshold is None else per_label(high_threshold, L, "compute_binary_predictions: high_threshold", np.float64)
+    gaps = per_label(0 if merge_gap_rows is None else merge_gap_rows, L, "compute_binary_predictions: merge_gap_rows", np.int64)
+    row_starts, row_stops, label_names = [], [], []
+    if len(overlap_count) == 0:
+        return row_starts, row_stops, label_names
+    top = np.max(overlap_count)
+    with np.errstate(divide="ignore", invalid="ignore"):  # a zero maximum: +inf (or NaN for a zero threshold), nothing is above it
+        lo = aggregated_predictions > low / top
+        hi = aggregated_predictions > high / top
+    if top == 0:
+        lo[:] = False
+    for i, label_name in enumerate(calls):
+        if lo[:, i].any():
+            row_start, row_stop = refined_runs(lo[:, i], hi[:, i], int(gaps[i]))
             row_starts += list(row_start)
             row_stops += list(row_stop)
             label_names += [label_name] * len(row_start)
@@ -296,9 +339,10 @@ def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_pa
     return {"pending": pending, "delta_t": delta_t, "orcai_parameter": orcai_parameter}
 
 
-def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None):
+def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None):
     """Second half of predict_wav (host): threshold, runs of ones, label table (predict.py:298-340).  thresholds: one per label (L floats) in place
-    of 0.5 on the host route; labels that came from the device were cut by the thresholds of their label_spec."""
+    of 0.5 on the host route; refine: resolve_refinement's dict, hysteresis and gap merging on the host route.  Labels that came from the device
+    were cut by the thresholds and the refinement of their label_spec."""
     pending, orcai_parameter = state["pending"], state["orcai_parameter"]
     aggregated_predictions, overlap_count = pending.result() if isinstance(pending, PendingAggregate) else pending
     device_result = state.get("device_labels_result")
@@ -307,11 +351,13 @@ def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = M
     if device_result is not None:
         return _finish_device_labels(device_result, pending.labels if isinstance(pending, PendingAggregate) else state["device_labels"],
                                      aggregated_predictions, state["delta_t"], msgr)
+    time_steps_per_output_step = 2 ** len(orcai_parameter["model"]["filters"])
     row_starts, row_stops, label_names = compute_binary_predictions(aggregated_predictions=aggregated_predictions, overlap_count=overlap_count,
                                                                     calls=orcai_parameter["calls"],
-                                                                    threshold=0.5 if thresholds is None else thresholds)
+                                                                    threshold=0.5 if thresholds is None else thresholds,
+                                                                    **_refine_arguments(refine, time_steps_per_output_step, state["delta_t"],
+                                                                                        "high_threshold", "merge_gap_rows"))
     msgr.info("converting binary predictions into start and stop frames")
-    time_steps_per_output_step = 2 ** len(orcai_parameter["model"]["filters"])
     predicted_labels = compute_labels(row_starts, row_stops, label_names, time_steps_per_output_step=time_steps_per_output_step, label_suffix=label_suffix)
     msgr.info(f"found {len(predicted_labels)} acoustic signals")
     msgr.success("Prediction finished.")
@@ -331,15 +377,18 @@ def _finish_device_labels(device_result: tuple, labels, aggregated_predictions, 
 
 
 def predict_wav(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*",
-                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False, thresholds=None):
+                msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False, thresholds=None,
+                high_thresholds=None, merge_gap=None):
     """(predicted_labels DataFrame, aggregated_predictions ndarray, delta_t) for one wav file (predict.py:367-471).  device_labels=True: the label
-    table comes from orcai_extract_labels (the same table).  thresholds: a dict {label: threshold} or the path of a thresholds.json."""
-    from orcai_amd.threshold_sweep import resolve_thresholds
+    table comes from orcai_extract_labels (the same table).  thresholds: a dict {label: threshold} or the path of a thresholds.json.
+    high_thresholds, merge_gap (seconds): a number, a dict {label: value} or the path of such a JSON file, as for predict()."""
+    from orcai_amd.threshold_sweep import resolve_refinement, resolve_thresholds
 
     thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
+    refine = resolve_refinement(high_thresholds, merge_gap, thresholds, orcai_parameter["calls"])
     state = predict_wav_launch(recording_path, channel, model, orcai_parameter, shape, msgr=msgr, progressbar=progressbar,
-                               device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds) if device_labels else None)
-    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
+                               device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine) if device_labels else None)
+    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
 
 
 def _too_short(n_frames: int, snippet_length: int) -> ValueError:
@@ -402,7 +451,7 @@ def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_fram
         yield queue()
 
 
-def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> list:
+def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> list:
     """The host half of one batch state: [(key, predict_wav's triple or the exception the recording raised)], the failed ones first."""
     out = list(state["failed"])
     if state["pending"] is not None:
@@ -411,7 +460,7 @@ def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messen
         for (key, delta_t), pair, device_result in zip(state["members"], state["pending"].results(), label_results):
             out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"],
                                                  "device_labels_result": device_result, "device_labels": labels}, label_suffix=label_suffix, msgr=msgr,
-                                                thresholds=thresholds)))
+                                                thresholds=thresholds, refine=refine)))
     return out
 
 
@@ -438,22 +487,24 @@ def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_fr
                            device_labels=device_labels)
 
 
-def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> list:
+def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> list:
     """Second half (host): [(index into items, (predicted_labels, aggregated_predictions, delta_t) or the exception that item raised)]."""
-    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
+    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
 
 
 def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*", max_frames: int | None = None,
-                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False, thresholds=None) -> list:
+                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False, thresholds=None, high_thresholds=None, merge_gap=None) -> list:
     """predict_wav for every (path, channel) of `items`, several recordings per detector pass: batches of at most max_frames spectrogram frames
     (batch.DEFAULT_MAX_FRAMES: an hour's worth) go through ONE forward pass and ONE overlap average, the host half of a batch runs beside the GPU
     half of the next.  Returns, per item, what predict_wav returns for it -- the same label table, the same f64 probabilities, the same delta_t --
     or the exception it raised (a missing file, a recording shorter than one snippet); the other items are unaffected.
     A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item.
-    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables).  thresholds: as for predict_wav."""
-    from orcai_amd.threshold_sweep import resolve_thresholds
+    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables).  thresholds, high_thresholds, merge_gap:
+    as for predict_wav."""
+    from orcai_amd.threshold_sweep import resolve_refinement, resolve_thresholds
 
     thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
+    refine = resolve_refinement(high_thresholds, merge_gap, thresholds, orcai_parameter["calls"])
     listed = None if thresholds is None else dict(zip(orcai_parameter["calls"], thresholds))
     items = list(items)
     results = [None] * len(items)
@@ -461,17 +512,18 @@ def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix:
         for i, (path, channel) in enumerate(items):
             try:
                 results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr, device_labels=device_labels,
-                                         thresholds=listed)
+                                         thresholds=listed, high_thresholds=high_thresholds, merge_gap=merge_gap)
             except Exception as e:
                 results[i] = e
         return results
 
     def finish(state):
-        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds):
+        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine):
             results[i] = result
 
     _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr,
-                                     device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds) if device_labels else None), finish)
+                                     device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine) if device_labels else None),
+                 finish)
     return results
 
 
@@ -540,9 +592,9 @@ def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_prob
 
 
 def _finish_recording(state: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                      msgr: Messenger = Messenger(verbosity=0), thresholds=None) -> None:
+                      msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> None:
     """predict.py:576-632: the host half -- labels, optional duration filter, files."""
-    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds)
+    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
     _save_recording(result, state["output_path"], state["orcai_parameter"], save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
                     label_suffix=label_suffix, msgr=msgr)
 
@@ -550,17 +602,17 @@ def _finish_recording(state: dict, save_probabilities: bool = False, call_durati
 def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
                       overwrite: bool = False, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
                       label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None,
-                      thresholds=None) -> None:
+                      thresholds=None, refine=None) -> None:
     """predict.py:534-632."""
     state = _launch_recording(recording_path, channel, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite, msgr=msgr,
                               progressbar=progressbar, device_labels=device_labels)
     _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
-                      thresholds=thresholds)
+                      thresholds=thresholds, refine=refine)
 
 
 def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default", overwrite: bool = False,
                           save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None, thresholds=None) -> None:
+                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None, thresholds=None, refine=None) -> None:
     """predict(channel="all"): one read and one upload of the file, every channel decoded by orcai_pcm_decode_planar, the channels as ONE batch through
     the detector.  One output file per channel, under the name -- and with the bytes -- predict(channel=c) gives it."""
     from orcai_amd.spectrogram import load_wav_all
@@ -573,7 +625,7 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
     errors = []
 
     def finish(state):
-        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds):
+        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine):
             if isinstance(result, Exception):
                 errors.append(result)
                 continue
@@ -588,7 +640,7 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
 
 def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter: dict, shape: dict, batch_frames: int, overwrite: bool,
                            save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm,
-                           device_labels: dict | None = None, thresholds=None) -> None:
+                           device_labels: dict | None = None, thresholds=None, refine=None) -> None:
     """Table mode with batch_frames > 0: the rows of the table in order, grouped into detector passes of at most batch_frames spectrogram frames.
     Per recording the output path, the overwrite check, the files and the error line are those of the one-by-one loop; one batch deep, so the host
     half of a batch (labels, files) runs beside the GPU half of the next."""
@@ -613,7 +665,7 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
             yield i, lambda path=path, channel=channel: load_wav(path, sr, channel, quiet)
 
     def finish(state):
-        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet, thresholds=thresholds):
+        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet, thresholds=thresholds, refine=refine):
             try:
                 if isinstance(result, Exception):
                     raise result
@@ -628,7 +680,8 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
 def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str | Path = DEFAULT_MODEL_DIR, output_path: str | Path = "default",
             overwrite: bool = False, save_probabilities: bool = False, base_dir_recording: str | Path | None = None,
             call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None,
-            batch_frames: int = 0, device_labels: bool = False, thresholds: str | Path | dict | None = None) -> None:
+            batch_frames: int = 0, device_labels: bool = False, thresholds: str | Path | dict | None = None,
+            high_thresholds: float | str | Path | dict | None = None, merge_gap: float | str | Path | dict | None = None) -> None:
     """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757).
     channel="all" (a wav file): every channel of the file from one read of its bytes, one output file per channel.
     batch_frames > 0 (a table): consecutive recordings go through the detector in batches of at most batch_frames spectrogram frames
@@ -639,29 +692,37 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     Ignored for a model without the native path.
     thresholds: a dict {label: threshold} or the path of such a JSON file (the thresholds.json of ``orcai test --threshold-sweep``): label l is cut at
     thresholds[l] in place of 0.5 on every route, with device_labels or without.  Labels it does not name keep 0.5; a label the model does not have
-    raises ValueError before the model is loaded."""
+    raises ValueError before the model is loaded.
+    high_thresholds, merge_gap: hysteresis and gap merging, each a number for all labels, a dict {label: value} or the path of such a
+    JSON file.  A stretch above its label's threshold is an interval only if it reaches the label's high threshold somewhere, and kept intervals of
+    one label at most merge_gap seconds apart are written as one.  Labels not named keep high = threshold and gap 0; both off (None) is the cut above
+    alone, through the calls made without them.  An unknown label, a negative gap or a high threshold below the label's threshold raises ValueError
+    before the model is loaded.  Every route, with device_labels (orcai_extract_labels_refined) or without: the same bytes."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Predicting calls")
     model_dir = Path(model_dir)
     recording_path = Path(recording_path)
-    if thresholds is not None:
-        from orcai_amd.threshold_sweep import resolve_thresholds
+    refine = None
+    if thresholds is not None or high_thresholds is not None or merge_gap is not None:
+        from orcai_amd.threshold_sweep import resolve_refinement, resolve_thresholds
 
-        thresholds = resolve_thresholds(thresholds, read_json(model_dir.joinpath("orcai_parameter.json"))["calls"])
+        calls = read_json(model_dir.joinpath("orcai_parameter.json"))["calls"]
+        thresholds = resolve_thresholds(thresholds, calls)
+        refine = resolve_refinement(high_thresholds, merge_gap, thresholds, calls)
     msgr.part(f"Loading model: {model_dir.stem}")
     model, orcai_parameter, shape = load_orcai_model(model_dir)
     spec = None
     if device_labels and hasattr(model, "predict_spectrogram"):
-        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities, thresholds=thresholds)
+        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities, thresholds=thresholds, refine=refine)
     if recording_path.suffix == ".wav" and channel == "all" and hasattr(model, "predict_batch"):
         return _predict_all_channels(recording_path, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite,
                                      save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
-                                     device_labels=spec, thresholds=thresholds)
+                                     device_labels=spec, thresholds=thresholds, refine=refine)
     if recording_path.suffix == ".wav":
         return _predict_and_save(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape,
                                  output_path=output_path, overwrite=overwrite, save_probabilities=save_probabilities,
                                  call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None, device_labels=spec,
-                                 thresholds=thresholds)
+                                 thresholds=thresholds, refine=refine)
     elif recording_path.suffix == ".csv":
         recording_table = pd.read_csv(recording_path)
     else:
@@ -691,7 +752,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     if batch_frames > 0 and hasattr(model, "predict_batch"):
         _predict_table_batched(recording_table, model, orcai_parameter, shape, batch_frames, overwrite=overwrite, save_probabilities=save_probabilities,
                                call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar, device_labels=spec,
-                               thresholds=thresholds)
+                               thresholds=thresholds, refine=refine)
         wavio.set_prefetcher(None)
         msgr.success("Predictions finished.")
         return
@@ -702,7 +763,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
         j, state = entry
         try:
             _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=quiet,
-                              thresholds=thresholds)
+                              thresholds=thresholds, refine=refine)
         except Exception as e:  # predict.py:752-755: log and continue with the next recording
             msgr.error(f"Error predicting {recording_table.loc[j, 'recording']}: {e.args[0] if e.args else e}")
 

@@ -142,6 +142,47 @@ def resolve_thresholds(thresholds, calls: list[str]) -> list[float] | None:
     return [float(thresholds.get(call, DEFAULT_THRESHOLD)) for call in calls]
 
 
+def _label_values(value, calls: list[str], what: str) -> dict:
+    """{label: float} from a number (every label), a dict {label: value} or the path of such a JSON file; a label the model does not have raises."""
+    if isinstance(value, str):
+        try:
+            value = float(value)
+        except ValueError:
+            pass
+    if isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):
+        return {call: float(value) for call in calls}
+    if not isinstance(value, dict):
+        from orcai_amd.io import read_json
+
+        value = read_json(value)
+    if not isinstance(value, dict):
+        return _label_values(value, calls, what)  # a JSON file holding one number
+    unknown = sorted(str(k) for k in value if k not in calls)
+    if unknown:
+        raise ValueError(f"{what} name labels the model does not have: {', '.join(unknown)} (its labels: {', '.join(calls)})")
+    return {k: float(v) for k, v in value.items()}
+
+
+def resolve_refinement(high_thresholds, merge_gap, thresholds: list[float] | None, calls: list[str]) -> dict | None:
+    """`orcai predict --high-thresholds --merge-gap` in the order of `calls`: {"high": L floats, "gap_seconds": L floats}, or None when neither is
+    given.  Each is a number (all labels), a dict {label: value} or the path of such a JSON file; `thresholds` is resolve_thresholds' answer (None:
+    0.5 everywhere).  Labels not named get high = their threshold and gap 0.  Raises ValueError for a label the model does not have, a gap that is
+    not >= 0 and a high threshold that is not >= the label's threshold."""
+    if high_thresholds is None and merge_gap is None:
+        return None
+    low = [DEFAULT_THRESHOLD] * len(calls) if thresholds is None else [float(t) for t in thresholds]
+    named_high = {} if high_thresholds is None else _label_values(high_thresholds, calls, "high thresholds")
+    named_gap = {} if merge_gap is None else _label_values(merge_gap, calls, "merge gaps")
+    high = [named_high.get(call, t) for call, t in zip(calls, low)]
+    gap = [named_gap.get(call, 0.0) for call in calls]
+    for call, t, h, g in zip(calls, low, high, gap):
+        if not h >= t:
+            raise ValueError(f"high threshold of {call} ({h}) is below its threshold ({t})")
+        if not g >= 0:
+            raise ValueError(f"merge gap of {call} ({g}) is negative")
+    return {"high": high, "gap_seconds": gap}
+
+
 def report_from_hist(hist: np.ndarray, thresholds, label_names: list[str]) -> dict:
     """What `orcai test --threshold-sweep` writes for one dataset: {"sweep": DataFrame, "auc": {...}, "thresholds": {label: threshold}}."""
     sweep = sweep_from_hist(hist, thresholds, label_names)
