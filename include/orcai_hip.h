@@ -449,7 +449,18 @@ int orcai_lstm_split(int on); /* 1 (default): the f32 path's LSTM recurrences (i
 int orcai_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int units, float* out, float* gates, float* cstate, void* stream);
 /* The f16 path's twin (same arguments, f32 tensors): the recurrent product on v_mfma_f32_16x16x32_f16 with h and U rounded to f16,
  * f32 accumulation on the f32 input projection, gates / cell state / outputs in f32; orcai_h_lstm_bwd likewise for the recurrent
- * term dz U^T of orcai_lstm_bwd (dz rounded to f16 for the product only; dxz is written in f32). */
+ * term dz U^T of orcai_lstm_bwd (dz rounded to f16 for the product only; dxz is written in f32).  units 160..256 run the f32 wide
+ * family, bit for bit the f32 entries' results.  Pinned down by tests/test_half_lstm_gpu.py:
+ *   - The f16 operand is the f32 product (o tanh c, resp. dz) rounded ONCE to f16 (v_fma_mixlo_f16), not the stored f32 value rounded
+ *     again: where the stored value is an exact f16 midpoint (2^-13 of the elements) the operand may be either neighbour.
+ *   - f16-subnormal A/B operands are KEPT by v_mfma_f32_16x16x32_f16 on gfx950 (measured on an MI355X: the kernels match a float64
+ *     reference that keeps them to 4e-7 / 2e-7 of max|dxz|, and miss one that flushes them by up to 0.2 of max|dxz|).
+ *   - Forward: h, gates and cell states within 2.5e-4 of the f32 entry (what rounding h and U to f16 costs over 46 steps).
+ *   - Backward: dz is cast to f16 WITHOUT rescaling, so dH is expected loss-scaled (half.LOSS_SCALE = 1024: max|dH| is 27 .. 270 in
+ *     training).  With dH = s x standard normal (max|dH| ~ 4.5 s; float64 reference on the CPU, units 64, T 46), the error of dxz
+ *     relative to max|dxz| is 7e-5 .. 1e-4 for s in [1e-3, 3] (the cost of f16 operands alone), 3e-4 at s = 1e-4, 3e-3 at 1e-5,
+ *     3e-2 at 1e-6, 0.14 at 1e-7, and for s <= 1e-9 every dz rounds to zero: the recurrent term is lost (back-propagation through
+ *     time is silently truncated to one step).  Keep max|dH| >= 4e-3.  There is no saturation either: |dz| > 65504 becomes inf. */
 int orcai_h_lstm_train_fwd(const float* xz, const float* Uw, int B, int T, int units, float* out, float* gates, float* cstate, void* stream);
 int orcai_h_lstm_bwd(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, int units, float* dxz, void* stream);
 /* Backward through time: dH f32[B][T][2*units] (gradient of the layer output) -> dxz f32[B][T][2][4*units] (permuted columns).

@@ -14,59 +14,10 @@ pytestmark = pytest.mark.gpu
 from oracle import model_ref as M  # noqa: E402
 from oracle import train_ref as T  # noqa: E402
 
+from lstm_ref import _bwd_ref, _fwd_ref, sig  # noqa: E402
+
 ROOT = Path(__file__).resolve().parent.parent
 CALLS12 = [f"C{i:02d}" for i in range(12)]
-
-sig = lambda a: 1.0 / (1.0 + np.exp(-a))  # noqa: E731
-
-
-def _fwd_ref(xz, Uw):
-    """float64 recurrence in the kernels' permuted column order (32-column groups (i, f | g, o) of 8 units): h, gates, cell states."""
-    B, Tn, _, U4 = xz.shape
-    U = U4 // 4
-    h = np.zeros((B, Tn, 2 * U))
-    g = np.zeros((B, Tn, 2, 4 * U))
-    c = np.zeros((B, Tn, 2, U))
-    for d in range(2):
-        hh, cc = np.zeros((B, U)), np.zeros((B, U))
-        W = Uw[d].astype(np.float64)
-        for step in range(Tn):
-            t = Tn - 1 - step if d else step
-            zz = (xz[:, t, d].astype(np.float64) + hh @ W).reshape(B, U // 8, 4, 8)
-            i_, f_, g_, o_ = sig(zz[:, :, 0]), sig(zz[:, :, 1]), np.tanh(zz[:, :, 2]), sig(zz[:, :, 3])
-            cc = (f_ * cc.reshape(B, U // 8, 8) + i_ * g_).reshape(B, U)
-            hh = (o_ * np.tanh(cc.reshape(B, U // 8, 8))).reshape(B, U)
-            h[:, t, d * U : (d + 1) * U] = hh
-            c[:, t, d] = cc
-            g[:, t, d] = np.stack([i_, f_, g_, o_], axis=2).reshape(B, 4 * U)
-    return h, g, c
-
-
-def _bwd_ref(dH, gates, cst, Uw):
-    """float64 backward through time of the same recurrence: dxz in the permuted column order."""
-    B, Tn, _, U4 = gates.shape
-    U = U4 // 4
-    dxz = np.zeros((B, Tn, 2, 4 * U))
-    for d in range(2):
-        W = Uw[d].astype(np.float64)
-        dc, dhr = np.zeros((B, U)), np.zeros((B, U))
-        for step in range(Tn):
-            t = step if d else Tn - 1 - step
-            tp = t + 1 if d else t - 1
-            gv = gates[:, t, d].astype(np.float64).reshape(B, U // 8, 4, 8)
-            i_, f_, g_, o_ = (gv[:, :, q].reshape(B, U) for q in range(4))
-            c = cst[:, t, d].astype(np.float64)
-            cp = cst[:, tp, d].astype(np.float64) if 0 <= tp < Tn else np.zeros((B, U))
-            dh = dH[:, t, d * U : (d + 1) * U].astype(np.float64) + dhr
-            tc = np.tanh(c)
-            dct = dc + dh * o_ * (1 - tc * tc)
-            dc = dct * f_
-            dz = np.stack([dct * g_ * i_ * (1 - i_), dct * cp * f_ * (1 - f_), dct * i_ * (1 - g_ * g_), dh * tc * o_ * (1 - o_)], axis=1)  # [B][4][U]
-            dz = dz.reshape(B, 4, U // 8, 8).transpose(0, 2, 1, 3).reshape(B, 4 * U)
-            dxz[:, t, d] = dz
-            dhr = dz @ W.T
-    return dxz
-
 
 @pytest.mark.parametrize("U", [32, 96, 160, 256])
 @pytest.mark.parametrize("B,Tn", [(7, 46), (20, 9), (65, 9)])
