@@ -362,6 +362,33 @@ int orcai_extract_labels_refined(const double* agg, const double* cnt, int L, co
                                  int tpo, int* runs, int64_t capacity, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
 size_t orcai_extract_labels_refined_workspace_bytes(int L, int R, int64_t S_total);
 
+/* A score for every interval an extraction call found (`orcai predict --scores`).  The call goes behind orcai_extract_labels,
+ * orcai_extract_labels_per_label or orcai_extract_labels_refined on the same stream and reads agg, table, runs, offsets and capacity as that call
+ * left them on the device; only min(offsets[R], capacity) runs are scored.  The recording of run i is found by a binary search of i in offsets.
+ * The contract, shared with the host route (orcai_amd/scores.py): for a run of label l in recording r over rows start_row .. stop_row inclusive
+ * (counted inside the recording, as runs stores them; for a merged run the rows of its gaps count), with p[s] = agg[row_r + s][l]:
+ *   peak      the largest p[s], as the f64 it is; NaN rows are skipped (a gap row may be NaN, a start row never is: NaN is above no threshold).
+ *   peak_row  the lowest row s that attains peak: ties go to the earlier row.
+ *   sum_q32   the sum of q[s] = rint(min(max(p[s], 0), 1) * 2^32) (round-half-even, NaN gives 0) as an unsigned 64-bit integer.  The scaling by a power
+ *             of two and the rint are exact and integer addition is associative, so every order of reduction gives the same bits; a run of fewer than
+ *             2^31 rows sums to less than 2^63.
+ *   mean      is NOT written: the caller forms sum_q32 / (n_rows * 2^32) in f64, within 2^-33 of the exact mean of the clamped rows by definition.
+ *   scores    24 bytes per run, in run order: {f64 peak, u64 sum_q32, i64 peak_row}, 8-byte aligned, `capacity` rows.  (A run whose rows are all NaN,
+ *             which no extraction call produces: peak NaN, peak_row -1.)
+ *   eager     NULL, or room for eager_runs rows of the same layout: the rows of the first eager_runs runs are written there AS WELL, so that a caller
+ *             can keep them next to the head of its run buffer and fetch both in one copy.
+ *   workspace orcai_interval_scores_workspace_bytes(L, R, S_total) bytes, 256-byte aligned (0 for sizes the call refuses).
+ * Two launches on `stream` (labels.hip).  Row tiles of 256 rows are cut on the GLOBAL rows of agg.  The first launch reads every tile's 256 x L slab
+ * once and leaves per (tile, label) the maximum, its first row and the q32 sum; the second gives every run 16 lanes, which share its head piece (at most
+ * 255 rows), the table entries of its whole tiles and its tail piece (at most 255 rows).  No lane walks a run; agg is read once by the first launch and,
+ * element for element, at most once more by the second.  No atomics: two calls write the same bytes.
+ * ORCAI_E_BADARG: a null agg / table / runs / offsets / scores / workspace, L outside 1..64, R < 1, S_total < 1, capacity < 0, eager_runs < 0, a
+ * workspace smaller than the size function answers, misaligned runs, scores, eager or workspace.  ORCAI_E_UNSUPPORTED (nothing launched):
+ * S_total >= 2^31 (global rows are kept as int32). */
+int orcai_interval_scores(const double* agg, int L, const int64_t* table, int R, int64_t S_total, const int* runs, const int64_t* offsets,
+                          int64_t capacity, void* scores, void* eager, int64_t eager_runs, void* workspace, size_t workspace_bytes, void* stream);
+size_t orcai_interval_scores_workspace_bytes(int L, int R, int64_t S_total);
+
 /* test.py:37-225: the integer counts behind the three tables of `orcai test` (compute_confusion_table, compute_misclassification_tables) for one
  * batch; the host forms the tables' float64 values from them (orcai_amd/device_tables.py).
  *   p, y       f32[M][L], M = snippets * time steps: probabilities, and labels in {0, 1, mask_value = -1}.  1 <= L <= 64.

@@ -194,6 +194,9 @@ _SIGNATURES = {
     "orcai_extract_labels_refined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_double, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "orcai_extract_labels_refined_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
+    "orcai_interval_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "orcai_interval_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "orcai_threshold_counts": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 

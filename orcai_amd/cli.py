@@ -65,6 +65,9 @@ def cli():
 @click.option("--merge-gap", "merge_gap", default=None, show_default="None",
               help="Gap merging: intervals of one label at most this many seconds apart are written as one. A number for all labels, or a JSON file "
                    "{label: seconds}; labels it does not name keep 0.")
+@click.option("--scores", "scores", is_flag=True,
+              help="Also write <stem>_scores.csv next to every label file: per interval its peak probability, the time of the peak and its mean "
+                   "probability. The label file stays the same bytes.")
 @click.option("--model", "-m", type=click.Choice(INCLUDED_MODELS, case_sensitive=False), default="orcai-V1", show_default=True,
               help="Builtin model to use for prediction. Overridden if model_dir is given.")
 @click.option("--model_dir", "-md", "model_dir", type=DirR, default=None, show_default="use builtin model", help="Path to a model directory.")

@@ -690,9 +690,187 @@ __global__ __launch_bounds__(256) void refine_edges_kernel(const u64* __restrict
   }
 }
 
+// ================================================================ orcai_interval_scores: peak, peak row and fixed-point sum per run
+// A segmented reduction over the runs an extraction call left in `runs` / `offsets`, in two launches.  Tiles are cut on GLOBAL rows (tile t = rows
+// 256 t .. 256 t + 255 of agg, whatever recording they lie in): a run lies inside one recording, so every tile wholly inside a run does too.
+//   S1 tiles  one workgroup per row tile reads its 256 x L slab once: per (tile, label) the maximum (NaN skipped), the first row that attains it and
+//             the sum of q32(p) = rint(clamp(p, 0, 1) * 2^32) as u64.  Thread = (row part, label), the labels of a row in neighbouring lanes, so a
+//             wave's load is a contiguous stretch of the slab; a thread reads at most 64 rows.
+//   S2 runs   SCORE_LANES = 16 lanes per run (a fixed grid strides over the runs; their number is only known on the device).  The recording of run i
+//             is a binary search of i in offsets.  The lanes share the head piece (the rows before the first whole tile, at most 255), the whole
+//             tiles (from S1's table) and the tail piece (at most 255 rows; a run without a whole tile is one piece of at most 510 rows), then merge
+//             through four xor shuffles.  A lane's work: at most 2 * 16 rows + (tiles of the run) / 16 table entries.
+// Merging keeps the larger value and, among equal values, the lower row; the sums are integers: every order of reduction gives the same bytes, and
+// nothing is claimed with an atomic.  agg is read once by S1 and, element for element, at most once more by S2 (the head and tail rows of a run).
+constexpr int SCORE_LANES = 16;
+constexpr int SCORE_GRID = 2048;  // workgroups of the run launch at most: 16 runs each per sweep
+
+struct ScoreLayout {
+  size_t tmax, tsum, trow, total;  // byte offsets into the workspace
+  int64_t tiles;
+};
+
+inline ScoreLayout score_layout(int L, int64_t S_total) {
+  ScoreLayout a;
+  a.tiles = (S_total + ROW_TILE - 1) / ROW_TILE;
+  a.tmax = 0;                                                   // f64 [tiles][L]
+  a.tsum = a.tmax + up256((size_t)a.tiles * L * 8);             // u64 [tiles][L]
+  a.trow = a.tsum + up256((size_t)a.tiles * L * 8);             // i32 [tiles][L]: the global row of the maximum, -1: every row of the tile is NaN
+  a.total = a.trow + up256((size_t)a.tiles * L * 4);
+  return a;
+}
+
+struct Score {
+  double m;  // the maximum so far; meaningless while r < 0
+  int r;     // its global row, -1: nothing but NaN so far
+  u64 s;     // sum of q32
+};
+
+__device__ __forceinline__ u64 q32(double p) {
+  if (!(p == p)) return 0;
+  p = p < 0.0 ? 0.0 : (p > 1.0 ? 1.0 : p);
+  return (u64)__builtin_rint(p * 4294967296.0);  // the product is exact (a power of two), rint is round-half-even
+}
+
+__device__ __forceinline__ void score_merge(Score& a, double m, int r, u64 s) {
+  a.s += s;
+  if (r >= 0 && (a.r < 0 || m > a.m || (m == a.m && r < a.r))) {
+    a.m = m;
+    a.r = r;
+  }
+}
+
+__device__ __forceinline__ void score_row(Score& a, double p, int row) { score_merge(a, p, p == p ? row : -1, q32(p)); }
+
+__device__ __forceinline__ void score_shuffle(Score& a, int d) {  // every lane of the wave takes part
+  const double m = __shfl_xor(a.m, d);
+  const int r = __shfl_xor(a.r, d);
+  const u64 s = __shfl_xor(a.s, d);
+  score_merge(a, m, r, s);
+}
+
+// ---------------------------------------------------------------- S1 tiles.  lg = log2 of L rounded up to a power of two (Lp): thread = part * Lp + l
+__global__ __launch_bounds__(256) void scores_tile_kernel(const double* __restrict__ agg, int L, int lg, int64_t S_total, double* __restrict__ tmax,
+                                                           u64* __restrict__ tsum, int* __restrict__ trow) {
+  __shared__ double wm[WAVES][64];
+  __shared__ u64 wsum[WAVES][64];
+  __shared__ int wrow[WAVES][64];
+  const int64_t tile = blockIdx.x;
+  const int Lp = 1 << lg, parts = ROW_TILE >> lg;
+  const int l = threadIdx.x & (Lp - 1), part = threadIdx.x >> lg;
+  Score a = {0.0, -1, 0};
+  if (l < L) {
+    const int64_t row0 = tile * ROW_TILE + part;  // rows row0, row0 + parts, ...: ascending, so the first maximum stays
+    for (int k0 = 0; k0 < Lp; k0 += 8) {           // eight loads in flight, then their eight rows in order
+      double v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int64_t row = row0 + (int64_t)(k0 + j) * parts;
+        v[j] = (k0 + j < Lp && row < S_total) ? agg[row * L + l] : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int64_t row = row0 + (int64_t)(k0 + j) * parts;
+        if (k0 + j < Lp && row < S_total) score_row(a, v[j], (int)row);
+      }
+    }
+  }
+  for (int d = Lp; d < 64; d <<= 1) score_shuffle(a, d);  // the parts of this wave: lanes of equal l
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  wm[wave][lane] = a.m;
+  wsum[wave][lane] = a.s;
+  wrow[wave][lane] = a.r;
+  __syncthreads();
+  if (threadIdx.x < L) {  // lane l of every wave holds that wave's result for label l
+    Score b = {0.0, -1, 0};
+    for (int w = 0; w < WAVES; ++w) score_merge(b, wm[w][threadIdx.x], wrow[w][threadIdx.x], wsum[w][threadIdx.x]);
+    tmax[tile * L + threadIdx.x] = b.m;
+    tsum[tile * L + threadIdx.x] = b.s;
+    trow[tile * L + threadIdx.x] = b.r;
+  }
+}
+
+// ---------------------------------------------------------------- S2 runs
+__global__ __launch_bounds__(256) void scores_run_kernel(const double* __restrict__ agg, int L, const int64_t* __restrict__ table, int R, int64_t S_total,
+                                                          const int4* __restrict__ runs, const int64_t* __restrict__ offsets, int64_t capacity,
+                                                          const double* __restrict__ tmax, const u64* __restrict__ tsum, const int* __restrict__ trow,
+                                                          u64* __restrict__ scores, u64* __restrict__ eager, int64_t eager_runs) {
+  constexpr int GROUPS = 256 / SCORE_LANES;
+  int64_t n = offsets[R];
+  if (n > capacity) n = capacity;  // runs behind the capacity were counted, not stored
+  const int group = threadIdx.x / SCORE_LANES, g = threadIdx.x % SCORE_LANES;
+  for (int64_t base = (int64_t)blockIdx.x * GROUPS; base < n; base += (int64_t)gridDim.x * GROUPS) {  // the same trips for every lane of the workgroup
+    const int64_t i = base + group;
+    Score a = {0.0, -1, 0};
+    int64_t first = 0;
+    if (i < n) {
+      const int4 run = runs[i];
+      int lo = 0, hi = R - 1;  // the last recording whose first run is <= i: the one that holds run i
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (offsets[mid] <= i) lo = mid; else hi = mid - 1;
+      }
+      first = table[4 * lo + 3];
+      const int l = run.z;
+      int64_t b = first + run.x, e = first + run.y + 1;  // global rows [b, e)
+      if (b < 0) b = 0;
+      if (e > S_total) e = S_total;
+      if (l >= 0 && l < L && b < e) {
+        int64_t t0 = (b + ROW_TILE - 1) / ROW_TILE, t1 = e / ROW_TILE;  // whole tiles [t0, t1)
+        int64_t head = t0 * ROW_TILE, tail = t1 * ROW_TILE;
+        if (t0 >= t1) {  // no whole tile: one piece
+          head = tail = e;
+          t0 = t1 = 0;
+        }
+        for (int64_t row = b + g; row < head; row += SCORE_LANES) score_row(a, agg[row * L + l], (int)row);
+        for (int64_t t = t0 + g; t < t1; t += SCORE_LANES) score_merge(a, tmax[t * L + l], trow[t * L + l], tsum[t * L + l]);
+        for (int64_t row = tail + g; row < e; row += SCORE_LANES) score_row(a, agg[row * L + l], (int)row);
+      }
+    }
+    for (int d = 1; d < SCORE_LANES; d <<= 1) score_shuffle(a, d);  // every lane of the group ends with the run's result
+    if (i < n && g < 3) {
+      const u64 word = g == 0 ? (u64)__double_as_longlong(a.r < 0 ? __builtin_nan("") : a.m) : (g == 1 ? a.s : (u64)(a.r < 0 ? (int64_t)-1 : (int64_t)a.r - first));
+      scores[3 * i + g] = word;
+      if (eager && i < eager_runs) eager[3 * i + g] = word;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t orcai_interval_scores_workspace_bytes(int L, int R, int64_t S_total) {
+  if (L < 1 || L > 64 || R < 1 || S_total < 1 || S_total > 0x7fffffff) return 0;
+  return score_layout(L, S_total).total;
+}
+
+int orcai_interval_scores(const double* agg, int L, const int64_t* table, int R, int64_t S_total, const int* runs, const int64_t* offsets, int64_t capacity,
+                          void* scores, void* eager, int64_t eager_runs, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!agg || !table || !runs || !offsets || !scores || !workspace) return ORCAI_E_BADARG;
+  if (L < 1 || L > 64 || R < 1 || S_total < 1 || capacity < 0 || eager_runs < 0) return ORCAI_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(runs) & 15) || (reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(eager) & 7) ||
+      (reinterpret_cast<uintptr_t>(workspace) & 255))
+    return ORCAI_E_BADARG;
+  if (S_total > 0x7fffffff) return ORCAI_E_UNSUPPORTED;  // global rows are int32 in the tile table
+  const ScoreLayout a = score_layout(L, S_total);
+  if (workspace_bytes < a.total) return ORCAI_E_BADARG;
+  char* ws = static_cast<char*>(workspace);
+  double* tmax = reinterpret_cast<double*>(ws + a.tmax);
+  u64* tsum = reinterpret_cast<u64*>(ws + a.tsum);
+  int* trow = reinterpret_cast<int*>(ws + a.trow);
+  int lg = 0;
+  while ((1 << lg) < L) ++lg;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(scores_tile_kernel, dim3((unsigned)a.tiles), dim3(ROW_TILE), 0, st, agg, L, lg, S_total, tmax, tsum, trow);
+  if (capacity > 0) {
+    const int64_t want = (capacity + 256 / SCORE_LANES - 1) / (256 / SCORE_LANES);
+    hipLaunchKernelGGL(scores_run_kernel, dim3((unsigned)(want < SCORE_GRID ? want : SCORE_GRID)), dim3(256), 0, st, agg, L, table, R, S_total,
+                       reinterpret_cast<const int4*>(runs), offsets, capacity, tmax, tsum, trow, reinterpret_cast<u64*>(scores),
+                       reinterpret_cast<u64*>(eager), eager_runs);
+  }
+  return (int)hipGetLastError();
+}
 
 size_t orcai_extract_labels_refined_workspace_bytes(int L, int R, int64_t S_total) {
   if (L < 1 || L > 64 || R < 1 || S_total < 1 || S_total > 0x7fffffff) return 0;

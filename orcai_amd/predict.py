@@ -110,20 +110,22 @@ class PendingAggregate:
 
 
 def label_spec(orcai_parameter: dict, label_suffix: str = "*", call_duration_limits=None, probabilities: bool = True, thresholds=None,
-               refine=None) -> dict:
+               refine=None, scores: bool = False) -> dict:
     """What the launch half needs to queue orcai_extract_labels behind the overlap average (device_labels=...): the label names, the suffix, the
     duration limits the kernel is to judge by (None: no filter), whether the averaged probabilities are still wanted on the host, and the per-label
     thresholds (L floats; None: 0.5 for every label through the scalar entry point).  refine (threshold_sweep.resolve_refinement's dict, or None):
-    the high thresholds and the merge gaps in seconds, for orcai_extract_labels_refined."""
+    the high thresholds and the merge gaps in seconds, for orcai_extract_labels_refined.  scores: orcai_interval_scores behind the extraction call
+    (DESIGN 4.16)."""
     return {"calls": orcai_parameter["calls"], "label_suffix": label_suffix, "call_duration_limits": call_duration_limits, "probabilities": probabilities,
-            "thresholds": thresholds, "refine": refine}
+            "thresholds": thresholds, "refine": refine, "scores": bool(scores)}
 
 
 def _queue_labels(spec: dict, agg: torch.Tensor, cnt: torch.Tensor, table: torch.Tensor, R: int, n_filters: int, delta_t: float):
     from orcai_amd.device_labels import extract_labels_device
 
     return extract_labels_device(agg, cnt, table, R, spec["calls"], spec["label_suffix"], 2**n_filters, delta_t, call_duration_limits=spec["call_duration_limits"],
-                                 thresholds=spec.get("thresholds"), **_refine_arguments(spec.get("refine"), 2**n_filters, delta_t, "high_thresholds", "gap_rows"))
+                                 thresholds=spec.get("thresholds"), **_refine_arguments(spec.get("refine"), 2**n_filters, delta_t, "high_thresholds", "gap_rows"),
+                                 **({"scores": True} if spec.get("scores") else {}))
 
 
 def _refine_arguments(refine: dict | None, time_steps_per_output_step: int, delta_t: float, high_name: str, gap_name: str) -> dict:
@@ -339,10 +341,12 @@ def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_pa
     return {"pending": pending, "delta_t": delta_t, "orcai_parameter": orcai_parameter}
 
 
-def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None):
+def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None,
+                       scores: bool = False):
     """Second half of predict_wav (host): threshold, runs of ones, label table (predict.py:298-340).  thresholds: one per label (L floats) in place
     of 0.5 on the host route; refine: resolve_refinement's dict, hysteresis and gap merging on the host route.  Labels that came from the device
-    were cut by the thresholds and the refinement of their label_spec."""
+    were cut by the thresholds and the refinement of their label_spec.  scores: the columns peak, peak_frame and mean on the host route
+    (scores.add_scores); labels from the device carry them when their label_spec asked for them."""
     pending, orcai_parameter = state["pending"], state["orcai_parameter"]
     aggregated_predictions, overlap_count = pending.result() if isinstance(pending, PendingAggregate) else pending
     device_result = state.get("device_labels_result")
@@ -359,6 +363,10 @@ def predict_wav_finish(state: dict, label_suffix: str = "*", msgr: Messenger = M
                                                                                         "high_threshold", "merge_gap_rows"))
     msgr.info("converting binary predictions into start and stop frames")
     predicted_labels = compute_labels(row_starts, row_stops, label_names, time_steps_per_output_step=time_steps_per_output_step, label_suffix=label_suffix)
+    if scores:
+        from orcai_amd.scores import add_scores
+
+        predicted_labels = add_scores(predicted_labels, aggregated_predictions, orcai_parameter["calls"], label_suffix, time_steps_per_output_step)
     msgr.info(f"found {len(predicted_labels)} acoustic signals")
     msgr.success("Prediction finished.")
     return predicted_labels, aggregated_predictions, state["delta_t"]
@@ -378,17 +386,18 @@ def _finish_device_labels(device_result: tuple, labels, aggregated_predictions, 
 
 def predict_wav(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*",
                 msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: bool = False, thresholds=None,
-                high_thresholds=None, merge_gap=None):
+                high_thresholds=None, merge_gap=None, scores: bool = False):
     """(predicted_labels DataFrame, aggregated_predictions ndarray, delta_t) for one wav file (predict.py:367-471).  device_labels=True: the label
     table comes from orcai_extract_labels (the same table).  thresholds: a dict {label: threshold} or the path of a thresholds.json.
-    high_thresholds, merge_gap (seconds): a number, a dict {label: value} or the path of such a JSON file, as for predict()."""
+    high_thresholds, merge_gap (seconds): a number, a dict {label: value} or the path of such a JSON file, as for predict().  scores=True: the table
+    has three more columns, peak (f64), peak_frame (in the unit of start / stop) and mean (f64) of every interval."""
     from orcai_amd.threshold_sweep import resolve_refinement, resolve_thresholds
 
     thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
     refine = resolve_refinement(high_thresholds, merge_gap, thresholds, orcai_parameter["calls"])
     state = predict_wav_launch(recording_path, channel, model, orcai_parameter, shape, msgr=msgr, progressbar=progressbar,
-                               device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine) if device_labels else None)
-    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
+                               device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine, scores=scores) if device_labels else None)
+    return predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine, scores=scores)
 
 
 def _too_short(n_frames: int, snippet_length: int) -> ValueError:
@@ -451,7 +460,7 @@ def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_fram
         yield queue()
 
 
-def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> list:
+def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None, scores: bool = False) -> list:
     """The host half of one batch state: [(key, predict_wav's triple or the exception the recording raised)], the failed ones first."""
     out = list(state["failed"])
     if state["pending"] is not None:
@@ -460,7 +469,7 @@ def _finish_batch(state: dict, label_suffix: str = "*", msgr: Messenger = Messen
         for (key, delta_t), pair, device_result in zip(state["members"], state["pending"].results(), label_results):
             out.append((key, predict_wav_finish({"pending": pair, "delta_t": delta_t, "orcai_parameter": state["orcai_parameter"],
                                                  "device_labels_result": device_result, "device_labels": labels}, label_suffix=label_suffix, msgr=msgr,
-                                                thresholds=thresholds, refine=refine)))
+                                                thresholds=thresholds, refine=refine, scores=scores)))
     return out
 
 
@@ -487,20 +496,22 @@ def predict_wavs_launch(items, model, orcai_parameter: dict, shape: dict, max_fr
                            device_labels=device_labels)
 
 
-def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> list:
+def predict_wavs_finish(state: dict, label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None,
+                        scores: bool = False) -> list:
     """Second half (host): [(index into items, (predicted_labels, aggregated_predictions, delta_t) or the exception that item raised)]."""
-    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
+    return _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine, scores=scores)
 
 
 def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix: str = "*", max_frames: int | None = None,
-                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False, thresholds=None, high_thresholds=None, merge_gap=None) -> list:
+                 msgr: Messenger = Messenger(verbosity=0), device_labels: bool = False, thresholds=None, high_thresholds=None, merge_gap=None,
+                 scores: bool = False) -> list:
     """predict_wav for every (path, channel) of `items`, several recordings per detector pass: batches of at most max_frames spectrogram frames
     (batch.DEFAULT_MAX_FRAMES: an hour's worth) go through ONE forward pass and ONE overlap average, the host half of a batch runs beside the GPU
     half of the next.  Returns, per item, what predict_wav returns for it -- the same label table, the same f64 probabilities, the same delta_t --
     or the exception it raised (a missing file, a recording shorter than one snippet); the other items are unaffected.
     A model without the native batch path (the reference's duck-typed ``.predict`` boundary) runs item by item.
-    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables).  thresholds, high_thresholds, merge_gap:
-    as for predict_wav."""
+    device_labels=True: the label tables of a batch come from one orcai_extract_labels (the same tables).  thresholds, high_thresholds, merge_gap,
+    scores: as for predict_wav."""
     from orcai_amd.threshold_sweep import resolve_refinement, resolve_thresholds
 
     thresholds = resolve_thresholds(thresholds, orcai_parameter["calls"])
@@ -512,17 +523,18 @@ def predict_wavs(items, model, orcai_parameter: dict, shape: dict, label_suffix:
         for i, (path, channel) in enumerate(items):
             try:
                 results[i] = predict_wav(path, channel, model, orcai_parameter, shape, label_suffix=label_suffix, msgr=msgr, device_labels=device_labels,
-                                         thresholds=listed, high_thresholds=high_thresholds, merge_gap=merge_gap)
+                                         thresholds=listed, high_thresholds=high_thresholds, merge_gap=merge_gap, scores=scores)
             except Exception as e:
                 results[i] = e
         return results
 
     def finish(state):
-        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine):
+        for i, result in predict_wavs_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine, scores=scores):
             results[i] = result
 
     _run_batches(predict_wavs_launch(items, model, orcai_parameter, shape, max_frames=max_frames, msgr=msgr,
-                                     device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine) if device_labels else None),
+                                     device_labels=label_spec(orcai_parameter, label_suffix, thresholds=thresholds, refine=refine, scores=scores)
+                                     if device_labels else None),
                  finish)
     return results
 
@@ -532,6 +544,19 @@ def save_predictions(predicted_labels: pd.DataFrame, output_path: Path | str, de
     predicted_labels = _convert_times_to_seconds(predicted_labels, delta_t)
     predicted_labels[["start", "stop", "label"]].round(4).to_csv(output_path, sep="\t", index=False)
     msgr.info(f"Predictions saved to {output_path}")
+
+
+def save_prediction_scores(predicted_labels: pd.DataFrame, output_path: Path | str, delta_t: float, msgr: Messenger = Messenger(verbosity=0)) -> None:
+    """save_predictions' sibling for a scored table: <stem>_scores.csv next to the label file, one line per line of the label file in
+    its order.  Tab-separated start / stop / label / peak_time / peak / mean with header; times in seconds rounded to 4 places as save_predictions
+    rounds them, peak and mean rounded to 6."""
+    output_path = Path(output_path)
+    scores_path = output_path.with_name(f"{output_path.stem}_scores.csv")
+    seconds = {name: np.round(predicted_labels[column].to_numpy() * delta_t, 4) for name, column in (("start", "start"), ("stop", "stop"), ("peak_time", "peak_frame"))}
+    pd.DataFrame({"start": seconds["start"], "stop": seconds["stop"], "label": predicted_labels["label"].to_numpy(), "peak_time": seconds["peak_time"],
+                  "peak": np.round(predicted_labels["peak"].to_numpy(), 6), "mean": np.round(predicted_labels["mean"].to_numpy(), 6)}).to_csv(
+        scores_path, sep="\t", index=False)
+    msgr.info(f"Interval scores saved to {scores_path}")
 
 
 def save_prediction_probabilities(aggregated_predictions: np.ndarray, orcai_parameter: dict, delta_t: float, output_path: Path | str,
@@ -545,8 +570,8 @@ def save_prediction_probabilities(aggregated_predictions: np.ndarray, orcai_para
 
 
 def _checked_output_path(recording_path: Path, channel: int, orcai_parameter: dict, output_path: Path | str = "default", overwrite: bool = False,
-                         msgr: Messenger = Messenger(verbosity=0)):
-    """predict.py:534-575: the output path of one recording and the overwrite check."""
+                         msgr: Messenger = Messenger(verbosity=0), scores: bool = False):
+    """predict.py:534-575: the output path of one recording and the overwrite check.  scores: the check covers <stem>_scores.csv as well."""
     if output_path is not None:
         if output_path == "default":
             filename = f"{recording_path.stem}_c{channel}_{orcai_parameter['name']}_predicted.txt"
@@ -559,14 +584,21 @@ def _checked_output_path(recording_path: Path, channel: int, orcai_parameter: di
                 msgr.warning(f"Output file {output_path} already exists. Overwriting.")
             else:
                 raise FileExistsError(f"Annotation file already exists: {output_path}")
+        scores_path = output_path.with_name(f"{output_path.stem}_scores.csv")
+        if scores and scores_path.exists():
+            if overwrite:
+                msgr.warning(f"Output file {scores_path} already exists. Overwriting.")
+            else:
+                raise FileExistsError(f"Score file already exists: {scores_path}")
     return output_path
 
 
 def _launch_recording(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
-                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None) -> dict:
+                      overwrite: bool = False, msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None,
+                      scores: bool = False) -> dict:
     """predict.py:534-575: output path and overwrite check, then the GPU half of the recording (queued, not waited for)."""
     recording_path = Path(recording_path)
-    output_path = _checked_output_path(recording_path, channel, orcai_parameter, output_path, overwrite, msgr)
+    output_path = _checked_output_path(recording_path, channel, orcai_parameter, output_path, overwrite, msgr, scores=scores)
     state = predict_wav_launch(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape, msgr=msgr,
                                progressbar=progressbar, device_labels=device_labels)
     state["output_path"] = output_path
@@ -574,8 +606,8 @@ def _launch_recording(recording_path: Path | str, channel: int, model, orcai_par
 
 
 def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
-                    label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0)) -> None:
-    """predict.py:576-632 after the labels: optional duration filter, files."""
+                    label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), scores: bool = False) -> None:
+    """predict.py:576-632 after the labels: optional duration filter, files.  scores: the score file of the (filtered) table beside the label file."""
     predicted_labels, aggregated_predictions, delta_t = result
     counts = predicted_labels.attrs.get("duration_filter")
     if counts is not None:  # device labels: the kernel judged every interval, the table is the filtered one
@@ -587,32 +619,35 @@ def _save_recording(result: tuple, output_path, orcai_parameter: dict, save_prob
     elif call_duration_limits is not None:
         predicted_labels = filter_predictions(predicted_labels, delta_t=delta_t, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr)
     save_predictions(predicted_labels=predicted_labels, output_path=output_path, delta_t=delta_t, msgr=msgr)
+    if scores and output_path is not None:
+        save_prediction_scores(predicted_labels=predicted_labels, output_path=output_path, delta_t=delta_t, msgr=msgr)
     if save_probabilities:
         save_prediction_probabilities(aggregated_predictions=aggregated_predictions, orcai_parameter=orcai_parameter, delta_t=delta_t, output_path=output_path, msgr=msgr)
 
 
 def _finish_recording(state: dict, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                      msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None) -> None:
+                      msgr: Messenger = Messenger(verbosity=0), thresholds=None, refine=None, scores: bool = False) -> None:
     """predict.py:576-632: the host half -- labels, optional duration filter, files."""
-    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine)
+    result = predict_wav_finish(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine, scores=scores)
     _save_recording(result, state["output_path"], state["orcai_parameter"], save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
-                    label_suffix=label_suffix, msgr=msgr)
+                    label_suffix=label_suffix, msgr=msgr, scores=scores)
 
 
 def _predict_and_save(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default",
                       overwrite: bool = False, save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None,
                       label_suffix: str = "*", msgr: Messenger = Messenger(verbosity=0), progressbar: tqdm = None, device_labels: dict | None = None,
-                      thresholds=None, refine=None) -> None:
+                      thresholds=None, refine=None, scores: bool = False) -> None:
     """predict.py:534-632."""
     state = _launch_recording(recording_path, channel, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite, msgr=msgr,
-                              progressbar=progressbar, device_labels=device_labels)
+                              progressbar=progressbar, device_labels=device_labels, scores=scores)
     _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
-                      thresholds=thresholds, refine=refine)
+                      thresholds=thresholds, refine=refine, scores=scores)
 
 
 def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, shape: dict, output_path: Path | str = "default", overwrite: bool = False,
                           save_probabilities: bool = False, call_duration_limits: (Path | str) | dict = None, label_suffix: str = "*",
-                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None, thresholds=None, refine=None) -> None:
+                          msgr: Messenger = Messenger(verbosity=0), device_labels: dict | None = None, thresholds=None, refine=None,
+                          scores: bool = False) -> None:
     """predict(channel="all"): one read and one upload of the file, every channel decoded by orcai_pcm_decode_planar, the channels as ONE batch through
     the detector.  One output file per channel, under the name -- and with the bytes -- predict(channel=c) gives it."""
     from orcai_amd.spectrogram import load_wav_all
@@ -620,17 +655,17 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
     if output_path is not None and output_path != "default":
         raise ValueError("channel='all' writes one file per channel next to the recording: output_path must be 'default' (or None)")
     pcms = load_wav_all(recording_path, orcai_parameter["spectrogram"]["sampling_rate"], msgr)
-    paths = {c: _checked_output_path(recording_path, c, orcai_parameter, output_path, overwrite, msgr) for c in range(1, len(pcms) + 1)}
+    paths = {c: _checked_output_path(recording_path, c, orcai_parameter, output_path, overwrite, msgr, scores=scores) for c in range(1, len(pcms) + 1)}
     sources = ((c, lambda pcm=pcm: pcm) for c, pcm in enumerate(pcms, start=1))
     errors = []
 
     def finish(state):
-        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine):
+        for c, result in _finish_batch(state, label_suffix=label_suffix, msgr=msgr, thresholds=thresholds, refine=refine, scores=scores):
             if isinstance(result, Exception):
                 errors.append(result)
                 continue
             _save_recording(result, paths[c], orcai_parameter, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
-                            label_suffix=label_suffix, msgr=msgr)
+                            label_suffix=label_suffix, msgr=msgr, scores=scores)
 
     total = sum(int(pcm.numel()) for pcm in pcms) // orcai_parameter["spectrogram"]["n_overlap"] + (shape["input_shape"][0] + 1) * len(pcms)
     _run_batches(_launch_batches(sources, model, orcai_parameter, shape, max_frames=total, msgr=msgr, device_labels=device_labels), finish)  # max_frames: all channels in one batch
@@ -640,7 +675,7 @@ def _predict_all_channels(recording_path: Path, model, orcai_parameter: dict, sh
 
 def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter: dict, shape: dict, batch_frames: int, overwrite: bool,
                            save_probabilities: bool, call_duration_limits, label_suffix: str, msgr: Messenger, progressbar: tqdm,
-                           device_labels: dict | None = None, thresholds=None, refine=None) -> None:
+                           device_labels: dict | None = None, thresholds=None, refine=None, scores: bool = False) -> None:
     """Table mode with batch_frames > 0: the rows of the table in order, grouped into detector passes of at most batch_frames spectrogram frames.
     Per recording the output path, the overwrite check, the files and the error line are those of the one-by-one loop; one batch deep, so the host
     half of a batch (labels, files) runs beside the GPU half of the next."""
@@ -658,19 +693,19 @@ def _predict_table_batched(recording_table: pd.DataFrame, model, orcai_parameter
             path = Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"])
             channel = recording_table.loc[i, "channel"]
             try:
-                outputs[i] = _checked_output_path(path, channel, orcai_parameter, recording_table.loc[i, "output_path"], overwrite, quiet)
+                outputs[i] = _checked_output_path(path, channel, orcai_parameter, recording_table.loc[i, "output_path"], overwrite, quiet, scores=scores)
             except Exception as e:
                 error(i, e)
                 continue
             yield i, lambda path=path, channel=channel: load_wav(path, sr, channel, quiet)
 
     def finish(state):
-        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet, thresholds=thresholds, refine=refine):
+        for i, result in _finish_batch(state, label_suffix=label_suffix, msgr=quiet, thresholds=thresholds, refine=refine, scores=scores):
             try:
                 if isinstance(result, Exception):
                     raise result
                 _save_recording(result, outputs[i], orcai_parameter, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits,
-                                label_suffix=label_suffix, msgr=quiet)
+                                label_suffix=label_suffix, msgr=quiet, scores=scores)
             except Exception as e:
                 error(i, e)
 
@@ -681,7 +716,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
             overwrite: bool = False, save_probabilities: bool = False, base_dir_recording: str | Path | None = None,
             call_duration_limits: str | Path | None = None, label_suffix: str = "*", verbosity: int = 2, msgr: Messenger | None = None,
             batch_frames: int = 0, device_labels: bool = False, thresholds: str | Path | dict | None = None,
-            high_thresholds: float | str | Path | dict | None = None, merge_gap: float | str | Path | dict | None = None) -> None:
+            high_thresholds: float | str | Path | dict | None = None, merge_gap: float | str | Path | dict | None = None, scores: bool = False) -> None:
     """Predict calls in a wav file or in every recording of a recording-table CSV (predict.py:635-757).
     channel="all" (a wav file): every channel of the file from one read of its bytes, one output file per channel.
     batch_frames > 0 (a table): consecutive recordings go through the detector in batches of at most batch_frames spectrogram frames
@@ -697,7 +732,11 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     JSON file.  A stretch above its label's threshold is an interval only if it reaches the label's high threshold somewhere, and kept intervals of
     one label at most merge_gap seconds apart are written as one.  Labels not named keep high = threshold and gap 0; both off (None) is the cut above
     alone, through the calls made without them.  An unknown label, a negative gap or a high threshold below the label's threshold raises ValueError
-    before the model is loaded.  Every route, with device_labels (orcai_extract_labels_refined) or without: the same bytes."""
+    before the model is loaded.  Every route, with device_labels (orcai_extract_labels_refined) or without: the same bytes.
+    scores=True: next to every label file, which stays byte for byte the file written without the option, <stem>_scores.csv with one
+    line per line of the label file: start, stop, label, peak_time, peak and mean -- the largest averaged probability of the interval, where it is
+    attained, and the interval's mean probability (the rows of merged gaps count).  Every route; with device_labels the scores come from
+    orcai_interval_scores and the file is the same bytes.  The overwrite check covers the score file."""
     if msgr is None:
         msgr = Messenger(verbosity=verbosity, title="Predicting calls")
     model_dir = Path(model_dir)
@@ -713,16 +752,17 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     model, orcai_parameter, shape = load_orcai_model(model_dir)
     spec = None
     if device_labels and hasattr(model, "predict_spectrogram"):
-        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities, thresholds=thresholds, refine=refine)
+        spec = label_spec(orcai_parameter, label_suffix, call_duration_limits, probabilities=save_probabilities, thresholds=thresholds, refine=refine,
+                          scores=scores)
     if recording_path.suffix == ".wav" and channel == "all" and hasattr(model, "predict_batch"):
         return _predict_all_channels(recording_path, model, orcai_parameter, shape, output_path=output_path, overwrite=overwrite,
                                      save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr,
-                                     device_labels=spec, thresholds=thresholds, refine=refine)
+                                     device_labels=spec, thresholds=thresholds, refine=refine, scores=scores)
     if recording_path.suffix == ".wav":
         return _predict_and_save(recording_path=recording_path, channel=channel, model=model, orcai_parameter=orcai_parameter, shape=shape,
                                  output_path=output_path, overwrite=overwrite, save_probabilities=save_probabilities,
                                  call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=None, device_labels=spec,
-                                 thresholds=thresholds, refine=refine)
+                                 thresholds=thresholds, refine=refine, scores=scores)
     elif recording_path.suffix == ".csv":
         recording_table = pd.read_csv(recording_path)
     else:
@@ -752,7 +792,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
     if batch_frames > 0 and hasattr(model, "predict_batch"):
         _predict_table_batched(recording_table, model, orcai_parameter, shape, batch_frames, overwrite=overwrite, save_probabilities=save_probabilities,
                                call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=msgr, progressbar=progressbar, device_labels=spec,
-                               thresholds=thresholds, refine=refine)
+                               thresholds=thresholds, refine=refine, scores=scores)
         wavio.set_prefetcher(None)
         msgr.success("Predictions finished.")
         return
@@ -763,7 +803,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
         j, state = entry
         try:
             _finish_recording(state, save_probabilities=save_probabilities, call_duration_limits=call_duration_limits, label_suffix=label_suffix, msgr=quiet,
-                              thresholds=thresholds, refine=refine)
+                              thresholds=thresholds, refine=refine, scores=scores)
         except Exception as e:  # predict.py:752-755: log and continue with the next recording
             msgr.error(f"Error predicting {recording_table.loc[j, 'recording']}: {e.args[0] if e.args else e}")
 
@@ -773,7 +813,7 @@ def predict(recording_path: str | Path, channel: int | str = 1, model_dir: str |
             launched = (i, _launch_recording(recording_path=Path(recording_table.loc[i, "base_dir_recording"]).joinpath(recording_table.loc[i, "rel_recording_path"]),
                                              channel=recording_table.loc[i, "channel"], model=model, orcai_parameter=orcai_parameter, shape=shape,
                                              output_path=recording_table.loc[i, "output_path"], overwrite=overwrite, msgr=quiet, progressbar=progressbar,
-                                             device_labels=spec))
+                                             device_labels=spec, scores=scores))
         except Exception as e:  # predict.py:752-755
             msgr.error(f"Error predicting {recording_table.loc[i, 'recording']}: {e.args[0] if e.args else e}")
         if in_flight is not None:
