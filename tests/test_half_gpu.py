@@ -16,30 +16,11 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from half_fwd_ref import from_octet_planes, to_octet_planes  # noqa: E402,F401  (moved there unchanged; other test modules import them from here)
 from oracle import model_ref as M  # noqa: E402
 
 ROOT = Path(__file__).resolve().parent.parent
 HPS = json.loads((ROOT / "orcai_amd" / "defaults" / "default_hps_parameter.json").read_text())
-
-
-def to_octet_planes(x, ksize):
-    """[B][C][H][W] -> f16 [B][ceil(C/8)][H + 2R][WP][8] with zero pads."""
-    B, C, H, W = x.shape
-    R = ksize // 2
-    WP = (W + R + 3) & ~3
-    CO = (C + 7) // 8
-    out = np.zeros((B, CO * 8, H + 2 * R, WP), dtype=np.float16)
-    out[:, :C, R : R + H, :W] = x
-    return np.ascontiguousarray(out.reshape(B, CO, 8, H + 2 * R, WP).transpose(0, 1, 3, 4, 2))
-
-
-def from_octet_planes(p, C, H, W, ksize):
-    B, CO, HP, WP, _ = p.shape
-    R = ksize // 2
-    full = p.transpose(0, 1, 4, 2, 3).reshape(B, CO * 8, HP, WP)
-    pads = full.copy()
-    pads[:, :C, R : R + H, :W] = 0
-    return full[:, :C, R : R + H, :W], pads
 
 
 def _sepconv_int_ref(x, dwk, pw, relu_in):
@@ -325,7 +306,7 @@ def test_half_forward_intermediates():
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Training on the f16 path: f16 activations / activation gradients (static loss scale), f16 MFMA contractions, f32 master weights.
-def _train_setup(cfg, B, seed, rate, precision, record=False):
+def _train_setup(cfg, B, seed, rate, precision, record=False, negate_odd_gamma=False):
     from oracle import train_ref as T
     from orcai_amd.architectures import ResNetLSTM
     from orcai_amd.training import Trainer
@@ -335,6 +316,10 @@ def _train_setup(cfg, B, seed, rate, precision, record=False):
     for k in p:
         if k.endswith(("gamma", "beta")):
             p[k] = (p[k] + 0.2 * rng.standard_normal(p[k].shape)).astype(np.float32)
+    if negate_odd_gamma:  # gamma < 0 on every odd channel of every BatchNorm: the pooling tails take the window minimum there, the backward its arg-min
+        for k in p:
+            if k.endswith("gamma"):
+                p[k][1::2] *= -1.0
     H, W, _ = cfg["input_shape"]
     steps = H // 2 ** len(cfg["filters"])
     L, u = cfg["num_labels"], cfg["lstm_units"]
@@ -357,15 +342,18 @@ def _train_setup(cfg, B, seed, rate, precision, record=False):
 
 
 @pytest.mark.parametrize(
-    "cfg,B",
+    "cfg,B,negate_odd_gamma",
     [
-        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 3),
-        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2),
-        (dict(input_shape=(32, 16, 1), filters=(10, 20), kernel_size=5, lstm_units=64, num_labels=2), 2),
-        (dict(input_shape=(64, 61, 1), filters=(30, 40, 50, 60), kernel_size=3, lstm_units=128, num_labels=7), 4),
+        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 3, False),
+        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2, False),
+        (dict(input_shape=(32, 16, 1), filters=(10, 20), kernel_size=5, lstm_units=64, num_labels=2), 2, False),
+        (dict(input_shape=(64, 61, 1), filters=(30, 40, 50, 60), kernel_size=3, lstm_units=128, num_labels=7), 4, False),
+        # gamma < 0 on every odd channel: the forward pools the window minimum there and the backward routes to its arg-min
+        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2, True),
     ],
+    ids=["cfg0-3", "cfg1-2", "cfg2-2", "cfg3-4", "negative_gamma"],  # the earlier cases keep their ids
 )
-def test_half_training_step_gradients_vs_autograd(cfg, B):
+def test_half_training_step_gradients_vs_autograd(cfg, B, negate_odd_gamma):
     """Forward in training mode + masked BCE + L2 + full backward on the f16 path against torch autograd (float64) on the CPU oracle.
     Every activation is rounded to 2^-11 relative in f16, so the ~1 % of pre-activations within that rounding of zero get the OTHER ReLU mask
     than in a float64 forward (and pooling windows another maximal element), and each such flip moves its gradient element by O(1): against
@@ -374,7 +362,9 @@ def test_half_training_step_gradients_vs_autograd(cfg, B):
     the ReLU masks and pooling selections are read back from the tensors the f16 forward stored (y0, y_a, the block outputs, v_b, the head's
     rectified tensors) and forced on the oracle (oracle.train_ref `forced`, self-checked on the CPU in tests/test_oracle_golden.py).  Held to:
     probabilities 5e-3, loss 5e-3 relative, every gradient tensor to relative L2 <= 2e-2 of the branch-matched float64 gradient."""
-    ref, tr, out = _train_setup(cfg, B, seed=5, rate=0.5, precision="f16")
+    ref, tr, out = _train_setup(cfg, B, seed=5, rate=0.5, precision="f16", negate_odd_gamma=negate_odd_gamma)
+    if negate_odd_gamma:
+        assert all((tr.P.W(f"b{i}/bn_b/gamma").cpu().numpy()[1::2] < 0).all() for i in (1, 2, 3))
     _check_half_step(cfg, B, ref, tr, out, seed=5)
 
 

@@ -16,7 +16,7 @@ from oracle import train_ref as T  # noqa: E402
 from recording_lib import RecordingLib  # noqa: E402
 
 
-def _run(cfg, B, seed, rate=0.5, record=False, dx=None):
+def _run(cfg, B, seed, rate=0.5, record=False, dx=None, negate_odd_gamma=False):
     from orcai_amd.architectures import ResNetLSTM
     from orcai_amd.training import Trainer
 
@@ -25,6 +25,10 @@ def _run(cfg, B, seed, rate=0.5, record=False, dx=None):
     for k in p:
         if k.endswith(("gamma", "beta")):
             p[k] = (p[k] + 0.2 * rng.standard_normal(p[k].shape)).astype(np.float32)
+    if negate_odd_gamma:  # gamma < 0 on every odd channel of every BatchNorm: the pooling tails take the window minimum there, the backward its arg-min
+        for k in p:
+            if k.endswith("gamma"):
+                p[k][1::2] *= -1.0
     H, W, _ = cfg["input_shape"]
     steps = H // 2 ** len(cfg["filters"])
     L, u = cfg["num_labels"], cfg["lstm_units"]
@@ -46,19 +50,24 @@ def _run(cfg, B, seed, rate=0.5, record=False, dx=None):
 
 
 @pytest.mark.parametrize(
-    "cfg,B",
+    "cfg,B,negate_odd_gamma",
     [
-        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 3),
-        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2),
-        (dict(input_shape=(32, 16, 1), filters=(10, 20), kernel_size=5, lstm_units=64, num_labels=2), 2),
+        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 3, False),
+        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2, False),
+        (dict(input_shape=(32, 16, 1), filters=(10, 20), kernel_size=5, lstm_units=64, num_labels=2), 2, False),
         # a first block wide enough for the strip-tile kernels (BatchNorm statistics reduced in the separable convs' epilogue)
-        (dict(input_shape=(16, 120, 1), filters=(20, 24), kernel_size=3, lstm_units=64, num_labels=3), 2),
+        (dict(input_shape=(16, 120, 1), filters=(20, 24), kernel_size=3, lstm_units=64, num_labels=3), 2, False),
         # B * 8 = 320 rows in the head's weight-gradient GEMMs: split-K, its zero fill meeting the Trainer's pre-cleared accumulator arena
-        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 40),
+        (dict(input_shape=(32, 12, 1), filters=(10, 20), kernel_size=3, lstm_units=64, num_labels=3), 40, False),
+        # gamma < 0 on every odd channel: the forward pools the window minimum there and the backward routes to its arg-min
+        (dict(input_shape=(48, 21, 1), filters=(12, 30, 40), kernel_size=3, lstm_units=64, num_labels=7), 2, True),
     ],
+    ids=["cfg0-3", "cfg1-2", "cfg2-2", "cfg3-2", "cfg4-40", "negative_gamma"],  # the earlier cases keep their ids
 )
-def test_full_step_gradients_vs_autograd(cfg, B):
-    ref, tr, out, p = _run(cfg, B, seed=5)
+def test_full_step_gradients_vs_autograd(cfg, B, negate_odd_gamma):
+    ref, tr, out, p = _run(cfg, B, seed=5, negate_odd_gamma=negate_odd_gamma)
+    if negate_odd_gamma:
+        assert all((p[f"b{i}/bn_b/gamma"][1::2] < 0).all() for i in (1, 2, 3))
     _check_step(ref, tr, out)
 
 
