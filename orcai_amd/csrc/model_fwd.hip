@@ -1545,14 +1545,15 @@ __global__ __launch_bounds__(256) void pool_res_add_kernel(const float* __restri
   const int CQ = (C + 3) >> 2, CQp = (Cp + 3) >> 2;
   const bool prev_compact = (xpooled & 2) != 0;  // prev = [B][CQp][Ho][Wo][4]: only the pixels (2i, 2j) the strided 1x1 conv samples
   xpooled &= 1;
-  const int plane = prev_compact ? Ho * Wo : (H + 2 * R) * WP, plane_o = (Ho + 2 * R) * WPo;
+  // plane: pixels per quad plane of s (when it is planes); plane_p: of prev, which may be the compact subsample while s is planes (flag word 2)
+  const int plane = (H + 2 * R) * WP, plane_p = prev_compact ? Ho * Wo : plane, plane_o = (Ho + 2 * R) * WPo;
   const int qbase = R * WPo + task * 64;
   const int q = qbase + lane;
   const int prow = (int)__umulhi((uint32_t)q, magic_WPo);
   const int pj = q - prow * WPo, pi = prow - R;
   const bool pvalid = pj < Wo && pi < Ho;
   const int srcpix = pvalid ? (prev_compact ? pi * Wo + pj : (2 * pi + R) * WP + 2 * pj) : 0;
-  const float4* pp = reinterpret_cast<const float4*>(prev) + (int64_t)b * CQp * plane + srcpix;
+  const float4* pp = reinterpret_cast<const float4*>(prev) + (int64_t)b * CQp * plane_p + srcpix;
 
   f32x4 acc[MT][4];
 #pragma unroll
@@ -1563,7 +1564,7 @@ __global__ __launch_bounds__(256) void pool_res_add_kernel(const float* __restri
   float4 nxt = pp[0];
   for (int cq = 0; cq < CQp; ++cq) {
     const float4 cur = nxt;
-    if (cq + 1 < CQp) nxt = pp[(int64_t)(cq + 1) * plane];
+    if (cq + 1 < CQp) nxt = pp[(int64_t)(cq + 1) * plane_p];
     float afrag[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
