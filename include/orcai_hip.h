@@ -1001,6 +1001,51 @@ int orcai_snippets_overlap_add(const float* dx, int i0, int nb, int H, int W, in
  * ORCAI_E_BADARG: null or misaligned p, bytes negative or not a multiple of 4. */
 int orcai_zero_fill(void* p, int64_t bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training augmentation behind the dataset (orcai_amd/augment.py holds the specification, plan_ref / apply_ref; csrc/augment.hip): time
+ * and frequency masks, an additive level shift and mixing of two snippets of a batch, on a batch x f32[B][H][W] (normalised dB values in [0, 1]) and
+ * its labels y f32[B][S][L] (values 0, 1 and -1 = masked), H a multiple of S.  The reference has no augmentation.  Two launches per batch.
+ *
+ * Draws.  Draw j (0 <= j < ORCAI_AUGMENT_DRAWS) of snippet b is z = finalise(batch_key + 0x9E3779B97F4A7C15 * (b * ORCAI_AUGMENT_DRAWS + j + 1)) in
+ * uint64 arithmetic, `finalise` the three lines of splitmix64 that orcai_dropout_mask uses; an integer in [0, n) is ((z >> 32) * n) >> 32, a uniform
+ * f32 in [0, 1) is (float)(z >> 40) * 2^-24.  Slots: 0 mix decision, 1 partner, 2 level shift, 3 + 2k / 4 + 2k height / start of time mask k,
+ * 19 + 2k / 20 + 2k height / start of frequency mask k (k < 8); slots 35 .. 39 are not used.
+ *
+ * Plan.  int32 plan[B][ORCAI_AUGMENT_PLAN_WORDS], every word written:
+ *   0        partner snippet (b + 1 + int in [0, B - 1)) mod B if uniform < mix_probability and B > 1, else -1 (not mixed)
+ *   1        the bits of the f32 shift (u + u - 1) * level_shift, rounded once
+ *   2, 3     time_masks, freq_masks
+ *   4 + 2k   start of time mask k, 5 + 2k its height: height in [0, time_mask_rows], start in [0, H - height]; 0, 0 for k >= time_masks
+ *   20 + 2k  start of frequency mask k, 21 + 2k its width: the same with W and freq_mask_bins
+ * ------------------------------------------------------------------------------------------ */
+#define ORCAI_AUGMENT_MAX_MASKS 8
+#define ORCAI_AUGMENT_DRAWS 40
+#define ORCAI_AUGMENT_PLAN_WORDS 36
+#define ORCAI_AUGMENT_MAX_H 4096 /* rows of the row-mask image in LDS */
+#define ORCAI_AUGMENT_MAX_W 1024 /* bins of the column-mask image in LDS */
+#define ORCAI_AUGMENT_LEVEL_SHIFT 1 /* flags of orcai_augment_apply: add the plan's shift and clamp to [0, 1] */
+#define ORCAI_AUGMENT_MASK_LABELS 2 /*   a label step whose H / S rows all lie in the union of the time masks becomes -1 */
+
+/* Draws the plan of one batch on the device; batch_key travels by value, so nothing is copied or synchronised.
+ * ORCAI_E_BADARG: null plan, non-positive B / H / W, a negative count, time_mask_rows outside [0, H], freq_mask_bins outside [0, W], level_shift or
+ * mix_probability outside [0, 1] (NaN included).  ORCAI_E_UNSUPPORTED (nothing launched): more than ORCAI_AUGMENT_MAX_MASKS masks of a kind,
+ * H > ORCAI_AUGMENT_MAX_H, W > ORCAI_AUGMENT_MAX_W, B > 65535. */
+int orcai_augment_plan(uint64_t batch_key, int B, int H, int W, int time_masks, int time_mask_rows, int freq_masks, int freq_mask_bins, float level_shift,
+                       float mix_probability, int32_t* plan, void* stream);
+/* Applies a plan, out of place, in one launch (one snippet per blockIdx.y; the workgroup expands the snippet's masks into a row image and a column
+ * image in LDS and looks every element up).  Per element of x[b][r][c], in this order:
+ *   v = fmaxf(x_in[b], x_in[partner]) if mixed (the louder of the two in the dB domain), else x_in[b];
+ *   with ORCAI_AUGMENT_LEVEL_SHIFT: v = fminf(fmaxf(v + shift, 0), 1);
+ *   v = mask_value if r lies in a time mask or c in a frequency mask.
+ * Labels y_out[b][s][l]: mixed -> 1 if either snippet has 1, else -1 if either has -1, else 0; not mixed -> y_in; with ORCAI_AUGMENT_MASK_LABELS a
+ * step whose rows are all masked -> -1 for every label.  A plan with no mix and no masks and flags 0 copies x_in and y_in bit for bit.  Accesses are
+ * 16 bytes wide when x_in's and the partner's block and x_out's block are 16-byte aligned and H * W is a multiple of 4, scalar otherwise; any
+ * 4-byte alignment is accepted.  Partner and counts read from the plan are clamped to [0, B) and [0, 8]: a damaged plan cannot reach outside x_in.
+ * ORCAI_E_BADARG: a null pointer, non-positive B / H / W / S / L, H % S != 0, mask_value not finite, unknown flag bits, x_out overlapping x_in or
+ * y_out overlapping y_in.  ORCAI_E_UNSUPPORTED (nothing launched): H > ORCAI_AUGMENT_MAX_H, W > ORCAI_AUGMENT_MAX_W, B > 65535, S * L >= 2^31. */
+int orcai_augment_apply(const float* x_in, const float* y_in, const int32_t* plan, float* x_out, float* y_out, int B, int H, int W, int S, int L,
+                        float mask_value, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

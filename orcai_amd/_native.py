@@ -198,6 +198,8 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "orcai_interval_scores_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "orcai_threshold_counts": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "orcai_augment_plan": (C.c_int, [C.c_uint64] + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "orcai_augment_apply": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p]),
 }
 
 

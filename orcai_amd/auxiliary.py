@@ -19,6 +19,7 @@ SEED_ID_LOAD_VAL_DATA = 8
 SEED_ID_LOAD_TEST_DATA = 9
 SEED_ID_UNFILTERED_TEST_DATA = 10
 SEED_ID_LOAD_UNFILTERED_TEST_DATA = 11
+SEED_ID_AUGMENT = 12  # not in the reference: the training augmentation's draws (orcai_amd/augment.py)
 
 # value used to mask labels in the dataset (auxiliary.py:26)
 MASK_VALUE = -1.0

@@ -20,7 +20,8 @@ import numpy as np
 import pandas as pd
 
 from orcai_amd.architectures import build_model
-from orcai_amd.auxiliary import SEED_ID_LOAD_TEST_DATA, SEED_ID_LOAD_VAL_DATA, Messenger
+from orcai_amd import augment
+from orcai_amd.auxiliary import SEED_ID_AUGMENT, SEED_ID_LOAD_TEST_DATA, SEED_ID_LOAD_VAL_DATA, Messenger
 from orcai_amd.datasets import load_dataset
 from orcai_amd.fit import EarlyStopping, ModelCheckpoint
 from orcai_amd.io import read_json, write_json
@@ -81,6 +82,9 @@ def hyperparameter_search(data_dir: Path | str, output_dir: Path | str, orcai_pa
     if not isinstance(hps_parameter, dict):
         hps_parameter = read_json(hps_parameter)
     dataset_shape = read_json(data_dir.joinpath("dataset_shapes.json"))
+    # model.augment (null = off): checked before anything is loaded, applied to every trial's training batches only
+    augment_spec = orcai_parameter["model"].get("augment")
+    augment.validate(augment_spec, dataset_shape["spectrogram"][0], dataset_shape["spectrogram"][1])
     monitor = orcai_parameter["model"]["monitor"]
     hps_logs_dir = output_dir.joinpath("hps_logs")
     msgr.part("Searching hyperparameters")
@@ -102,6 +106,8 @@ def hyperparameter_search(data_dir: Path | str, output_dir: Path | str, orcai_pa
         # over the ranks (dp_batch "split"; orcai_parameter["model"]["dp_batch"] = "replicate" makes it the per-GPU batch instead)
         dpb = p["model"].get("dp_batch", "split")
         train_ds = load_dataset(data_dir.joinpath("train_dataset"), bs, compression=data_compression, seed=[SEED_ID_LOAD_TEST_DATA, orcai_parameter["seed"]], rank=rank, world_size=world, dp_batch=dpb)
+        # a promoted configuration goes on with the keys of the epochs it has not seen yet
+        train_ds = augment.augmented(train_ds, augment_spec, seed=[SEED_ID_AUGMENT, seed], rank=rank, first_epoch=initial_epoch)
         val_ds = load_dataset(data_dir.joinpath("val_dataset"), bs, compression=data_compression, seed=[SEED_ID_LOAD_VAL_DATA, orcai_parameter["seed"]], rank=rank, world_size=world, dp_batch=dpb)
         # the checkpoint is one weights file for trials of different architectures: the trial that writes it leaves its parameters beside it
         checkpoint.sidecar = {"orcai_parameter.json": p, "model_shape.json": {"input_shape": list(dataset_shape["spectrogram"]), "num_labels": len(p["calls"]), "hyperparameters": hp}}

@@ -17,7 +17,8 @@ import numpy as np
 
 from orcai_amd import parallel
 from orcai_amd.architectures import build_model
-from orcai_amd.auxiliary import SEED_ID_LOAD_TRAIN_DATA, SEED_ID_LOAD_VAL_DATA, Messenger
+from orcai_amd import augment
+from orcai_amd.auxiliary import SEED_ID_AUGMENT, SEED_ID_LOAD_TRAIN_DATA, SEED_ID_LOAD_VAL_DATA, Messenger
 from orcai_amd.datasets import load_dataset
 from orcai_amd.fit import EarlyStopping, ModelCheckpoint, ReduceLROnPlateau
 from orcai_amd.io import load_orcai_model, read_json, write_json
@@ -52,11 +53,15 @@ def train(data_dir: Path | str, output_dir: Path | str, orcai_parameter: (Path |
     else:
         msgr.info("Using default OrcAI dataset shapes")
         dataset_shape = {"spectrogram": [736, 171, 1], "labels": [46, 7]}
+    # model.augment (not in the reference; null = off): checked before anything is loaded, applied to the training batches only
+    augment_spec = model_parameter.get("augment")
+    augment.validate(augment_spec, dataset_shape["spectrogram"][0], dataset_shape["spectrogram"][1])
     # more than one rank (torchrun; the reference trains on one device, train.py:155): "replicate" = batch_size per GPU (throughput mode, the
     # optimiser sees batch_size x world), "split" = batch_size is the global batch as under the reference's MirroredStrategy
     dp_batch = model_parameter.get("dp_batch", "replicate")
     train_dataset = load_dataset(data_dir.joinpath("train_dataset"), model_parameter["batch_size"], compression=data_compression,
                                  seed=[SEED_ID_LOAD_TRAIN_DATA, orcai_parameter["seed"]], rank=rank, world_size=world, dp_batch=dp_batch)
+    train_dataset = augment.augmented(train_dataset, augment_spec, seed=[SEED_ID_AUGMENT, int(orcai_parameter["seed"] or 0)], rank=rank)
     val_dataset = load_dataset(data_dir.joinpath("val_dataset"), model_parameter["batch_size"], compression=data_compression,
                                seed=[SEED_ID_LOAD_VAL_DATA, orcai_parameter["seed"]], rank=rank, world_size=world, dp_batch=dp_batch)
     if model_parameter.get("call_weights") is not None:
