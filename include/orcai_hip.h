@@ -120,6 +120,8 @@ int orcai_quantile_select(const float* x, int64_t n, int64_t rank_lo, int64_t ra
 /* Turn the selected raw order statistics into clip bounds.
  *   use_ref = 1: values are un-referenced dB from orcai_stft_db; ref_db = 10*log10(max(pmax,1e-10)),
  *                bound = max(selected - ref_db, -top_db)                    (spectrogram.py:51-53)
+ *   use_ref = 2: as 1 with selected - ref_db rounded ONCE in f32 (use_ref = 1 fuses it into the multiplication that forms ref_db), so that the
+ *                bound is bit for bit the value orcai_clip_normalize gives the selected element: what orcai_make_mel_spectrogram uses
  *   use_ref = 0: values already are final dB (drop-in preprocess entry): bound = selected. */
 int orcai_frontend_finalize(int use_ref, float top_db, void* workspace, void* stream);
 
@@ -143,6 +145,34 @@ int orcai_frontend_stats_host(const void* workspace, float stats_host[6], void* 
  * n = n_frames * k_crop. */
 int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop,
                            int64_t rank_lo, int64_t rank_hi, float top_db, float* out, void* workspace, void* stream);
+
+/* Mel front end (no counterpart in the reference; semantics are librosa's documented defaults, parity unpinned):
+ *   S[k,t] = |stft(pcm, n_fft, hop, hann, center=True, zero padding)|^2,   M[m,t] = sum_k W[m][k] S[k,t],
+ *   out_db[t*n_mels + m] = 10*log10(max(M[m,t], 1e-10))
+ * fused: the linear spectrum never goes to memory.  W is a SPARSE band table: band m covers the FFT bins [band_lo[m], band_hi[m]) with the f32
+ * weights weights[band_off[m] .. band_off[m] + band_hi[m] - band_lo[m]) (orcai_amd.mel.band_table builds it from librosa.filters.mel's triangles).
+ *   band_lo, band_hi, band_off   int[n_mels] in HOST memory: read and checked during the call, handed to the kernels by value (nothing to keep alive)
+ *   weights    f32[n_weights] on the device, 16-byte aligned, 1 <= n_weights <= 65535
+ *   n_mels     8..256;  n_frames = 1 + n_samples / hop
+ *   out_db     f32[n_frames * n_mels], layout [frame][band], 16-byte aligned
+ * The workspace is left exactly as orcai_stft_db leaves it -- the level-1 histogram of the values written and, in the slot of max |X|^2, the maximum
+ * of M as a POWER (orcai_frontend_finalize(1, top_db) turns it into ref_db = 10*log10(max(max M, 1e-10)): power_to_db(ref=np.max, amin=1e-10)) --
+ * so orcai_quantile_select, orcai_frontend_finalize(1, .) and orcai_clip_normalize run unchanged behind it.  A band sum adds its bins in a fixed
+ * order and there are no float atomics on values: two calls give the same bytes.
+ * n_fft = 512: a mel epilogue of the tuned STFT kernel (powers, band table and weights in LDS; same three launch routes); the other powers of two
+ * from 128 to 4096 (and 512 with more than 1024 weights): one workgroup per frame + a separate level-1 histogram pass.
+ * ORCAI_E_BADARG (nothing launched, nothing written): null or misaligned pointer, non-positive size, n_mels outside 8..256, n_weights outside
+ * 1..65535, n_frames other than 1 + n_samples / hop, a band with band_lo < 0, band_hi < band_lo, band_hi > 1 + n_fft/2 or weights outside
+ * [0, n_weights).  ORCAI_E_UNSUPPORTED: n_fft that is no power of two from 128 to 4096. */
+int orcai_stft_mel_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                      const int* band_off, const float* weights, int n_weights, float* out_db, void* workspace, void* stream);
+int orcai_stft_mel_occupancy(void); /* workgroups of the 512-point mel kernel per compute unit as the runtime computes it */
+
+/* One call = reset + stft_mel_db + select + finalize(2, top_db) + clip_normalize: orcai_make_spectrogram for the mel route.  rank_lo / rank_hi as for
+ * orcai_quantile_select with n = n_frames * n_mels; out f32[n_frames * n_mels] in [0, 1]. */
+int orcai_make_mel_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo,
+                               const int* band_hi, const int* band_off, const float* weights, int n_weights, int64_t rank_lo, int64_t rank_hi,
+                               float top_db, float* out, void* workspace, void* stream);
 
 /* The statistics of the front-end run that just finished on `stream`, {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} as
  * orcai_frontend_stats_host returns them, copied by a one-thread launch into the caller's device buffer f32[6]: no host

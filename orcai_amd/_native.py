@@ -169,6 +169,9 @@ _SIGNATURES = {
     "orcai_l2_values": (C.c_int, [C.c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "orcai_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "orcai_make_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int, c_i64, c_i64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_stft_mel_db": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "orcai_stft_mel_occupancy": (C.c_int, []),
+    "orcai_make_mel_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, c_i64, c_i64, C.c_float] + [C.c_void_p] * 3),
     "orcai_frontend_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "orcai_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "orcai_sigmoid_bwd": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),

@@ -186,12 +186,42 @@ __device__ __forceinline__ void wave_lds_fence() {
 // FAST_ONLY: every group in [g_begin, g_end) is known (by the launcher) to satisfy the fast-path conditions for all four of its
 // waves, so the generic body is not even instantiated (134 VGPRs and no spills instead of 168 + spills).  KC > 0: k_crop is the
 // compile-time constant KC (171 for orcai-V1), which removes the per-bin crop branches from the real-FFT split.
-template <bool EVEN_HOP, bool FAST_ONLY, int KC>
-__global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames,
-                                                       int k_crop_arg, float* __restrict__ out, Workspace* __restrict__ ws, int64_t g_begin,
-                                                       int64_t g_end) {
+//
+// MEL (orcai_stft_mel_db): the same transform with a mel epilogue instead of the crop.  k_crop_arg is n_mels.  The 257 powers of each of the wave's four
+// frames are parked in the wave's tile (MEL_PSTRIDE floats per frame: 272 = 16 mod 64, so the four frames' 16 lanes write 64 different banks), the 64
+// lanes then sum the 4 x n_mels bands (task = frame * n_mels + band, one lane per task, bins in ascending order: a fixed order, no atomics on values)
+// from the band table and the packed weights, both resident in LDS (MelLds) for the life of the workgroup, and stage the dB values BEHIND the powers
+// in the same tile (4352 + 4 x 256 x 4 = 8448 <= 9216 B), from where they leave as the linear path's do.  The running maximum tracks the band powers.
+constexpr int MEL_MAX = 256;       // bands
+constexpr int MEL_W_LDS = 1024;    // packed weights the 512-point kernel keeps in LDS (triangles over 257 bins have at most 514)
+constexpr int MEL_PSTRIDE = 272;   // floats between the parked power rows of a wave's frames
+
+struct MelBands {  // kernel argument, by value: band m covers bins [lo, lo + n) with weights w[off .. off + n)
+  uint16_t lo[MEL_MAX], n[MEL_MAX], off[MEL_MAX];
+};
+struct MelLds {
+  float w[MEL_W_LDS];
+  uint16_t lo[MEL_MAX], n[MEL_MAX], off[MEL_MAX];
+};
+
+template <bool EVEN_HOP, bool FAST_ONLY, int KC, bool MEL>
+__device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames, int k_crop_arg,
+                                             float* __restrict__ out, Workspace* __restrict__ ws, int64_t g_begin, int64_t g_end,
+                                             const MelBands* __restrict__ mel_bands, const float* __restrict__ mel_w, int n_weights) {
+  static_assert(!MEL || KC == 0, "the mel epilogue has no compile-time crop");
   const int k_crop = KC > 0 ? KC : k_crop_arg;
   __shared__ StftLds lds;
+  MelLds* mel = nullptr;
+  if constexpr (MEL) {
+    __shared__ MelLds mel_lds;
+    mel = &mel_lds;
+    for (int i = threadIdx.x; i < n_weights; i += 256) mel_lds.w[i] = mel_w[i];
+    for (int i = threadIdx.x; i < k_crop; i += 256) {
+      mel_lds.lo[i] = mel_bands->lo[i];
+      mel_lds.n[i] = mel_bands->n[i];
+      mel_lds.off[i] = mel_bands->off[i];
+    }
+  }
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
@@ -286,7 +316,7 @@ __global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict
     if (l16 == 0) zt[256] = z[P16(0)];  // so that bin 256 - k needs no wrap: the mirrored address is one per-lane base + a compile-time offset
     wave_lds_fence();
     const c2* zm = zt + (16 - l16);  // Z[256 - (16 k1 + k2)] = zm[16 (15 - k1)]
-    float Lk[(KC > 0 ? (KC + 15) / 16 : 16)];
+    float Lk[(KC > 0 ? (KC + 15) / 16 : 16)];  // MEL: 4 |X|^2 of the lane's 16 bins
     const c2 z0 = z[P16(0)];
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) {
@@ -301,17 +331,49 @@ __global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict
       asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(P) : "v"(O), "v"(cs), "v"(T));  // (s O.im + ., -s O.re + .)
       const c2 X2 = E + P;
       const float p4 = fmaf(X2.x, X2.x, X2.y * X2.y);  // 4 |X|^2
-      if (valid) pmax = fmaxf(pmax, p4);
-      if (KC > 0 ? (16 * k1 < KC) : true) Lk[KC > 0 ? k1 : k1] = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
+      if constexpr (MEL) {
+        Lk[k1] = p4;
+      } else {
+        if (valid) pmax = fmaxf(pmax, p4);
+        if (KC > 0 ? (16 * k1 < KC) : true) Lk[KC > 0 ? k1 : k1] = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
+      }
     }
     float Lnyq = 0.0f;
     if (l16 == 0) {  // Nyquist bin 256: X = Re Z0 - Im Z0
       const float x = z0.x - z0.y;
       const float p4 = 4.0f * x * x;
-      if (valid) pmax = fmaxf(pmax, p4);
-      Lnyq = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
+      if constexpr (MEL) {
+        Lnyq = p4;
+      } else {
+        if (valid) pmax = fmaxf(pmax, p4);
+        Lnyq = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
+      }
     }
     wave_lds_fence();  // every mirrored read is done before the tile becomes the output staging
+    if constexpr (MEL) {
+      float* pw = reinterpret_cast<float*>(my_tile) + fsub * MEL_PSTRIDE;  // |X|^2 (the exact quarter of what the loop tracked); frames past the end hold zeros
+#pragma unroll
+      for (int k1 = 0; k1 < 16; ++k1) pw[16 * k1 + l16] = 0.25f * Lk[k1];
+      if (l16 == 0) pw[256] = 0.25f * Lnyq;
+      wave_lds_fence();  // the band sums read every lane's powers
+      float* stage = reinterpret_cast<float*>(my_tile) + 4 * MEL_PSTRIDE;  // behind the powers: no band sum reads what another lane stages
+      const int nm = k_crop;
+      for (int idx = lane; idx < 4 * nm; idx += 64) {
+        const int f = (idx >= nm) + (idx >= 2 * nm) + (idx >= 3 * nm);
+        const int m = idx - f * nm;
+        const float* w = mel->w + mel->off[m];
+        const float* p = reinterpret_cast<const float*>(my_tile) + f * MEL_PSTRIDE + mel->lo[m];
+        const int nk = mel->n[m];
+        float acc = 0.0f;
+        for (int j = 0; j < nk; ++j) acc = fmaf(w[j], p[j], acc);  // ascending bins: the same order on every launch
+        const float L = power_to_db(acc);
+        stage[idx] = L;
+        if (FAST || t0w + f < n_frames) {
+          pmax = fmaxf(pmax, acc);
+          atomicAdd(&lds.hist[bucket1f(L)], 1u);
+        }
+      }
+    } else {
     float* stage = reinterpret_cast<float*>(my_tile) + fsub * k_crop;
 #pragma unroll
     for (int k1 = 0; k1 < (KC > 0 ? (KC + 15) / 16 : 16); ++k1) {
@@ -325,6 +387,7 @@ __global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict
       stage[256] = Lnyq;
       if (valid) atomicAdd(&lds.hist[bucket1f(Lnyq)], 1u);
     }
+    }
     wave_lds_fence();
 
     // step 6: the wave's valid frames are one contiguous run of out[]
@@ -332,7 +395,7 @@ __global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict
     nv = nv < 0 ? 0 : (nv > 4 ? 4 : nv);
     const int count = (int)nv * k_crop;
     float* dst = out + t0w * (int64_t)k_crop;  // 16-byte aligned: t0w % 4 == 0
-    const float* src = reinterpret_cast<const float*>(my_tile);
+    const float* src = reinterpret_cast<const float*>(my_tile) + (MEL ? 4 * MEL_PSTRIDE : 0);
     const int n4 = count >> 2;
     for (int i = lane; i < n4; i += 64) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
     for (int i = (n4 << 2) + lane; i < count; i += 64) dst[i] = src[i];
@@ -381,12 +444,27 @@ __global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict
   // wave max -> one atomic per wave
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) pmax = fmaxf(pmax, __shfl_xor(pmax, off, 64));
-  if (lane == 0) atomicMax(&ws->pmax_bits, __float_as_uint(0.25f * pmax));  // the loop tracked 4 |X|^2 (exact scaling)
+  if (lane == 0) atomicMax(&ws->pmax_bits, __float_as_uint(MEL ? pmax : 0.25f * pmax));  // the linear loop tracked 4 |X|^2 (exact scaling), the mel one band powers
   __syncthreads();
   for (int i = tid; i < NB1; i += 256) {
     uint32_t c = lds.hist[i];
     if (c) atomicAdd(&ws->hist1[i], c);
   }
+}
+
+template <bool EVEN_HOP, bool FAST_ONLY, int KC>
+__global__ __launch_bounds__(256, 3) void stft_db_kernel(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames,
+                                                       int k_crop_arg, float* __restrict__ out, Workspace* __restrict__ ws, int64_t g_begin,
+                                                       int64_t g_end) {
+  stft_db_body<EVEN_HOP, FAST_ONLY, KC, false>(pcm, n_samples, hop, n_frames, k_crop_arg, out, ws, g_begin, g_end, nullptr, nullptr, 0);
+}
+
+// The mel variant: 58 944 B of LDS (StftLds + MelLds), two workgroups per compute unit where the linear kernel has three.
+template <bool EVEN_HOP, bool FAST_ONLY>
+__global__ __launch_bounds__(256, 2) void stft_mel_kernel(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames, int n_mels,
+                                                        float* __restrict__ out, Workspace* __restrict__ ws, int64_t g_begin, int64_t g_end,
+                                                        const MelBands bands, const float* __restrict__ weights, int n_weights) {
+  stft_db_body<EVEN_HOP, FAST_ONLY, 0, true>(pcm, n_samples, hop, n_frames, n_mels, out, ws, g_begin, g_end, &bands, weights, n_weights);
 }
 
 // ---------------------------------------------------------------- STFT + dB for any power-of-two transform size (the reference reads nfft
@@ -439,6 +517,65 @@ __global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
   if ((tid & 63) == 0) wmax[tid >> 6] = pmax;
+  __syncthreads();
+  if (tid == 0) atomicMax(&ws->pmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+}
+
+// ---------------------------------------------------------------- STFT + mel + dB for the powers of two from 128 to 4096 (orcai_stft_mel_db away from the
+// tuned 512-point kernel).  stft_any_kernel's transform, then |X|^2 of all 1 + nfft/2 bins parked in LDS and one WAVE per band: lane l adds bins
+// lo + l, lo + l + 64, ... in ascending order and the 64 partial sums meet in a fixed butterfly, so two launches give the same bits.  Weights come
+// from global memory (a few KiB, cached), the band table from the kernel argument.  max M as stft_any_kernel leaves max |X|^2; the level-1 histogram
+// is orcai_hist_level1's second pass.
+__global__ __launch_bounds__(256) void stft_mel_any_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                            int n_mels, float* __restrict__ out_db, Workspace* __restrict__ ws, const MelBands bands,
+                                                            const float* __restrict__ weights) {
+  __shared__ float2 buf[NFFT_ANY_MAX];
+  __shared__ float pw[NFFT_ANY_MAX / 2 + 1];
+  __shared__ float wmax[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = n_fft >> 1;
+  float pmax = 0.0f;
+  for (int64_t t = blockIdx.x; t < n_frames; t += gridDim.x) {
+    const int64_t s0 = t * hop - half;
+    for (int n = tid; n < n_fft; n += 256) {
+      const int64_t i = s0 + n;
+      const float x = (i >= 0 && i < n_samples) ? pcm[i] : 0.0f;
+      const float sw = sinpif((float)n / (float)n_fft);  // periodic Hann as sin^2(pi n / N), as stft_any_kernel
+      buf[__brev((uint32_t)n) >> (32 - log2n)] = make_float2(x * (sw * sw), 0.0f);
+    }
+    __syncthreads();
+    for (int st = 1; st <= log2n; ++st) {
+      const int hm = 1 << (st - 1);
+      for (int j = tid; j < half; j += 256) {
+        const int k = j & (hm - 1);
+        const int i0 = ((j >> (st - 1)) << st) + k, i1 = i0 + hm;
+        float sn, cs;
+        sincospif(-(float)k / (float)hm, &sn, &cs);
+        const float2 a = buf[i0], b = buf[i1];
+        const float2 tb = make_float2(fmaf(b.x, cs, -b.y * sn), fmaf(b.x, sn, b.y * cs));
+        buf[i0] = make_float2(a.x + tb.x, a.y + tb.y);
+        buf[i1] = make_float2(a.x - tb.x, a.y - tb.y);
+      }
+      __syncthreads();
+    }
+    for (int k = tid; k <= half; k += 256) {
+      const float2 z = buf[k];
+      pw[k] = fmaf(z.x, z.x, z.y * z.y);
+    }
+    __syncthreads();
+    for (int m = wave; m < n_mels; m += 4) {  // wave-uniform
+      const int lo = bands.lo[m], nk = bands.n[m];
+      const float* w = weights + bands.off[m];
+      float acc = 0.0f;
+      for (int j = lane; j < nk; j += 64) acc = fmaf(w[j], pw[lo + j], acc);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // a + b == b + a: every lane holds the same bits
+      if (lane == 0) out_db[t * (int64_t)n_mels + m] = power_to_db(acc);
+      pmax = fmaxf(pmax, acc);
+    }
+    __syncthreads();
+  }
+  if (lane == 0) wmax[wave] = pmax;
   __syncthreads();
   if (tid == 0) atomicMax(&ws->pmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
 }
@@ -661,6 +798,11 @@ __global__ __launch_bounds__(1024) void select_scan2_kernel(Workspace* __restric
   }
 }
 
+__device__ __forceinline__ float sub_rounded_once(float a, float b) {  // a - b that is never fused into the multiplication that produced b
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 __global__ void finalize_kernel(Workspace* __restrict__ ws, int use_ref, float top_db) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const float lo = key2f(ws->sel[0].klo), hi = key2f(ws->sel[1].klo);
@@ -679,6 +821,22 @@ __global__ void finalize_kernel(Workspace* __restrict__ ws, int use_ref, float t
     ws->p_lo = lo;
     ws->p_hi = hi;
   }
+}
+
+// use_ref = 2 (the mel route), a kernel of its own so that finalize_kernel's code stays what it is: the bound is the clipped value of the selected
+// element bit for bit -- x - ref_db rounded once, as clip_normalize_kernel computes it -- where finalize_kernel fuses the subtraction into the
+// multiplication that forms ref_db.
+__global__ void finalize_once_kernel(Workspace* __restrict__ ws, float top_db) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float lo = key2f(ws->sel[0].klo), hi = key2f(ws->sel[1].klo);
+  const float ref_db = power_to_db(__uint_as_float(ws->pmax_bits));
+  ws->sel_raw[0] = lo;
+  ws->sel_raw[1] = hi;
+  ws->use_ref = 2u;
+  ws->ref_db = ref_db;
+  ws->floor_db = -top_db;
+  ws->p_lo = fmaxf(sub_rounded_once(lo, ref_db), -top_db);
+  ws->p_hi = fmaxf(sub_rounded_once(hi, ref_db), -top_db);
 }
 
 __device__ __forceinline__ float norm1(float x, float ref_db, float floor_db, float lo, float hi, float range) {
@@ -980,6 +1138,73 @@ int orcai_stft_occupancy(void) {  // workgroups of stft_db_kernel<true, true, 17
   return n;
 }
 
+int orcai_stft_mel_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                      const int* band_off, const float* weights, int n_weights, float* out_db, void* workspace, void* stream) {
+  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !out_db || !workspace) return ORCAI_E_BADARG;
+  if (n_samples <= 0 || hop <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
+  if (((uintptr_t)out_db & 15) || ((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15)) return ORCAI_E_BADARG;
+  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
+  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
+  MelBands bands;
+  std::memset(&bands, 0, sizeof(bands));
+  const int n_bins = 1 + n_fft / 2;
+  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernels by value
+    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
+    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
+    bands.lo[m] = (uint16_t)lo;
+    bands.n[m] = (uint16_t)(hi - lo);
+    bands.off[m] = (uint16_t)off;
+  }
+  Workspace* ws = (Workspace*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_fft != NFFT || n_weights > MEL_W_LDS) {  // (512 with a table wider than the tuned kernel's LDS copy -- no triangular one is -- runs here too)
+    int log2n = 0;
+    while ((1 << log2n) < n_fft) ++log2n;
+    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
+    hipLaunchKernelGGL(stft_mel_any_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out_db, ws, bands, weights);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return orcai_hist_level1(out_db, n_frames * (int64_t)n_mels, workspace, stream);
+  }
+  std::call_once(g_tables_once, init_tables);
+  if (g_tables_err) return g_tables_err;
+  const int64_t n_groups = (n_frames + 15) / 16;
+  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
+  if ((hop & 1) != 0) {
+    hipLaunchKernelGGL((stft_mel_kernel<false, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0,
+                       n_groups, bands, weights, n_weights);
+    return (int)hipGetLastError();
+  }
+  int64_t g_lo = n_groups, g_hi = n_groups;  // the interior groups, by orcai_stft_db's rule
+  if (hop == 256) {
+    g_lo = 1;
+    const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;
+    const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;
+    g_hi = by_samples < by_frames ? by_samples : by_frames;
+    if (g_hi > n_groups) g_hi = n_groups;
+    if (g_hi < g_lo) g_lo = g_hi = n_groups;
+  }
+  if (g_hi > g_lo) {
+    hipLaunchKernelGGL((stft_mel_kernel<true, true>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, g_lo, g_hi, bands,
+                       weights, n_weights);
+    hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0, g_lo, bands,
+                       weights, n_weights);
+    if (g_hi < n_groups)
+      hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, g_hi,
+                         n_groups, bands, weights, n_weights);
+  } else {
+    hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0, n_groups,
+                       bands, weights, n_weights);
+  }
+  return (int)hipGetLastError();
+}
+
+int orcai_stft_mel_occupancy(void) {  // workgroups of stft_mel_kernel<true, true> the runtime says fit one compute unit
+  int n = -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)stft_mel_kernel<true, true>, 256, 0) != hipSuccess) return -1;
+  return n;
+}
+
 int orcai_hist_level1(const float* x, int64_t n, void* workspace, void* stream) {
   if (!x || !workspace || n <= 0 || ((uintptr_t)x & 15)) return ORCAI_E_BADARG;
   int grid = grid_for(0, (n / 4 + 255) / 256);
@@ -1005,7 +1230,8 @@ int orcai_quantile_select(const float* x, int64_t n, int64_t rank_lo, int64_t ra
 
 int orcai_frontend_finalize(int use_ref, float top_db, void* workspace, void* stream) {
   if (!workspace) return ORCAI_E_BADARG;
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (Workspace*)workspace, use_ref, top_db);
+  if (use_ref == 2) hipLaunchKernelGGL(finalize_once_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (Workspace*)workspace, top_db);
+  else hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (Workspace*)workspace, use_ref, top_db);
   return (int)hipGetLastError();
 }
 
@@ -1092,6 +1318,23 @@ int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int h
   e = orcai_quantile_select(out, n, rank_lo, rank_hi, workspace, stream);
   if (e) return e;
   e = orcai_frontend_finalize(1, top_db, workspace, stream);
+  if (e) return e;
+  return orcai_clip_normalize(out, n, workspace, stream);
+}
+
+int orcai_make_mel_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                               const int* band_off, const float* weights, int n_weights, int64_t rank_lo, int64_t rank_hi, float top_db, float* out,
+                               void* workspace, void* stream) {
+  const int64_t n = n_frames * (int64_t)n_mels;
+  if (!workspace || !out || n_mels < 8 || n_mels > MEL_MAX || n_frames <= 0 || rank_lo < 0 || rank_hi < 0 || rank_lo >= n || rank_hi >= n)
+    return ORCAI_E_BADARG;  // what the later steps would refuse, before the first one runs
+  int e = orcai_frontend_reset(workspace, stream);
+  if (e) return e;
+  e = orcai_stft_mel_db(pcm, n_samples, n_fft, hop, n_frames, n_mels, band_lo, band_hi, band_off, weights, n_weights, out, workspace, stream);
+  if (e) return e;
+  e = orcai_quantile_select(out, n, rank_lo, rank_hi, workspace, stream);
+  if (e) return e;
+  e = orcai_frontend_finalize(2, top_db, workspace, stream);
   if (e) return e;
   return orcai_clip_normalize(out, n, workspace, stream);
 }

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from orcai_amd import _native as N
+from orcai_amd import mel
 
 TOP_DB = 80.0  # librosa.amplitude_to_db default, spectrogram.py:51-53
 
@@ -49,6 +50,7 @@ class FrontEnd:
         self.device = torch.device(device)
         nbytes = self.lib.orcai_frontend_workspace_bytes()
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._mel_tables: dict = {}
 
     @staticmethod
     def _check_nfft(n_fft: int) -> None:
@@ -64,6 +66,9 @@ class FrontEnd:
     # -- the whole of make_spectrogram after decode (spectrogram.py:90-147) -----------------
     def _kept_bins(self, spectrogram_parameter: dict) -> int:
         """K of make_spectrogram's [T, K]; the parameter's own refusals."""
+        cfg = mel.mel_config(spectrogram_parameter)
+        if cfg is not None:  # the mel route: K = n_mels, no frequency crop
+            return cfg["n_mels"]
         n_fft = int(spectrogram_parameter["nfft"])
         self._check_nfft(n_fft)
         freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
@@ -71,6 +76,14 @@ class FrontEnd:
         if f_lo != 0:
             raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
         return f_hi
+
+    def _mel_table(self, spectrogram_parameter: dict, cfg: dict):
+        """(host band table, packed weights on this device) of a mel parameter: uploaded once per (device, parameter) and kept."""
+        key = (float(spectrogram_parameter["sampling_rate"]), int(spectrogram_parameter["nfft"]), *(cfg[k] for k in mel.MEL_KEYS))
+        if key not in self._mel_tables:
+            t = mel.table_for(spectrogram_parameter, cfg)
+            self._mel_tables[key] = (t, torch.from_numpy(t["weights"].copy()).to(self.device))
+        return self._mel_tables[key]
 
     def spectrogram_shape(self, n_samples: int, spectrogram_parameter: dict) -> tuple[int, int]:
         """(T, K) of make_spectrogram's result for a signal of n_samples at the parameter's rate: host arithmetic only."""
@@ -97,6 +110,19 @@ class FrontEnd:
         total = T * K
         r_lo = nearest_rank_index(total, spectrogram_parameter["quantiles"][0])
         r_hi = nearest_rank_index(total, spectrogram_parameter["quantiles"][1])
+        cfg = mel.mel_config(spectrogram_parameter)
+        if cfg is not None:
+            t, weights = self._mel_table(spectrogram_parameter, cfg)
+            N.check(
+                self.lib.orcai_make_mel_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights),
+                                                    weights.numel(), r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()),
+                "orcai_make_mel_spectrogram",
+            )
+            if return_stats:
+                stats = torch.empty(6, dtype=torch.float32, device=self.device)
+                N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
+                return out, stats
+            return out
         N.check(
             self.lib.orcai_make_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()),
             "orcai_make_spectrogram",
@@ -118,6 +144,9 @@ class FrontEnd:
     def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
         returned for the same pcm.  ref_db, p_lo and p_hi are constants of the backward (include/orcai_hip.h: orcai_spectrogram_bwd)."""
+        if mel.mel_config(spectrogram_parameter) is not None:
+            raise NotImplementedError("spectrogram_backward: the gradient w.r.t. the audio is not implemented for the mel front end (spectrogram parameter "
+                                      "mel is set); the linear front end (mel absent or null) has it")
         n_fft = int(spectrogram_parameter["nfft"])
         hop = int(spectrogram_parameter["n_overlap"])
         self._check_nfft(n_fft)

@@ -314,6 +314,14 @@ def _convert_times_to_seconds(predicted_labels: pd.DataFrame, delta_t: float) ->
     return predicted_labels
 
 
+def _mel_width_hint(orcai_parameter: dict) -> str:
+    """Tail of the width error when the mel front end is on: the width is then n_mels, not the freq_range crop."""
+    mel = orcai_parameter["spectrogram"].get("mel")
+    if mel is None:
+        return ""
+    return f": spectrogram parameter mel is set, so the width is mel.n_mels = {mel.get('n_mels')}; the model must have been trained at that width"
+
+
 def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_parameter: dict, shape: dict, msgr: Messenger = Messenger(verbosity=0),
                        progressbar: tqdm = None, device_labels: dict | None = None) -> dict:
     """First half of predict_wav: spectrogram, snippets through the model and the overlap average are QUEUED on the GPU, the averaged
@@ -331,7 +339,8 @@ def predict_wav_launch(recording_path: Path | str, channel: int, model, orcai_pa
         spectrogram, _, times = make_spectrogram(recording_path, channel, orcai_parameter, msgr=msgr)
     delta_t = times[1] - times[0]
     if spectrogram.shape[1] != shape["input_shape"][1]:
-        raise ValueError(f"Spectrogram shape ({spectrogram.shape[1]}) for {recording_path.stem} not equal to input shape ({shape['input_shape'][1]})")
+        raise ValueError(f"Spectrogram shape ({spectrogram.shape[1]}) for {recording_path.stem} not equal to input shape ({shape['input_shape'][1]})"
+                         + _mel_width_hint(orcai_parameter))
     msgr.part(f"Prediction of annotations for wav_file: {recording_path.stem}")
     if progressbar:
         progressbar.set_description(f"{recording_path.stem} - Predicting annotations")
@@ -446,7 +455,7 @@ def _launch_batches(sources, model, orcai_parameter: dict, shape: dict, max_fram
             times = fe.frames_to_time(min(T, 2), sp["sampling_rate"], sp["n_overlap"])
             delta_t = times[1] - times[0]
             if K != W:
-                raise ValueError(f"Spectrogram shape ({K}) for {getattr(key, 'stem', key)} not equal to input shape ({W})")
+                raise ValueError(f"Spectrogram shape ({K}) for {getattr(key, 'stem', key)} not equal to input shape ({W})" + _mel_width_hint(orcai_parameter))
             if T < H:
                 raise _too_short(T, H)
         except Exception as e:  # this recording alone; the batch goes on

@@ -16,6 +16,7 @@ import torch
 from tqdm import tqdm
 
 from orcai_amd import frontend as fe
+from orcai_amd import mel
 from orcai_amd.auxiliary import Messenger
 from orcai_amd.io import read_json, save_array, write_vector_to_json
 from orcai_amd import wavio
@@ -64,8 +65,15 @@ def load_wav_all(wav_file_path: Path | str, sampling_rate: int, msgr: Messenger)
     return pcms
 
 
+def _linear_only(spectrogram_parameter: dict, what: str) -> None:
+    """The two-step API returns and takes the LINEAR dB spectrum (the reference's contract); the mel route exists as make_spectrogram only."""
+    if spectrogram_parameter.get("mel") is not None:
+        raise NotImplementedError(f"{what}: the two-step API is linear-only; with spectrogram parameter mel set use make_spectrogram (or set mel to null)")
+
+
 def calculate_spectrogram(wav_file_path: Path, channel: int, spectrogram_parameter: dict, msgr: Messenger = Messenger(verbosity=0)):
     """dB spectrogram [257, T] (float32), frequencies [257], times [T] (spectrogram.py:15-55)."""
+    _linear_only(spectrogram_parameter, "calculate_spectrogram")
     sr = spectrogram_parameter["sampling_rate"]
     n_fft = spectrogram_parameter["nfft"]
     hop = spectrogram_parameter["n_overlap"]
@@ -79,6 +87,7 @@ def calculate_spectrogram(wav_file_path: Path, channel: int, spectrogram_paramet
 
 def preprocess_spectrogram(spectrogram: np.ndarray, frequencies: np.ndarray, spectrogram_parameter: dict) -> np.ndarray:
     """Crop to freq_range, clip to the quantiles, normalise to [0, 1], transpose (spectrogram.py:58-87)."""
+    _linear_only(spectrogram_parameter, "preprocess_spectrogram")
     f_lo, f_hi = fe.crop_indices(frequencies, spectrogram_parameter["freq_range"])
     x = torch.from_numpy(np.ascontiguousarray(spectrogram, dtype=np.float32)).cuda()
     out = fe.get_frontend().preprocess_db(x, f_lo, f_hi, spectrogram_parameter["quantiles"])
@@ -86,11 +95,16 @@ def preprocess_spectrogram(spectrogram: np.ndarray, frequencies: np.ndarray, spe
 
 
 def make_spectrogram_device(wav_file_path: Path | str, channel: int, orcai_parameter: dict, msgr: Messenger):
-    """make_spectrogram with the spectrogram left on the GPU: (f32 cuda tensor [T, K], frequencies, times)."""
+    """make_spectrogram with the spectrogram left on the GPU: (f32 cuda tensor [T, K], frequencies, times).  With spectrogram parameter mel set K is
+    n_mels and frequencies are the n_mels band centres; otherwise the uncropped FFT frequencies, as the reference returns them."""
     sp = orcai_parameter["spectrogram"]
+    cfg = mel.mel_config(sp)  # the parameter's refusals, before the file is read
     pcm = load_wav(wav_file_path, sp["sampling_rate"], channel, msgr)
     spec = fe.get_frontend().make_spectrogram(pcm, sp)
-    frequencies = fe.fft_frequencies(sp["sampling_rate"], sp["nfft"])
+    if cfg is not None:  # the mel route: one frequency per column, the bands' centres
+        frequencies = mel.table_for(sp, cfg)["centres"].copy()
+    else:
+        frequencies = fe.fft_frequencies(sp["sampling_rate"], sp["nfft"])
     times = fe.frames_to_time(spec.shape[0], sp["sampling_rate"], sp["n_overlap"])
     return spec, frequencies, times
 

@@ -5,6 +5,7 @@ known without a GPU.
 
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.mel_spectrogram(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -29,6 +30,9 @@ normalisation statistics are held constant), so the chain pcm -> spectrogram -> 
 waveform.  ``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
 same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
 sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
+``mel_spectrogram`` is the mel route of the front end (``orcai_make_mel_spectrogram``: the mel filterbank and the dB step fused into the STFT kernel, no
+frequency crop).  It has a fake implementation and NO autograd: the gradient through the mel route is not implemented, ``spectrogram_wrt_pcm`` has no mel
+argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` key is set (NotImplementedError).
 ``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
 of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
 bytes, so it has no autograd.
@@ -293,6 +297,31 @@ def spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: f
 def _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
     T = 1 + (pcm.shape[0] - (nfft & 1)) // hop
     return pcm.new_empty((T, _bins(sampling_rate, nfft, freq_hi)), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::mel_spectrogram
+# The mel route of the front end (spectrogram parameter "mel"; orcai_make_mel_spectrogram): no frequency crop, K = n_mels.  Forward only -- the
+# gradient through the mel route does not exist, so the op has NO autograd formula and a pcm that requires grad gets PyTorch's own refusal.
+def _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo=0.0, q_hi=1.0) -> dict:
+    return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [fmin, fmax], "quantiles": [q_lo, q_hi],
+            "mel": {"n_mels": n_mels, "fmin": fmin, "fmax": fmax, "htk": htk, "norm": "slaney" if slaney_norm else None}}
+
+
+@torch.library.custom_op("orcai::mel_spectrogram", mutates_args=())
+def mel_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                    q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the mel parameter {n_mels, fmin, fmax, htk, norm = "slaney" if
+    slaney_norm else null}: f32[T, n_mels] in [0, 1].  nfft a power of two from 128 to 4096."""
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::mel_spectrogram")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(pcm, _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi))
+
+
+@mel_spectrogram.register_fake
+def _mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
+    return pcm.new_empty((1 + pcm.shape[0] // hop, n_mels), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
@@ -620,6 +649,9 @@ class WaveformFrontEnd(torch.nn.Module):
     def __init__(self, spectrogram_parameter: dict, native_rate: int):
         super().__init__()
         sp = spectrogram_parameter
+        if sp.get("mel") is not None:
+            raise NotImplementedError("WaveformFrontEnd: spectrogram parameter mel is set and the mel front end has no gradient w.r.t. the audio "
+                                      "(orcai::mel_spectrogram is forward-only); set mel to null for the differentiable linear front end")
         if float(sp["freq_range"][0]) != 0.0:
             raise ValueError(f"WaveformFrontEnd: freq_range must start at 0 (orcai::spectrogram keeps the leading bins), got {sp['freq_range']}")
         self.native_rate = int(native_rate)
