@@ -216,12 +216,18 @@ int orcai_padded_width(int W, int ksize);
 
 /* Knob of the separable-conv launcher for k = 3 launches with plane or x-pooled output (the inference trunk, the training forward
  * with its depthwise-output store, the input-gradient passes).  1 (default): the LDS-shared-row kernels -- sepconv_tile_kernel (a
- * workgroup of 8 waves owns 8 image rows x 64 columns; the tile's 10 input rows per channel quad are fetched once by LDS-DMA) for
- * planes at least two strips wide with Cout in 17..32 and <= 8 input quads, sepconv_ftile_kernel (8 consecutive windows of the flat
- * plane share one contiguous range of rows) for the rest; 2: sepconv_ftile_kernel for all of them; 0: the one-window-per-wave
- * sepconv_kernel everywhere.  All three perform the same arithmetic in the same order (bit-identical results).  Returns the previous
- * value; values outside [0, 2] only query.  Process-wide, not thread-safe. */
+ * workgroup of 8 waves owns 8 image rows x 64 columns; the tile's 10 input rows per channel quad are fetched once by LDS-DMA) on the
+ * "strip" route, sepconv_ftile_kernel (8 consecutive windows of the flat plane share one contiguous range of rows) on the "flat"
+ * route; 2: no strips; 0: the one-window-per-wave sepconv_kernel everywhere.  Which shape takes which route is stated once, in
+ * orcai_amd/csrc/sep_route.h, and reported by orcai_sepconv_route.  All three perform the same arithmetic in the same order
+ * (bit-identical results).  Returns the previous value; values outside [0, 2] only query.  Process-wide, not thread-safe. */
 int orcai_sepconv_tile_mode(int mode);
+
+/* The route of a k = 3 launch on R = 1 planes under the current orcai_sepconv_tile_mode: 0 window, 1 strip, 2 flat.  Pure host code,
+ * no GPU call.  half: 0 the f32 launcher, 1 the f16 one.  extras: 0 none, 1 depthwise-output store, 2 + output statistics
+ * (orcai_[h_]sepconv[_planes]_stats), 3 + BatchNorm folded on load (..._stats_bn), 4 / 5 epi 2 / 3 of orcai_sepconv_planes_epi (f32
+ * only).  The entry points with extras >= 2 return ORCAI_E_UNSUPPORTED exactly where this says window.  ORCAI_E_BADARG on nonsense. */
+int orcai_sepconv_route(int half, int Cin, int Cout, int H, int W, int out_layout, int extras);
 
 /* Same kind of knob for orcai_conv0_sepconv: windows per wave (>= 1; the next window's inputs are prefetched while the current
  * one is computed).  Returns the previous value; values outside [1, 64] only query. */
@@ -576,7 +582,7 @@ int orcai_bn_planes_stats(const float* v, int B, int C, int H, int W, int ksize,
  * (train.py:155-219 runs keras' SeparableConv2D -> BatchNormalization(training=True)): = orcai_sepconv_planes_u(ksize_planes = ktap = 3,
  * relu_out = 0, out_layout = 0) followed by the sums of orcai_bn_planes_stats, without the read pass over `out`.
  *   shards   f64[32][ceil(Cout/4)][8] accumulator copies (zeroed here); orcai_bn_finish_sharded turns them into mean / biased variance
- * Only the shapes the LDS-tile kernels take (every plane up to ~500 pixels wide with orcai_sepconv_tile_mode != 0): ORCAI_E_UNSUPPORTED
+ * Only the shapes the LDS-tile kernels take (orcai_sepconv_route(0, ..., 0, 2) != 0; sep_route.h states the rule): ORCAI_E_UNSUPPORTED
  * otherwise, with nothing touched, and the caller runs the two calls above.  Per-workgroup partial sums are f32 (512 pixels), accumulated
  * in f64. */
 int orcai_sepconv_planes_stats(const float* in, int B, int Cin, int H, int W, int relu_in, const float* dw, const float* pw, const float* scale, const float* shift,
@@ -595,7 +601,8 @@ int orcai_sepconv_planes_stats_bn(const float* v_in, int B, int Cin, int H, int 
  *          `shards` as scratch2C = dbeta[4 CQo] | dgamma[4 CQo] doubles (shards: 32 * 8 * CQo doubles of workspace): the next
  *          orcai_bn_bwd_pointwise(_wgrad) call takes sums_ready = 1 and the read pass over (dy, v) is gone;
  *   epi 3: out = ref > 0 ? out : 0 (the ReLU in front of the conv, folded: no separate orcai_planes_relu_bwd pass).
- * ORCAI_E_UNSUPPORTED (before anything is touched) for shapes the LDS-tile kernels do not take: the caller runs the separate passes. */
+ * ORCAI_E_UNSUPPORTED (before anything is touched) for shapes the LDS-tile kernels do not take (orcai_sepconv_route(0, ..., 0, 2 + epi)
+ * == 0): the caller runs the separate passes. */
 int orcai_sepconv_planes_epi(const float* in, int B, int Cin, int H, int W, const float* dw, const float* pw, const float* scale, const float* shift, int Cout, float* out,
                              int epi, const float* ref, const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu, double* shards,
                              void* stream);

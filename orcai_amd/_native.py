@@ -49,6 +49,7 @@ _SIGNATURES = {
     "orcai_pool_res_add_scatter_families": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "orcai_padded_width": (C.c_int, [C.c_int, C.c_int]),
     "orcai_sepconv_tile_mode": (C.c_int, [C.c_int]),
+    "orcai_sepconv_route": (C.c_int, [C.c_int] * 7),
     "orcai_entry_windows": (C.c_int, [C.c_int]),
     "orcai_entry_tile": (C.c_int, [C.c_int]),
     "orcai_conv0_sepconv": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

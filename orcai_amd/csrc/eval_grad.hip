@@ -19,6 +19,7 @@
 
 #include <cstdint>
 
+#include "lds_optin.h"
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
@@ -472,12 +473,7 @@ int launch_dgrad(const float* g, const float* y_gate, const float* x_gate, int B
                  hipStream_t st) {
   const int CQ = (Cin + 3) / 4, WP = orcai_padded_width(W, 3);
   const size_t lds = (size_t)DG_SLOTS * CQ * DG_PITCH * sizeof(float4);
-  static size_t lds_set = 0;  // dynamic LDS beyond the 64 KiB default needs the opt-in
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)sepconv_dgrad_kernel<MTI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    lds_set = lds;
-  }
+  if (const hipError_t e = orcai_lds::ensure_dynamic_lds<sepconv_dgrad_kernel<MTI>>(lds); e != hipSuccess) return (int)e;
   const int strips = (W + DG_VALID - 1) / DG_VALID;
   int band_rows = 32;  // 2 recomputed halo rows per band; shorter bands while the grid would leave compute units idle
   while (band_rows > 8 && (int64_t)B * strips * ((H + band_rows - 1) / band_rows) < 1024) band_rows >>= 1;
@@ -544,12 +540,7 @@ int orcai_sepconv_wgrad_frozen(const float* x, const float* g, const float* y_ga
   if (workspace_floats < nwg * S) return ORCAI_E_UNSUPPORTED;  // the size the header states
   const int CiP = (Cin + 15) / 16 * 16, CoP = (Cout + 15) / 16 * 16;
   const size_t lds = sizeof(float) * ((size_t)CiP * WF_HALO + (size_t)(CoP + 2 * CiP) * WF_PITCH + (size_t)CoP * CiP);
-  static size_t lds_set = 0;  // dynamic LDS beyond the 64 KiB default needs the opt-in
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)sepconv_wgrad_frozen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    lds_set = lds;
-  }
+  if (const hipError_t e = orcai_lds::ensure_dynamic_lds<sepconv_wgrad_frozen_kernel>(lds); e != hipSuccess) return (int)e;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sepconv_wgrad_frozen_kernel, dim3((unsigned)nwg), dim3(256), lds, st, x, g, y_gate, taps, wts, Cin, Cout, H, W, WP, relu_in, TY, TX, (int)ntiles, workspace);
   hipLaunchKernelGGL(wgrad_frozen_fold_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, workspace, nwg, Cin, Cout, G, dbeta, dWdw);

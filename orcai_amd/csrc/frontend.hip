@@ -29,6 +29,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "lds_optin.h"
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
@@ -1066,18 +1067,8 @@ int orcai_stft_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64
     if (n_fft > NFFT_ANY_MAX) return ORCAI_E_UNSUPPORTED;
     if (n_fft < 32 || (n_fft & (n_fft - 1))) {  // not a power of two (or a tiny one): the direct transform
       const size_t lds = sizeof(double) * ((size_t)n_fft + (n_fft & 1) + 2 * (size_t)n_fft);
-      if (lds > 48 * 1024) {
-        static bool opted_dev[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return (int)e;
-        if (dev < 0 || dev >= 64) return ORCAI_E_UNSUPPORTED;
-        if (!opted_dev[dev]) {
-          e = hipFuncSetAttribute((const void*)stft_dft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * NFFT_ANY_MAX * (int)sizeof(double));
-          if (e != hipSuccess) return (int)e;
-          opted_dev[dev] = true;
-        }
-      }
+      if (lds > 48 * 1024)
+        if (const hipError_t e = orcai_lds::ensure_dynamic_lds<stft_dft_kernel>(3 * NFFT_ANY_MAX * sizeof(double)); e != hipSuccess) return (int)e;
       const int64_t blocks = n_frames < 256 * 4 ? n_frames : 256 * 4;
       hipLaunchKernelGGL(stft_dft_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, hop, n_frames, k_crop, out_db, (Workspace*)workspace);
       hipError_t e = hipGetLastError();

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "half_planes.h"
+#include "lds_optin.h"
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
@@ -1362,12 +1363,7 @@ int orcai_h_outer_reduce(const void* A, int Ca, const void* Bq, int Cb, int B, i
   if (!A || !Bq || !D || !workspace || Ca <= 0 || Cb <= 0 || Ca > 64 || Cb > 64 || B <= 0 || workspace_floats < (int64_t)Ca * Cb) return ORCAI_E_BADARG;
   const int WP = orcai_padded_width(W, ksize), R = ksize / 2;
   const size_t lds = (size_t)256 * (((Ca + 15) / 16) * 16 + 8 + ((Cb + 15) / 16) * 16 + 8) * sizeof(h16);
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)outer_reduce_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    lds_set = lds;
-  }
+  if (const hipError_t e = orcai_lds::ensure_dynamic_lds<outer_reduce_h_kernel>(lds); e != hipSuccess) return (int)e;
   const int64_t plane = (int64_t)(H + 2 * R) * WP;
   if (plane >= (1ll << 30)) return ORCAI_E_UNSUPPORTED;
   const int64_t nchunks = (int64_t)B * ((plane + 255) / 256);

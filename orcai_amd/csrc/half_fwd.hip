@@ -11,6 +11,7 @@
 #include "half_planes.h"
 #include "lds_dma.h"
 #include "orcai_hip.h"
+#include "sep_route.h"
 #include "zero_fill.h"
 
 namespace {
@@ -772,29 +773,22 @@ struct SepArgsH {
 };
 
 template <int KS, int MT>
-int launch_sepconv_h(hipStream_t st, const SepArgsH& a) {
-  const int lo = (a.out_layout == 2) ? ((KS / 2 + 1) & ~1) : KS / 2;  // x-pooled output: windows start on an even pixel
-  const int VAL = 64 - 2 * lo;
-  const int tasks = (a.H * a.WP + VAL - 1) / VAL;
-  if ((int64_t)(a.H + 2 * a.RP) * a.WP >= (1ll << 29)) return ORCAI_E_UNSUPPORTED;
-  if constexpr (KS == 3) {  // k = 3, plane or x-pooled output: rows shared through LDS (the f32 launcher's rule, orcai_sepconv_tile_mode)
-    const int nchunk = (7 * VAL + 64 + 2 * a.WP + 63) / 64;
-    const int KG = ((a.Cin + 7) / 8 + 3) / 4;
-    const size_t lds = ((size_t)2 * nchunk * 64 + (size_t)KG * MT * 64) * 16;
-    if (orcai_sepconv_tile_mode(-1) != 0 && a.RP == 1 && (a.out_layout == 0 || (a.out_layout == 2 && !a.u_out)) && nchunk <= 24 && lds <= 64 * 1024 &&
-        (int64_t)((a.Cout + 7) / 8) * (a.H + 2) * a.WP < (1ll << 27)) {
-      dim3 tgrid((tasks + 7) / 8, a.B);
+int launch_sepconv_h(hipStream_t st, const SepArgsH& a, const orcai_route::Plan& p) {
+  if ((int64_t)(a.H + 2 * a.RP) * a.WP >= orcai_route::kMaxPlanePixels) return ORCAI_E_UNSUPPORTED;
+  if constexpr (KS == 3) {  // k = 3, plane or x-pooled output: rows shared through LDS where sep_route.h says so
+    if (p.route == orcai_route::kFlat) {
+      dim3 tgrid((p.tasks + 7) / 8, a.B);
 #define ORCAI_HFTILE(XP, UOUT)                                                                                                                       \
-  hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, XP, UOUT>), tgrid, dim3(512), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pwf, a.scale, \
-                     a.shift, a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out)
+  hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, XP, UOUT>), tgrid, dim3(512), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pwf, a.scale, \
+                     a.shift, a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out)
       if (a.out_layout == 2) ORCAI_HFTILE(true, false);
       else if (a.u_out && a.shards) {
         if (a.ib.mean)
-          hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, false, true, true, true>), tgrid, dim3(512), lds, st, a.in, a.Cin, a.H, a.W, a.WP, 0, a.dw, a.pwf, a.scale, a.shift,
-                             a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards, a.ib);
+          hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, false, true, true, true>), tgrid, dim3(512), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, 0, a.dw, a.pwf, a.scale, a.shift,
+                             a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards, a.ib);
         else
-          hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, false, true, true>), tgrid, dim3(512), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pwf, a.scale, a.shift,
-                             a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards);
+          hipLaunchKernelGGL((sepconv_h_ftile_kernel<MT, false, true, true>), tgrid, dim3(512), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pwf, a.scale, a.shift,
+                             a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards);
       }
       else if (a.u_out) ORCAI_HFTILE(false, true);
       else ORCAI_HFTILE(false, false);
@@ -803,19 +797,19 @@ int launch_sepconv_h(hipStream_t st, const SepArgsH& a) {
     }
   }
   if (a.shards) return ORCAI_E_UNSUPPORTED;  // the statistics epilogue exists in the flat-tile kernel only
-  dim3 grid((tasks + 3) / 4, a.B);
+  dim3 grid((p.tasks + 3) / 4, a.B);
   hipLaunchKernelGGL((sepconv_h_kernel<KS, MT>), grid, dim3(256), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pwf, a.scale, a.shift, a.Cout, a.relu_out,
-                     a.out_layout, a.out, tasks, magic_for(a.WP), lo, a.RP, a.H2, a.WP2, a.u_out);
+                     a.out_layout, a.out, p.tasks, magic_for(a.WP), p.lo, a.RP, a.H2, a.WP2, a.u_out);
   return (int)hipGetLastError();
 }
 
 template <int KS>
-int launch_sepconv_h_mt(hipStream_t st, const SepArgsH& a) {
+int launch_sepconv_h_mt(hipStream_t st, const SepArgsH& a, const orcai_route::Plan& p) {
   switch ((a.Cout + 15) / 16) {
-    case 1: return launch_sepconv_h<KS, 1>(st, a);
-    case 2: return launch_sepconv_h<KS, 2>(st, a);
-    case 3: return launch_sepconv_h<KS, 3>(st, a);
-    case 4: return launch_sepconv_h<KS, 4>(st, a);
+    case 1: return launch_sepconv_h<KS, 1>(st, a, p);
+    case 2: return launch_sepconv_h<KS, 2>(st, a, p);
+    case 3: return launch_sepconv_h<KS, 3>(st, a, p);
+    case 4: return launch_sepconv_h<KS, 4>(st, a, p);
     default: return ORCAI_E_UNSUPPORTED;
   }
 }
@@ -864,11 +858,13 @@ int orcai_h_sepconv(const void* in, int B, int Cin, int H, int W, int ksize_plan
   SepArgsH a{(const h16*)in, (const h16*)dw, (const h16*)pwf, scale, shift, out, B, Cin, H, W, orcai_padded_width(W, ksize_planes), ksize_planes / 2, Cout, relu_in,
              relu_out, out_layout, H2, out_layout == 3 ? orcai_padded_width(W2, ksize_planes) : 0, (h16*)u_out};
   hipStream_t st = (hipStream_t)stream;
+  const orcai_route::Plan p = ktap == 3 ? orcai_route::plan_f16(Cin, Cout, H, W, a.WP, a.RP, out_layout, u_out ? orcai_route::kDwStore : orcai_route::kNone, orcai_sepconv_tile_mode(-1))
+                                        : orcai_route::window_plan(ktap, H, a.WP, out_layout);
   switch (ktap) {
-    case 1: return launch_sepconv_h_mt<1>(st, a);
-    case 3: return launch_sepconv_h_mt<3>(st, a);
-    case 5: return launch_sepconv_h_mt<5>(st, a);
-    case 7: return launch_sepconv_h_mt<7>(st, a);
+    case 1: return launch_sepconv_h_mt<1>(st, a, p);
+    case 3: return launch_sepconv_h_mt<3>(st, a, p);
+    case 5: return launch_sepconv_h_mt<5>(st, a, p);
+    case 7: return launch_sepconv_h_mt<7>(st, a, p);
     default: return ORCAI_E_UNSUPPORTED;
   }
 }
@@ -877,21 +873,14 @@ static int h_sepconv_stats_impl(const void* in, int B, int Cin, int H, int W, in
                                 void* out, void* u_out, double* shards, const InBnH& ib, void* stream) {
   if (!in || !dw || !pwf || !scale || !shift || !out || !u_out || !shards || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return ORCAI_E_BADARG;
   if (Cout > 64 || Cin > 64 || (((uintptr_t)in | (uintptr_t)dw | (uintptr_t)pwf | (uintptr_t)out | (uintptr_t)u_out) & 15) || B > 65535) return ORCAI_E_UNSUPPORTED;
-  // the launcher's own conditions for the flat-tile kernel, checked BEFORE anything is touched
-  const int WP = orcai_padded_width(W, 3), nchunk = (7 * 62 + 64 + 2 * WP + 63) / 64, KG = ((Cin + 7) / 8 + 3) / 4, MTv = (Cout + 15) / 16;
-  const size_t lds = ((size_t)2 * nchunk * 64 + (size_t)KG * MTv * 64) * 16;
-  if (orcai_sepconv_tile_mode(-1) == 0 || nchunk > 24 || lds + 4096 + 512 > 64 * 1024 /*+ the kernel's static statistics slots and folded input BatchNorm*/ || (int64_t)((Cout + 7) / 8) * (H + 2) * WP >= (1ll << 27) ||
-      (int64_t)(H + 2) * WP >= (1ll << 29))
-    return ORCAI_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int nacc = 16 * ((Cout + 7) / 8) * 32;
-  {
-    hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * nacc, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  SepArgsH a{(const h16*)in, (const h16*)dw, (const h16*)pwf, scale, shift, out, B, Cin, H, W, WP, 1, Cout, relu_in, 0, 0, 0, 0, (h16*)u_out, shards};
+  SepArgsH a{(const h16*)in, (const h16*)dw, (const h16*)pwf, scale, shift, out, B, Cin, H, W, orcai_padded_width(W, 3), 1, Cout, relu_in, 0, 0, 0, 0, (h16*)u_out, shards};
   a.ib = ib;
-  return launch_sepconv_h_mt<3>(st, a);
+  // the statistics epilogue exists in the flat-tile kernel only: the route is decided BEFORE anything is touched, and the launcher gets the same plan
+  const orcai_route::Plan p = orcai_route::plan_f16(Cin, Cout, H, W, a.WP, 1, 0, ib.mean ? orcai_route::kDwStatsBn : orcai_route::kDwStats, orcai_sepconv_tile_mode(-1));
+  if (p.route == orcai_route::kWindow) return ORCAI_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (const hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * 16 * ((Cout + 7) / 8) * 32, st); e != hipSuccess) return (int)e;
+  return launch_sepconv_h_mt<3>(st, a, p);
 }
 
 int orcai_h_sepconv_stats(const void* in, int B, int Cin, int H, int W, int relu_in, const void* dw, const void* pwf, const float* scale, const float* shift, int Cout,

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "lds_optin.h"
 #include "orcai_hip.h"
 
 namespace {
@@ -254,13 +255,9 @@ hipError_t launch_fwd(const float* xz, const float* Uw, int B, int T, float* out
 }
 
 template <int U>
-hipError_t launch_bwd(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, float* dxz, hipStream_t st, bool& opted) {
-  const size_t lds = (size_t)2 * 16 * (4 * U + 4) * sizeof(float);  // 83 456 B at U = 160 ... 131 584 B at U = 256: above 64 KiB, opt in once per device
-  if (!opted) {
-    const hipError_t e = hipFuncSetAttribute((const void*)lstm_wide_bwd_kernel<U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    opted = true;
-  }
+hipError_t launch_bwd(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, float* dxz, hipStream_t st) {
+  const size_t lds = (size_t)2 * 16 * (4 * U + 4) * sizeof(float);  // 83 456 B at U = 160 ... 131 584 B at U = 256: above 64 KiB
+  if (const hipError_t e = orcai_lds::ensure_dynamic_lds<lstm_wide_bwd_kernel<U>>(lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(lstm_wide_bwd_kernel<U>, dim3((B + 15) / 16, 2), dim3(U * 4), lds, st, dH, gates, cstate, Uw, B, T, dxz);
   return hipGetLastError();
 }
@@ -284,19 +281,12 @@ __attribute__((visibility("hidden"))) int lstm_wide_fwd_launch(const float* xz, 
 
 __attribute__((visibility("hidden"))) int lstm_wide_bwd_launch(const float* dH, const float* gates, const float* cstate, const float* Uw, int B, int T, int units, float* dxz, void* stream) {
   if (((uintptr_t)Uw | (uintptr_t)dxz) & 15) return ORCAI_E_BADARG;  // float4 reads of U rows, float4 stores of dxz rows
-  // the > 64 KiB LDS opt-in is a per-device function attribute: once per (device, width), on the device's first call (never inside a capture)
-  constexpr int MAXDEV = 64;
-  static bool opted_dev[MAXDEV][4] = {};
-  int devid = 0;
-  const hipError_t e = hipGetDevice(&devid);
-  if (e != hipSuccess) return (int)e;
-  if (devid < 0 || devid >= MAXDEV) return ORCAI_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  switch (units) {
-    case 160: return (int)launch_bwd<160>(dH, gates, cstate, Uw, B, T, dxz, st, opted_dev[devid][0]);
-    case 192: return (int)launch_bwd<192>(dH, gates, cstate, Uw, B, T, dxz, st, opted_dev[devid][1]);
-    case 224: return (int)launch_bwd<224>(dH, gates, cstate, Uw, B, T, dxz, st, opted_dev[devid][2]);
-    case 256: return (int)launch_bwd<256>(dH, gates, cstate, Uw, B, T, dxz, st, opted_dev[devid][3]);
+  switch (units) {  // the > 64 KiB LDS opt-in happens on a device's first call per width, which is never inside a capture (lds_optin.h)
+    case 160: return (int)launch_bwd<160>(dH, gates, cstate, Uw, B, T, dxz, st);
+    case 192: return (int)launch_bwd<192>(dH, gates, cstate, Uw, B, T, dxz, st);
+    case 224: return (int)launch_bwd<224>(dH, gates, cstate, Uw, B, T, dxz, st);
+    case 256: return (int)launch_bwd<256>(dH, gates, cstate, Uw, B, T, dxz, st);
     default: return ORCAI_E_BADARG;
   }
 }

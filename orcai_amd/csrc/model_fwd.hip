@@ -19,6 +19,7 @@
 
 #include "lds_dma.h"
 #include "orcai_hip.h"
+#include "sep_route.h"
 #include "zero_fill.h"
 
 // lstm_wide.hip: the recurrences for 128 < units <= 256 (gates == NULL: inference)
@@ -2424,36 +2425,33 @@ struct SepArgs {
 int g_pool_vert = 1;       // inference pooling kernel on stacked tiles where the plane is wide enough (orcai_pool_vertical: A/B)
 int g_entry_windows = 4;   // windows per wave of conv0_sep_kernel
 int g_entry_tile = 10;     // waves per workgroup of conv0_sep_tile_kernel (10 or 16); 0 = conv0_sep_kernel everywhere
-int g_tile_mode = 1;  // k = 3 launches with plane / x-pooled output: 1 = sepconv_tile_kernel for wide planes with two output tiles (<= 8 input quads,
-                      // >= 2 strips that cover the width with <= 15 % waste) and sepconv_ftile_kernel otherwise; 2 = sepconv_ftile_kernel for
-                      // all of them; 0 = sepconv_kernel everywhere (the reference the bit-identity tests compare with)
+int g_tile_mode = 1;  // k = 3 launches with plane / x-pooled output: 1 = strip tiles where sep_route.h allows them and flat tiles otherwise;
+                      // 2 = flat tiles for all of them; 0 = sepconv_kernel everywhere (the reference the bit-identity tests compare with)
 
 template <int MT, int CQ>
-int launch_sepconv_tile(hipStream_t st, const SepArgs& a, int nstrip) {
+int launch_sepconv_tile(hipStream_t st, const SepArgs& a, const orcai_route::Plan& p) {
   constexpr int TR = 8;
-  dim3 grid(nstrip * ((a.H + TR - 1) / TR), a.B);
+  dim3 grid(p.nstrip * ((a.H + TR - 1) / TR), a.B);
 #define ORCAI_TILE_LAUNCH(XP, RELU, UOUT)                                                                                                       \
   hipLaunchKernelGGL((sepconv_tile_kernel<MT, CQ, XP, RELU, TR, UOUT>), grid, dim3(64 * TR), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, \
-                     a.shift, a.Cout, a.relu_out, a.out, nstrip, a.u_out)
+                     a.shift, a.Cout, a.relu_out, a.out, p.nstrip, a.u_out)
   if (a.epi == 2) {  // input-gradient pass with the BatchNorm backward sums of its output (no ReLU on load, no depthwise-output store)
     if constexpr (MT == 2)
       hipLaunchKernelGGL((sepconv_tile_kernel<MT, CQ, false, false, TR, false, 2>), grid, dim3(64 * TR), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                         a.Cout, a.relu_out, a.out, nstrip, a.u_out, a.shards, a.er);
-  } else if (a.epi) {
-    return -1;  // EPI 3 lives in the flat-tile kernel only
-  } else if (a.out_layout == 2) {
+                         a.Cout, a.relu_out, a.out, p.nstrip, a.u_out, a.shards, a.er);
+  } else if (a.out_layout == 2) {  // (EPI 3 lives in the flat-tile kernel only: the plan never sends it here)
     if (a.relu_in) ORCAI_TILE_LAUNCH(true, true, false); else ORCAI_TILE_LAUNCH(true, false, false);
   } else if (a.u_out && a.shards) {
     if constexpr (MT == 2) {
       if (a.ib.mean)
         hipLaunchKernelGGL((sepconv_tile_kernel<MT, CQ, false, false, TR, true, 1, true>), grid, dim3(64 * TR), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                           a.Cout, a.relu_out, a.out, nstrip, a.u_out, a.shards, EpiRef{}, a.ib);
+                           a.Cout, a.relu_out, a.out, p.nstrip, a.u_out, a.shards, EpiRef{}, a.ib);
       else if (a.relu_in)
         hipLaunchKernelGGL((sepconv_tile_kernel<MT, CQ, false, true, TR, true, 1>), grid, dim3(64 * TR), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                           a.Cout, a.relu_out, a.out, nstrip, a.u_out, a.shards);
+                           a.Cout, a.relu_out, a.out, p.nstrip, a.u_out, a.shards);
       else
         hipLaunchKernelGGL((sepconv_tile_kernel<MT, CQ, false, false, TR, true, 1>), grid, dim3(64 * TR), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                           a.Cout, a.relu_out, a.out, nstrip, a.u_out, a.shards);
+                           a.Cout, a.relu_out, a.out, p.nstrip, a.u_out, a.shards);
     }
   } else if (a.u_out) {
     if (a.relu_in) ORCAI_TILE_LAUNCH(false, true, true); else ORCAI_TILE_LAUNCH(false, false, true);
@@ -2465,37 +2463,30 @@ int launch_sepconv_tile(hipStream_t st, const SepArgs& a, int nstrip) {
 }
 
 template <int MT>
-int launch_sepconv_ftile(hipStream_t st, const SepArgs& a, int tasks) {
-  constexpr int NWV = 8;
-  const int lo = a.out_layout == 2 ? 2 : 1, VAL = 64 - 2 * lo;
-  const int nchunk = ((NWV - 1) * VAL + 64 + 2 * a.WP + 63) / 64;
-  const int CQr = (a.Cin + 3) / 4;
-  const size_t lds = (size_t)(2 * nchunk * 256 + CQr * 64 * MT + 2 * MT * 16) * sizeof(float);
-  if (nchunk > 3 * NWV || lds > 64 * 1024) return -1;  // planes wider than ~500 pixels: not this kernel's shape, the caller falls back
-  dim3 grid((tasks + NWV - 1) / NWV, a.B);
+int launch_sepconv_ftile(hipStream_t st, const SepArgs& a, const orcai_route::Plan& p) {
+  constexpr int NWV = orcai_route::kFlatWaves;
+  dim3 grid((p.tasks + NWV - 1) / NWV, a.B);
 #define ORCAI_FTILE_LAUNCH(XP, RELU, UOUT)                                                                                                       \
-  hipLaunchKernelGGL((sepconv_ftile_kernel<MT, XP, RELU, UOUT, NWV>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, \
-                     a.shift, a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out)
+  hipLaunchKernelGGL((sepconv_ftile_kernel<MT, XP, RELU, UOUT, NWV>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, \
+                     a.shift, a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out)
   if (a.epi == 2) {
-    if (lds + sizeof(float) * (NWV * 4 * 8 * MT + 4 * MT * 16) > 64 * 1024) return -1;  // + the kernel's static statistics slots and BatchNorm constants
-    hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, false, NWV, 2>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                       a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards, a.er);
+    hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, false, NWV, 2>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
+                       a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards, a.er);
   } else if (a.epi == 3) {
-    hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, false, NWV, 3>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                       a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards, a.er);
+    hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, false, NWV, 3>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
+                       a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards, a.er);
   } else if (a.out_layout == 2) {
     if (a.relu_in) ORCAI_FTILE_LAUNCH(true, true, false); else ORCAI_FTILE_LAUNCH(true, false, false);
   } else if (a.u_out && a.shards) {
-    if (lds + sizeof(float) * (NWV * 4 * 8 * MT + (a.ib.mean ? 128 : 0)) > 64 * 1024) return -1;  // + the kernel's static statistics slots (and folded input BatchNorm)
     if (a.ib.mean)
-      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, true, NWV, 1, true>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                         a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards, EpiRef{}, a.ib);
+      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, true, NWV, 1, true>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
+                         a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards, EpiRef{}, a.ib);
     else if (a.relu_in)
-      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, true, true, NWV, 1>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                         a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards);
+      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, true, true, NWV, 1>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
+                         a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards);
     else
-      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, true, NWV, 1>), grid, dim3(64 * NWV), lds, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
-                         a.Cout, a.relu_out, a.out, tasks, magic_for(a.WP), nchunk, a.u_out, a.shards);
+      hipLaunchKernelGGL((sepconv_ftile_kernel<MT, false, false, true, NWV, 1>), grid, dim3(64 * NWV), p.lds_bytes, st, a.in, a.Cin, a.H, a.W, a.WP, a.dw, a.pw, a.scale, a.shift,
+                         a.Cout, a.relu_out, a.out, p.tasks, magic_for(a.WP), p.nchunk, a.u_out, a.shards);
   } else if (a.u_out) {
     if (a.relu_in) ORCAI_FTILE_LAUNCH(false, true, true); else ORCAI_FTILE_LAUNCH(false, false, true);
   } else {
@@ -2506,41 +2497,30 @@ int launch_sepconv_ftile(hipStream_t st, const SepArgs& a, int tasks) {
 }
 
 template <int KS, int MT>
-int launch_sepconv_impl(hipStream_t st, const SepArgs& a) {
-  const int lo = (a.out_layout == 2) ? ((KS / 2 + 1) & ~1) : KS / 2;  // x-pooled output: windows start on an even pixel
-  const int VAL = 64 - 2 * lo;
-  const int tasks = (a.H * a.WP + VAL - 1) / VAL;  // 64-pixel windows covering the H image rows of a plane
-  if ((int64_t)(a.H + 2 * a.RP) * a.WP >= (1ll << 29)) return ORCAI_E_UNSUPPORTED;
+int launch_sepconv_impl(hipStream_t st, const SepArgs& a, const orcai_route::Plan& p) {
+  if ((int64_t)(a.H + 2 * a.RP) * a.WP >= orcai_route::kMaxPlanePixels) return ORCAI_E_UNSUPPORTED;
   if constexpr (KS == 3) {
     // k = 3, plane or x-pooled output (optionally with the depthwise-output store of the training forward): the LDS-shared-row kernels.
     // Wide planes with two output tiles (orcai-V1 block 1) take the 2-D strip tiles, which fetch 10 rows per 8 windows; everything else
     // the flat-range tiles (b1/sep_b: strip 3.3 ms, flat 3.45 ms per 611 snippets; the one-window kernels 3.8 ms).
-    const int CQ = (a.Cin + 3) / 4, CQo = (a.Cout + 3) / 4;
-    if (g_tile_mode && a.RP == 1 && (a.out_layout == 0 || (a.out_layout == 2 && !a.u_out)) && (int64_t)CQo * (a.H + 2) * a.WP < (1ll << 27) &&
-        (int64_t)CQ * (a.H + 2) * a.WP < (1ll << 27)) {
-      if constexpr (MT == 2) {
-        const int VALt = a.out_layout == 2 ? 60 : 62, nstrip = (a.W + VALt - 1) / VALt;
-        if (g_tile_mode == 1 && a.epi != 3 && CQ <= 8 && nstrip >= 2 && a.W * 100 >= nstrip * VALt * 85)
-          return CQ <= 4 ? launch_sepconv_tile<2, 4>(st, a, nstrip) : launch_sepconv_tile<2, 8>(st, a, nstrip);
-      }
-      const int rc = launch_sepconv_ftile<MT>(st, a, tasks);
-      if (rc >= 0) return rc;
-    }
+    if constexpr (MT == 2)
+      if (p.route == orcai_route::kStrip) return a.Cin <= 16 ? launch_sepconv_tile<2, 4>(st, a, p) : launch_sepconv_tile<2, 8>(st, a, p);
+    if (p.route == orcai_route::kFlat) return launch_sepconv_ftile<MT>(st, a, p);
   }
   if (a.shards || a.epi) return ORCAI_E_UNSUPPORTED;  // the epilogue extras exist in the LDS-tile kernels only
-  dim3 grid((tasks + 3) / 4, a.B);
+  dim3 grid((p.tasks + 3) / 4, a.B);
   hipLaunchKernelGGL((sepconv_kernel<KS, MT>), grid, dim3(256), 0, st, a.in, a.Cin, a.H, a.W, a.WP, a.relu_in, a.dw, a.pw, a.scale, a.shift, a.Cout, a.relu_out,
-                     a.out_layout, a.out, tasks, magic_for(a.WP), lo, a.RP, a.H2, a.WP2, a.u_out);
+                     a.out_layout, a.out, p.tasks, magic_for(a.WP), p.lo, a.RP, a.H2, a.WP2, a.u_out);
   return (int)hipGetLastError();
 }
 
 template <int KS>
-int launch_sepconv(hipStream_t st, const SepArgs& a) {
+int launch_sepconv(hipStream_t st, const SepArgs& a, const orcai_route::Plan& p) {
   switch ((a.Cout + 15) / 16) {
-    case 1: return launch_sepconv_impl<KS, 1>(st, a);
-    case 2: return launch_sepconv_impl<KS, 2>(st, a);
-    case 3: return launch_sepconv_impl<KS, 3>(st, a);
-    case 4: return launch_sepconv_impl<KS, 4>(st, a);
+    case 1: return launch_sepconv_impl<KS, 1>(st, a, p);
+    case 2: return launch_sepconv_impl<KS, 2>(st, a, p);
+    case 3: return launch_sepconv_impl<KS, 3>(st, a, p);
+    case 4: return launch_sepconv_impl<KS, 4>(st, a, p);
     default: return ORCAI_E_UNSUPPORTED;
   }
 }
@@ -2581,6 +2561,15 @@ int orcai_sepconv_tile_mode(int mode) {
   const int prev = g_tile_mode;
   if (mode >= 0 && mode <= 2) g_tile_mode = mode;
   return prev;
+}
+
+int orcai_sepconv_route(int half, int Cin, int Cout, int H, int W, int out_layout, int extras) {
+  using namespace orcai_route;
+  if ((half != 0 && half != 1) || Cin <= 0 || Cout <= 0 || Cout > 64 || (half && Cin > 64) || H <= 0 || W <= 0 || H > (1 << 30) || W > (1 << 30) || out_layout < 0 || out_layout > 3 || extras < kNone ||
+      extras > (half ? kDwStatsBn : kEpi3))
+    return ORCAI_E_BADARG;
+  const int WP = orcai_padded_width(W, 3);
+  return (half ? plan_f16 : plan_f32)(Cin, Cout, H, W, WP, 1, out_layout, (Extras)extras, g_tile_mode).route;
 }
 
 int orcai_conv0_bn_relu(const float* in, int64_t snippet_stride, int B, int H, int W, int ksize, const float* w, const float* scale,
@@ -2644,8 +2633,8 @@ int orcai_conv0_sepconv(const float* in, int64_t snippet_stride, int B, int H, i
   const int WP = orcai_padded_width(W, 3);
   if ((int64_t)((Cout + 3) / 4) * (H + 2) * WP >= (1ll << 28)) return ORCAI_E_UNSUPPORTED;  // 32-bit byte offsets inside a snippet's planes
   hipStream_t st = (hipStream_t)stream;
-  const int nstrip = (W + 61) / 62;
-  if (g_entry_tile && Cout > 16 && Cout <= 32 && nstrip >= 2 && W * 100 >= nstrip * 62 * 85) {  // wide planes: entry rows shared through LDS
+  const int nstrip = orcai_route::wide_strips(W, 62);
+  if (g_entry_tile && Cout > 16 && Cout <= 32 && nstrip) {  // wide planes: entry rows shared through LDS
     if (g_entry_tile == 16) {
       dim3 grid(nstrip * ((H + 13) / 14), B);
       hipLaunchKernelGGL((conv0_sep_tile_kernel<2, 16>), grid, dim3(1024), 0, st, in, snippet_stride, H, W, WP, w0, scale0, shift0, dw, pw, scale, shift, Cout,
@@ -2681,23 +2670,15 @@ static int sepconv_planes_stats_impl(const float* in, int B, int Cin, int H, int
                                      int Cout, float* out, float* u_out, double* shards, const InBn& ib, void* stream) {
   if (!in || !dw || !pw || !scale || !shift || !out || !u_out || !shards || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return ORCAI_E_BADARG;
   if (((uintptr_t)in & 15) || B > 65535 || Cout > 64 || Cin > 64) return ORCAI_E_UNSUPPORTED;
-  // the shapes launch_sepconv_impl<3, MT> hands to the LDS-tile kernels, checked BEFORE anything is touched; everything else:
-  // ORCAI_E_UNSUPPORTED, and the caller runs orcai_sepconv_planes_u + orcai_bn_planes_stats
-  const int CQ = (Cin + 3) / 4, CQo = (Cout + 3) / 4, WP = orcai_padded_width(W, 3), MTv = (Cout + 15) / 16;
-  const int nchunk = (7 * 62 + 64 + 2 * WP + 63) / 64;
-  const size_t lds = (size_t)(2 * nchunk * 256 + CQ * 64 * MTv + 2 * MTv * 16 + 8 * 4 * 8 * MTv + (ib.mean ? 128 : 0)) * sizeof(float);
-  const int nstrip = (W + 61) / 62;
-  const bool strip = g_tile_mode == 1 && MTv == 2 && CQ <= 8 && nstrip >= 2 && W * 100 >= nstrip * 62 * 85;
-  if (g_tile_mode == 0 || (int64_t)CQo * (H + 2) * WP >= (1ll << 27) || (int64_t)CQ * (H + 2) * WP >= (1ll << 27) || (!strip && (nchunk > 24 || lds > 64 * 1024)))
-    return ORCAI_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  {
-    hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * 8 * CQo * 32, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  SepArgs a{in, dw, pw, scale, shift, out, B, Cin, H, W, WP, 1, Cout, relu_in, 0, 0, 0, 0, u_out, shards};
+  SepArgs a{in, dw, pw, scale, shift, out, B, Cin, H, W, orcai_padded_width(W, 3), 1, Cout, relu_in, 0, 0, 0, 0, u_out, shards};
   a.ib = ib;
-  return launch_sepconv<3>(st, a);
+  // the statistics epilogue exists in the LDS-tile kernels only: the route is decided BEFORE anything is touched, and the launcher gets
+  // the same plan; on ORCAI_E_UNSUPPORTED the caller runs orcai_sepconv_planes_u + orcai_bn_planes_stats
+  const orcai_route::Plan p = orcai_route::plan_f32(Cin, Cout, H, W, a.WP, 1, 0, ib.mean ? orcai_route::kDwStatsBn : orcai_route::kDwStats, g_tile_mode);
+  if (p.route == orcai_route::kWindow) return ORCAI_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (const hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * 8 * ((Cout + 3) / 4) * 32, st); e != hipSuccess) return (int)e;
+  return launch_sepconv<3>(st, a, p);
 }
 
 int orcai_sepconv_planes_stats(const float* in, int B, int Cin, int H, int W, int relu_in, const float* dw, const float* pw, const float* scale, const float* shift,
@@ -2720,24 +2701,18 @@ int orcai_sepconv_planes_epi(const float* in, int B, int Cin, int H, int W, cons
   if (!in || !dw || !pw || !scale || !shift || !out || !ref || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (epi != 2 && epi != 3)) return ORCAI_E_BADARG;
   if (epi == 2 && (!mean || !var || !gamma || !beta || !shards)) return ORCAI_E_BADARG;
   if (((uintptr_t)in & 15) || ((uintptr_t)ref & 15) || B > 65535 || Cout > 64) return ORCAI_E_UNSUPPORTED;
-  // the shapes launch_sepconv_impl<3, MT> hands to the LDS-tile kernels, checked BEFORE anything is touched (as orcai_sepconv_planes_stats)
-  const int CQ = (Cin + 3) / 4, CQo = (Cout + 3) / 4, WP = orcai_padded_width(W, 3), MTv = (Cout + 15) / 16;
-  const int nchunk = (7 * 62 + 64 + 2 * WP + 63) / 64;
-  const size_t lds = (size_t)(2 * nchunk * 256 + CQ * 64 * MTv + 2 * MTv * 16 + 8 * 4 * 8 * MTv + 4 * MTv * 16) * sizeof(float);
-  const int nstrip = (W + 61) / 62;
-  const bool strip = epi == 2 && g_tile_mode == 1 && MTv == 2 && CQ <= 8 && nstrip >= 2 && W * 100 >= nstrip * 62 * 85;
-  if (g_tile_mode == 0 || (int64_t)CQo * (H + 2) * WP >= (1ll << 27) || (int64_t)CQ * (H + 2) * WP >= (1ll << 27) || (!strip && (nchunk > 24 || lds > 64 * 1024)))
-    return ORCAI_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (epi == 2) {
-    hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * 8 * CQo * 32, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  SepArgs a{in, dw, pw, scale, shift, out, B, Cin, H, W, WP, 1, Cout, 0, 0, 0, 0, 0, nullptr, epi == 2 ? shards : nullptr};
+  const int CQo = (Cout + 3) / 4;
+  SepArgs a{in, dw, pw, scale, shift, out, B, Cin, H, W, orcai_padded_width(W, 3), 1, Cout, 0, 0, 0, 0, 0, nullptr, epi == 2 ? shards : nullptr};
   a.epi = epi;
   a.er.ref = ref;
   a.er.mean = mean; a.er.var = var; a.er.gamma = gamma; a.er.beta = beta; a.er.eps = eps; a.er.relu = relu;
-  const int rc = launch_sepconv<3>(st, a);
+  // the route is decided BEFORE anything is touched (as orcai_sepconv_planes_stats), and the launcher gets the same plan
+  const orcai_route::Plan p = orcai_route::plan_f32(Cin, Cout, H, W, a.WP, 1, 0, epi == 2 ? orcai_route::kEpi2 : orcai_route::kEpi3, g_tile_mode);
+  if (p.route == orcai_route::kWindow) return ORCAI_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (epi == 2)
+    if (const hipError_t e = orcai_zero::zero_async(shards, sizeof(double) * 8 * CQo * 32, st); e != hipSuccess) return (int)e;
+  const int rc = launch_sepconv<3>(st, a, p);
   if (rc != 0) return rc;
   if (epi == 2) hipLaunchKernelGGL(bn_bwd_sums_compact_kernel, dim3(1), dim3(256), 0, st, shards, CQo);
   return (int)hipGetLastError();
@@ -2751,11 +2726,13 @@ int orcai_sepconv_planes_u(const float* in, int B, int Cin, int H, int W, int ks
   SepArgs a{in, dw, pw, scale, shift, out, B, Cin, H, W, orcai_padded_width(W, ksize_planes), ksize_planes / 2, Cout, relu_in, relu_out, out_layout,
             H2, out_layout == 3 ? orcai_padded_width(W2, ksize_planes) : 0, u_out};
   hipStream_t st = (hipStream_t)stream;
+  const orcai_route::Plan p = ktap == 3 ? orcai_route::plan_f32(Cin, Cout, H, W, a.WP, a.RP, out_layout, u_out ? orcai_route::kDwStore : orcai_route::kNone, g_tile_mode)
+                                        : orcai_route::window_plan(ktap, H, a.WP, out_layout);
   switch (ktap) {
-    case 1: return launch_sepconv<1>(st, a);
-    case 3: return launch_sepconv<3>(st, a);
-    case 5: return launch_sepconv<5>(st, a);
-    case 7: return launch_sepconv<7>(st, a);
+    case 1: return launch_sepconv<1>(st, a, p);
+    case 3: return launch_sepconv<3>(st, a, p);
+    case 5: return launch_sepconv<5>(st, a, p);
+    case 7: return launch_sepconv<7>(st, a, p);
     default: return ORCAI_E_UNSUPPORTED;
   }
 }
@@ -2818,8 +2795,8 @@ int orcai_sepconv_pool_res(const float* in, const float* prev, int B, int Cin, i
   if (!in || !prev || !dw || !pw || !scale || !shift || !wr || !br || !out || B <= 0 || Cin <= 0 || C <= 0 || Cp <= 0 || H <= 0 || W <= 0) return ORCAI_E_BADARG;
   // the marching kernel's shapes: k = 3, two output tiles (17 .. 32 channels), <= 8 input quads, <= 4 quads of prev, an even number of rows (pooling pads
   // at the bottom only), a plane wide enough for the 60-column strips of sepconv_tile_kernel; everything else: the caller's two launches
-  const int nstrip = (W + 59) / 60, CQ = (Cin + 3) / 4, WP = orcai_padded_width(W, 3);
-  if (g_pool_fused_nt <= 0 || g_tile_mode != 1 || ksize != 3 || (C + 15) / 16 != 2 || CQ < 5 || CQ > 8 || Cp > 16 || (H & 1) || nstrip < 2 || W * 100 < nstrip * 60 * 85 ||
+  const int nstrip = orcai_route::wide_strips(W, 60), CQ = (Cin + 3) / 4, WP = orcai_padded_width(W, 3);
+  if (g_pool_fused_nt <= 0 || g_tile_mode != 1 || ksize != 3 || (C + 15) / 16 != 2 || CQ < 5 || CQ > 8 || Cp > 16 || (H & 1) || !nstrip ||
       ((uintptr_t)in & 15) || ((uintptr_t)prev & 15) || ((uintptr_t)out & 15) || B > 65535 || (int64_t)8 * (H + 2) * WP >= (1ll << 27))
     return ORCAI_E_UNSUPPORTED;
   const int Ho = H / 2, Wo = (W + 1) / 2, WPo = orcai_padded_width(Wo, 3);

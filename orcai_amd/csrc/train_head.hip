@@ -8,6 +8,7 @@
 
 #include <cstdint>
 
+#include "lds_optin.h"
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
@@ -1638,39 +1639,16 @@ int orcai_h_lstm_bwd(const float* dH, const float* gates, const float* cstate, c
   if (units > 128) return lstm_wide_bwd_launch(dH, gates, cstate, Uw, B, T, units, dxz, stream);  // the f32 wide kernel (f32 products: more accurate than f16)
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
-  if (units == 128) {
-    const size_t lds = (size_t)2 * 16 * (4 * 128 + 4) * 4 + (size_t)2 * 16 * (4 * 128 + 8) * 2;  // 99 328 B > 64 KiB: opt in once per device
-    static bool opted_dev[64] = {};
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return (int)e;
-    if (devid < 0 || devid >= 64) return ORCAI_E_UNSUPPORTED;
-    if (!opted_dev[devid]) {
-      e = hipFuncSetAttribute((const void*)lstm_bwd_h_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      opted_dev[devid] = true;
-    }
-    hipLaunchKernelGGL(lstm_bwd_h_kernel<128>, grid, dim3(512), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-  } else if (units == 64) {
-    const size_t lds = (size_t)2 * 16 * (4 * 64 + 4) * 4 + (size_t)2 * 16 * (4 * 64 + 8) * 2;  // 50 176 B
-    hipLaunchKernelGGL(lstm_bwd_h_kernel<64>, grid, dim3(256), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-  } else if (units == 96) {
-    const size_t lds = (size_t)2 * 16 * (4 * 96 + 4) * 4 + (size_t)2 * 16 * (4 * 96 + 8) * 2;  // 74 752 B > 64 KiB: opt in once per device
-    static bool opted96_dev[64] = {};
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return (int)e;
-    if (devid < 0 || devid >= 64) return ORCAI_E_UNSUPPORTED;
-    if (!opted96_dev[devid]) {
-      e = hipFuncSetAttribute((const void*)lstm_bwd_h_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      opted96_dev[devid] = true;
-    }
-    hipLaunchKernelGGL(lstm_bwd_h_kernel<96>, grid, dim3(384), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-  } else {  // 32
-    const size_t lds = (size_t)2 * 16 * (4 * 32 + 4) * 4 + (size_t)2 * 16 * (4 * 32 + 8) * 2;  // 25 600 B
-    hipLaunchKernelGGL(lstm_bwd_h_kernel<32>, grid, dim3(128), lds, st, dH, gates, cstate, Uw, B, T, dxz);
+  // LDS: 99 328 B at 128 units, 74 752 at 96 (beyond 64 KiB: opt in), 50 176 at 64, 25 600 at 32
+#define ORCAI_LBH(U)                                                                                                       \
+  {                                                                                                                        \
+    const size_t lds = (size_t)2 * 16 * (4 * U + 4) * 4 + (size_t)2 * 16 * (4 * U + 8) * 2;                                \
+    if (lds > 64 * 1024)                                                                                                   \
+      if (const hipError_t e = orcai_lds::ensure_dynamic_lds<lstm_bwd_h_kernel<U>>(lds); e != hipSuccess) return (int)e; \
+    hipLaunchKernelGGL(lstm_bwd_h_kernel<U>, grid, dim3(4 * U), lds, st, dH, gates, cstate, Uw, B, T, dxz);                \
   }
+  if (units == 128) ORCAI_LBH(128) else if (units == 64) ORCAI_LBH(64) else if (units == 96) ORCAI_LBH(96) else ORCAI_LBH(32)
+#undef ORCAI_LBH
   return (int)hipGetLastError();
 }
 
@@ -1697,12 +1675,11 @@ int orcai_lstm_bwd(const float* dH, const float* gates, const float* cstate, con
   dim3 grid((B + 15) / 16, 2);
   hipStream_t st = (hipStream_t)stream;
   if (g_orcai_lstm_split) {
-    // per DEVICE: the address of the max accumulator (a __device__ symbol has one instance per device) and the > 64 KiB LDS opt-ins (function
-    // attributes are per device too).  Looked up on a device's first call, which is never inside a stream capture (warm-up steps come first).
+    // per DEVICE: the address of the max accumulator (a __device__ symbol has one instance per device); the > 64 KiB LDS opt-ins are per
+    // device too (lds_optin.h).  Looked up on a device's first call, which is never inside a stream capture (warm-up steps come first).
     // The scale itself travels through the device global g_lstm_grad_scale: ONE backward recurrence in flight per device (include/orcai_hip.h).
     constexpr int MAXDEV = 64;
     static uint32_t* maxbits_dev[MAXDEV] = {};
-    static bool opted_dev[MAXDEV][4] = {};
     int devid = 0;
     hipError_t e = hipGetDevice(&devid);
     if (e != hipSuccess) return (int)e;
@@ -1716,30 +1693,15 @@ int orcai_lstm_bwd(const float* dH, const float* gates, const float* cstate, con
     hipLaunchKernelGGL(lstm_grad_max_kernel, dim3((unsigned)((n + 256 * 16 - 1) / (256 * 16))), dim3(256), 0, st, dH, n, maxbits);
     hipLaunchKernelGGL(lstm_grad_scale_kernel, dim3(1), dim3(64), 0, st, maxbits);
     const size_t lds = (size_t)2 * 16 * (4 * units + 4) * 4 + (size_t)2 * 2 * 16 * (4 * units + 8) * 2;  // f32 rows + hi + lo operands
-    if (units == 128) {
-      if (!opted_dev[devid][0]) {  // 132 352 B > 64 KiB: opt in once per device
-        e = hipFuncSetAttribute((const void*)lstm_bwd_split_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        opted_dev[devid][0] = true;
-      }
-      hipLaunchKernelGGL(lstm_bwd_split_kernel<128>, grid, dim3(512), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-    } else if (units == 64) {
-      if (!opted_dev[devid][1]) {  // 66 816 B
-        e = hipFuncSetAttribute((const void*)lstm_bwd_split_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        opted_dev[devid][1] = true;
-      }
-      hipLaunchKernelGGL(lstm_bwd_split_kernel<64>, grid, dim3(256), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-    } else if (units == 96) {
-      if (!opted_dev[devid][2]) {  // 99 840 B
-        e = hipFuncSetAttribute((const void*)lstm_bwd_split_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        opted_dev[devid][2] = true;
-      }
-      hipLaunchKernelGGL(lstm_bwd_split_kernel<96>, grid, dim3(384), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-    } else {  // 32: 34 304 B
-      hipLaunchKernelGGL(lstm_bwd_split_kernel<32>, grid, dim3(128), lds, st, dH, gates, cstate, Uw, B, T, dxz);
-    }
+    // 132 352 B at 128 units, 99 840 at 96, 66 816 at 64 (beyond 64 KiB: opt in), 34 304 at 32
+#define ORCAI_LBS(U)                                                                                                                                       \
+  {                                                                                                                                                        \
+    if (lds > 64 * 1024)                                                                                                                                   \
+      if (const hipError_t eo = orcai_lds::ensure_dynamic_lds<lstm_bwd_split_kernel<U>>(lds); eo != hipSuccess) return (int)eo;                            \
+    hipLaunchKernelGGL(lstm_bwd_split_kernel<U>, grid, dim3(4 * U), lds, st, dH, gates, cstate, Uw, B, T, dxz);                                            \
+  }
+    if (units == 128) ORCAI_LBS(128) else if (units == 64) ORCAI_LBS(64) else if (units == 96) ORCAI_LBS(96) else ORCAI_LBS(32)
+#undef ORCAI_LBS
     return (int)hipGetLastError();
   }
   switch (units) {

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "lds_optin.h"
 #include "orcai_hip.h"
 #include "zero_fill.h"
 
@@ -2072,12 +2073,7 @@ int orcai_bn_bwd_pointwise_wgrad(const float* dy, const float* v, const float* u
   orcai_profile_take(&prof0, &prof1);  // measurement hook (orcai_profile_bracket): events around the main kernel only
 #define ORCAI_BBW(MT_, NT_, NW_)                                                                                                                       \
   {                                                                                                                                                    \
-    static bool attr_set = false;                                                                                                                      \
-    if (!attr_set) {                                                                                                                                   \
-      hipError_t e = hipFuncSetAttribute((const void*)bn_bwd_pw_wgrad_kernel<MT_, NT_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return (int)e;                                                                                                              \
-      attr_set = true;                                                                                                                                 \
-    }                                                                                                                                                  \
+    if (const hipError_t e = orcai_lds::ensure_dynamic_lds<bn_bwd_pw_wgrad_kernel<MT_, NT_, NW_>>(lds); e != hipSuccess) return (int)e;                \
     if (prof0) (void)hipEventRecord((hipEvent_t)prof0, st);                                                                                                \
     hipLaunchKernelGGL((bn_bwd_pw_wgrad_kernel<MT_, NT_, NW_>), grid, dim3(64 * NW_), lds, st, dy, v, u, C, H, W, WP, R, mean, var, gamma, beta, eps, relu, db, \
                        dg, inv_count, wt, Cin, du, tasks, magic_for(WP), workspace);                                                                    \
@@ -2160,13 +2156,8 @@ int orcai_outer_reduce(const float* A, int Ca, const float* Bq, int Cb, int B, i
   // of 99-132)
   const int PP = MTN <= 4 ? 256 : 128;
   const size_t lds = (size_t)(MTN * 16) * (PP + 2) * sizeof(float);
-  static size_t lds_set[2] = {0, 0};
-  if (lds > lds_set[PP == 256]) {
-    hipError_t e = PP == 256 ? hipFuncSetAttribute((const void*)outer_reduce_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                             : hipFuncSetAttribute((const void*)outer_reduce_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    lds_set[PP == 256] = lds;
-  }
+  if (const hipError_t e = PP == 256 ? orcai_lds::ensure_dynamic_lds<outer_reduce_kernel<256>>(lds) : orcai_lds::ensure_dynamic_lds<outer_reduce_kernel<128>>(lds); e != hipSuccess)
+    return (int)e;
   const int plane = (H + 2 * R) * WP;
   const int64_t nchunks = (int64_t)B * ((plane + PP - 1) / PP);
   const int64_t cap = PP == 256 ? 512 : 768;  // two / three workgroups per compute unit

@@ -58,6 +58,35 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.orcai_version()
 
 
+def test_sepconv_route_query_agrees_with_the_launch_geometry_model():
+    """tests/launch_geometry.py keeps an independent model of the k = 3 route rule (the CPU bounds sweep picks its kernel model with it);
+    orcai_sepconv_route is the library's own answer (csrc/sep_route.h).  The shape sweep of
+    test_tile_kernels_stay_inside_their_operands_and_lds under every tile mode: the two agree, and all three routes occur."""
+    import itertools
+
+    import launch_geometry as LG
+
+    lib = N.lib()
+    code = {"window": 0, "tile": 1, "ftile": 2}
+    seen = set()
+    prev = lib.orcai_sepconv_tile_mode(-1)
+    try:
+        for mode in (0, 1, 2):
+            lib.orcai_sepconv_tile_mode(mode)
+            for (H, W), (Cin, Cout), layout, u_out in itertools.product(
+                    [(1, 3), (5, 61), (7, 62), (9, 63), (8, 106), (13, 118), (16, 171), (33, 124), (3, 250), (2, 500), (4, 520)],
+                    [(16, 30), (30, 30), (13, 17), (40, 40), (16, 16), (60, 60), (7, 64)], (0, 2), (False, True)):
+                want = LG.f32_k3_variant(Cin, Cout, H, W, layout, u_out, mode)
+                got = lib.orcai_sepconv_route(0, Cin, Cout, H, W, layout, 1 if u_out else 0)
+                assert got == code[want], (mode, H, W, Cin, Cout, layout, u_out, got, want)
+                seen.add(got)
+    finally:
+        lib.orcai_sepconv_tile_mode(prev)
+    assert seen == {0, 1, 2}
+    assert lib.orcai_sepconv_route(2, 16, 16, 8, 8, 0, 0) == -1 and lib.orcai_sepconv_route(0, 16, 65, 8, 8, 0, 0) == -1  # ORCAI_E_BADARG
+    assert lib.orcai_sepconv_route(1, 16, 16, 8, 8, 0, 4) == -1  # the f16 path has no epi launches
+
+
 def test_bench_kernel_symbols_are_in_the_newest_pmc_traffic_table():
     """bench.py's `roofline.traffic` is looked up by kernel symbol in profiles/rNN_pmc_traffic.json.  The symbol bench_predict.kernel_symbol()
     builds for the bracketed layers must be one the newest table (made from rocprofv3 --pmc passes of the same command at the same

@@ -183,20 +183,46 @@ def test_clamps_and_guards_are_load_bearing():
 def test_kernels_with_dynamic_lds_opt_in_beyond_64_kib():
     """Source lint for the round-1 abort's most probable cause: a kernel that takes `extern __shared__` memory sized by its launcher
     (outer_reduce: 16.5 KB per 16-channel tile row -- over the 64 KiB default as soon as an operand has more than 32 channels, which
-    of the round-1 test shapes only the aborting one had) must either opt in with hipFuncSetAttribute(MaxDynamicSharedMemorySize) or
-    bound its request at 64 KiB in the launcher."""
-    import re
+    of the round-1 test shapes only the aborting one had) must, in every launcher and for the instantiation launched there, either opt
+    in with ensure_dynamic_lds<kernel<...>> (csrc/lds_optin.h, the one caller of hipFuncSetAttribute(MaxDynamicSharedMemorySize)) or
+    bound its request at 64 KiB: in that launcher (a check, or a named 64 KiB budget the request is cut from), or in the route header
+    (csrc/sep_route.h) whose plan the launch takes its size from."""
     from pathlib import Path
 
+    assert _dynamic_lds_lint(Path(__file__).resolve().parent.parent / "orcai_amd" / "csrc") >= 3
+
+
+def _dynamic_lds_lint(csrc):
+    """Asserts the rule above for every kernel of csrc/*.hip with `extern __shared__`; returns how many it saw."""
+    import re
+
+    helper = (csrc / "lds_optin.h").read_text()
+    assert re.search(r"hipFuncSetAttribute\(\(const void\*\)Kernel,\s*hipFuncAttributeMaxDynamicSharedMemorySize,", helper)
+    route = (csrc / "sep_route.h").read_text()
+    route_bounds = re.search(r"kLdsLimit\s*=\s*64\s*\*\s*1024;", route) and re.search(r"if\s*\(lds_bytes\s*\+\s*static_bytes\s*>\s*kLdsLimit\)\s*return\b", route)
     seen = 0
-    for src in sorted((Path(__file__).resolve().parent.parent / "orcai_amd" / "csrc").glob("*.hip")):
+    for src in sorted(csrc.glob("*.hip")):
         text = src.read_text()
         for m in re.finditer(r"extern\s+__shared__", text):
             head = text[: m.start()]
             kernel = re.findall(r"void\s+(\w+)\s*\(", head)[-1]  # the nearest function definition above the declaration
             seen += 1
-            opted_in = re.search(r"hipFuncSetAttribute\(\(const void\*\)\(?" + kernel + r"\b[^;]*hipFuncAttributeMaxDynamicSharedMemorySize", text)
-            # "lds > 64 * 1024) return ..." (refuse) or "... && lds <= 64 * 1024 ..." (fall back to a kernel without dynamic LDS)
-            bounded = re.search(r"lds\s*>\s*64\s*\*\s*1024\)\s*return\b|lds\s*<=\s*64\s*\*\s*1024", text)
-            assert opted_in or bounded, f"{src.name}: {kernel} uses dynamic LDS without opting in beyond 64 KiB or bounding its size"
-    assert seen >= 3
+            launches = list(re.finditer(r"hipLaunchKernelGGL\(\(?(" + kernel + r")\b", text))
+            assert launches, f"{src.name}: {kernel} uses dynamic LDS and no launch of it was found"
+            for ln in launches:
+                inst, i, depth = kernel, ln.end(1), 0  # the instantiation as written: the kernel's name and its template arguments, if any
+                while text[i] == "<" or depth:
+                    depth += {"<": 1, ">": -1}.get(text[i], 0)
+                    inst, i = inst + text[i], i + 1
+                # the launcher: the top-level function around the launch (their closing braces are the only bare ones in column 0)
+                body = text[text.rfind("\n}\n", 0, ln.start()) + 1 : text.find("\n}\n", ln.start())]
+                # outer_reduce_kernel<256> and <128> are two kernels: the opt-in must name the instantiation the launcher launches
+                opted_in = "ensure_dynamic_lds<" + inst + ">(" in body
+                # "lds > 64 * 1024) return ..." (refuse) or "... && lds <= 64 * 1024 ..." (fall back to a kernel without dynamic LDS)
+                bounded = re.search(r"lds\s*>\s*64\s*\*\s*1024\)\s*return\b|lds\s*<=\s*64\s*\*\s*1024", body)
+                # the request is what is left of a named 64 KiB budget: "(NAME_LDS_MAX - ...) / per_item"
+                budget = re.search(r"\((\w+_LDS_MAX) - ", body)
+                budgeted = budget and re.search(r"constexpr size_t " + budget.group(1) + r" = 64 \* 1024;", text)
+                planned = route_bounds and re.search(r"const orcai_route::Plan&\s*p\b", body) and ", p.lds_bytes, st," in text[ln.start() : ln.start() + 400]
+                assert opted_in or bounded or budgeted or planned, f"{src.name}: {inst} uses dynamic LDS without opting in beyond 64 KiB or bounding its size"
+    return seen
