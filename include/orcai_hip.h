@@ -200,6 +200,35 @@ int orcai_frontend_stats_dev(const void* workspace, float* stats_dev, void* stre
 int orcai_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout,
                           const float* stats_dev, float top_db, float* dpcm, void* stream);
 
+/* Gradient of orcai_make_mel_spectrogram w.r.t. the audio.  Notation as above and at orcai_stft_mel_db.  With Re, Im, P = Re^2 + Im^2 the centred,
+ * zero-padded, periodic-Hann STFT, M[m] = sum_k W[m][k] P[k], Ldb = 10 log10(max(M, 1e-10)), v = max(Ldb - ref_db, -top_db),
+ * out = (clip(v, p_lo, p_hi) - p_lo) / (p_hi - p_lo) and g = dL/dout, f32[n_frames][n_mels]:
+ *   g_L[m]  = g[m] / (p_hi - p_lo)  where M[m] > 1e-10, Ldb - ref_db > -top_db and p_lo < v < p_hi (all strict); 0 otherwise
+ *   dM[m]   = g_L[m] * 10 / (ln 10 * M[m])
+ *   dP[k]   = sum_m W[m][k] dM[m]                      (a bin lies under at most two triangles)
+ *   dRe[k]  = 2 Re[k] dP[k],  dIm[k] = 2 Im[k] dP[k]
+ *   dframe_t[n] = w[n] * sum_k (dRe[k] cos(2 pi k n / N) - dIm[k] sin(2 pi k n / N)),  N = n_fft
+ *   dpcm[s] = sum over the frames t that cover s of dframe_t[s - t * hop + N/2]
+ * ref_db, p_lo and p_hi are HELD CONSTANT, as in orcai_spectrogram_bwd and for the same reason; they are read on the device from stats_dev.  M, Re
+ * and Im are recomputed from pcm (the forward stores nothing but out).  The filterbank weights receive no gradient.
+ *   pcm, n_samples, n_fft, hop, n_frames, n_mels, band_lo, band_hi, band_off, weights, n_weights   exactly as for orcai_stft_mel_db: the band arrays
+ *              in HOST memory (read and checked during the call, handed to the kernel by value), weights on the device
+ *   gout       f32[n_frames * n_mels], layout [frame][band]
+ *   stats_dev  f32[6] from orcai_frontend_stats_dev after the forward of the same pcm
+ *   dpcm       f32[n_samples]: every element is WRITTEN, nothing is accumulated in memory; no float atomics -- a band sum adds its bins in a fixed
+ *              order and dP[k] is gathered per bin, even band first, then the odd one -- so two launches give identical bytes
+ * The gather keeps ONE even-numbered and ONE odd-numbered band per bin (built per workgroup in LDS from the band arrays; no extra pointer): two
+ * non-empty bands of equal parity must not share a bin, i.e. band_hi[m] <= band_lo[m + 2] -- what every table of orcai_amd.mel.band_table
+ * satisfies.  n_fft: the powers of two from 128 to 4096, as the mel forward; hop is arbitrary.  At n_fft = 4096 (and 2048 with more than 202 bands) the launch asks
+ * for more than 64 KiB of LDS: the first such call per device must come outside a stream capture.
+ * ORCAI_E_BADARG (nothing launched, nothing written): null pointer, pcm or weights not 16-byte aligned, non-positive size, n_mels outside 8..256,
+ * n_weights outside 1..65535, n_frames other than 1 + n_samples / hop, a band with band_lo < 0, band_hi < band_lo, band_hi > 1 + n_fft/2 or weights
+ * outside [0, n_weights).  ORCAI_E_UNSUPPORTED (likewise): n_fft that is no power of two from 128 to 4096; two bands of equal parity that overlap. */
+int orcai_mel_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo,
+                              const int* band_hi, const int* band_off, const float* weights, int n_weights, const float* gout,
+                              const float* stats_dev, float top_db, float* dpcm, void* stream);
+int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels); /* workgroups of that launch per compute unit as the runtime computes it; -1 if refused */
+
 
 /* ------------------------------------------------------------------------------------------
  * Model forward, inference (architectures.py:162-241 as executed by model.predict, predict.py:265-268)

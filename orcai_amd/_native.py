@@ -175,6 +175,8 @@ _SIGNATURES = {
     "orcai_make_mel_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, c_i64, c_i64, C.c_float] + [C.c_void_p] * 3),
     "orcai_frontend_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "orcai_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "orcai_mel_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "orcai_mel_spectrogram_bwd_occupancy": (C.c_int, [C.c_int, C.c_int]),
     "orcai_sigmoid_bwd": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_prepare_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "orcai_sepconv_dgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4),

@@ -906,97 +906,46 @@ __device__ __forceinline__ void group_sync() {
 
 constexpr float DB_GRAD = 4.3429448190325183f;  // 10 / ln 10
 
+// The body is spectrogram_bwd_body.inc, included as text in the two kernels below (see there for why it is no function).
+// MEL (orcai_mel_spectrogram_bwd): the same two transforms with the filterbank between them; k_crop is n_mels.  With X[k] standing in buf, SUB lanes per
+// band (1 for the wave-per-run kernel, a wavefront for the workgroup-per-run one) add w[j] |X[lo + j]|^2 in ascending j, strided by SUB, and meet in a
+// fixed butterfly; the band's dM -- three gates, g / range * 10 / (ln 10 M) -- replaces the sum in the group's n_mels floats.  G[k] is then a GATHER:
+// triangles m and m + 2 never overlap (the launcher refuses a table where they do), so a bin has at most one band of each parity, and a table built once
+// per workgroup names them: per bin and parity the band (a byte, 0xFF = none) and the index of its weight in the packed weights.  dP[k] = w_even dM_even
+// + w_odd dM_odd in that order.  The table, the band arrays and dM live in LDS behind the accumulators; the weights are read from global memory (a few
+// KiB, read-only, shared by every frame of every workgroup) in both steps.
+struct MelBwdLds {
+  float* dM;                   // per group: [n_mels]
+  uint16_t *widx_e, *widx_o;   // [n_bins]: index into weights of the bin's even / odd band, 0xFFFF = none (n_weights <= 65535)
+  uint16_t *lo, *n, *off;      // [n_mels]
+  uint8_t *band_e, *band_o;    // [n_bins]: m >> 1 of the bin's even / odd band
+};
+constexpr size_t mel_bwd_lds_bytes(int groups, int n_fft, int n_mels) {
+  const size_t nb = (size_t)(n_fft / 2 + 4) & ~(size_t)3;  // 1 + n_fft / 2 bins, padded to a multiple of 4
+  return (size_t)groups * n_mels * sizeof(float) + 2 * nb * sizeof(uint16_t) + 3 * (size_t)n_mels * sizeof(uint16_t) + 2 * nb;
+}
+
 template <int NT>
 __global__ __launch_bounds__(256) void spectrogram_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
                                                                int k_crop, const float* __restrict__ gout, const float* __restrict__ stats, float top_db,
                                                                float* __restrict__ dpcm, int run, int64_t n_runs) {
-  extern __shared__ float4 bwd_lds[];  // tw[n_fft/2] | per group: buf[n_fft] complex | per group: acc[run]
-  constexpr int GROUPS = 256 / NT;
-  const int half = n_fft >> 1;
-  float2* tw = reinterpret_cast<float2*>(bwd_lds);
-  const int grp = threadIdx.x / NT, gid = threadIdx.x % NT;
-  float2* buf = tw + half + grp * n_fft;
-  float* acc = reinterpret_cast<float*>(tw + half + GROUPS * n_fft) + grp * run;
-  for (int j = threadIdx.x; j < half; j += 256) {  // exp(-2 pi i j / n_fft)
-    float sn, cs;
-    sincospif(-2.0f * (float)j / (float)n_fft, &sn, &cs);
-    tw[j] = make_float2(cs, sn);
-  }
-  __syncthreads();
-  const float ref_db = stats[1], p_lo = stats[2], p_hi = stats[3];
-  const float range = p_hi - p_lo;
-  auto window = [&](int n) { return 0.5f - 0.5f * (n < half ? tw[n].x : -tw[n - half].x); };  // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = false;
+  const MelBands* const bands = nullptr;
+  const float* const weights = nullptr;
+#include "spectrogram_bwd_body.inc"
+}
 
-  for (int64_t r = (int64_t)blockIdx.x * GROUPS + grp; r < n_runs; r += (int64_t)gridDim.x * GROUPS) {  // (NT == 256: uniform over the workgroup)
-    const int64_t s0 = r * run;
-    const int len = (int)(n_samples - s0 < run ? n_samples - s0 : run);
-    for (int i = gid; i < len; i += NT) acc[i] = 0.0f;
-    // frames with [t hop - N/2, t hop + N/2) meeting [s0, s0 + len)
-    const int64_t t_lo = s0 - half < 0 ? 0 : (s0 - half) / hop + 1;
-    int64_t t_hi = (s0 + len + half - 1) / hop;
-    if (t_hi > n_frames - 1) t_hi = n_frames - 1;
-    for (int64_t t = t_lo; t <= t_hi; ++t) {
-      const int64_t base = t * hop - half;
-      for (int n = gid; n < n_fft; n += NT) {
-        const int64_t i = base + n;
-        const float x = (i >= 0 && i < n_samples) ? pcm[i] : 0.0f;
-        buf[n] = make_float2(x * window(n), 0.0f);
-      }
-      group_sync<NT>();
-      for (int st = log2n; st >= 1; --st) {  // forward, decimation in frequency
-        const int hm = 1 << (st - 1);
-        for (int j = gid; j < half; j += NT) {
-          const int k = j & (hm - 1);
-          const int i0 = ((j >> (st - 1)) << st) + k, i1 = i0 + hm;
-          const float2 w = tw[k << (log2n - st)];
-          const float2 a = buf[i0], b = buf[i1];
-          const float2 d = make_float2(a.x - b.x, a.y - b.y);
-          buf[i0] = make_float2(a.x + b.x, a.y + b.y);
-          buf[i1] = make_float2(fmaf(d.x, w.x, -d.y * w.y), fmaf(d.x, w.y, d.y * w.x));
-        }
-        group_sync<NT>();
-      }
-      const float* g = gout + t * (int64_t)k_crop;
-      for (int p = gid; p < n_fft; p += NT) {  // X[k] -> G[k] where it stands
-        const int k = (int)(__brev((uint32_t)p) >> (32 - log2n));
-        float2 G = make_float2(0.0f, 0.0f);
-        if (k < k_crop) {  // k_crop <= 1 + n_fft / 2
-          const float2 z = buf[p];
-          const float P = fmaf(z.x, z.x, z.y * z.y);
-          if (P > AMIN_POW) {
-            const float v = power_to_db(P) - ref_db;
-            if (v > -top_db && v > p_lo && v < p_hi) {
-              const float dP = (g[k] / range) * DB_GRAD / P;
-              G = make_float2(2.0f * z.x * dP, 2.0f * z.y * dP);
-            }
-          }
-        }
-        buf[p] = G;
-      }
-      group_sync<NT>();
-      for (int st = 1; st <= log2n; ++st) {  // inverse (unnormalised), decimation in time
-        const int hm = 1 << (st - 1);
-        for (int j = gid; j < half; j += NT) {
-          const int k = j & (hm - 1);
-          const int i0 = ((j >> (st - 1)) << st) + k, i1 = i0 + hm;
-          const float2 w = tw[k << (log2n - st)];  // conjugated below
-          const float2 a = buf[i0], b = buf[i1];
-          const float2 tb = make_float2(fmaf(b.x, w.x, b.y * w.y), fmaf(b.y, w.x, -b.x * w.y));
-          buf[i0] = make_float2(a.x + tb.x, a.y + tb.y);
-          buf[i1] = make_float2(a.x - tb.x, a.y - tb.y);
-        }
-        group_sync<NT>();
-      }
-      for (int n = gid; n < n_fft; n += NT) {  // overlap-add: one thread per n, frames in order
-        const int64_t q = base + n - s0;
-        if (q >= 0 && q < len) acc[q] += window(n) * buf[n].x;
-      }
-      group_sync<NT>();
-    }
-    group_sync<NT>();
-    for (int i = gid; i < len; i += NT) dpcm[s0 + i] = acc[i];
-    group_sync<NT>();
-  }
+template <int NT>
+__global__ __launch_bounds__(256) void mel_spectrogram_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                                   int n_mels, const float* __restrict__ gout, const float* __restrict__ stats, float top_db,
+                                                                   float* __restrict__ dpcm, int run, int64_t n_runs, const MelBands bands_by_value,
+                                                                   const float* __restrict__ weights) {
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = true;
+  const MelBands* const bands = &bands_by_value;
+  const int k_crop = n_mels;
+#include "spectrogram_bwd_body.inc"
 }
 
 __global__ void stats_dev_kernel(const Workspace* __restrict__ ws, float* __restrict__ out) {
@@ -1297,6 +1246,69 @@ int orcai_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int ho
     hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop,
                        gout, stats_dev, top_db, dpcm, run, n_runs);
   return (int)hipGetLastError();
+}
+
+int orcai_mel_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                              const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, float top_db, float* dpcm,
+                              void* stream) {
+  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !gout || !stats_dev || !dpcm) return ORCAI_E_BADARG;
+  if (n_samples <= 0 || hop <= 0 || n_frames <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15) || ((uintptr_t)gout & 3) || ((uintptr_t)stats_dev & 3) || ((uintptr_t)dpcm & 3)) return ORCAI_E_BADARG;
+  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
+  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
+  MelBands bands;
+  std::memset(&bands, 0, sizeof(bands));
+  const int n_bins = 1 + n_fft / 2;
+  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernel by value
+    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
+    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
+    bands.lo[m] = (uint16_t)lo;
+    bands.n[m] = (uint16_t)(hi - lo);
+    bands.off[m] = (uint16_t)off;
+  }
+  // The per-bin gather has one even-band and one odd-band entry: bands of equal parity must not share a bin.  Checked against the running end of the
+  // non-empty bands of each parity, so an empty band between two overlapping ones hides nothing.
+  int end[2] = {0, 0};
+  for (int m = 0; m < n_mels; ++m) {
+    if (band_hi[m] == band_lo[m]) continue;
+    if (band_lo[m] < end[m & 1]) return ORCAI_E_UNSUPPORTED;
+    end[m & 1] = band_hi[m];
+  }
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  const bool wave = n_fft <= 512;  // runs and groups as orcai_spectrogram_bwd
+  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  const int groups = wave ? 4 : 1;
+  const int64_t n_runs = (n_samples + run - 1) / run;
+  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
+                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
+  constexpr size_t LDS_MAX = 64 * 1024 + mel_bwd_lds_bytes(1, NFFT_ANY_MAX, MEL_MAX);  // the request at n_fft = 4096 with 256 bands: 80 408 B, two per compute unit
+  if (lds > LDS_MAX) return ORCAI_E_UNSUPPORTED;  // (never)
+  if (wave && lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: the wave-per-run kernel asks for at most 58 392 B and does not opt in)
+  if (lds > 64 * 1024)  // n_fft = 4096, and 2048 with more than 202 bands
+    if (const hipError_t e = orcai_lds::ensure_dynamic_lds<mel_spectrogram_bwd_kernel<256>>(LDS_MAX); e != hipSuccess) return (int)e;
+  int64_t blocks = (n_runs + groups - 1) / groups;
+  if (blocks > 256 * 12) blocks = 256 * 12;
+  if (wave)
+    hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames,
+                       n_mels, gout, stats_dev, top_db, dpcm, run, n_runs, bands, weights);
+  else
+    hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<256>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames,
+                       n_mels, gout, stats_dev, top_db, dpcm, run, n_runs, bands, weights);
+  return (int)hipGetLastError();
+}
+
+int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels) {  // workgroups of the mel backward the runtime says fit one compute unit; -1 on refusal
+  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1)) || n_mels < 8 || n_mels > MEL_MAX) return -1;
+  const bool wave = n_fft <= 512;
+  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  const int groups = wave ? 4 : 1;
+  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
+                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
+  int n = -1;
+  const hipError_t e = wave ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<64>, 256, lds)
+                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<256>, 256, lds);
+  return e == hipSuccess ? n : -1;
 }
 
 int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, int64_t rank_lo,

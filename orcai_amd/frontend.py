@@ -145,8 +145,8 @@ class FrontEnd:
         """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
         returned for the same pcm.  ref_db, p_lo and p_hi are constants of the backward (include/orcai_hip.h: orcai_spectrogram_bwd)."""
         if mel.mel_config(spectrogram_parameter) is not None:
-            raise NotImplementedError("spectrogram_backward: the gradient w.r.t. the audio is not implemented for the mel front end (spectrogram parameter "
-                                      "mel is set); the linear front end (mel absent or null) has it")
+            raise NotImplementedError("spectrogram_backward is the linear front end's gradient and the spectrogram parameter mel is set: "
+                                      "FrontEnd.mel_spectrogram_backward is the gradient of the mel front end")
         n_fft = int(spectrogram_parameter["nfft"])
         hop = int(spectrogram_parameter["n_overlap"])
         self._check_nfft(n_fft)
@@ -172,6 +172,39 @@ class FrontEnd:
             self.lib.orcai_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, f_hi, N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm),
                                            N.stream_ptr()),
             "orcai_spectrogram_bwd",
+        )
+        return dpcm
+
+    def mel_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
+        """spectrogram_backward for a spectrogram parameter whose mel key is set: dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, n_mels]
+        and the f32[6] statistics of that forward.  ref_db, p_lo and p_hi are constants of the backward and the filterbank weights get no gradient
+        (include/orcai_hip.h: orcai_mel_spectrogram_bwd).  The parameter's refusals are mel.mel_config's."""
+        cfg = mel.mel_config(spectrogram_parameter)
+        if cfg is None:
+            raise ValueError("mel_spectrogram_backward: the spectrogram parameter mel is absent or null; FrontEnd.spectrogram_backward is the gradient "
+                             "of the linear front end")
+        n_fft = int(spectrogram_parameter["nfft"])
+        hop = int(spectrogram_parameter["n_overlap"])
+        n_mels = cfg["n_mels"]
+        if hop < 1:
+            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
+        pcm = self._check_pcm(pcm)
+        n = pcm.numel()
+        T = 1 + n // hop
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, n_mels)):
+            raise ValueError(f"mel_spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {n_mels}] (nfft = {n_fft}, n_mels = {n_mels}, hop = {hop}, "
+                             f"{n} samples), got {getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
+            raise ValueError(f"mel_spectrogram_backward (nfft = {n_fft}, n_mels = {n_mels}): stats must be the float32 CUDA tensor [6] of "
+                             "make_spectrogram(..., return_stats=True)")
+        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dpcm
+        t, weights = self._mel_table(spectrogram_parameter, cfg)
+        N.check(
+            self.lib.orcai_mel_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, n_mels, t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights),
+                                               weights.numel(), N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm), N.stream_ptr()),
+            "orcai_mel_spectrogram_bwd",
         )
         return dpcm
 

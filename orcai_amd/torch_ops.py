@@ -6,6 +6,7 @@ known without a GPU.
     torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.mel_spectrogram(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
+    torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -31,8 +32,11 @@ waveform.  ``resample`` is the polyphase resampler ``orcai predict`` runs on a r
 same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
 sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
 ``mel_spectrogram`` is the mel route of the front end (``orcai_make_mel_spectrogram``: the mel filterbank and the dB step fused into the STFT kernel, no
-frequency crop).  It has a fake implementation and NO autograd: the gradient through the mel route is not implemented, ``spectrogram_wrt_pcm`` has no mel
-argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` key is set (NotImplementedError).
+frequency crop).  It has a fake implementation and NO autograd of its own, as ``spectrogram`` has none: ``mel_spectrogram_wrt_pcm`` is the same
+computation (same bits) whose backward delivers dL/dpcm through the functional op ``orcai::mel_spectrogram_backward(grad, pcm, stats, ...)``
+(``orcai_mel_spectrogram_bwd``; the three statistics held constant, the filterbank weights get no gradient).  ``spectrogram_wrt_pcm`` has no mel
+argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` key is set (NotImplementedError): ``MelWaveformFrontEnd`` is its mel
+counterpart, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns whichever of the two the parameter asks for.
 ``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
 of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
 bytes, so it has no autograd.
@@ -60,8 +64,9 @@ at their native rate.
 
 What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``orcai train`` on the frozen network (its fused ``Trainer`` step is training mode),
 a backward of ``orcai::predict_spectrogram`` itself (the shared-trunk kernels are not differentiated: ``detect_recording`` recomputes the snippets as a batch),
-any input gradient on the f16 path (f32 models only); ``orcai::spectrogram``
-itself has no backward, and ``orcai::resample`` / ``orcai::resample_backward`` have no second derivative.
+any input gradient on the f16 path (f32 models only); ``orcai::spectrogram`` and ``orcai::mel_spectrogram``
+themselves have no backward, the mel filterbank weights and the three normalisation statistics get no gradient, and ``orcai::resample`` /
+``orcai::resample_backward`` and the two front-end backwards have no second derivative.
 """
 
 from __future__ import annotations
@@ -300,8 +305,8 @@ def _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::mel_spectrogram
-# The mel route of the front end (spectrogram parameter "mel"; orcai_make_mel_spectrogram): no frequency crop, K = n_mels.  Forward only -- the
-# gradient through the mel route does not exist, so the op has NO autograd formula and a pcm that requires grad gets PyTorch's own refusal.
+# The mel route of the front end (spectrogram parameter "mel"; orcai_make_mel_spectrogram): no frequency crop, K = n_mels.  This op has NO autograd
+# formula and a pcm that requires grad gets PyTorch's own refusal; orcai::mel_spectrogram_wrt_pcm below is the differentiable one.
 def _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo=0.0, q_hi=1.0) -> dict:
     return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [fmin, fmax], "quantiles": [q_lo, q_hi],
             "mel": {"n_mels": n_mels, "fmin": fmin, "fmax": fmax, "htk": htk, "norm": "slaney" if slaney_norm else None}}
@@ -514,6 +519,80 @@ _register("spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft
           _spectrogram_wrt_pcm_impl, _spectrogram_fake, _spectrogram_wrt_pcm_autograd)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::mel_spectrogram_wrt_pcm
+# orcai::mel_spectrogram with the gradient w.r.t. the audio, built the way spectrogram_wrt_pcm is: orcai::mel_spectrogram's schema and behaviour stay
+# what they are (no autograd), the forward here is the same launch sequence (same bits) and keeps the run's six statistics when pcm requires grad, and
+# the backward is the functional op orcai::mel_spectrogram_backward (orcai_mel_spectrogram_bwd), which holds ref_db, p_lo and p_hi constant.
+@torch.library.custom_op("orcai::mel_spectrogram_with_stats", mutates_args=())
+def mel_spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                               q_lo: float, q_hi: float) -> tuple[Tensor, Tensor]:
+    """orcai::mel_spectrogram and the f32[6] statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the run, on the device."""
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::mel_spectrogram_with_stats")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi),
+                                                         return_stats=True)
+
+
+@mel_spectrogram_with_stats.register_fake
+def _mel_spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
+    return (_mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi), pcm.new_empty((6,), dtype=torch.float32))
+
+
+@torch.library.custom_op("orcai::mel_spectrogram_backward", mutates_args=())
+def mel_spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float,
+                             htk: bool, slaney_norm: bool) -> Tensor:
+    """dL/dpcm f32[n] from grad = dL/d(mel spectrogram) f32[T, n_mels], the pcm of the forward and the statistics orcai::mel_spectrogram_with_stats returned."""
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::mel_spectrogram_backward")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).mel_spectrogram_backward(pcm.detach(), grad.contiguous(), stats,
+                                                                 _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm))
+
+
+@mel_spectrogram_backward.register_fake
+def _mel_spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm):
+    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
+
+
+def mel_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                            q_lo: float, q_hi: float) -> Tensor:
+    """orcai::mel_spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 128 to 4096."""
+    return torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+
+
+def _mel_spectrogram_wrt_pcm_impl(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
+    return torch.ops.orcai.mel_spectrogram(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+
+
+class _MelSpectrogramFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
+        with torch._C._AutoDispatchBelowAutograd():
+            spec, stats = torch.ops.orcai.mel_spectrogram_with_stats(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+        ctx.args = (sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm)
+        ctx.save_for_backward(pcm, stats)
+        return spec
+
+    @staticmethod
+    def backward(ctx, grad):
+        pcm, stats = ctx.saved_tensors
+        return (torch.ops.orcai.mel_spectrogram_backward(grad, pcm, stats, *ctx.args),) + (None,) * 10
+
+
+def _mel_spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _MelSpectrogramFunction.apply(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+
+
+_register("mel_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, SymInt n_mels, float fmin, float fmax, bool htk, "
+          "bool slaney_norm, float q_lo, float q_hi) -> Tensor", _mel_spectrogram_wrt_pcm_impl, _mel_spectrogram_fake, _mel_spectrogram_wrt_pcm_autograd)
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::resample
 # The project's polyphase resampler (orcai_amd/resample.py, what `orcai predict` runs on a recording that is not at the model's rate) as an op with
 # autograd w.r.t. the audio.  It is linear, so its backward is its adjoint with the same table: the functional op orcai::resample_backward
@@ -650,8 +729,8 @@ class WaveformFrontEnd(torch.nn.Module):
         super().__init__()
         sp = spectrogram_parameter
         if sp.get("mel") is not None:
-            raise NotImplementedError("WaveformFrontEnd: spectrogram parameter mel is set and the mel front end has no gradient w.r.t. the audio "
-                                      "(orcai::mel_spectrogram is forward-only); set mel to null for the differentiable linear front end")
+            raise NotImplementedError("WaveformFrontEnd: spectrogram parameter mel is set and this class is the linear front end; "
+                                      "torch_ops.waveform_front_end(spectrogram_parameter, native_rate) returns MelWaveformFrontEnd for it")
         if float(sp["freq_range"][0]) != 0.0:
             raise ValueError(f"WaveformFrontEnd: freq_range must start at 0 (orcai::spectrogram keeps the leading bins), got {sp['freq_range']}")
         self.native_rate = int(native_rate)
@@ -666,6 +745,44 @@ class WaveformFrontEnd(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, freq_hi={self.freq_hi}"
+
+
+class MelWaveformFrontEnd(torch.nn.Module):
+    """WaveformFrontEnd for a spectrogram parameter whose ``mel`` key is set: forward(pcm f32[n] at native_rate) =
+    mel_spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...) -> [T, n_mels], differentiable down to those samples.  The parameter is
+    validated as mel.mel_config does (ValueError names the key, NotImplementedError an nfft the mel route does not take)."""
+
+    def __init__(self, spectrogram_parameter: dict, native_rate: int):
+        super().__init__()
+        from orcai_amd import mel
+
+        sp = spectrogram_parameter
+        cfg = mel.mel_config(sp)
+        if cfg is None:
+            raise ValueError("MelWaveformFrontEnd: spectrogram parameter mel is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
+                             "native_rate) returns WaveformFrontEnd for it")
+        self.native_rate = int(native_rate)
+        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
+        self.n_mels, self.fmin, self.fmax, self.htk, self.slaney_norm = cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney"
+        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
+        _check_rates(self.native_rate, self.sampling_rate, "MelWaveformFrontEnd")
+
+    def forward(self, pcm: Tensor) -> Tensor:
+        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
+        return torch.ops.orcai.mel_spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, self.n_mels, self.fmin, self.fmax, self.htk,
+                                                       self.slaney_norm, self.q_lo, self.q_hi)
+
+    def extra_repr(self) -> str:
+        return (f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, n_mels={self.n_mels}, fmin={self.fmin}, "
+                f"fmax={self.fmax}, htk={self.htk}, slaney_norm={self.slaney_norm}")
+
+
+def waveform_front_end(spectrogram_parameter: dict, native_rate: int) -> torch.nn.Module:
+    """The differentiable front end of a parameter file's "spectrogram" section: MelWaveformFrontEnd when its ``mel`` key is set, WaveformFrontEnd
+    when it is absent or null."""
+    if spectrogram_parameter.get("mel") is not None:
+        return MelWaveformFrontEnd(spectrogram_parameter, native_rate)
+    return WaveformFrontEnd(spectrogram_parameter, native_rate)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::detect_wrt_input
