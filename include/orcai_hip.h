@@ -229,6 +229,51 @@ int orcai_mel_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, in
                               const float* stats_dev, float top_db, float* dpcm, void* stream);
 int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels); /* workgroups of that launch per compute unit as the runtime computes it; -1 if refused */
 
+/* PCEN front end (spectrogram parameter "pcen"; no counterpart in the reference; semantics are librosa.pcen's, parity unpinned; the float64
+ * specification is orcai_amd.pcen.pcen_ref).
+ *
+ * Linear energies out of the STFT, the input of orcai_pcen: orcai_stft_db / orcai_stft_mel_db with a linear epilogue, and neither running maximum
+ * nor histogram (hence no workspace):
+ *   orcai_stft_energy       out[t*k_crop + k] = |X[k,t]|, k < k_crop: the magnitude the dB step takes the logarithm of
+ *   orcai_stft_mel_energy   out[t*n_mels + m] = M[m,t] = sum_k W[m][k] |X[k,t]|^2: the band power, summed in orcai_stft_mel_db's order
+ * Arguments as for orcai_stft_db / orcai_stft_mel_db.  n_fft: the powers of two from 32 (mel: 128) to 4096 -- 512 runs the tuned kernel, the
+ * others the one-workgroup-per-frame kernel; every other size is ORCAI_E_UNSUPPORTED (the direct transform has no energy epilogue).
+ * ORCAI_E_BADARG as for the dB calls. */
+int orcai_stft_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, float* out, void* stream);
+int orcai_stft_mel_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                          const int* band_off, const float* weights, int n_weights, float* out, void* stream);
+
+/* Frames per chunk of orcai_pcen's scan.  Part of the ABI: the f32 result depends on where the chunks end. */
+#define ORCAI_PCEN_CHUNK 256
+
+/* Per-channel energy normalisation of x = f32[n_frames][k] non-negative energies, IN PLACE:
+ *   S = scale x,  M[0] = S[0],  M[t] = a M[t-1] + b S[t],  x <- (S (eps + M)^-gain + bias)^power - bias^power
+ * The recursion along time runs as a chunked scan, ORCAI_PCEN_CHUNK frames per chunk, in three launches: per (chunk, column) the chain
+ * m = fma(a, m, b S) over the chunk from m = 0 (chunk 0: from M[0] = S[0]); per column the carries in chunk order, C[0] = P[0],
+ * C[j] = fma(a^L_j, C[j-1], P[j]) with L_j the chunk's own length and a^L_j computed in float64 on the host; per (chunk, column) the chain again
+ * from C[j-1], the result written over the energy just read.  The powers are exp2(p log2 .) on the hardware's exp2 / log2; bias^power is formed on
+ * the device by the same instructions, so x = 0 in a channel whose M is finite gives exactly 0.  No float atomics and a fixed order everywhere: the
+ * same input gives the same bytes on every launch.
+ *   a, b       the smoother, 0 <= a < 1, 0 < b <= 1 (orcai_amd.pcen.smoother: b from the time constant in frames, a = 1 - b)
+ *   scale > 0, 0 <= gain <= 1, bias >= 0, 0 < power <= 1, eps > 0
+ *   scratch    orcai_pcen_scratch_bytes(n_frames, k) bytes on the device, 4-byte aligned: f32[ceil(n_frames / 256)][k] partials, then as many carries
+ * ORCAI_E_BADARG (nothing launched): null or misaligned pointer, non-positive size, a parameter outside its range. */
+size_t orcai_pcen_scratch_bytes(int64_t n_frames, int k);
+int orcai_pcen(float* x, int64_t n_frames, int k, float a, float b, float scale, float gain, float bias, float power, float eps, void* scratch,
+               void* stream);
+/* orcai_pcen with HIP events around its three launches: stage_ms = {partials, carries, apply} in milliseconds.  A measuring tool (tools/time_pcen.py):
+ * it SYNCHRONISES on the last event, so it is not capturable. */
+int orcai_pcen_stage_ms(float* x, int64_t n_frames, int k, float a, float b, float scale, float gain, float bias, float power, float eps, void* scratch,
+                        void* stream, float stage_ms[3]);
+
+/* One call = reset + stft_energy (band_lo null) or stft_mel_energy + pcen + hist_level1 + select + finalize(0) + clip_normalize: orcai_make_spectrogram
+ * for a spectrogram parameter with "pcen" set.  k is k_crop or n_mels; the band arguments as for orcai_stft_mel_db, all ignored when band_lo is null.
+ * The percentile clip runs on the PCEN values: no dB reference, no top_db.  rank_lo / rank_hi as for orcai_quantile_select with n = n_frames * k;
+ * out f32[n_frames * k] in [0, 1].  No host synchronisation; orcai_frontend_stats_dev behind it reports p_lo / p_hi as PCEN values (pmax and ref_db 0). */
+int orcai_make_pcen_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
+                                const int* band_off, const float* weights, int n_weights, float a, float b, float scale, float gain, float bias,
+                                float power, float eps, int64_t rank_lo, int64_t rank_hi, float* out, void* scratch, void* workspace, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Model forward, inference (architectures.py:162-241 as executed by model.predict, predict.py:265-268)

@@ -205,7 +205,11 @@ struct MelLds {
   uint16_t lo[MEL_MAX], n[MEL_MAX], off[MEL_MAX];
 };
 
-template <bool EVEN_HOP, bool FAST_ONLY, int KC, bool MEL>
+//
+// ENERGY (orcai_stft_energy / orcai_stft_mel_energy, the input of orcai_pcen): the same transform, staging and stores with a linear epilogue -- the
+// magnitude |X[k]| = sqrt(4 |X|^2) / 2 of the kept bins, or the band power acc as it stands -- and neither running maximum nor histogram (ws is unused
+// and may be null).  A separate instantiation: the dB ones compile to what they were.
+template <bool EVEN_HOP, bool FAST_ONLY, int KC, bool MEL, bool ENERGY = false>
 __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames, int k_crop_arg,
                                              float* __restrict__ out, Workspace* __restrict__ ws, int64_t g_begin, int64_t g_end,
                                              const MelBands* __restrict__ mel_bands, const float* __restrict__ mel_w, int n_weights) {
@@ -231,7 +235,8 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
 
   for (int i = tid; i < 256; i += 256) lds.tw256[i] = g_tw256[i];
   for (int i = tid; i < 257; i += 256) lds.tw512[i] = g_tw512[i];
-  for (int i = tid; i < NB1_PAD; i += 256) lds.hist[i] = 0u;
+  if constexpr (!ENERGY)
+    for (int i = tid; i < NB1_PAD; i += 256) lds.hist[i] = 0u;
 
   for (int i = tid; i < 256; i += 256) lds.win2[i] = *reinterpret_cast<const float2*>(&g_window[2 * i]);
   __syncthreads();
@@ -334,6 +339,8 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
       const float p4 = fmaf(X2.x, X2.x, X2.y * X2.y);  // 4 |X|^2
       if constexpr (MEL) {
         Lk[k1] = p4;
+      } else if constexpr (ENERGY) {
+        if (KC > 0 ? (16 * k1 < KC) : true) Lk[k1] = 0.5f * sqrtf(p4);  // |X|
       } else {
         if (valid) pmax = fmaxf(pmax, p4);
         if (KC > 0 ? (16 * k1 < KC) : true) Lk[KC > 0 ? k1 : k1] = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
@@ -345,6 +352,8 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
       const float p4 = 4.0f * x * x;
       if constexpr (MEL) {
         Lnyq = p4;
+      } else if constexpr (ENERGY) {
+        Lnyq = 0.5f * sqrtf(p4);
       } else {
         if (valid) pmax = fmaxf(pmax, p4);
         Lnyq = (__builtin_amdgcn_logf(fmaxf(p4, 4.0f * AMIN_POW)) - 2.0f) * DB_PER_LOG2;
@@ -367,11 +376,15 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
         const int nk = mel->n[m];
         float acc = 0.0f;
         for (int j = 0; j < nk; ++j) acc = fmaf(w[j], p[j], acc);  // ascending bins: the same order on every launch
-        const float L = power_to_db(acc);
-        stage[idx] = L;
-        if (FAST || t0w + f < n_frames) {
-          pmax = fmaxf(pmax, acc);
-          atomicAdd(&lds.hist[bucket1f(L)], 1u);
+        if constexpr (ENERGY) {
+          stage[idx] = acc;
+        } else {
+          const float L = power_to_db(acc);
+          stage[idx] = L;
+          if (FAST || t0w + f < n_frames) {
+            pmax = fmaxf(pmax, acc);
+            atomicAdd(&lds.hist[bucket1f(L)], 1u);
+          }
         }
       }
     } else {
@@ -381,12 +394,14 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
       const int k = 16 * k1 + l16;
       if (k < k_crop) {
         stage[k] = Lk[k1];
-        if (valid) atomicAdd(&lds.hist[bucket1f(Lk[k1])], 1u);
+        if constexpr (!ENERGY)
+          if (valid) atomicAdd(&lds.hist[bucket1f(Lk[k1])], 1u);
       }
     }
     if (l16 == 0 && 256 < k_crop) {
       stage[256] = Lnyq;
-      if (valid) atomicAdd(&lds.hist[bucket1f(Lnyq)], 1u);
+      if constexpr (!ENERGY)
+        if (valid) atomicAdd(&lds.hist[bucket1f(Lnyq)], 1u);
     }
     }
     wave_lds_fence();
@@ -442,6 +457,7 @@ __device__ __forceinline__ void stft_db_body(const float* __restrict__ pcm, int6
     }
   }
 
+  if constexpr (ENERGY) return;
   // wave max -> one atomic per wave
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) pmax = fmaxf(pmax, __shfl_xor(pmax, off, 64));
@@ -468,6 +484,20 @@ __global__ __launch_bounds__(256, 2) void stft_mel_kernel(const float* __restric
   stft_db_body<EVEN_HOP, FAST_ONLY, 0, true>(pcm, n_samples, hop, n_frames, n_mels, out, ws, g_begin, g_end, &bands, weights, n_weights);
 }
 
+// The energy variants (ENERGY above): same launch bounds, same LDS, no workspace.
+template <bool EVEN_HOP, bool FAST_ONLY, int KC>
+__global__ __launch_bounds__(256, 3) void stft_energy_kernel(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames, int k_crop_arg,
+                                                           float* __restrict__ out, int64_t g_begin, int64_t g_end) {
+  stft_db_body<EVEN_HOP, FAST_ONLY, KC, false, true>(pcm, n_samples, hop, n_frames, k_crop_arg, out, nullptr, g_begin, g_end, nullptr, nullptr, 0);
+}
+
+template <bool EVEN_HOP, bool FAST_ONLY>
+__global__ __launch_bounds__(256, 2) void stft_mel_energy_kernel(const float* __restrict__ pcm, int64_t n_samples, int hop, int64_t n_frames, int n_mels,
+                                                               float* __restrict__ out, int64_t g_begin, int64_t g_end, const MelBands bands,
+                                                               const float* __restrict__ weights, int n_weights) {
+  stft_db_body<EVEN_HOP, FAST_ONLY, 0, true, true>(pcm, n_samples, hop, n_frames, n_mels, out, nullptr, g_begin, g_end, &bands, weights, n_weights);
+}
+
 // ---------------------------------------------------------------- STFT + dB for any power-of-two transform size (the reference reads nfft
 // from the parameter file, spectrogram.py:34-39; every shipped file says 512 and runs stft_db_kernel above).  Plain and slow by comparison: one
 // workgroup per frame, the windowed frame (centred, zero padding, periodic Hann: librosa.stft's defaults) bit-reversed into LDS, log2(nfft) radix-2
@@ -475,8 +505,10 @@ __global__ __launch_bounds__(256, 2) void stft_mel_kernel(const float* __restric
 // taken by hist1_kernel in a second pass over L (the 512-point kernel builds it on the fly).
 constexpr int NFFT_ANY_MAX = 4096;
 
-__global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames, int k_crop,
-                                                        float* __restrict__ out_db, Workspace* __restrict__ ws) {
+// ENERGY (stft_any_energy_kernel): |X[k]| of the kept bins instead of dB, no maximum, ws unused.
+template <bool ENERGY>
+__device__ __forceinline__ void stft_any_body(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames, int k_crop,
+                                              float* __restrict__ out_db, Workspace* __restrict__ ws) {
   __shared__ float2 buf[NFFT_ANY_MAX];
   __shared__ float wmax[4];
   const int tid = threadIdx.x;
@@ -510,11 +542,16 @@ __global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__
     for (int k = tid; k <= half; k += 256) {
       const float2 z = buf[k];
       const float p = fmaf(z.x, z.x, z.y * z.y);
-      pmax = fmaxf(pmax, p);
-      if (k < k_crop) out_db[t * (int64_t)k_crop + k] = power_to_db(p);
+      if constexpr (ENERGY) {
+        if (k < k_crop) out_db[t * (int64_t)k_crop + k] = sqrtf(p);
+      } else {
+        pmax = fmaxf(pmax, p);
+        if (k < k_crop) out_db[t * (int64_t)k_crop + k] = power_to_db(p);
+      }
     }
     __syncthreads();
   }
+  if constexpr (ENERGY) return;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
   if ((tid & 63) == 0) wmax[tid >> 6] = pmax;
@@ -522,14 +559,26 @@ __global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__
   if (tid == 0) atomicMax(&ws->pmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
 }
 
+__global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames, int k_crop,
+                                                        float* __restrict__ out_db, Workspace* __restrict__ ws) {
+  stft_any_body<false>(pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, out_db, ws);
+}
+
+__global__ __launch_bounds__(256) void stft_any_energy_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                               int k_crop, float* __restrict__ out) {
+  stft_any_body<true>(pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, out, nullptr);
+}
+
 // ---------------------------------------------------------------- STFT + mel + dB for the powers of two from 128 to 4096 (orcai_stft_mel_db away from the
 // tuned 512-point kernel).  stft_any_kernel's transform, then |X|^2 of all 1 + nfft/2 bins parked in LDS and one WAVE per band: lane l adds bins
 // lo + l, lo + l + 64, ... in ascending order and the 64 partial sums meet in a fixed butterfly, so two launches give the same bits.  Weights come
 // from global memory (a few KiB, cached), the band table from the kernel argument.  max M as stft_any_kernel leaves max |X|^2; the level-1 histogram
 // is orcai_hist_level1's second pass.
-__global__ __launch_bounds__(256) void stft_mel_any_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
-                                                            int n_mels, float* __restrict__ out_db, Workspace* __restrict__ ws, const MelBands bands,
-                                                            const float* __restrict__ weights) {
+// ENERGY (stft_mel_any_energy_kernel): the band power as summed, no dB and no maximum, ws unused.
+template <bool ENERGY>
+__device__ __forceinline__ void stft_mel_any_body(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                  int n_mels, float* __restrict__ out_db, Workspace* __restrict__ ws, const MelBands& bands,
+                                                  const float* __restrict__ weights) {
   __shared__ float2 buf[NFFT_ANY_MAX];
   __shared__ float pw[NFFT_ANY_MAX / 2 + 1];
   __shared__ float wmax[4];
@@ -571,14 +620,26 @@ __global__ __launch_bounds__(256) void stft_mel_any_kernel(const float* __restri
       for (int j = lane; j < nk; j += 64) acc = fmaf(w[j], pw[lo + j], acc);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // a + b == b + a: every lane holds the same bits
-      if (lane == 0) out_db[t * (int64_t)n_mels + m] = power_to_db(acc);
+      if (lane == 0) out_db[t * (int64_t)n_mels + m] = ENERGY ? acc : power_to_db(acc);
       pmax = fmaxf(pmax, acc);
     }
     __syncthreads();
   }
+  if constexpr (ENERGY) return;
   if (lane == 0) wmax[wave] = pmax;
   __syncthreads();
   if (tid == 0) atomicMax(&ws->pmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+}
+
+__global__ __launch_bounds__(256) void stft_mel_any_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                            int n_mels, float* __restrict__ out_db, Workspace* __restrict__ ws, const MelBands bands,
+                                                            const float* __restrict__ weights) {
+  stft_mel_any_body<false>(pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out_db, ws, bands, weights);
+}
+
+__global__ __launch_bounds__(256) void stft_mel_any_energy_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                                   int n_mels, float* __restrict__ out, const MelBands bands, const float* __restrict__ weights) {
+  stft_mel_any_body<true>(pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out, nullptr, bands, weights);
 }
 
 // ---------------------------------------------------------------- STFT + dB for ANY transform size 2 .. 4096 (odd, 500, 1000 ...: the reference passes
@@ -1143,6 +1204,106 @@ int orcai_stft_mel_occupancy(void) {  // workgroups of stft_mel_kernel<true, tru
   int n = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)stft_mel_kernel<true, true>, 256, 0) != hipSuccess) return -1;
   return n;
+}
+
+// The interior groups [g_lo, g_hi) of a 512-point launch at hop 256, by orcai_stft_db's rule; g_lo == g_hi == n_groups when there are none.
+static void stft_interior_groups(int64_t n_samples, int hop, int64_t n_frames, int64_t n_groups, int64_t& g_lo, int64_t& g_hi) {
+  g_lo = g_hi = n_groups;
+  if (hop != 256) return;
+  g_lo = 1;
+  const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;
+  const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;
+  g_hi = by_samples < by_frames ? by_samples : by_frames;
+  if (g_hi > n_groups) g_hi = n_groups;
+  if (g_hi < g_lo) g_lo = g_hi = n_groups;
+}
+
+int orcai_stft_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, float* out, void* stream) {
+  if (!pcm || !out || n_samples <= 0 || hop <= 0 || k_crop < 1 || n_fft < 2 || k_crop > 1 + n_fft / 2) return ORCAI_E_BADARG;
+  if (((uintptr_t)out & 15) || ((uintptr_t)pcm & 15)) return ORCAI_E_BADARG;
+  if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // the direct transform has no energy epilogue
+  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
+  hipStream_t st = (hipStream_t)stream;
+  if (n_fft != NFFT) {
+    int log2n = 0;
+    while ((1 << log2n) < n_fft) ++log2n;
+    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
+    hipLaunchKernelGGL(stft_any_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, out);
+    return (int)hipGetLastError();
+  }
+  std::call_once(g_tables_once, init_tables);
+  if (g_tables_err) return g_tables_err;
+  const int64_t n_groups = (n_frames + 15) / 16;
+  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
+  if ((hop & 1) != 0) {
+    hipLaunchKernelGGL((stft_energy_kernel<false, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, n_groups);
+    return (int)hipGetLastError();
+  }
+  int64_t g_lo, g_hi;
+  stft_interior_groups(n_samples, hop, n_frames, n_groups, g_lo, g_hi);
+  if (g_hi > g_lo) {
+    if (k_crop == 171)
+      hipLaunchKernelGGL((stft_energy_kernel<true, true, 171>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_lo, g_hi);
+    else
+      hipLaunchKernelGGL((stft_energy_kernel<true, true, 0>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_lo, g_hi);
+    hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, g_lo);
+    if (g_hi < n_groups)
+      hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_hi, n_groups);
+  } else {
+    hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, n_groups);
+  }
+  return (int)hipGetLastError();
+}
+
+int orcai_stft_mel_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                          const int* band_off, const float* weights, int n_weights, float* out, void* stream) {
+  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !out) return ORCAI_E_BADARG;
+  if (n_samples <= 0 || hop <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
+  if (((uintptr_t)out & 15) || ((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15)) return ORCAI_E_BADARG;
+  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
+  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;
+  MelBands bands;
+  std::memset(&bands, 0, sizeof(bands));
+  const int n_bins = 1 + n_fft / 2;
+  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernels by value
+    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
+    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
+    bands.lo[m] = (uint16_t)lo;
+    bands.n[m] = (uint16_t)(hi - lo);
+    bands.off[m] = (uint16_t)off;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (n_fft != NFFT || n_weights > MEL_W_LDS) {
+    int log2n = 0;
+    while ((1 << log2n) < n_fft) ++log2n;
+    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
+    hipLaunchKernelGGL(stft_mel_any_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out, bands, weights);
+    return (int)hipGetLastError();
+  }
+  std::call_once(g_tables_once, init_tables);
+  if (g_tables_err) return g_tables_err;
+  const int64_t n_groups = (n_frames + 15) / 16;
+  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
+  if ((hop & 1) != 0) {
+    hipLaunchKernelGGL((stft_mel_energy_kernel<false, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, n_groups,
+                       bands, weights, n_weights);
+    return (int)hipGetLastError();
+  }
+  int64_t g_lo, g_hi;
+  stft_interior_groups(n_samples, hop, n_frames, n_groups, g_lo, g_hi);
+  if (g_hi > g_lo) {
+    hipLaunchKernelGGL((stft_mel_energy_kernel<true, true>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, g_lo, g_hi, bands,
+                       weights, n_weights);
+    hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, g_lo, bands,
+                       weights, n_weights);
+    if (g_hi < n_groups)
+      hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, g_hi, n_groups,
+                         bands, weights, n_weights);
+  } else {
+    hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, n_groups,
+                       bands, weights, n_weights);
+  }
+  return (int)hipGetLastError();
 }
 
 int orcai_hist_level1(const float* x, int64_t n, void* workspace, void* stream) {

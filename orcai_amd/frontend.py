@@ -14,6 +14,7 @@ import torch
 
 from orcai_amd import _native as N
 from orcai_amd import mel
+from orcai_amd import pcen
 
 TOP_DB = 80.0  # librosa.amplitude_to_db default, spectrogram.py:51-53
 
@@ -51,6 +52,7 @@ class FrontEnd:
         nbytes = self.lib.orcai_frontend_workspace_bytes()
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._mel_tables: dict = {}
+        self._pcen_scratch: torch.Tensor | None = None  # orcai_pcen's partials and carries, grown on demand
 
     @staticmethod
     def _check_nfft(n_fft: int) -> None:
@@ -66,6 +68,7 @@ class FrontEnd:
     # -- the whole of make_spectrogram after decode (spectrogram.py:90-147) -----------------
     def _kept_bins(self, spectrogram_parameter: dict) -> int:
         """K of make_spectrogram's [T, K]; the parameter's own refusals."""
+        pcen.pcen_config(spectrogram_parameter)
         cfg = mel.mel_config(spectrogram_parameter)
         if cfg is not None:  # the mel route: K = n_mels, no frequency crop
             return cfg["n_mels"]
@@ -93,6 +96,8 @@ class FrontEnd:
 
     def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False, out: torch.Tensor | None = None):
         """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
+        With the parameter's pcen key set the values are PCEN (orcai_amd/pcen.py) of the magnitudes -- of the mel band powers when mel is set too --
+        clipped and normalised by the same quantiles; the statistics then hold p_lo / p_hi as PCEN values, pmax and ref_db 0.
         Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
         sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which spectrogram_backward needs -- the
         workspace itself is overwritten by the next recording.  out: a contiguous f32[T, K] of this device to write into (a recording's rows of a
@@ -111,6 +116,27 @@ class FrontEnd:
         r_lo = nearest_rank_index(total, spectrogram_parameter["quantiles"][0])
         r_hi = nearest_rank_index(total, spectrogram_parameter["quantiles"][1])
         cfg = mel.mel_config(spectrogram_parameter)
+        pc = pcen.pcen_config(spectrogram_parameter)
+        if pc is not None:  # PCEN of the magnitudes, or of the mel band powers when mel is set as well
+            a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
+            need = self.lib.orcai_pcen_scratch_bytes(T, K) // 4
+            if self._pcen_scratch is None or self._pcen_scratch.numel() < need:
+                self._pcen_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+            if cfg is not None:
+                t, weights = self._mel_table(spectrogram_parameter, cfg)
+                bands = (t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights), weights.numel())
+            else:
+                bands = (None, None, None, None, 0)
+            N.check(
+                self.lib.orcai_make_pcen_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, *bands, a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"], pc["eps"],
+                                                     r_lo, r_hi, N.ptr(out), N.ptr(self._pcen_scratch), N.ptr(self.workspace), N.stream_ptr()),
+                "orcai_make_pcen_spectrogram",
+            )
+            if return_stats:
+                stats = torch.empty(6, dtype=torch.float32, device=self.device)
+                N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
+                return out, stats
+            return out
         if cfg is not None:
             t, weights = self._mel_table(spectrogram_parameter, cfg)
             N.check(
@@ -141,9 +167,16 @@ class FrontEnd:
             raise NotImplementedError(f"spectrogram parameter nfft = {n_fft}: the gradient w.r.t. the audio is implemented for powers of two from 32 to "
                                       "4096 (512, the value of orcai-V1, included); the forward runs every size from 2 to 4096")
 
+    @staticmethod
+    def _no_pcen_gradient(spectrogram_parameter: dict, who: str) -> None:
+        if pcen.pcen_config(spectrogram_parameter) is not None:
+            raise NotImplementedError(f"{who}: the spectrogram parameter pcen is set and the gradient of the PCEN front end is not implemented "
+                                      "(set pcen to null for the dB front end's gradient)")
+
     def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
         returned for the same pcm.  ref_db, p_lo and p_hi are constants of the backward (include/orcai_hip.h: orcai_spectrogram_bwd)."""
+        self._no_pcen_gradient(spectrogram_parameter, "spectrogram_backward")
         if mel.mel_config(spectrogram_parameter) is not None:
             raise NotImplementedError("spectrogram_backward is the linear front end's gradient and the spectrogram parameter mel is set: "
                                       "FrontEnd.mel_spectrogram_backward is the gradient of the mel front end")
@@ -179,6 +212,7 @@ class FrontEnd:
         """spectrogram_backward for a spectrogram parameter whose mel key is set: dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, n_mels]
         and the f32[6] statistics of that forward.  ref_db, p_lo and p_hi are constants of the backward and the filterbank weights get no gradient
         (include/orcai_hip.h: orcai_mel_spectrogram_bwd).  The parameter's refusals are mel.mel_config's."""
+        self._no_pcen_gradient(spectrogram_parameter, "mel_spectrogram_backward")
         cfg = mel.mel_config(spectrogram_parameter)
         if cfg is None:
             raise ValueError("mel_spectrogram_backward: the spectrogram parameter mel is absent or null; FrontEnd.spectrogram_backward is the gradient "

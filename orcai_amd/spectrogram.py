@@ -17,6 +17,7 @@ from tqdm import tqdm
 
 from orcai_amd import frontend as fe
 from orcai_amd import mel
+from orcai_amd import pcen
 from orcai_amd.auxiliary import Messenger
 from orcai_amd.io import read_json, save_array, write_vector_to_json
 from orcai_amd import wavio
@@ -69,6 +70,8 @@ def _linear_only(spectrogram_parameter: dict, what: str) -> None:
     """The two-step API returns and takes the LINEAR dB spectrum (the reference's contract); the mel route exists as make_spectrogram only."""
     if spectrogram_parameter.get("mel") is not None:
         raise NotImplementedError(f"{what}: the two-step API is linear-only; with spectrogram parameter mel set use make_spectrogram (or set mel to null)")
+    if spectrogram_parameter.get("pcen") is not None:
+        raise NotImplementedError(f"{what}: the two-step API is the dB spectrum; with spectrogram parameter pcen set use make_spectrogram (or set pcen to null)")
 
 
 def calculate_spectrogram(wav_file_path: Path, channel: int, spectrogram_parameter: dict, msgr: Messenger = Messenger(verbosity=0)):
@@ -99,6 +102,7 @@ def make_spectrogram_device(wav_file_path: Path | str, channel: int, orcai_param
     n_mels and frequencies are the n_mels band centres; otherwise the uncropped FFT frequencies, as the reference returns them."""
     sp = orcai_parameter["spectrogram"]
     cfg = mel.mel_config(sp)  # the parameter's refusals, before the file is read
+    pcen.pcen_config(sp)
     pcm = load_wav(wav_file_path, sp["sampling_rate"], channel, msgr)
     spec = fe.get_frontend().make_spectrogram(pcm, sp)
     if cfg is not None:  # the mel route: one frequency per column, the bands' centres

@@ -7,6 +7,8 @@ known without a GPU.
     torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.mel_spectrogram(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
     torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
+    torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
+                                     scale, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -37,6 +39,10 @@ computation (same bits) whose backward delivers dL/dpcm through the functional o
 (``orcai_mel_spectrogram_bwd``; the three statistics held constant, the filterbank weights get no gradient).  ``spectrogram_wrt_pcm`` has no mel
 argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` key is set (NotImplementedError): ``MelWaveformFrontEnd`` is its mel
 counterpart, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns whichever of the two the parameter asks for.
+``pcen_spectrogram`` is the front end with the spectrogram parameter ``pcen`` set (``orcai_make_pcen_spectrogram``; orcai_amd/pcen.py): n_mels = 0 is PCEN of
+the magnitudes of the bins 0 .. freq_hi (the mel arguments are ignored), n_mels > 0 PCEN of the mel band powers (freq_hi is ignored).  Forward only: it has a
+fake implementation, and a backward through it raises NotImplementedError -- the gradient of PCEN is not implemented; ``WaveformFrontEnd`` and
+``MelWaveformFrontEnd`` refuse a parameter whose ``pcen`` key is set for the same reason.
 ``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
 of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
 bytes, so it has no autograd.
@@ -329,6 +335,64 @@ def _mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk
     return pcm.new_empty((1 + pcm.shape[0] // hop, n_mels), dtype=torch.float32)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram
+# The front end with the spectrogram parameter "pcen" set (orcai_make_pcen_spectrogram), beside the linear and the mel op.  Forward only: the op HAS
+# an autograd registration, whose backward raises the NotImplementedError FrontEnd.spectrogram_backward raises for such a parameter.
+def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo=0.0, q_hi=1.0) -> dict:
+    if n_mels > 0:
+        sp = _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    else:
+        sp = _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+    sp["pcen"] = {"time_constant": time_constant, "gain": gain, "bias": bias, "power": power, "eps": eps, "scale": scale}
+    return sp
+
+
+def _pcen_spectrogram_impl(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::pcen_spectrogram")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(
+            pcm.detach(), _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi))
+
+
+def _pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
+    K = n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi)
+    return pcm.new_empty((1 + pcm.shape[0] // hop, K), dtype=torch.float32)
+
+
+class _PcenSpectrogramFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, *args):
+        with torch._C._AutoDispatchBelowAutograd():
+            return torch.ops.orcai.pcen_spectrogram(pcm, *args)
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("orcai::pcen_spectrogram: the gradient of the PCEN front end (spectrogram parameter pcen) is not implemented; "
+                                  "spectrogram_wrt_pcm and mel_spectrogram_wrt_pcm differentiate the dB front ends")
+
+
+def _pcen_spectrogram_autograd(pcm, *args):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _PcenSpectrogramFunction.apply(pcm, *args)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.pcen_spectrogram(pcm, *args)
+
+
+_register("pcen_spectrogram", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, "
+          "bool slaney_norm, float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi) -> Tensor",
+          _pcen_spectrogram_impl, _pcen_spectrogram_fake, _pcen_spectrogram_autograd)
+
+
+def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                     time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the pcen parameter {time_constant, gain, bias, power, eps, scale}: n_mels = 0
+    on the bins 0 .. freq_hi, n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1]; nfft a power of two.  No gradient."""
+    return torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale,
+                                            q_lo, q_hi)
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
 # forward_wrt_input is orcai::forward with the gradient w.r.t. the snippets as well: for something trainable or differentiable IN FRONT of the
 # detector (a learnable gain / equaliser / denoiser on the spectrogram, differentiable augmentation, adversarial or gradient-penalty training,
@@ -597,6 +661,12 @@ _register("mel_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt 
 # The project's polyphase resampler (orcai_amd/resample.py, what `orcai predict` runs on a recording that is not at the model's rate) as an op with
 # autograd w.r.t. the audio.  It is linear, so its backward is its adjoint with the same table: the functional op orcai::resample_backward
 # (orcai_resample_polyphase_bwd).  Nothing is saved for the backward but the input's length.  Equal rates: both ops copy (an op may not alias its input).
+def _no_pcen(spectrogram_parameter: dict, who: str) -> None:
+    if spectrogram_parameter.get("pcen") is not None:
+        raise NotImplementedError(f"{who}: spectrogram parameter pcen is set and the gradient of the PCEN front end is not implemented; "
+                                  "torch.ops.orcai.pcen_spectrogram is its forward")
+
+
 def _check_rates(sr_in, sr_out, who: str) -> None:
     if sr_in <= 0 or sr_out <= 0:
         raise ValueError(f"{who}: sr_in and sr_out must be positive, got {sr_in} and {sr_out}")
@@ -728,6 +798,7 @@ class WaveformFrontEnd(torch.nn.Module):
     def __init__(self, spectrogram_parameter: dict, native_rate: int):
         super().__init__()
         sp = spectrogram_parameter
+        _no_pcen(sp, "WaveformFrontEnd")
         if sp.get("mel") is not None:
             raise NotImplementedError("WaveformFrontEnd: spectrogram parameter mel is set and this class is the linear front end; "
                                       "torch_ops.waveform_front_end(spectrogram_parameter, native_rate) returns MelWaveformFrontEnd for it")
@@ -757,6 +828,7 @@ class MelWaveformFrontEnd(torch.nn.Module):
         from orcai_amd import mel
 
         sp = spectrogram_parameter
+        _no_pcen(sp, "MelWaveformFrontEnd")
         cfg = mel.mel_config(sp)
         if cfg is None:
             raise ValueError("MelWaveformFrontEnd: spectrogram parameter mel is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
