@@ -150,10 +150,50 @@ def _bwd(dH, gates, cst, Uw, rnd, dxz_forced, flush=False, ties=False):
     return dxz
 
 
+# The shapes the recurrence tests share (tests/test_lstm_f32_gpu.py): every width the launchers accept, and the batch / time edges of kernels
+# that work on 16-row batch tiles, double-buffer on step & 1 and prefetch step + 1.
+LSTM_WIDTHS = (32, 64, 96, 128, 160, 192, 224, 256)  # up to 128 the register-resident kernels, above the L2-streamed family (lstm_wide.hip)
+LSTM_FWD_SHAPES = (
+    (1, 1),  # smallest batch and time
+    (16, 1),  # exactly one tile
+    (17, 2),  # the second tile holds one live row; one buffer flip
+    (15, 3),  # ragged single tile
+    (33, 9),  # three tiles, ragged last
+    (7, 46),  # the model's own T
+)
+LSTM_BWD_CASES = (  # (B, T, gscale)
+    (1, 1, 0.1),
+    (16, 1, 0.1),
+    (17, 2, 1e-2),
+    (15, 3, 3.0),
+    (33, 9, 1e-9),
+    (20, 46, 1e-4),
+    (7, 9, 0.0),  # dH identically zero
+)
+LSTM_HOT_WIDTHS = (32, 128, 224)  # one narrow width, the shipped one, and the wide width no other shape list has
+LSTM_HOT_SHAPE = (17, 46)
+HOT_SCALE, HOT_LEVEL = 30.0, 20.0
+
+
 def lstm_inputs_fwd(rng, U, B, Tn):
     """The f32 tests' forward inputs: xz standard normal, Uw standard normal x 0.8 / sqrt(U)."""
     xz = rng.standard_normal((B, Tn, 2, 4 * U)).astype(np.float32)
     Uw = (rng.standard_normal((2, U, 4 * U)) * (0.8 / np.sqrt(U))).astype(np.float32)
+    return xz, Uw
+
+
+def lstm_inputs_fwd_hot(rng, U, B, Tn):
+    """Forward inputs that saturate the activations and let the cell state grow: Uw (and the draws) of lstm_inputs_fwd, and xz by batch row --
+    even rows: HOT_SCALE x standard normal; row 1: every pre-activation +HOT_LEVEL at every step (i = f = o = 1 and g = 1 to f32: the cell state
+    climbs by about 1 per step); row 3: the same with g at -HOT_LEVEL (the cell state falls); the other odd rows: plain standard normal."""
+    xz, Uw = lstm_inputs_fwd(rng, U, B, Tn)
+    xz[0::2] *= np.float32(HOT_SCALE)
+    for row, g_level in ((1, HOT_LEVEL), (3, -HOT_LEVEL)):
+        if row < B:
+            z = np.empty((U // 8, 4, 8), np.float32)  # the layout _gates reads: groups of 32 columns = [gate i, f, g, o][8 units]
+            z[:, (0, 1, 3)] = HOT_LEVEL
+            z[:, 2] = g_level
+            xz[row] = z.reshape(4 * U)
     return xz, Uw
 
 

@@ -1,10 +1,27 @@
 """tests/lstm_ref.py on the CPU: the float64 backward against torch autograd, the teacher-forced f16 references against a float32 emulation of
-the f16 kernels (a stand-in device), and the subnormal-flush switch."""
+the f16 kernels (a stand-in device), the subnormal-flush switch, and the saturating forward case with the shape tables the GPU modules share."""
 
 import numpy as np
 import pytest
 
-from lstm_ref import _bwd_ref, _fwd_ref, bwd_ref_f16, f16_ties, fwd_ref_f16, lstm_inputs_bwd, lstm_inputs_fwd, round_f16
+from lstm_ref import (
+    HOT_LEVEL,
+    LSTM_BWD_CASES,
+    LSTM_FWD_SHAPES,
+    LSTM_HOT_SHAPE,
+    LSTM_HOT_WIDTHS,
+    LSTM_WIDTHS,
+    _bwd_ref,
+    _fwd_ref,
+    _gates,
+    bwd_ref_f16,
+    f16_ties,
+    fwd_ref_f16,
+    lstm_inputs_bwd,
+    lstm_inputs_fwd,
+    lstm_inputs_fwd_hot,
+    round_f16,
+)
 
 f32 = np.float32
 
@@ -205,3 +222,37 @@ def test_f16_midpoints_are_found_and_resolved_from_the_next_step():
     plain, hinted = bwd_ref_f16(dH, gates, cst, Uw, dxz_forced=forced), bwd_ref_f16(dH, gates, cst, Uw, dxz_forced=forced, ties=True)
     scale = np.abs(forced).max()
     assert np.abs(plain - forced)[2, 0, 0].max() > 1e-5 * scale and np.abs(hinted - forced)[:, 0, 0].max() <= 1e-6 * scale
+
+
+def test_shared_shape_tables():
+    """The tables tests/test_lstm_f32_gpu.py is parametrised by: every width the launchers accept, T = 1 and T = 2, B = 1 and B at 15, 16, 17."""
+    assert LSTM_WIDTHS == tuple(range(32, 257, 32))
+    for shapes in (LSTM_FWD_SHAPES, [c[:2] for c in LSTM_BWD_CASES]):
+        assert {1, 2} <= {t for _, t in shapes} and {1, 15, 16, 17} <= {b for b, _ in shapes}
+    assert [c for c in LSTM_BWD_CASES if c[2] == 0.0] and set(LSTM_HOT_WIDTHS) <= set(LSTM_WIDTHS)
+
+
+@pytest.mark.parametrize("U", LSTM_HOT_WIDTHS)
+def test_hot_forward_inputs_saturate_and_grow(U):
+    """lstm_inputs_fwd_hot: Uw and the odd rows past 3 are lstm_inputs_fwd's; the float64 reference stays finite without an overflow (|z| far
+    below 700); row 1's cell state ends above T - 1 and row 3's below -(T - 1) in the forward direction; and the even rows really saturate."""
+    B, Tn = LSTM_HOT_SHAPE
+    xz, Uw = lstm_inputs_fwd_hot(np.random.default_rng(U), U, B, Tn)
+    plain_xz, plain_Uw = lstm_inputs_fwd(np.random.default_rng(U), U, B, Tn)
+    assert xz.dtype == Uw.dtype == f32 and np.array_equal(Uw, plain_Uw) and np.array_equal(xz[5::2], plain_xz[5::2])
+    assert np.array_equal(xz[0::2], plain_xz[0::2] * f32(30.0))
+    for row, g_level in ((1, HOT_LEVEL), (3, -HOT_LEVEL)):  # through the reader of the layout, not by index: sigmoid / tanh of the levels
+        i_, f_, g_, o_ = _gates(xz[row].reshape(Tn * 2, 4 * U).astype(np.float64))
+        s = 1.0 / (1.0 + np.exp(-HOT_LEVEL))
+        assert (i_ == s).all() and (f_ == s).all() and (o_ == s).all() and (g_ == np.tanh(g_level)).all()
+    zmax = float(np.abs(xz).max() + np.abs(Uw).sum(axis=1).max())  # |h| <= 1
+    assert zmax < 350.0, zmax
+    with np.errstate(over="raise", invalid="raise", divide="raise"):
+        h, g, c = _fwd_ref(xz, Uw)
+    assert all(np.isfinite(a).all() for a in (h, g, c))
+    assert c[1, Tn - 1, 0].min() > Tn - 1 and c[3, Tn - 1, 0].max() < -(Tn - 1)
+    ge = g[0::2].reshape(-1, Tn, 2, U // 8, 4, 8)
+    lo, hi = 1e-4, 1.0 - 1e-4
+    sat = np.concatenate([((ge[..., q, :] < lo) | (ge[..., q, :] > hi)).ravel() for q in (0, 1, 3)] + [(np.abs(ge[..., 2, :]) > hi).ravel()])
+    print(f"U {U}: {sat.mean():.2f} of the even rows' gate activations are saturated, max |c| {np.abs(c).max():.1f}, bound on |z| {zmax:.0f}")
+    assert sat.mean() >= 0.25
