@@ -274,6 +274,57 @@ int orcai_make_pcen_spectrogram(const float* pcm, int64_t n_samples, int n_fft, 
                                 const int* band_off, const float* weights, int n_weights, float a, float b, float scale, float gain, float bias,
                                 float power, float eps, int64_t rank_lo, int64_t rank_hi, float* out, void* scratch, void* workspace, void* stream);
 
+/* Gradient of the PCEN front end w.r.t. the audio.  Notation as at orcai_pcen and orcai_spectrogram_bwd.  Forward: E the magnitude |X[k,t]| (linear
+ * route) or the band power (mel route), S = scale E, M the smoother, r = (eps + M)^-gain, u = S r + bias, y = u^power - bias^power,
+ * out = (clip(y, p_lo, p_hi) - p_lo) / (p_hi - p_lo).  With g = dL/dout, and p_lo / p_hi read on the device from stats_dev[2..3] and HELD CONSTANT:
+ *   g_y[t]  = g[t] / (p_hi - p_lo)  where p_lo < y[t] < p_hi (both strict); exactly 0 otherwise (a select, never 0 * inf)
+ *   h[t]    = g_y[t] power u[t]^(power - 1)
+ *   d[t]    = h[t] r[t]                                    the direct path into S[t]
+ *   q[t]    = -gain h[t] S[t] r[t] / (eps + M[t])          dL/dM[t], local part
+ *   lam[T-1] = q[T-1];  lam[t] = q[t] + a lam[t+1]         the smoother's adjoint: the recursion BACKWARD in time
+ *   dE[t]   = scale (d[t] + b lam[t]) for t >= 1;  dE[0] = scale (d[0] + lam[0])      (M[0] = S[0]: coefficient 1, not b)
+ * A clipped or silent element has d = q = 0 and still receives b lam from later frames.  The PCEN parameters, the filterbank and the two statistics get
+ * no gradient; there is no second derivative and no f16 path.
+ *
+ * orcai_pcen_bwd is that map g -> dE alone: E f32[n_frames][k] (const, not overwritten), gout and dE likewise; EVERY element of dE is written.  y and M
+ * are recomputed by the forward's instructions at the forward's chunk boundaries (ORCAI_PCEN_CHUNK), so the gate agrees bit for bit with what
+ * orcai_clip_normalize clipped.  Six launches: the forward's partials and carries; the forward chain again writing d and q; per (chunk, column) the
+ * reverse partial R[j] = the chain lam = fma(a, lam, q[t]) from 0, last frame of the chunk to its first; per column D[last] = R[last],
+ * D[j] = fma(a^256, D[j+1], R[j]) in descending chunk order (a^256 in float64 on the host); the reverse chain again from D[j+1] writing dE.  One fixed
+ * order everywhere and no float atomics: the same input gives the same bytes on every launch.
+ *   scratch    orcai_pcen_bwd_scratch_bytes(n_frames, k) bytes on the device, 4-byte aligned: four f32[ceil(n_frames / 256)][k] (partials, carries and
+ *              their reverse counterparts), then the planes d and q, f32[n_frames][k] each
+ * ORCAI_E_BADARG (nothing launched, dE untouched): as orcai_pcen, and a null or misaligned E, gout, stats_dev or dE. */
+size_t orcai_pcen_bwd_scratch_bytes(int64_t n_frames, int k);
+int orcai_pcen_bwd(const float* E, const float* gout, const float* stats_dev, int64_t n_frames, int k, float a, float b, float scale, float gain, float bias,
+                   float power, float eps, float* dE, void* scratch, void* stream);
+/* orcai_pcen_bwd with HIP events around its six launches: stage_ms = {partials, carries, local, reverse partials, reverse carries, apply}.  A measuring
+ * tool (tools/time_pcen_grad.py): it SYNCHRONISES on the last event, so it is not capturable. */
+int orcai_pcen_bwd_stage_ms(const float* E, const float* gout, const float* stats_dev, int64_t n_frames, int k, float a, float b, float scale, float gain,
+                            float bias, float power, float eps, float* dE, void* scratch, void* stream, float stage_ms[6]);
+
+/* From the gradient w.r.t. the energies to the samples: orcai_spectrogram_bwd / orcai_mel_spectrogram_bwd with a linear epilogue in place of the dB
+ * gates and the 10 / (ln 10 P) factor -- the same kernels' text, two more instantiations; neither stats_dev nor top_db.
+ *   orcai_stft_energy_bwd      gE = dL/d|X[k,t]| f32[n_frames][k_crop]: dRe[k] = gE[k] Re[k] / |X[k]|, dIm[k] = gE[k] Im[k] / |X[k]|, both exactly 0
+ *                              where |X[k]| = 0 (a select) and for the bins from k_crop on
+ *   orcai_stft_mel_energy_bwd  gE = dL/dM[m,t] f32[n_frames][n_mels]: dP[k] = sum_m W[m][k] gE[m], gathered even band first, then the odd one;
+ *                              dRe = 2 Re dP, dIm = 2 Im dP
+ * then the inverse transform and the frame-ordered overlap-add of orcai_spectrogram_bwd: every element of dpcm is written, no float atomics, two
+ * launches give identical bytes.  Sizes (32, mel 128, to 4096), alignment, refusals and the LDS opt-in as for the two dB backwards. */
+int orcai_stft_energy_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gE, float* dpcm, void* stream);
+int orcai_stft_mel_energy_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                              const int* band_off, const float* weights, int n_weights, const float* gE, float* dpcm, void* stream);
+
+/* One call = stft_energy (band_lo null) or stft_mel_energy into scratch (the forward keeps nothing but out) + pcen_bwd + the matching energy backward:
+ * the gradient of orcai_make_pcen_spectrogram w.r.t. pcm.  Arguments as there; gout f32[n_frames * k]; stats_dev from orcai_frontend_stats_dev after
+ * the forward of the same pcm; dpcm f32[n_samples], every element written.  scratch: orcai_pcen_spectrogram_bwd_scratch_bytes(n_frames, k) bytes,
+ * 16-byte aligned (E and dE, f32[n_frames * k] each rounded up to 16 bytes, then orcai_pcen_bwd's).  No host synchronisation.  Refusals are those of
+ * the steps; the transform's arguments are refused by the first step, before anything is launched. */
+size_t orcai_pcen_spectrogram_bwd_scratch_bytes(int64_t n_frames, int k);
+int orcai_pcen_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
+                               const int* band_off, const float* weights, int n_weights, float a, float b, float scale, float gain, float bias, float power,
+                               float eps, const float* gout, const float* stats_dev, float* dpcm, void* scratch, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Model forward, inference (architectures.py:162-241 as executed by model.predict, predict.py:265-268)

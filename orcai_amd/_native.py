@@ -184,6 +184,13 @@ _SIGNATURES = {
     "orcai_pcen_stage_ms": (C.c_int, [C.c_void_p, c_i64, C.c_int] + [C.c_float] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "orcai_make_pcen_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 7 + [c_i64, c_i64]
                                     + [C.c_void_p] * 4),
+    "orcai_pcen_bwd_scratch_bytes": (C.c_size_t, [c_i64, C.c_int]),
+    "orcai_pcen_bwd": (C.c_int, [C.c_void_p] * 3 + [c_i64, C.c_int] + [C.c_float] * 7 + [C.c_void_p] * 3),
+    "orcai_pcen_bwd_stage_ms": (C.c_int, [C.c_void_p] * 3 + [c_i64, C.c_int] + [C.c_float] * 7 + [C.c_void_p] * 3 + [C.POINTER(C.c_float)]),
+    "orcai_stft_energy_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_stft_mel_energy_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "orcai_pcen_spectrogram_bwd_scratch_bytes": (C.c_size_t, [c_i64, C.c_int]),
+    "orcai_pcen_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 7 + [C.c_void_p] * 5),
     "orcai_sigmoid_bwd":(C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_prepare_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "orcai_sepconv_dgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4),

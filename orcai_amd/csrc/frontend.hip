@@ -992,8 +992,23 @@ __global__ __launch_bounds__(256) void spectrogram_bwd_kernel(const float* __res
                                                                float* __restrict__ dpcm, int run, int64_t n_runs) {
   extern __shared__ float4 bwd_lds[];
   constexpr bool MEL = false;
+  constexpr bool ENERGY = false;
   const MelBands* const bands = nullptr;
   const float* const weights = nullptr;
+#include "spectrogram_bwd_body.inc"
+}
+
+// The linear epilogue (orcai_stft_energy_bwd): gout is dL/d|X[k]|.  A kernel of its own, so that the dB kernel above compiles to what it was.
+template <int NT>
+__global__ __launch_bounds__(256) void stft_energy_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                               int k_crop, const float* __restrict__ gout, float* __restrict__ dpcm, int run, int64_t n_runs) {
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = false;
+  constexpr bool ENERGY = true;
+  const MelBands* const bands = nullptr;
+  const float* const weights = nullptr;
+  const float* const stats = nullptr;
+  const float top_db = 0.0f;
 #include "spectrogram_bwd_body.inc"
 }
 
@@ -1004,8 +1019,24 @@ __global__ __launch_bounds__(256) void mel_spectrogram_bwd_kernel(const float* _
                                                                    const float* __restrict__ weights) {
   extern __shared__ float4 bwd_lds[];
   constexpr bool MEL = true;
+  constexpr bool ENERGY = false;
   const MelBands* const bands = &bands_by_value;
   const int k_crop = n_mels;
+#include "spectrogram_bwd_body.inc"
+}
+
+// orcai_stft_mel_energy_bwd: gout is dL/dM[m], the band power's gradient; the gather and everything behind it are the dB kernel's.
+template <int NT>
+__global__ __launch_bounds__(256) void stft_mel_energy_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                                   int n_mels, const float* __restrict__ gout, float* __restrict__ dpcm, int run, int64_t n_runs,
+                                                                   const MelBands bands_by_value, const float* __restrict__ weights) {
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = true;
+  constexpr bool ENERGY = true;
+  const MelBands* const bands = &bands_by_value;
+  const int k_crop = n_mels;
+  const float* const stats = nullptr;
+  const float top_db = 0.0f;
 #include "spectrogram_bwd_body.inc"
 }
 
@@ -1049,6 +1080,108 @@ inline int grid_for(int64_t items_per_block_unit, int64_t n_units) {
   if (g > 256 * 8) g = 256 * 8;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// The launchers behind orcai_spectrogram_bwd (ENERGY = false) and orcai_stft_energy_bwd (ENERGY = true: stats_dev and top_db are not looked at).
+template <bool ENERGY>
+int spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout, const float* stats_dev,
+                           float top_db, float* dpcm, void* stream) {
+  if (!pcm || !gout || (!ENERGY && !stats_dev) || !dpcm || n_samples <= 0 || hop <= 0 || n_frames <= 0 || k_crop < 1 || n_fft < 2) return ORCAI_E_BADARG;
+  if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // powers of two from 32 to 4096 only
+  if (k_crop > 1 + n_fft / 2 || n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;         // librosa's centred frame count (n_fft is even)
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  // Run of output samples per group: 2048 for the wave-per-run kernel (LDS 2 KiB twiddles + 4 x (4 + 8) KiB at 512: three workgroups per compute unit),
+  // 4 n_fft for the workgroup-per-run kernel, n_fft at 4096 (twiddles + frame + accumulator = 64 KiB, the most a launch gets without opting in).
+  const bool wave = n_fft <= 512;
+  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  const int groups = wave ? 4 : 1;
+  const int64_t n_runs = (n_samples + run - 1) / run;
+  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run);
+  if (lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: 64 KiB at n_fft = 4096 is the largest request)
+  int64_t blocks = (n_runs + groups - 1) / groups;
+  if (blocks > 256 * 12) blocks = 256 * 12;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if constexpr (ENERGY) {
+    if (wave) hipLaunchKernelGGL((stft_energy_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, run, n_runs);
+    else hipLaunchKernelGGL((stft_energy_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, run, n_runs);
+  } else {
+    if (wave)
+      hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, run,
+                         n_runs);
+    else
+      hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, run,
+                         n_runs);
+  }
+  return (int)hipGetLastError();
+}
+
+// Likewise behind orcai_mel_spectrogram_bwd and orcai_stft_mel_energy_bwd.
+template <bool ENERGY>
+int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                               const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, float top_db, float* dpcm,
+                               void* stream) {
+  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !gout || (!ENERGY && !stats_dev) || !dpcm) return ORCAI_E_BADARG;
+  if (n_samples <= 0 || hop <= 0 || n_frames <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15) || ((uintptr_t)gout & 3) || ((uintptr_t)stats_dev & 3) || ((uintptr_t)dpcm & 3)) return ORCAI_E_BADARG;
+  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
+  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
+  MelBands bands;
+  std::memset(&bands, 0, sizeof(bands));
+  const int n_bins = 1 + n_fft / 2;
+  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernel by value
+    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
+    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
+    bands.lo[m] = (uint16_t)lo;
+    bands.n[m] = (uint16_t)(hi - lo);
+    bands.off[m] = (uint16_t)off;
+  }
+  // The per-bin gather has one even-band and one odd-band entry: bands of equal parity must not share a bin.  Checked against the running end of the
+  // non-empty bands of each parity, so an empty band between two overlapping ones hides nothing.
+  int end[2] = {0, 0};
+  for (int m = 0; m < n_mels; ++m) {
+    if (band_hi[m] == band_lo[m]) continue;
+    if (band_lo[m] < end[m & 1]) return ORCAI_E_UNSUPPORTED;
+    end[m & 1] = band_hi[m];
+  }
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  const bool wave = n_fft <= 512;  // runs and groups as orcai_spectrogram_bwd
+  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  const int groups = wave ? 4 : 1;
+  const int64_t n_runs = (n_samples + run - 1) / run;
+  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
+                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
+  constexpr size_t LDS_MAX = 64 * 1024 + mel_bwd_lds_bytes(1, NFFT_ANY_MAX, MEL_MAX);  // the request at n_fft = 4096 with 256 bands: 80 408 B, two per compute unit
+  if (lds > LDS_MAX) return ORCAI_E_UNSUPPORTED;  // (never)
+  if (wave && lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: the wave-per-run kernel asks for at most 58 392 B and does not opt in)
+  if (lds > 64 * 1024) {  // n_fft = 4096, and 2048 with more than 202 bands
+    hipError_t e;
+    if constexpr (ENERGY) e = orcai_lds::ensure_dynamic_lds<stft_mel_energy_bwd_kernel<256>>(LDS_MAX);
+    else e = orcai_lds::ensure_dynamic_lds<mel_spectrogram_bwd_kernel<256>>(LDS_MAX);
+    if (e != hipSuccess) return (int)e;
+  }
+  int64_t blocks = (n_runs + groups - 1) / groups;
+  if (blocks > 256 * 12) blocks = 256 * 12;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t st = (hipStream_t)stream;
+  if constexpr (ENERGY) {
+    if (wave)
+      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, run, n_runs, bands,
+                         weights);
+    else
+      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, run, n_runs, bands,
+                         weights);
+  } else {
+    if (wave)
+      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm, run,
+                         n_runs, bands, weights);
+    else
+      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm, run,
+                         n_runs, bands, weights);
+  }
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -1385,78 +1518,23 @@ int orcai_frontend_stats_dev(const void* workspace, float* stats_dev, void* stre
 
 int orcai_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout, const float* stats_dev,
                           float top_db, float* dpcm, void* stream) {
-  if (!pcm || !gout || !stats_dev || !dpcm || n_samples <= 0 || hop <= 0 || n_frames <= 0 || k_crop < 1 || n_fft < 2) return ORCAI_E_BADARG;
-  if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // powers of two from 32 to 4096 only
-  if (k_crop > 1 + n_fft / 2 || n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;         // librosa's centred frame count (n_fft is even)
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) ++log2n;
-  // Run of output samples per group: 2048 for the wave-per-run kernel (LDS 2 KiB twiddles + 4 x (4 + 8) KiB at 512: three workgroups per compute unit),
-  // 4 n_fft for the workgroup-per-run kernel, n_fft at 4096 (twiddles + frame + accumulator = 64 KiB, the most a launch gets without opting in).
-  const bool wave = n_fft <= 512;
-  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
-  const int groups = wave ? 4 : 1;
-  const int64_t n_runs = (n_samples + run - 1) / run;
-  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run);
-  if (lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: 64 KiB at n_fft = 4096 is the largest request)
-  int64_t blocks = (n_runs + groups - 1) / groups;
-  if (blocks > 256 * 12) blocks = 256 * 12;
-  if (wave)
-    hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop,
-                       gout, stats_dev, top_db, dpcm, run, n_runs);
-  else
-    hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop,
-                       gout, stats_dev, top_db, dpcm, run, n_runs);
-  return (int)hipGetLastError();
+  return spectrogram_bwd_launch<false>(pcm, n_samples, n_fft, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, stream);
+}
+
+int orcai_stft_energy_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gE, float* dpcm, void* stream) {
+  return spectrogram_bwd_launch<true>(pcm, n_samples, n_fft, hop, n_frames, k_crop, gE, nullptr, 0.0f, dpcm, stream);
 }
 
 int orcai_mel_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
                               const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, float top_db, float* dpcm,
                               void* stream) {
-  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !gout || !stats_dev || !dpcm) return ORCAI_E_BADARG;
-  if (n_samples <= 0 || hop <= 0 || n_frames <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
-  if (((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15) || ((uintptr_t)gout & 3) || ((uintptr_t)stats_dev & 3) || ((uintptr_t)dpcm & 3)) return ORCAI_E_BADARG;
-  if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
-  if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
-  MelBands bands;
-  std::memset(&bands, 0, sizeof(bands));
-  const int n_bins = 1 + n_fft / 2;
-  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernel by value
-    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
-    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
-    bands.lo[m] = (uint16_t)lo;
-    bands.n[m] = (uint16_t)(hi - lo);
-    bands.off[m] = (uint16_t)off;
-  }
-  // The per-bin gather has one even-band and one odd-band entry: bands of equal parity must not share a bin.  Checked against the running end of the
-  // non-empty bands of each parity, so an empty band between two overlapping ones hides nothing.
-  int end[2] = {0, 0};
-  for (int m = 0; m < n_mels; ++m) {
-    if (band_hi[m] == band_lo[m]) continue;
-    if (band_lo[m] < end[m & 1]) return ORCAI_E_UNSUPPORTED;
-    end[m & 1] = band_hi[m];
-  }
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) ++log2n;
-  const bool wave = n_fft <= 512;  // runs and groups as orcai_spectrogram_bwd
-  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
-  const int groups = wave ? 4 : 1;
-  const int64_t n_runs = (n_samples + run - 1) / run;
-  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
-                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
-  constexpr size_t LDS_MAX = 64 * 1024 + mel_bwd_lds_bytes(1, NFFT_ANY_MAX, MEL_MAX);  // the request at n_fft = 4096 with 256 bands: 80 408 B, two per compute unit
-  if (lds > LDS_MAX) return ORCAI_E_UNSUPPORTED;  // (never)
-  if (wave && lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: the wave-per-run kernel asks for at most 58 392 B and does not opt in)
-  if (lds > 64 * 1024)  // n_fft = 4096, and 2048 with more than 202 bands
-    if (const hipError_t e = orcai_lds::ensure_dynamic_lds<mel_spectrogram_bwd_kernel<256>>(LDS_MAX); e != hipSuccess) return (int)e;
-  int64_t blocks = (n_runs + groups - 1) / groups;
-  if (blocks > 256 * 12) blocks = 256 * 12;
-  if (wave)
-    hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames,
-                       n_mels, gout, stats_dev, top_db, dpcm, run, n_runs, bands, weights);
-  else
-    hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<256>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames,
-                       n_mels, gout, stats_dev, top_db, dpcm, run, n_runs, bands, weights);
-  return (int)hipGetLastError();
+  return mel_spectrogram_bwd_launch<false>(pcm, n_samples, n_fft, hop, n_frames, n_mels, band_lo, band_hi, band_off, weights, n_weights, gout, stats_dev, top_db, dpcm,
+                                           stream);
+}
+
+int orcai_stft_mel_energy_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
+                              const int* band_off, const float* weights, int n_weights, const float* gE, float* dpcm, void* stream) {
+  return mel_spectrogram_bwd_launch<true>(pcm, n_samples, n_fft, hop, n_frames, n_mels, band_lo, band_hi, band_off, weights, n_weights, gE, nullptr, 0.0f, dpcm, stream);
 }
 
 int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels) {  // workgroups of the mel backward the runtime says fit one compute unit; -1 on refusal

@@ -1,8 +1,10 @@
 // The body shared by spectrogram_bwd_kernel<NT> (MEL = false) and mel_spectrogram_bwd_kernel<NT> (MEL = true), included as TEXT inside each kernel:
 // a __device__ function called from two one-line kernels made the compiler order the linear kernels' address arithmetic differently (same bits,
 // 2.4 % slower on the hour at 512 / 256), and the linear kernels are to compile to the instructions they had.  The including kernel provides: the
-// linear kernel's parameters under their names (k_crop = n_mels with MEL), `constexpr bool MEL`, `const MelBands* bands`, `const float* weights`
-// (null without MEL) and `extern __shared__ float4 bwd_lds[]`.  Layout of bwd_lds: tw[n_fft/2] | per group: buf[n_fft] complex | per group:
+// linear kernel's parameters under their names (k_crop = n_mels with MEL), `constexpr bool MEL`, `constexpr bool ENERGY`, `const MelBands* bands`,
+// `const float* weights` (null without MEL) and `extern __shared__ float4 bwd_lds[]`.  ENERGY (orcai_stft_energy_bwd / orcai_stft_mel_energy_bwd): gout is
+// the gradient w.r.t. the magnitude |X[k]| (linear) or the band power (MEL) itself -- no dB gates, no 10 / (ln 10 P); stats is null and never read, top_db
+// unused.  Layout of bwd_lds: tw[n_fft/2] | per group: buf[n_fft] complex | per group:
 // acc[run] | MEL: MelBwdLds.
   constexpr int GROUPS = 256 / NT;
   const int half = n_fft >> 1;
@@ -48,7 +50,7 @@
     tw[j] = make_float2(cs, sn);
   }
   __syncthreads();
-  const float ref_db = stats[1], p_lo = stats[2], p_hi = stats[3];
+  const float ref_db = ENERGY ? 0.0f : stats[1], p_lo = ENERGY ? 0.0f : stats[2], p_hi = ENERGY ? 0.0f : stats[3];
   const float range = p_hi - p_lo;
   auto window = [&](int n) { return 0.5f - 0.5f * (n < half ? tw[n].x : -tw[n - half].x); };  // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
 
@@ -82,7 +84,10 @@
         group_sync<NT>();
       }
       const float* g = gout + t * (int64_t)k_crop;
-      if constexpr (MEL) {
+      if constexpr (MEL && ENERGY) {  // the band power's own gradient: nothing to sum, nothing to gate
+        for (int m = gid; m < k_crop; m += NT) ml.dM[m] = g[m];
+        group_sync<NT>();
+      } else if constexpr (MEL) {
         constexpr int SUB = NT == 64 ? 1 : 64;  // lanes per band
         const int sl = gid % SUB;
         for (int m = gid / SUB; m < k_crop; m += NT / SUB) {  // (SUB == 64: uniform over the wavefront)
@@ -119,7 +124,13 @@
         } else if (k < k_crop) {  // k_crop <= 1 + n_fft / 2
           const float2 z = buf[p];
           const float P = fmaf(z.x, z.x, z.y * z.y);
-          if (P > AMIN_POW) {
+          if constexpr (ENERGY) {
+            const float mag = sqrtf(P);
+            if (mag > 0.0f) {  // d|X| / d(Re, Im) = (Re, Im) / |X|; exactly 0 at |X| = 0
+              const float c = g[k] / mag;
+              G = make_float2(z.x * c, z.y * c);
+            }
+          } else if (P > AMIN_POW) {
             const float v = power_to_db(P) - ref_db;
             if (v > -top_db && v > p_lo && v < p_hi) {
               const float dP = (g[k] / range) * DB_GRAD / P;

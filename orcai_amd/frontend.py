@@ -53,6 +53,7 @@ class FrontEnd:
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._mel_tables: dict = {}
         self._pcen_scratch: torch.Tensor | None = None  # orcai_pcen's partials and carries, grown on demand
+        self._pcen_bwd_scratch: torch.Tensor | None = None  # orcai_pcen_spectrogram_bwd's energies, planes and carries, grown on demand
 
     @staticmethod
     def _check_nfft(n_fft: int) -> None:
@@ -170,8 +171,8 @@ class FrontEnd:
     @staticmethod
     def _no_pcen_gradient(spectrogram_parameter: dict, who: str) -> None:
         if pcen.pcen_config(spectrogram_parameter) is not None:
-            raise NotImplementedError(f"{who}: the spectrogram parameter pcen is set and the gradient of the PCEN front end is not implemented "
-                                      "(set pcen to null for the dB front end's gradient)")
+            raise NotImplementedError(f"{who} is a dB front end's gradient and the spectrogram parameter pcen is set: "
+                                      "FrontEnd.pcen_spectrogram_backward is the gradient of the PCEN front end")
 
     def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
@@ -239,6 +240,50 @@ class FrontEnd:
             self.lib.orcai_mel_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, n_mels, t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights),
                                                weights.numel(), N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm), N.stream_ptr()),
             "orcai_mel_spectrogram_bwd",
+        )
+        return dpcm
+
+    def pcen_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
+        """spectrogram_backward for a spectrogram parameter whose pcen key is set, on either route (the mel one when mel is set as well): dL/dpcm f32[N]
+        from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics of that forward.  p_lo and p_hi are constants of the backward; the
+        PCEN parameters and the filterbank weights get no gradient (include/orcai_hip.h: orcai_pcen_spectrogram_bwd)."""
+        pc = pcen.pcen_config(spectrogram_parameter)
+        if pc is None:
+            raise ValueError("pcen_spectrogram_backward: the spectrogram parameter pcen is absent or null; FrontEnd.spectrogram_backward and "
+                             "FrontEnd.mel_spectrogram_backward are the gradients of the dB front ends")
+        cfg = mel.mel_config(spectrogram_parameter)
+        n_fft = int(spectrogram_parameter["nfft"])
+        hop = int(spectrogram_parameter["n_overlap"])
+        if cfg is None:
+            self._check_nfft(n_fft)
+            self._check_nfft_backward(n_fft)
+        K = self._kept_bins(spectrogram_parameter)
+        if hop < 1:
+            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
+        pcm = self._check_pcm(pcm)
+        n = pcm.numel()
+        T = 1 + n // hop
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, K)):
+            raise ValueError(f"pcen_spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {K}] (nfft = {n_fft}, hop = {hop}, {n} samples), got "
+                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
+            raise ValueError(f"pcen_spectrogram_backward (nfft = {n_fft}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
+        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dpcm
+        a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
+        need = self.lib.orcai_pcen_spectrogram_bwd_scratch_bytes(T, K) // 4
+        if self._pcen_bwd_scratch is None or self._pcen_bwd_scratch.numel() < need:
+            self._pcen_bwd_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+        if cfg is not None:
+            t, weights = self._mel_table(spectrogram_parameter, cfg)
+            bands = (t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights), weights.numel())
+        else:
+            bands = (None, None, None, None, 0)
+        N.check(
+            self.lib.orcai_pcen_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, K, *bands, a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"], pc["eps"],
+                                                N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), N.ptr(dpcm), N.ptr(self._pcen_bwd_scratch), N.stream_ptr()),
+            "orcai_pcen_spectrogram_bwd",
         )
         return dpcm
 

@@ -8,7 +8,8 @@ M[0] = S[0], ``scale`` = 2**31 as its convention for float audio in [-1, 1].  li
 
 With ``mel`` set as well the energies are the mel band powers; without it the magnitudes |X[k]| of the kept bins.  After PCEN the exact percentile
 clip and the normalisation to [0, 1] run on the PCEN values (``quantiles`` keeps its meaning; there is no dB reference and no top_db).  The gradient
-w.r.t. the audio is not implemented for a parameter with ``pcen`` set.
+w.r.t. the audio is ``FrontEnd.pcen_spectrogram_backward`` (``orcai_pcen_spectrogram_bwd``; ``pcen_bwd_ref`` below specifies its reverse-time scan); the
+two dB backward methods keep refusing a parameter with ``pcen`` set.
 """
 
 from __future__ import annotations
@@ -80,6 +81,40 @@ def pcen_ref(E, cfg: dict, sampling_rate: float, hop: int) -> np.ndarray:
     for t in range(1, S.shape[0]):
         M[t] = a * M[t - 1] + b * S[t]
     return pcen_values(S, M, cfg)
+
+
+def pcen_bwd_ref(E, g_y, cfg: dict, sampling_rate: float, hop: int) -> np.ndarray:
+    """The float64 specification of orcai_pcen_bwd's map g_y -> dE, sequential in time (include/orcai_hip.h).  E: [T, K] (or [T]) non-negative
+    energies; g_y = dL/dy of pcen_ref's values y, the same shape -- the clip's gate and its 1 / (p_hi - p_lo) are the caller's, so an element that is
+    clipped, or has u = 0, comes with g_y = 0 and contributes exactly nothing (a select).  With S, M, r = (eps + M)^-gain, u = S r + bias of pcen_ref:
+        h = g_y power u^(power - 1),  d = h r,  q = -gain d S / (eps + M)
+        lam[T-1] = q[T-1],  lam[t] = q[t] + a lam[t+1]
+        dE[t] = scale (d[t] + b lam[t]) for t >= 1,  dE[0] = scale (d[0] + lam[0])   (M[0] = S[0]: coefficient 1, not b)"""
+    S = cfg["scale"] * np.asarray(E, dtype=np.float64)
+    g_y = np.asarray(g_y, dtype=np.float64)
+    if g_y.shape != S.shape:
+        raise ValueError(f"pcen_bwd_ref: g_y {g_y.shape} and E {S.shape} differ in shape")
+    a, b = smoother(cfg["time_constant"], sampling_rate, hop)
+    gain, bias, power, eps = cfg["gain"], cfg["bias"], cfg["power"], cfg["eps"]
+    T = S.shape[0]
+    M = np.empty_like(S)
+    if T:
+        M[0] = S[0]
+    for t in range(1, T):
+        M[t] = a * M[t - 1] + b * S[t]
+    r = (eps + M) ** (-gain)
+    u = S * r + bias
+    live = g_y != 0
+    h = np.zeros_like(S)
+    h[live] = g_y[live] * power * u[live] ** (power - 1.0)
+    d = h * r
+    q = -gain * d * (S / (eps + M))
+    dE = np.empty_like(S)
+    lam = np.zeros_like(S[0]) if T else None
+    for t in range(T - 1, -1, -1):
+        lam = q[t] + a * lam
+        dE[t] = cfg["scale"] * (d[t] + (b if t else 1.0) * lam)
+    return dE
 
 
 def pcen_values(S: np.ndarray, M: np.ndarray, cfg: dict) -> np.ndarray:

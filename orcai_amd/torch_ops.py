@@ -9,6 +9,7 @@ known without a GPU.
     torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> f32[T, n_mels]
     torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
                                      scale, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -41,8 +42,10 @@ argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` 
 counterpart, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns whichever of the two the parameter asks for.
 ``pcen_spectrogram`` is the front end with the spectrogram parameter ``pcen`` set (``orcai_make_pcen_spectrogram``; orcai_amd/pcen.py): n_mels = 0 is PCEN of
 the magnitudes of the bins 0 .. freq_hi (the mel arguments are ignored), n_mels > 0 PCEN of the mel band powers (freq_hi is ignored).  Forward only: it has a
-fake implementation, and a backward through it raises NotImplementedError -- the gradient of PCEN is not implemented; ``WaveformFrontEnd`` and
-``MelWaveformFrontEnd`` refuse a parameter whose ``pcen`` key is set for the same reason.
+fake implementation, and a backward through it raises NotImplementedError that names ``pcen_spectrogram_wrt_pcm`` -- the same computation (same bits) whose
+backward delivers dL/dpcm through the functional op ``orcai::pcen_spectrogram_backward(grad, pcm, stats, ...)`` (``orcai_pcen_spectrogram_bwd``: the
+smoother's adjoint as a reverse-time scan; p_lo and p_hi held constant, the PCEN parameters and the filterbank get no gradient).  ``WaveformFrontEnd``,
+``MelWaveformFrontEnd`` and ``waveform_front_end`` refuse a parameter whose ``pcen`` key is set: ``PcenWaveformFrontEnd`` is the class for it, on either route.
 ``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
 of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
 bytes, so it has no autograd.
@@ -72,7 +75,7 @@ What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``o
 a backward of ``orcai::predict_spectrogram`` itself (the shared-trunk kernels are not differentiated: ``detect_recording`` recomputes the snippets as a batch),
 any input gradient on the f16 path (f32 models only); ``orcai::spectrogram`` and ``orcai::mel_spectrogram``
 themselves have no backward, the mel filterbank weights and the three normalisation statistics get no gradient, and ``orcai::resample`` /
-``orcai::resample_backward`` and the two front-end backwards have no second derivative.
+``orcai::resample_backward`` and the three front-end backwards have no second derivative.
 """
 
 from __future__ import annotations
@@ -337,7 +340,7 @@ def _mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram
 # The front end with the spectrogram parameter "pcen" set (orcai_make_pcen_spectrogram), beside the linear and the mel op.  Forward only: the op HAS
-# an autograd registration, whose backward raises the NotImplementedError FrontEnd.spectrogram_backward raises for such a parameter.
+# an autograd registration, whose backward raises a NotImplementedError that names orcai::pcen_spectrogram_wrt_pcm (further down), the differentiable one.
 def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo=0.0, q_hi=1.0) -> dict:
     if n_mels > 0:
         sp = _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
@@ -369,8 +372,8 @@ class _PcenSpectrogramFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        raise NotImplementedError("orcai::pcen_spectrogram: the gradient of the PCEN front end (spectrogram parameter pcen) is not implemented; "
-                                  "spectrogram_wrt_pcm and mel_spectrogram_wrt_pcm differentiate the dB front ends")
+        raise NotImplementedError("orcai::pcen_spectrogram has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
+                                  "orcai::pcen_spectrogram_wrt_pcm is the same computation with the gradient w.r.t. pcm")
 
 
 def _pcen_spectrogram_autograd(pcm, *args):
@@ -388,7 +391,8 @@ _register("pcen_spectrogram", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, S
 def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
                      time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float, q_hi: float) -> Tensor:
     """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the pcen parameter {time_constant, gain, bias, power, eps, scale}: n_mels = 0
-    on the bins 0 .. freq_hi, n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1]; nfft a power of two.  No gradient."""
+    on the bins 0 .. freq_hi, n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1]; nfft a power of two.  No gradient:
+    pcen_spectrogram_wrt_pcm has it."""
     return torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale,
                                             q_lo, q_hi)
 
@@ -657,14 +661,90 @@ _register("mel_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt 
           "bool slaney_norm, float q_lo, float q_hi) -> Tensor", _mel_spectrogram_wrt_pcm_impl, _mel_spectrogram_fake, _mel_spectrogram_wrt_pcm_autograd)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram_wrt_pcm
+# orcai::pcen_spectrogram with the gradient w.r.t. the audio, the mel trio over again: orcai::pcen_spectrogram keeps its schema and its refusal, the
+# forward here is the same launch sequence (same bits) and keeps the run's statistics when pcm requires grad, and the backward is the functional op
+# orcai::pcen_spectrogram_backward (orcai_pcen_spectrogram_bwd), which holds p_lo and p_hi constant.
+@torch.library.custom_op("orcai::pcen_spectrogram_with_stats", mutates_args=())
+def pcen_spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool,
+                                slaney_norm: bool, time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float,
+                                q_hi: float) -> tuple[Tensor, Tensor]:
+    """orcai::pcen_spectrogram and the f32[6] statistics of the run on the device: p_lo / p_hi as PCEN values, pmax and ref_db 0."""
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::pcen_spectrogram_with_stats")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(
+            pcm.detach(), _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi),
+            return_stats=True)
+
+
+@pcen_spectrogram_with_stats.register_fake
+def _pcen_spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
+    return (_pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi),
+            pcm.new_empty((6,), dtype=torch.float32))
+
+
+@torch.library.custom_op("orcai::pcen_spectrogram_backward", mutates_args=())
+def pcen_spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float,
+                              htk: bool, slaney_norm: bool, time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float) -> Tensor:
+    """dL/dpcm f32[n] from grad = dL/d(PCEN spectrogram) f32[T, K], the pcm of the forward and the statistics orcai::pcen_spectrogram_with_stats returned."""
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::pcen_spectrogram_backward")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).pcen_spectrogram_backward(
+            pcm.detach(), grad.contiguous(), stats,
+            _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale))
+
+
+@pcen_spectrogram_backward.register_fake
+def _pcen_spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale):
+    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
+
+
+def pcen_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                             time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float, q_hi: float) -> Tensor:
+    """orcai::pcen_spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 (n_mels > 0: 128) to 4096."""
+    return torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
+                                                    scale, q_lo, q_hi)
+
+
+class _PcenSpectrogramWrtPcmFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, *args):
+        with torch._C._AutoDispatchBelowAutograd():
+            spec, stats = torch.ops.orcai.pcen_spectrogram_with_stats(pcm, *args)
+        ctx.args = args[:-2]  # all but the quantiles
+        ctx.save_for_backward(pcm, stats)
+        return spec
+
+    @staticmethod
+    def backward(ctx, grad):
+        pcm, stats = ctx.saved_tensors
+        return (torch.ops.orcai.pcen_spectrogram_backward(grad, pcm, stats, *ctx.args),) + (None,) * 17
+
+
+def _pcen_spectrogram_wrt_pcm_autograd(pcm, *args):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _PcenSpectrogramWrtPcmFunction.apply(pcm, *args)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, *args)
+
+
+_register("pcen_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, "
+          "bool slaney_norm, float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi) -> Tensor",
+          _pcen_spectrogram_impl, _pcen_spectrogram_fake, _pcen_spectrogram_wrt_pcm_autograd)
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::resample
 # The project's polyphase resampler (orcai_amd/resample.py, what `orcai predict` runs on a recording that is not at the model's rate) as an op with
 # autograd w.r.t. the audio.  It is linear, so its backward is its adjoint with the same table: the functional op orcai::resample_backward
 # (orcai_resample_polyphase_bwd).  Nothing is saved for the backward but the input's length.  Equal rates: both ops copy (an op may not alias its input).
 def _no_pcen(spectrogram_parameter: dict, who: str) -> None:
     if spectrogram_parameter.get("pcen") is not None:
-        raise NotImplementedError(f"{who}: spectrogram parameter pcen is set and the gradient of the PCEN front end is not implemented; "
-                                  "torch.ops.orcai.pcen_spectrogram is its forward")
+        raise NotImplementedError(f"{who}: spectrogram parameter pcen is set and this is a dB front end; "
+                                  "torch_ops.PcenWaveformFrontEnd(spectrogram_parameter, native_rate) is the differentiable PCEN front end")
 
 
 def _check_rates(sr_in, sr_out, who: str) -> None:
@@ -849,9 +929,46 @@ class MelWaveformFrontEnd(torch.nn.Module):
                 f"fmax={self.fmax}, htk={self.htk}, slaney_norm={self.slaney_norm}")
 
 
+class PcenWaveformFrontEnd(torch.nn.Module):
+    """WaveformFrontEnd for a spectrogram parameter whose ``pcen`` key is set, on either route (the mel one when ``mel`` is set as well):
+    forward(pcm f32[n] at native_rate) = pcen_spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...) -> [T, K], differentiable down to those
+    samples.  The parameter is validated as pcen.pcen_config and mel.mel_config do; p_lo and p_hi are held constant in the backward."""
+
+    def __init__(self, spectrogram_parameter: dict, native_rate: int):
+        super().__init__()
+        from orcai_amd import mel, pcen
+
+        sp = spectrogram_parameter
+        pc = pcen.pcen_config(sp)
+        if pc is None:
+            raise ValueError("PcenWaveformFrontEnd: spectrogram parameter pcen is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
+                             "native_rate) returns the dB front end for it")
+        cfg = mel.mel_config(sp)
+        if cfg is None and float(sp["freq_range"][0]) != 0.0:
+            raise ValueError(f"PcenWaveformFrontEnd: freq_range must start at 0 (orcai::pcen_spectrogram keeps the leading bins), got {sp['freq_range']}")
+        self.native_rate = int(native_rate)
+        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
+        if cfg is None:
+            self.route = (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
+        else:
+            self.route = (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
+        self.pcen = tuple(pc[k] for k in pcen.PCEN_KEYS)  # time_constant, gain, bias, power, eps, scale: the op's order
+        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
+        _check_rates(self.native_rate, self.sampling_rate, "PcenWaveformFrontEnd")
+
+    def forward(self, pcm: Tensor) -> Tensor:
+        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
+        return torch.ops.orcai.pcen_spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, *self.route, *self.pcen, self.q_lo, self.q_hi)
+
+    def extra_repr(self) -> str:
+        freq_hi, n_mels = self.route[:2]
+        return (f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, " + (f"n_mels={n_mels}" if n_mels else f"freq_hi={freq_hi}")
+                + f", time_constant={self.pcen[0]}, gain={self.pcen[1]}, bias={self.pcen[2]}, power={self.pcen[3]}, eps={self.pcen[4]}, scale={self.pcen[5]}")
+
+
 def waveform_front_end(spectrogram_parameter: dict, native_rate: int) -> torch.nn.Module:
-    """The differentiable front end of a parameter file's "spectrogram" section: MelWaveformFrontEnd when its ``mel`` key is set, WaveformFrontEnd
-    when it is absent or null."""
+    """The differentiable dB front end of a parameter file's "spectrogram" section: MelWaveformFrontEnd when its ``mel`` key is set, WaveformFrontEnd
+    when it is absent or null.  A parameter whose ``pcen`` key is set is refused by both (NotImplementedError): PcenWaveformFrontEnd is its class."""
     if spectrogram_parameter.get("mel") is not None:
         return MelWaveformFrontEnd(spectrogram_parameter, native_rate)
     return WaveformFrontEnd(spectrogram_parameter, native_rate)
