@@ -8,6 +8,7 @@ Wraps the C ABI calls of include/orcai_hip.h that replace reference
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -43,6 +44,38 @@ def nearest_rank_index(n: int, q_fraction: float) -> int:
     return int(np.around(np.float32(n - 1) * q))
 
 
+def n_frames(n, nfft, hop):
+    """Frames of a signal of n samples -- librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop.  Plain integer arithmetic: n may be a SymInt."""
+    return 1 + (n - (nfft & 1)) // hop
+
+
+class Route(NamedTuple):
+    """What a spectrogram parameter asks of the front end (resolve_route): the transform, K of the [T, K] result and which of the three C entry points
+    serves it -- pcen set: the PCEN one, on the mel bands when mel is set too; else mel set: the mel one; else the linear one."""
+
+    nfft: int
+    hop: int
+    K: int
+    mel: dict | None  # mel.mel_config's result
+    pcen: dict | None  # pcen.pcen_config's result
+
+
+def resolve_route(spectrogram_parameter: dict) -> Route:
+    """The parameter's route, and its own refusals: pcen's, mel's, the transform size and the crop, in that order."""
+    pc = pcen.pcen_config(spectrogram_parameter)
+    cfg = mel.mel_config(spectrogram_parameter)
+    n_fft = int(spectrogram_parameter["nfft"])
+    if cfg is not None:  # the mel route: K = n_mels, no frequency crop
+        K = cfg["n_mels"]
+    else:
+        FrontEnd._check_nfft(n_fft)
+        freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
+        f_lo, K = crop_indices(freqs, spectrogram_parameter["freq_range"])
+        if f_lo != 0:
+            raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
+    return Route(n_fft, int(spectrogram_parameter["n_overlap"]), K, cfg, pc)
+
+
 class FrontEnd:
     """Owns the selection workspace; one instance per device/stream."""
 
@@ -52,8 +85,7 @@ class FrontEnd:
         nbytes = self.lib.orcai_frontend_workspace_bytes()
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._mel_tables: dict = {}
-        self._pcen_scratch: torch.Tensor | None = None  # orcai_pcen's partials and carries, grown on demand
-        self._pcen_bwd_scratch: torch.Tensor | None = None  # orcai_pcen_spectrogram_bwd's energies, planes and carries, grown on demand
+        self._scratch: dict = {}  # grown on demand: "pcen" orcai_pcen's partials and carries, "pcen_bwd" orcai_pcen_spectrogram_bwd's energies, planes and carries
 
     @staticmethod
     def _check_nfft(n_fft: int) -> None:
@@ -69,17 +101,7 @@ class FrontEnd:
     # -- the whole of make_spectrogram after decode (spectrogram.py:90-147) -----------------
     def _kept_bins(self, spectrogram_parameter: dict) -> int:
         """K of make_spectrogram's [T, K]; the parameter's own refusals."""
-        pcen.pcen_config(spectrogram_parameter)
-        cfg = mel.mel_config(spectrogram_parameter)
-        if cfg is not None:  # the mel route: K = n_mels, no frequency crop
-            return cfg["n_mels"]
-        n_fft = int(spectrogram_parameter["nfft"])
-        self._check_nfft(n_fft)
-        freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
-        f_lo, f_hi = crop_indices(freqs, spectrogram_parameter["freq_range"])
-        if f_lo != 0:
-            raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
-        return f_hi
+        return resolve_route(spectrogram_parameter).K
 
     def _mel_table(self, spectrogram_parameter: dict, cfg: dict):
         """(host band table, packed weights on this device) of a mel parameter: uploaded once per (device, parameter) and kept."""
@@ -89,26 +111,42 @@ class FrontEnd:
             self._mel_tables[key] = (t, torch.from_numpy(t["weights"].copy()).to(self.device))
         return self._mel_tables[key]
 
+    def _bands(self, spectrogram_parameter: dict, cfg: dict | None) -> tuple:
+        """The band arguments (lo, hi, off, weights, n_weights) of the C calls; the five nulls of a parameter without mel."""
+        if cfg is None:
+            return (None, None, None, None, 0)
+        t, weights = self._mel_table(spectrogram_parameter, cfg)
+        return (t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights), weights.numel())
+
+    def _grown(self, name: str, need: int) -> torch.Tensor:
+        """The f32 scratch tensor `name` of this front end, replaced by a larger one when it holds fewer than need floats."""
+        if name not in self._scratch or self._scratch[name].numel() < need:
+            self._scratch[name] = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._scratch[name]
+
+    def _stats_dev(self) -> torch.Tensor:
+        """The last run's six statistics as a device tensor f32[6] (no host synchronisation)."""
+        stats = torch.empty(6, dtype=torch.float32, device=self.device)
+        N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
+        return stats
+
     def spectrogram_shape(self, n_samples: int, spectrogram_parameter: dict) -> tuple[int, int]:
         """(T, K) of make_spectrogram's result for a signal of n_samples at the parameter's rate: host arithmetic only."""
-        K = self._kept_bins(spectrogram_parameter)
-        n_fft, hop = int(spectrogram_parameter["nfft"]), int(spectrogram_parameter["n_overlap"])
-        return 1 + (n_samples - (n_fft & 1)) // hop, K  # librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop
+        route = resolve_route(spectrogram_parameter)
+        return n_frames(n_samples, route.nfft, route.hop), route.K
 
     def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False, out: torch.Tensor | None = None):
         """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
         With the parameter's pcen key set the values are PCEN (orcai_amd/pcen.py) of the magnitudes -- of the mel band powers when mel is set too --
         clipped and normalised by the same quantiles; the statistics then hold p_lo / p_hi as PCEN values, pmax and ref_db 0.
         Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
-        sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which spectrogram_backward needs -- the
+        sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which backward needs -- the
         workspace itself is overwritten by the next recording.  out: a contiguous f32[T, K] of this device to write into (a recording's rows of a
         batch buffer, predict.predict_wavs) instead of a new tensor."""
-        n_fft = int(spectrogram_parameter["nfft"])
-        hop = int(spectrogram_parameter["n_overlap"])
-        K = self._kept_bins(spectrogram_parameter)
+        n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         pcm = self._check_pcm(pcm)
         n = pcm.numel()
-        T = 1 + (n - (n_fft & 1)) // hop  # librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop
+        T = n_frames(n, n_fft, hop)
         if out is None:
             out = torch.empty((T, K), dtype=torch.float32, device=self.device)
         elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, K) and out.is_contiguous()):
@@ -116,51 +154,22 @@ class FrontEnd:
         total = T * K
         r_lo = nearest_rank_index(total, spectrogram_parameter["quantiles"][0])
         r_hi = nearest_rank_index(total, spectrogram_parameter["quantiles"][1])
-        cfg = mel.mel_config(spectrogram_parameter)
-        pc = pcen.pcen_config(spectrogram_parameter)
+        signal = (N.ptr(pcm), n, n_fft, hop, T, K)
         if pc is not None:  # PCEN of the magnitudes, or of the mel band powers when mel is set as well
             a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
-            need = self.lib.orcai_pcen_scratch_bytes(T, K) // 4
-            if self._pcen_scratch is None or self._pcen_scratch.numel() < need:
-                self._pcen_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
-            if cfg is not None:
-                t, weights = self._mel_table(spectrogram_parameter, cfg)
-                bands = (t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights), weights.numel())
-            else:
-                bands = (None, None, None, None, 0)
-            N.check(
-                self.lib.orcai_make_pcen_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, *bands, a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"], pc["eps"],
-                                                     r_lo, r_hi, N.ptr(out), N.ptr(self._pcen_scratch), N.ptr(self.workspace), N.stream_ptr()),
-                "orcai_make_pcen_spectrogram",
-            )
-            if return_stats:
-                stats = torch.empty(6, dtype=torch.float32, device=self.device)
-                N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
-                return out, stats
-            return out
-        if cfg is not None:
-            t, weights = self._mel_table(spectrogram_parameter, cfg)
-            N.check(
-                self.lib.orcai_make_mel_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights),
-                                                    weights.numel(), r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()),
-                "orcai_make_mel_spectrogram",
-            )
-            if return_stats:
-                stats = torch.empty(6, dtype=torch.float32, device=self.device)
-                N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
-                return out, stats
-            return out
-        N.check(
-            self.lib.orcai_make_spectrogram(N.ptr(pcm), n, n_fft, hop, T, K, r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()),
-            "orcai_make_spectrogram",
-        )
-        if return_stats:
-            stats = torch.empty(6, dtype=torch.float32, device=self.device)
-            N.check(self.lib.orcai_frontend_stats_dev(N.ptr(self.workspace), N.ptr(stats), N.stream_ptr()), "orcai_frontend_stats_dev")
-            return out, stats
-        return out
+            scratch = self._grown("pcen", self.lib.orcai_pcen_scratch_bytes(T, K) // 4)
+            rc = self.lib.orcai_make_pcen_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"],
+                                                      pc["eps"], r_lo, r_hi, N.ptr(out), N.ptr(scratch), N.ptr(self.workspace), N.stream_ptr())
+            N.check(rc, "orcai_make_pcen_spectrogram")
+        elif cfg is not None:
+            rc = self.lib.orcai_make_mel_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace),
+                                                     N.stream_ptr())
+            N.check(rc, "orcai_make_mel_spectrogram")
+        else:
+            N.check(self.lib.orcai_make_spectrogram(*signal, r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()), "orcai_make_spectrogram")
+        return (out, self._stats_dev()) if return_stats else out
 
-    # -- the gradient of make_spectrogram w.r.t. the audio (orcai_spectrogram_bwd; the statistics are held constant) -----------------
+    # -- the gradient of make_spectrogram w.r.t. the audio (the statistics are held constant) -----------------
     @staticmethod
     def _check_nfft_backward(n_fft: int) -> None:
         n = int(n_fft)
@@ -168,6 +177,45 @@ class FrontEnd:
             raise NotImplementedError(f"spectrogram parameter nfft = {n_fft}: the gradient w.r.t. the audio is implemented for powers of two from 32 to "
                                       "4096 (512, the value of orcai-V1, included); the forward runs every size from 2 to 4096")
 
+    def backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict, who: str = "backward") -> torch.Tensor:
+        """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
+        returned for the same pcm, on the route the parameter asks for: orcai_pcen_spectrogram_bwd with pcen set (on the mel bands when mel is set
+        too), orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  ref_db, p_lo and p_hi are constants of the backward; the
+        filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry."""
+        n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
+        if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
+            self._check_nfft_backward(n_fft)
+        if hop < 1:
+            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
+        pcm = self._check_pcm(pcm)
+        n = pcm.numel()
+        T = n_frames(n, n_fft, hop)
+        sizes = f"nfft = {n_fft}" if cfg is None else f"nfft = {n_fft}, n_mels = {K}"
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, K)):
+            raise ValueError(f"{who}: grad must be a float32 CUDA tensor [{T}, {K}] ({sizes}, hop = {hop}, {n} samples), got "
+                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
+            raise ValueError(f"{who} ({sizes}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
+        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dpcm
+        signal = (N.ptr(pcm), n, n_fft, hop, T, K)
+        grad, stats = grad.contiguous(), stats.contiguous()
+        if pc is not None:
+            a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
+            scratch = self._grown("pcen_bwd", self.lib.orcai_pcen_spectrogram_bwd_scratch_bytes(T, K) // 4)
+            rc = self.lib.orcai_pcen_spectrogram_bwd(*signal, *self._bands(spectrogram_parameter, cfg), a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"],
+                                                     pc["eps"], N.ptr(grad), N.ptr(stats), N.ptr(dpcm), N.ptr(scratch), N.stream_ptr())
+            N.check(rc, "orcai_pcen_spectrogram_bwd")
+        elif cfg is not None:
+            rc = self.lib.orcai_mel_spectrogram_bwd(*signal, *self._bands(spectrogram_parameter, cfg), N.ptr(grad), N.ptr(stats), TOP_DB, N.ptr(dpcm),
+                                                    N.stream_ptr())
+            N.check(rc, "orcai_mel_spectrogram_bwd")
+        else:
+            N.check(self.lib.orcai_spectrogram_bwd(*signal, N.ptr(grad), N.ptr(stats), TOP_DB, N.ptr(dpcm), N.stream_ptr()), "orcai_spectrogram_bwd")
+        return dpcm
+
+    # The three named entries: each insists on its own route and is `backward` otherwise.
     @staticmethod
     def _no_pcen_gradient(spectrogram_parameter: dict, who: str) -> None:
         if pcen.pcen_config(spectrogram_parameter) is not None:
@@ -175,117 +223,28 @@ class FrontEnd:
                                       "FrontEnd.pcen_spectrogram_backward is the gradient of the PCEN front end")
 
     def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
-        """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
-        returned for the same pcm.  ref_db, p_lo and p_hi are constants of the backward (include/orcai_hip.h: orcai_spectrogram_bwd)."""
+        """backward for the linear dB front end only (orcai_spectrogram_bwd): a parameter whose mel or pcen key is set is refused."""
         self._no_pcen_gradient(spectrogram_parameter, "spectrogram_backward")
         if mel.mel_config(spectrogram_parameter) is not None:
             raise NotImplementedError("spectrogram_backward is the linear front end's gradient and the spectrogram parameter mel is set: "
                                       "FrontEnd.mel_spectrogram_backward is the gradient of the mel front end")
-        n_fft = int(spectrogram_parameter["nfft"])
-        hop = int(spectrogram_parameter["n_overlap"])
-        self._check_nfft(n_fft)
-        self._check_nfft_backward(n_fft)
-        if hop < 1:
-            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
-        freqs = fft_frequencies(spectrogram_parameter["sampling_rate"], n_fft)
-        f_lo, f_hi = crop_indices(freqs, spectrogram_parameter["freq_range"])
-        if f_lo != 0:
-            raise NotImplementedError("HIP front end keeps leading bins only (reference crop start is always bin 0)")
-        pcm = self._check_pcm(pcm)
-        n = pcm.numel()
-        T = 1 + n // hop
-        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, f_hi)):
-            raise ValueError(f"spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {f_hi}] (nfft = {n_fft}, hop = {hop}, {n} samples), got "
-                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
-        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
-            raise ValueError(f"spectrogram_backward (nfft = {n_fft}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
-        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
-        if n == 0:
-            return dpcm
-        N.check(
-            self.lib.orcai_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, f_hi, N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm),
-                                           N.stream_ptr()),
-            "orcai_spectrogram_bwd",
-        )
-        return dpcm
+        return self.backward(pcm, grad, stats, spectrogram_parameter, who="spectrogram_backward")
 
     def mel_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
-        """spectrogram_backward for a spectrogram parameter whose mel key is set: dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, n_mels]
-        and the f32[6] statistics of that forward.  ref_db, p_lo and p_hi are constants of the backward and the filterbank weights get no gradient
-        (include/orcai_hip.h: orcai_mel_spectrogram_bwd).  The parameter's refusals are mel.mel_config's."""
+        """backward for the mel dB front end only (orcai_mel_spectrogram_bwd): grad is f32[T, n_mels]; a parameter without mel, or with pcen, is
+        refused.  The parameter's refusals are mel.mel_config's."""
         self._no_pcen_gradient(spectrogram_parameter, "mel_spectrogram_backward")
-        cfg = mel.mel_config(spectrogram_parameter)
-        if cfg is None:
+        if mel.mel_config(spectrogram_parameter) is None:
             raise ValueError("mel_spectrogram_backward: the spectrogram parameter mel is absent or null; FrontEnd.spectrogram_backward is the gradient "
                              "of the linear front end")
-        n_fft = int(spectrogram_parameter["nfft"])
-        hop = int(spectrogram_parameter["n_overlap"])
-        n_mels = cfg["n_mels"]
-        if hop < 1:
-            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
-        pcm = self._check_pcm(pcm)
-        n = pcm.numel()
-        T = 1 + n // hop
-        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, n_mels)):
-            raise ValueError(f"mel_spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {n_mels}] (nfft = {n_fft}, n_mels = {n_mels}, hop = {hop}, "
-                             f"{n} samples), got {getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
-        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
-            raise ValueError(f"mel_spectrogram_backward (nfft = {n_fft}, n_mels = {n_mels}): stats must be the float32 CUDA tensor [6] of "
-                             "make_spectrogram(..., return_stats=True)")
-        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
-        if n == 0:
-            return dpcm
-        t, weights = self._mel_table(spectrogram_parameter, cfg)
-        N.check(
-            self.lib.orcai_mel_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, n_mels, t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights),
-                                               weights.numel(), N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), TOP_DB, N.ptr(dpcm), N.stream_ptr()),
-            "orcai_mel_spectrogram_bwd",
-        )
-        return dpcm
+        return self.backward(pcm, grad, stats, spectrogram_parameter, who="mel_spectrogram_backward")
 
     def pcen_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
-        """spectrogram_backward for a spectrogram parameter whose pcen key is set, on either route (the mel one when mel is set as well): dL/dpcm f32[N]
-        from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics of that forward.  p_lo and p_hi are constants of the backward; the
-        PCEN parameters and the filterbank weights get no gradient (include/orcai_hip.h: orcai_pcen_spectrogram_bwd)."""
-        pc = pcen.pcen_config(spectrogram_parameter)
-        if pc is None:
+        """backward for the PCEN front end only, on either route (orcai_pcen_spectrogram_bwd): a parameter without pcen is refused."""
+        if pcen.pcen_config(spectrogram_parameter) is None:
             raise ValueError("pcen_spectrogram_backward: the spectrogram parameter pcen is absent or null; FrontEnd.spectrogram_backward and "
                              "FrontEnd.mel_spectrogram_backward are the gradients of the dB front ends")
-        cfg = mel.mel_config(spectrogram_parameter)
-        n_fft = int(spectrogram_parameter["nfft"])
-        hop = int(spectrogram_parameter["n_overlap"])
-        if cfg is None:
-            self._check_nfft(n_fft)
-            self._check_nfft_backward(n_fft)
-        K = self._kept_bins(spectrogram_parameter)
-        if hop < 1:
-            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
-        pcm = self._check_pcm(pcm)
-        n = pcm.numel()
-        T = 1 + n // hop
-        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, K)):
-            raise ValueError(f"pcen_spectrogram_backward: grad must be a float32 CUDA tensor [{T}, {K}] (nfft = {n_fft}, hop = {hop}, {n} samples), got "
-                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
-        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
-            raise ValueError(f"pcen_spectrogram_backward (nfft = {n_fft}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
-        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
-        if n == 0:
-            return dpcm
-        a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
-        need = self.lib.orcai_pcen_spectrogram_bwd_scratch_bytes(T, K) // 4
-        if self._pcen_bwd_scratch is None or self._pcen_bwd_scratch.numel() < need:
-            self._pcen_bwd_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
-        if cfg is not None:
-            t, weights = self._mel_table(spectrogram_parameter, cfg)
-            bands = (t["lo"].ctypes.data, t["hi"].ctypes.data, t["off"].ctypes.data, N.ptr(weights), weights.numel())
-        else:
-            bands = (None, None, None, None, 0)
-        N.check(
-            self.lib.orcai_pcen_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, K, *bands, a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"], pc["eps"],
-                                                N.ptr(grad.contiguous()), N.ptr(stats.contiguous()), N.ptr(dpcm), N.ptr(self._pcen_bwd_scratch), N.stream_ptr()),
-            "orcai_pcen_spectrogram_bwd",
-        )
-        return dpcm
+        return self.backward(pcm, grad, stats, spectrogram_parameter, who="pcen_spectrogram_backward")
 
     # -- calculate_spectrogram (spectrogram.py:15-55): dB of all bins, referenced and floored ----
     def calculate_db(self, pcm: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
@@ -293,7 +252,7 @@ class FrontEnd:
         self._check_nfft(n_fft)
         pcm = self._check_pcm(pcm)
         n = pcm.numel()
-        T = 1 + (n - (n_fft & 1)) // hop  # librosa, center=True: 1 + (n + 2 (nfft // 2) - nfft) // hop
+        T = n_frames(n, n_fft, hop)
         K = 1 + n_fft // 2
         out = torch.empty((T, K), dtype=torch.float32, device=self.device)
         s = N.stream_ptr()

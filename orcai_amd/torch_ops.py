@@ -29,28 +29,26 @@ still alive raises instead of overwriting what that graph's backward needs (``fo
 
 ``forward`` differentiates w.r.t. the weights only and refuses an ``x`` that requires grad; ``forward_wrt_input`` is the same computation
 whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
-detector.  ``spectrogram_wrt_pcm`` is ``spectrogram`` (same bits) whose backward delivers dL/dpcm (``orcai_spectrogram_bwd``; the three
-normalisation statistics are held constant), so the chain pcm -> spectrogram -> snippets -> probabilities is differentiable down to the
-waveform.  ``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
+detector.
+
+The front end has three routes, one op each, all ``FrontEnd.make_spectrogram``: ``spectrogram`` (the bins 0 .. freq_hi in dB; ``orcai_make_spectrogram``),
+``mel_spectrogram`` (the spectrogram parameter ``mel``: filterbank and dB fused into the STFT kernel, no frequency crop; ``orcai_make_mel_spectrogram``) and
+``pcen_spectrogram`` (the spectrogram parameter ``pcen``, orcai_amd/pcen.py; ``orcai_make_pcen_spectrogram``: n_mels = 0 is PCEN of the magnitudes of the bins
+0 .. freq_hi and the mel arguments are ignored, n_mels > 0 PCEN of the mel band powers and freq_hi is ignored).  These three are forward only: they have fake
+implementations and NO autograd of their own (a backward through ``pcen_spectrogram`` raises NotImplementedError that names ``pcen_spectrogram_wrt_pcm``).  Each has a
+differentiable twin built by one wiring (``_register_wrt_pcm``): ``<op>_wrt_pcm`` is the same computation (same bits) whose backward delivers dL/dpcm through
+the functional op ``orcai::<op>_backward(grad, pcm, stats, <the arguments but the quantiles>)`` -- ``FrontEnd.backward``, i.e. ``orcai_spectrogram_bwd``,
+``orcai_mel_spectrogram_bwd`` or ``orcai_pcen_spectrogram_bwd`` -- from the six statistics ``orcai::<op>_with_stats`` returned beside the forward; the
+normalisation statistics are held constant, the filterbank weights and the PCEN parameters get no gradient.  So the chain pcm -> spectrogram -> snippets ->
+probabilities is differentiable down to the waveform.  ``WaveformFrontEnd``, ``MelWaveformFrontEnd`` and ``PcenWaveformFrontEnd`` are resample + the route's
+``_wrt_pcm`` op as a ``torch.nn.Module``; each refuses a parameter of another route, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns
+whichever of the first two the parameter asks for (a parameter whose ``pcen`` key is set: NotImplementedError that names ``PcenWaveformFrontEnd``).
+``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
 same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
 sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
-``mel_spectrogram`` is the mel route of the front end (``orcai_make_mel_spectrogram``: the mel filterbank and the dB step fused into the STFT kernel, no
-frequency crop).  It has a fake implementation and NO autograd of its own, as ``spectrogram`` has none: ``mel_spectrogram_wrt_pcm`` is the same
-computation (same bits) whose backward delivers dL/dpcm through the functional op ``orcai::mel_spectrogram_backward(grad, pcm, stats, ...)``
-(``orcai_mel_spectrogram_bwd``; the three statistics held constant, the filterbank weights get no gradient).  ``spectrogram_wrt_pcm`` has no mel
-argument and ``WaveformFrontEnd`` refuses a spectrogram parameter whose ``mel`` key is set (NotImplementedError): ``MelWaveformFrontEnd`` is its mel
-counterpart, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns whichever of the two the parameter asks for.
-``pcen_spectrogram`` is the front end with the spectrogram parameter ``pcen`` set (``orcai_make_pcen_spectrogram``; orcai_amd/pcen.py): n_mels = 0 is PCEN of
-the magnitudes of the bins 0 .. freq_hi (the mel arguments are ignored), n_mels > 0 PCEN of the mel band powers (freq_hi is ignored).  Forward only: it has a
-fake implementation, and a backward through it raises NotImplementedError that names ``pcen_spectrogram_wrt_pcm`` -- the same computation (same bits) whose
-backward delivers dL/dpcm through the functional op ``orcai::pcen_spectrogram_backward(grad, pcm, stats, ...)`` (``orcai_pcen_spectrogram_bwd``: the
-smoother's adjoint as a reverse-time scan; p_lo and p_hi held constant, the PCEN parameters and the filterbank get no gradient).  ``WaveformFrontEnd``,
-``MelWaveformFrontEnd`` and ``waveform_front_end`` refuse a parameter whose ``pcen`` key is set: ``PcenWaveformFrontEnd`` is the class for it, on either route.
-``decode_pcm`` is the stage in front of it: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
+``decode_pcm`` is the stage in front of both: the data chunk of a WAV file, uploaded as the bytes of the file (``wavio.read_wav_raw``), -> the f32 samples
 of one 0-based channel (``orcai_pcm_decode``; format 0 U8, 1 S16, 2 S24, 3 S32, 4 F32, 5 F64; the same bits as ``wavio.read_wav``).  Its input is integer
 bytes, so it has no autograd.
-``WaveformFrontEnd(spectrogram_parameter, native_rate)`` is the two stages as one ``torch.nn.Module``: the waveform at the rate it was recorded
-at -> the [T, K] spectrogram, differentiable down to those samples.
 
 ``detect_wrt_input`` is the PREDICT-TIME network (BatchNorm with the moving statistics, no Dropout, nothing written to ``stats``) with
 autograd w.r.t. ``x`` only: saliency, robustness probes, training something in front of the detector that will be deployed
@@ -293,6 +291,25 @@ def _bins(sampling_rate: int, nfft: int, freq_hi: float) -> int:
     return crop_indices(fft_frequencies(sampling_rate, nfft), [0, freq_hi])[1]
 
 
+def _spec_fake(pcm, nfft, hop, K):
+    from orcai_amd.frontend import n_frames
+
+    return pcm.new_empty((n_frames(pcm.shape[0], nfft, hop), K), dtype=torch.float32)
+
+
+def _front_end_impl(who: str, parameter, return_stats: bool = False):
+    """The kernel of a front-end op (pcm, *args): FrontEnd.make_spectrogram with the spectrogram parameter that `parameter` makes of args."""
+
+    def impl(pcm, *args):
+        from orcai_amd.frontend import get_frontend
+
+        _check_pcm(pcm, who)
+        with torch.cuda.device(pcm.device):
+            return get_frontend(pcm.device).make_spectrogram(pcm.detach(), parameter(*args), return_stats=return_stats)
+
+    return impl
+
+
 def _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo=0.0, q_hi=1.0) -> dict:
     return {"sampling_rate": sampling_rate, "nfft": nfft, "n_overlap": hop, "freq_range": [0, freq_hi], "quantiles": [q_lo, q_hi]}
 
@@ -309,8 +326,7 @@ def spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: f
 
 @spectrogram.register_fake
 def _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
-    T = 1 + (pcm.shape[0] - (nfft & 1)) // hop
-    return pcm.new_empty((T, _bins(sampling_rate, nfft, freq_hi)), dtype=torch.float32)
+    return _spec_fake(pcm, nfft, hop, _bins(sampling_rate, nfft, freq_hi))
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::mel_spectrogram
@@ -335,7 +351,7 @@ def mel_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels
 
 @mel_spectrogram.register_fake
 def _mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
-    return pcm.new_empty((1 + pcm.shape[0] // hop, n_mels), dtype=torch.float32)
+    return _spec_fake(pcm, nfft, hop, n_mels)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram
@@ -350,18 +366,8 @@ def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, 
     return sp
 
 
-def _pcen_spectrogram_impl(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::pcen_spectrogram")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(
-            pcm.detach(), _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi))
-
-
-def _pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
-    K = n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi)
-    return pcm.new_empty((1 + pcm.shape[0] // hop, K), dtype=torch.float32)
+def _pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, *rest):
+    return _spec_fake(pcm, nfft, hop, n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi))
 
 
 class _PcenSpectrogramFunction(torch.autograd.Function):
@@ -383,9 +389,10 @@ def _pcen_spectrogram_autograd(pcm, *args):
         return torch.ops.orcai.pcen_spectrogram(pcm, *args)
 
 
-_register("pcen_spectrogram", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, "
-          "bool slaney_norm, float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi) -> Tensor",
-          _pcen_spectrogram_impl, _pcen_spectrogram_fake, _pcen_spectrogram_autograd)
+_PCEN_ARGUMENTS = ("SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
+                   "float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi")
+_register("pcen_spectrogram", f"(Tensor pcm, {_PCEN_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::pcen_spectrogram", _pcen_parameter), _pcen_spectrogram_fake,
+          _pcen_spectrogram_autograd)
 
 
 def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
@@ -513,116 +520,81 @@ _register("forward_wrt_input", _FORWARD_SCHEMA, _forward_impl, _probs_fake, _tra
     "input, too, needs the forward with training=True"))
 
 
-# ---------------------------------------------------------------------------------------------------------------- orcai::spectrogram_wrt_pcm
-# orcai::spectrogram with the gradient w.r.t. the audio, for anything trainable or differentiable in the WAVEFORM domain in front of the detector
+# ---------------------------------------------------------------------------------------------------------------- orcai::*_wrt_pcm
+# The three front-end ops with the gradient w.r.t. the audio, for anything trainable or differentiable in the WAVEFORM domain in front of the detector
 # (a learnable band-pass or denoiser on the hydrophone signal, adversarial or gradient-penalty robustness on audio, saliency of a detection in the
-# recording).  Its own op, as forward_wrt_input is: orcai::spectrogram's schema and behaviour stay what they are.  The forward is the same launch
-# sequence (same bits); with a pcm that requires grad it also keeps the run's six statistics (orcai_frontend_stats_dev), and the backward is the
-# functional op orcai::spectrogram_backward (orcai_spectrogram_bwd), which holds ref_db, p_lo and p_hi constant (include/orcai_hip.h).
-@torch.library.custom_op("orcai::spectrogram_with_stats", mutates_args=())
-def spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> tuple[Tensor, Tensor]:
-    """orcai::spectrogram and the f32[6] statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the run, on the device."""
-    from orcai_amd.frontend import get_frontend
+# recording).  Each is its own op, as forward_wrt_input is: the schema and behaviour of orcai::<base> stay what they are.  One wiring serves the three
+# routes (_register_wrt_pcm): orcai::<base>_wrt_pcm runs the same launch sequence as orcai::<base> (same bits); with a pcm that requires grad its
+# Autograd kernel runs orcai::<base>_with_stats instead, which also returns the run's six statistics (orcai_frontend_stats_dev), and its backward is the
+# functional op orcai::<base>_backward (FrontEnd.backward), which holds the statistics constant (include/orcai_hip.h).
+class _WrtPcmFunction(torch.autograd.Function):
+    """forward(pcm, base, check, *args) of orcai::<base>_wrt_pcm(pcm, *args); check(*args), when given, refuses before the forward what the backward
+    could not differentiate.  All of args but the two quantiles go to the backward op."""
 
-    _check_pcm(pcm, "orcai::spectrogram_with_stats")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi), return_stats=True)
-
-
-@spectrogram_with_stats.register_fake
-def _spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
-    return _spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi), pcm.new_empty((6,), dtype=torch.float32)
-
-
-@torch.library.custom_op("orcai::spectrogram_backward", mutates_args=())
-def spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float) -> Tensor:
-    """dL/dpcm f32[n] from grad = dL/dspectrogram f32[T, K], the pcm of the forward and the statistics orcai::spectrogram_with_stats returned."""
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::spectrogram_backward")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).spectrogram_backward(pcm.detach(), grad.contiguous(), stats, _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi))
-
-
-@spectrogram_backward.register_fake
-def _spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, freq_hi):
-    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
-
-
-def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
-    """orcai::spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 to 4096."""
-    return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-
-
-def _spectrogram_wrt_pcm_impl(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
-    return torch.ops.orcai.spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-
-
-class _SpectrogramFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
-        from orcai_amd.frontend import FrontEnd
-
-        FrontEnd._check_nfft_backward(nfft)  # refuse before the forward what the backward could not differentiate
+    def forward(ctx, pcm, base, check, *args):
+        if check is not None:
+            check(*args)
         with torch._C._AutoDispatchBelowAutograd():
-            spec, stats = torch.ops.orcai.spectrogram_with_stats(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-        ctx.args = (sampling_rate, nfft, hop, freq_hi)
+            spec, stats = getattr(torch.ops.orcai, base + "_with_stats")(pcm, *args)
+        ctx.backward_op, ctx.args, ctx.n_inputs = getattr(torch.ops.orcai, base + "_backward"), args[:-2], 2 + len(args)
         ctx.save_for_backward(pcm, stats)
         return spec
 
     @staticmethod
     def backward(ctx, grad):
         pcm, stats = ctx.saved_tensors
-        return (torch.ops.orcai.spectrogram_backward(grad, pcm, stats, *ctx.args), None, None, None, None, None, None)
+        return (ctx.backward_op(grad, pcm, stats, *ctx.args),) + (None,) * ctx.n_inputs
 
 
-def _spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _SpectrogramFunction.apply(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+_FRONT_END_OPS: dict = {}  # name -> CustomOpDef of the inner ops (torch refers to a definition weakly: dropping it would unregister the op)
 
 
-_register("spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi) -> Tensor",
-          _spectrogram_wrt_pcm_impl, _spectrogram_fake, _spectrogram_wrt_pcm_autograd)
+def _register_wrt_pcm(base: str, schema: str, parameter, fake, check=None) -> None:
+    """orcai::<base>_wrt_pcm, orcai::<base>_with_stats and orcai::<base>_backward.  schema: the arguments of orcai::<base> after pcm, the two
+    quantiles last; parameter: the spectrogram parameter of those arguments (the quantiles optional); fake: orcai::<base>'s fake implementation."""
+    no_quantiles = schema.removesuffix(", float q_lo, float q_hi")
+    assert no_quantiles != schema, schema
+
+    def backward_impl(grad, pcm, stats, *args):
+        from orcai_amd.frontend import get_frontend
+
+        _check_pcm(pcm, f"orcai::{base}_backward")
+        with torch.cuda.device(pcm.device):
+            return get_frontend(pcm.device).backward(pcm.detach(), grad.contiguous(), stats, parameter(*args), who=base + "_backward")
+
+    def autograd(pcm, *args):
+        if torch.is_grad_enabled() and pcm.requires_grad:
+            return _WrtPcmFunction.apply(pcm, base, check, *args)
+        with torch._C._AutoDispatchBelowAutograd():
+            return getattr(torch.ops.orcai, base + "_wrt_pcm")(pcm, *args)
+
+    with_stats = torch.library.custom_op(f"orcai::{base}_with_stats", _front_end_impl(f"orcai::{base}_with_stats", parameter, return_stats=True), mutates_args=(),
+                                         schema=f"(Tensor pcm, {schema}) -> (Tensor, Tensor)")
+    with_stats.register_fake(lambda pcm, *args: (fake(pcm, *args), pcm.new_empty((6,), dtype=torch.float32)))
+    backward = torch.library.custom_op(f"orcai::{base}_backward", backward_impl, mutates_args=(), schema=f"(Tensor grad, Tensor pcm, Tensor stats, {no_quantiles}) -> Tensor")
+    backward.register_fake(lambda grad, pcm, stats, *args: pcm.new_empty((pcm.shape[0],), dtype=torch.float32))
+    _FRONT_END_OPS[base + "_with_stats"], _FRONT_END_OPS[base + "_backward"] = with_stats, backward
+    _register(base + "_wrt_pcm", f"(Tensor pcm, {schema}) -> Tensor", _front_end_impl("orcai::" + base, parameter), fake, autograd)
 
 
-# ---------------------------------------------------------------------------------------------------------------- orcai::mel_spectrogram_wrt_pcm
-# orcai::mel_spectrogram with the gradient w.r.t. the audio, built the way spectrogram_wrt_pcm is: orcai::mel_spectrogram's schema and behaviour stay
-# what they are (no autograd), the forward here is the same launch sequence (same bits) and keeps the run's six statistics when pcm requires grad, and
-# the backward is the functional op orcai::mel_spectrogram_backward (orcai_mel_spectrogram_bwd), which holds ref_db, p_lo and p_hi constant.
-@torch.library.custom_op("orcai::mel_spectrogram_with_stats", mutates_args=())
-def mel_spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
-                               q_lo: float, q_hi: float) -> tuple[Tensor, Tensor]:
-    """orcai::mel_spectrogram and the f32[6] statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the run, on the device."""
-    from orcai_amd.frontend import get_frontend
+def _linear_gradient_sizes(sampling_rate, nfft, *rest) -> None:
+    """Of the three routes only the linear one has a forward that takes sizes its backward does not."""
+    from orcai_amd.frontend import FrontEnd
 
-    _check_pcm(pcm, "orcai::mel_spectrogram_with_stats")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi),
-                                                         return_stats=True)
+    FrontEnd._check_nfft_backward(nfft)
 
 
-@mel_spectrogram_with_stats.register_fake
-def _mel_spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
-    return (_mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi), pcm.new_empty((6,), dtype=torch.float32))
+_register_wrt_pcm("spectrogram", "SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi", _spectrogram_parameter, _spectrogram_fake,
+                  check=_linear_gradient_sizes)
+_register_wrt_pcm("mel_spectrogram", "SymInt sampling_rate, SymInt nfft, SymInt hop, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
+                  "float q_lo, float q_hi", _mel_parameter, _mel_spectrogram_fake)
+_register_wrt_pcm("pcen_spectrogram", _PCEN_ARGUMENTS, _pcen_parameter, _pcen_spectrogram_fake)
 
 
-@torch.library.custom_op("orcai::mel_spectrogram_backward", mutates_args=())
-def mel_spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float,
-                             htk: bool, slaney_norm: bool) -> Tensor:
-    """dL/dpcm f32[n] from grad = dL/d(mel spectrogram) f32[T, n_mels], the pcm of the forward and the statistics orcai::mel_spectrogram_with_stats returned."""
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::mel_spectrogram_backward")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).mel_spectrogram_backward(pcm.detach(), grad.contiguous(), stats,
-                                                                 _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm))
-
-
-@mel_spectrogram_backward.register_fake
-def _mel_spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm):
-    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
+def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
+    """orcai::spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 to 4096."""
+    return torch.ops.orcai.spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
 
 
 def mel_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
@@ -631,110 +603,11 @@ def mel_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int
     return torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
 
 
-def _mel_spectrogram_wrt_pcm_impl(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
-    return torch.ops.orcai.mel_spectrogram(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-
-
-class _MelSpectrogramFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
-        with torch._C._AutoDispatchBelowAutograd():
-            spec, stats = torch.ops.orcai.mel_spectrogram_with_stats(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-        ctx.args = (sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm)
-        ctx.save_for_backward(pcm, stats)
-        return spec
-
-    @staticmethod
-    def backward(ctx, grad):
-        pcm, stats = ctx.saved_tensors
-        return (torch.ops.orcai.mel_spectrogram_backward(grad, pcm, stats, *ctx.args),) + (None,) * 10
-
-
-def _mel_spectrogram_wrt_pcm_autograd(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _MelSpectrogramFunction.apply(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.mel_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-
-
-_register("mel_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, SymInt n_mels, float fmin, float fmax, bool htk, "
-          "bool slaney_norm, float q_lo, float q_hi) -> Tensor", _mel_spectrogram_wrt_pcm_impl, _mel_spectrogram_fake, _mel_spectrogram_wrt_pcm_autograd)
-
-
-# ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram_wrt_pcm
-# orcai::pcen_spectrogram with the gradient w.r.t. the audio, the mel trio over again: orcai::pcen_spectrogram keeps its schema and its refusal, the
-# forward here is the same launch sequence (same bits) and keeps the run's statistics when pcm requires grad, and the backward is the functional op
-# orcai::pcen_spectrogram_backward (orcai_pcen_spectrogram_bwd), which holds p_lo and p_hi constant.
-@torch.library.custom_op("orcai::pcen_spectrogram_with_stats", mutates_args=())
-def pcen_spectrogram_with_stats(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool,
-                                slaney_norm: bool, time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float,
-                                q_hi: float) -> tuple[Tensor, Tensor]:
-    """orcai::pcen_spectrogram and the f32[6] statistics of the run on the device: p_lo / p_hi as PCEN values, pmax and ref_db 0."""
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::pcen_spectrogram_with_stats")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(
-            pcm.detach(), _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi),
-            return_stats=True)
-
-
-@pcen_spectrogram_with_stats.register_fake
-def _pcen_spectrogram_with_stats_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi):
-    return (_pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo, q_hi),
-            pcm.new_empty((6,), dtype=torch.float32))
-
-
-@torch.library.custom_op("orcai::pcen_spectrogram_backward", mutates_args=())
-def pcen_spectrogram_backward(grad: Tensor, pcm: Tensor, stats: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float,
-                              htk: bool, slaney_norm: bool, time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float) -> Tensor:
-    """dL/dpcm f32[n] from grad = dL/d(PCEN spectrogram) f32[T, K], the pcm of the forward and the statistics orcai::pcen_spectrogram_with_stats returned."""
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::pcen_spectrogram_backward")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).pcen_spectrogram_backward(
-            pcm.detach(), grad.contiguous(), stats,
-            _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale))
-
-
-@pcen_spectrogram_backward.register_fake
-def _pcen_spectrogram_backward_fake(grad, pcm, stats, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale):
-    return pcm.new_empty((pcm.shape[0],), dtype=torch.float32)
-
-
 def pcen_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
                              time_constant: float, gain: float, bias: float, power: float, eps: float, scale: float, q_lo: float, q_hi: float) -> Tensor:
     """orcai::pcen_spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 (n_mels > 0: 128) to 4096."""
     return torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
                                                     scale, q_lo, q_hi)
-
-
-class _PcenSpectrogramWrtPcmFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pcm, *args):
-        with torch._C._AutoDispatchBelowAutograd():
-            spec, stats = torch.ops.orcai.pcen_spectrogram_with_stats(pcm, *args)
-        ctx.args = args[:-2]  # all but the quantiles
-        ctx.save_for_backward(pcm, stats)
-        return spec
-
-    @staticmethod
-    def backward(ctx, grad):
-        pcm, stats = ctx.saved_tensors
-        return (torch.ops.orcai.pcen_spectrogram_backward(grad, pcm, stats, *ctx.args),) + (None,) * 17
-
-
-def _pcen_spectrogram_wrt_pcm_autograd(pcm, *args):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _PcenSpectrogramWrtPcmFunction.apply(pcm, *args)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, *args)
-
-
-_register("pcen_spectrogram_wrt_pcm", "(Tensor pcm, SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, "
-          "bool slaney_norm, float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi) -> Tensor",
-          _pcen_spectrogram_impl, _pcen_spectrogram_fake, _pcen_spectrogram_wrt_pcm_autograd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::resample
@@ -869,76 +742,89 @@ def _decode_pcm_autograd(frames, channels, channel, format):
 _register("decode_pcm", "(Tensor frames, SymInt channels, SymInt channel, SymInt format) -> Tensor", _decode_pcm_impl, _decode_pcm_fake, _decode_pcm_autograd)
 
 
-class WaveformFrontEnd(torch.nn.Module):
+class _WaveformFrontEnd(torch.nn.Module):
+    """What the three front-end modules share: forward(pcm f32[n] at native_rate) = orcai::<_op>(resample(pcm, native_rate, sampling_rate), sampling_rate,
+    nfft, hop, *_args, q_lo, q_hi).  A subclass names its op, refuses in _route what is not its route and keeps there what _args and extra_repr read."""
+
+    _op: str
+
+    def __init__(self, spectrogram_parameter: dict, native_rate: int):
+        super().__init__()
+        sp = spectrogram_parameter
+        self._route(sp)
+        self.native_rate = int(native_rate)
+        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
+        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
+        _check_rates(self.native_rate, self.sampling_rate, type(self).__name__)
+
+    def forward(self, pcm: Tensor) -> Tensor:
+        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
+        return getattr(torch.ops.orcai, self._op)(at_rate, self.sampling_rate, self.nfft, self.hop, *self._args, self.q_lo, self.q_hi)
+
+    def extra_repr(self) -> str:
+        return f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, "
+
+
+class WaveformFrontEnd(_WaveformFrontEnd):
     """A recording at the rate it was made at -> the [T, K] spectrogram the detector reads, differentiable down to those samples:
     forward(pcm f32[n] at native_rate) = spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...), the two stages `orcai predict` runs in
     front of the model (same bits).  spectrogram_parameter is the "spectrogram" section of a model's parameter file (sampling_rate, nfft,
     n_overlap = the hop, freq_range = [0, freq_hi], quantiles).  The three normalisation statistics are held constant in the backward."""
 
-    def __init__(self, spectrogram_parameter: dict, native_rate: int):
-        super().__init__()
-        sp = spectrogram_parameter
+    _op = "spectrogram_wrt_pcm"
+
+    def _route(self, sp: dict) -> None:
         _no_pcen(sp, "WaveformFrontEnd")
         if sp.get("mel") is not None:
             raise NotImplementedError("WaveformFrontEnd: spectrogram parameter mel is set and this class is the linear front end; "
                                       "torch_ops.waveform_front_end(spectrogram_parameter, native_rate) returns MelWaveformFrontEnd for it")
         if float(sp["freq_range"][0]) != 0.0:
             raise ValueError(f"WaveformFrontEnd: freq_range must start at 0 (orcai::spectrogram keeps the leading bins), got {sp['freq_range']}")
-        self.native_rate = int(native_rate)
-        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
         self.freq_hi = float(sp["freq_range"][1])
-        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
-        _check_rates(self.native_rate, self.sampling_rate, "WaveformFrontEnd")
 
-    def forward(self, pcm: Tensor) -> Tensor:
-        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
-        return torch.ops.orcai.spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, self.freq_hi, self.q_lo, self.q_hi)
+    @property
+    def _args(self) -> tuple:
+        return (self.freq_hi,)
 
     def extra_repr(self) -> str:
-        return f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, freq_hi={self.freq_hi}"
+        return super().extra_repr() + f"freq_hi={self.freq_hi}"
 
 
-class MelWaveformFrontEnd(torch.nn.Module):
+class MelWaveformFrontEnd(_WaveformFrontEnd):
     """WaveformFrontEnd for a spectrogram parameter whose ``mel`` key is set: forward(pcm f32[n] at native_rate) =
     mel_spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...) -> [T, n_mels], differentiable down to those samples.  The parameter is
     validated as mel.mel_config does (ValueError names the key, NotImplementedError an nfft the mel route does not take)."""
 
-    def __init__(self, spectrogram_parameter: dict, native_rate: int):
-        super().__init__()
+    _op = "mel_spectrogram_wrt_pcm"
+
+    def _route(self, sp: dict) -> None:
         from orcai_amd import mel
 
-        sp = spectrogram_parameter
         _no_pcen(sp, "MelWaveformFrontEnd")
         cfg = mel.mel_config(sp)
         if cfg is None:
             raise ValueError("MelWaveformFrontEnd: spectrogram parameter mel is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
                              "native_rate) returns WaveformFrontEnd for it")
-        self.native_rate = int(native_rate)
-        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
         self.n_mels, self.fmin, self.fmax, self.htk, self.slaney_norm = cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney"
-        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
-        _check_rates(self.native_rate, self.sampling_rate, "MelWaveformFrontEnd")
 
-    def forward(self, pcm: Tensor) -> Tensor:
-        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
-        return torch.ops.orcai.mel_spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, self.n_mels, self.fmin, self.fmax, self.htk,
-                                                       self.slaney_norm, self.q_lo, self.q_hi)
+    @property
+    def _args(self) -> tuple:
+        return (self.n_mels, self.fmin, self.fmax, self.htk, self.slaney_norm)
 
     def extra_repr(self) -> str:
-        return (f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, n_mels={self.n_mels}, fmin={self.fmin}, "
-                f"fmax={self.fmax}, htk={self.htk}, slaney_norm={self.slaney_norm}")
+        return super().extra_repr() + f"n_mels={self.n_mels}, fmin={self.fmin}, fmax={self.fmax}, htk={self.htk}, slaney_norm={self.slaney_norm}"
 
 
-class PcenWaveformFrontEnd(torch.nn.Module):
+class PcenWaveformFrontEnd(_WaveformFrontEnd):
     """WaveformFrontEnd for a spectrogram parameter whose ``pcen`` key is set, on either route (the mel one when ``mel`` is set as well):
     forward(pcm f32[n] at native_rate) = pcen_spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...) -> [T, K], differentiable down to those
     samples.  The parameter is validated as pcen.pcen_config and mel.mel_config do; p_lo and p_hi are held constant in the backward."""
 
-    def __init__(self, spectrogram_parameter: dict, native_rate: int):
-        super().__init__()
+    _op = "pcen_spectrogram_wrt_pcm"
+
+    def _route(self, sp: dict) -> None:
         from orcai_amd import mel, pcen
 
-        sp = spectrogram_parameter
         pc = pcen.pcen_config(sp)
         if pc is None:
             raise ValueError("PcenWaveformFrontEnd: spectrogram parameter pcen is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
@@ -946,23 +832,19 @@ class PcenWaveformFrontEnd(torch.nn.Module):
         cfg = mel.mel_config(sp)
         if cfg is None and float(sp["freq_range"][0]) != 0.0:
             raise ValueError(f"PcenWaveformFrontEnd: freq_range must start at 0 (orcai::pcen_spectrogram keeps the leading bins), got {sp['freq_range']}")
-        self.native_rate = int(native_rate)
-        self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
         if cfg is None:
             self.route = (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
         else:
             self.route = (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
         self.pcen = tuple(pc[k] for k in pcen.PCEN_KEYS)  # time_constant, gain, bias, power, eps, scale: the op's order
-        self.q_lo, self.q_hi = (float(q) for q in sp["quantiles"])
-        _check_rates(self.native_rate, self.sampling_rate, "PcenWaveformFrontEnd")
 
-    def forward(self, pcm: Tensor) -> Tensor:
-        at_rate = torch.ops.orcai.resample(pcm, self.native_rate, self.sampling_rate)
-        return torch.ops.orcai.pcen_spectrogram_wrt_pcm(at_rate, self.sampling_rate, self.nfft, self.hop, *self.route, *self.pcen, self.q_lo, self.q_hi)
+    @property
+    def _args(self) -> tuple:
+        return (*self.route, *self.pcen)
 
     def extra_repr(self) -> str:
         freq_hi, n_mels = self.route[:2]
-        return (f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, " + (f"n_mels={n_mels}" if n_mels else f"freq_hi={freq_hi}")
+        return (super().extra_repr() + (f"n_mels={n_mels}" if n_mels else f"freq_hi={freq_hi}")
                 + f", time_constant={self.pcen[0]}, gain={self.pcen[1]}, bias={self.pcen[2]}, power={self.pcen[3]}, eps={self.pcen[4]}, scale={self.pcen[5]}")
 
 

@@ -1,6 +1,6 @@
 """Times the gradient of the PCEN front end on the 1 h 48 kHz synthetic recording at nfft 512 / hop 256 on cuda:0, in one process:
 
-  whole   FrontEnd.pcen_spectrogram_backward on the linear route (K = 171) and on mel-64, beside spectrogram_backward / mel_spectrogram_backward (dB)
+  whole   FrontEnd.backward with pcen set on the linear route (K = 171) and on mel-64, beside the two dB routes
   stages  orcai_pcen_bwd's six launches on their own (orcai_pcen_bwd_stage_ms) on [T, 171] and [T, 64]
   steps   the three calls orcai_pcen_spectrogram_bwd is made of, one by one, on both routes
   parent  with --parent-lib (a liborcai_hip.so built from the parent commit, loaded beside this tree's): orcai_spectrogram_bwd and
@@ -65,9 +65,8 @@ def main() -> None:
         spec, stats = fe.make_spectrogram(pcm, sp, return_stats=True)
         g = torch.randn(spec.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
         del spec
-        method = fe.pcen_spectrogram_backward if "pcen" in extra else (fe.mel_spectrogram_backward if "mel" in extra else fe.spectrogram_backward)
         keep[name] = (sp, g, stats)
-        whole[name] = lambda method=method, sp=sp, g=g, stats=stats: method(pcm, g, stats, sp)
+        whole[name] = lambda sp=sp, g=g, stats=stats: fe.backward(pcm, g, stats, sp)
         result["routes"][name] = {"width": g.shape[1], "parameter": extra}
     times = {name: [] for name in whole}
     for r in rounds:
