@@ -1074,12 +1074,99 @@ void init_tables() {
   g_tables_err = (int)e;
 }
 
-inline int grid_for(int64_t items_per_block_unit, int64_t n_units) {
-  (void)items_per_block_unit;
+inline int grid_for(int64_t n_units) {
   int64_t g = n_units;
   if (g > 256 * 8) g = 256 * 8;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+inline int ilog2(int n_fft) {  // of a power of two
+  int log2n = 0;
+  while ((1 << log2n) < n_fft) ++log2n;
+  return log2n;
+}
+
+// One workgroup per frame (per group of 16 frames for the 512-point kernels), at most `cap`: the kernels stride over the rest.
+inline dim3 frames_grid(int64_t n_frames, int64_t cap) { return dim3((unsigned)(n_frames < cap ? n_frames : cap)); }
+
+// The band table is HOST memory: checked here, handed to the kernels by value.  Bands of equal parity may overlap (only the backward minds).
+int pack_mel_bands(const int* band_lo, const int* band_hi, const int* band_off, int n_mels, int n_fft, int n_weights, MelBands& bands) {
+  std::memset(&bands, 0, sizeof(bands));
+  const int n_bins = 1 + n_fft / 2;
+  for (int m = 0; m < n_mels; ++m) {
+    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
+    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
+    bands.lo[m] = (uint16_t)lo;
+    bands.n[m] = (uint16_t)(hi - lo);
+    bands.off[m] = (uint16_t)off;
+  }
+  return 0;
+}
+
+// The interior groups [g_lo, g_hi) of a 512-point launch, the only ones the FAST_ONLY kernel may run (it reads pcm without bounds checks, 16 bytes
+// at a time): all 16 frames of the group exist and the samples of every wave lie inside the recording, 16-byte aligned (hop 256 only) --
+// t0w >= 1 for the first wave of the group, so g >= 1; (16g + 12) * 256 + 1024 <= n_samples and 16g + 15 < n_frames for the last.
+// g_lo == g_hi == n_groups when there are none; g_lo == 1 when there are.
+void stft_interior_groups(int64_t n_samples, int hop, int64_t n_frames, int64_t n_groups, int64_t& g_lo, int64_t& g_hi) {
+  g_lo = g_hi = n_groups;
+  if (hop != 256) return;
+  g_lo = 1;
+  const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;  // groups g with (16g+12)*256+1024 <= n_samples
+  const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;                       // groups g with 16g + 15 < n_frames
+  g_hi = by_samples < by_frames ? by_samples : by_frames;
+  if (g_hi > n_groups) g_hi = n_groups;
+  if (g_hi < g_lo) g_lo = g_hi = n_groups;  // no interior: everything goes through the mixed kernel
+}
+
+// The launches of a tuned 512-point kernel over the groups of 16 frames: an odd hop is one launch of the <false, false> instantiation; an even hop
+// with an interior is the fast kernel on it, then the mixed <true, false> one on the leading and on the trailing edge; without one, the mixed kernel
+// on everything.  launch(variant, grid, g_begin, g_end) names the entry's kernels and arguments.  Called after every argument refusal.
+enum class Stft512 { ANY_HOP, FAST, MIXED };  // <EVEN_HOP, FAST_ONLY> = <false, false>, <true, true>, <true, false>
+
+template <class Launch>
+int launch_stft512(int64_t n_samples, int hop, int64_t n_frames, Launch&& launch) {
+  std::call_once(g_tables_once, init_tables);  // no-op: orcai_frontend_workspace_bytes() already ran it (kept for callers that size the workspace themselves)
+  if (g_tables_err) return g_tables_err;
+  const int64_t n_groups = (n_frames + 15) / 16;
+  const auto run = [&](Stft512 variant, int64_t g_begin, int64_t g_end) { launch(variant, frames_grid(g_end - g_begin, STFT_BLOCKS), g_begin, g_end); };
+  int64_t g_lo, g_hi;
+  stft_interior_groups(n_samples, hop, n_frames, n_groups, g_lo, g_hi);
+  if ((hop & 1) != 0) {
+    run(Stft512::ANY_HOP, 0, n_groups);
+  } else if (g_hi > g_lo) {
+    run(Stft512::FAST, g_lo, g_hi);
+    run(Stft512::MIXED, 0, g_lo);  // never empty: g_lo == 1
+    if (g_hi < n_groups) run(Stft512::MIXED, g_hi, n_groups);
+  } else {
+    run(Stft512::MIXED, 0, n_groups);
+  }
+  return (int)hipGetLastError();
+}
+
+// The launch geometry of the four backward kernels.  Run of output samples per group: 2048 for the wave-per-run kernel (LDS 2 KiB twiddles +
+// 4 x (4 + 8) KiB at 512: three workgroups per compute unit), 4 n_fft for the workgroup-per-run kernel, n_fft at 4096 (twiddles + frame +
+// accumulator = 64 KiB, the most a launch gets without opting in).  n_mels = 0: the linear routes; otherwise the mel gather's LDS comes on top.
+struct BwdPlan {
+  bool wave;   // n_fft <= 512: the <64> instantiation, a wave per run and four runs per workgroup; else <256>, a workgroup per run
+  int run;     // output samples per run
+  int groups;  // runs per workgroup
+  size_t lds;  // dynamic LDS bytes of the launch
+  int64_t n_runs(int64_t n_samples) const { return (n_samples + run - 1) / run; }
+  dim3 grid(int64_t n_samples) const {
+    const int64_t blocks = (n_runs(n_samples) + groups - 1) / groups;
+    return dim3((unsigned)(blocks < 256 * 12 ? blocks : 256 * 12));
+  }
+};
+
+BwdPlan bwd_plan(int n_fft, int n_mels) {
+  BwdPlan p;
+  p.wave = n_fft <= 512;
+  p.run = p.wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
+  p.groups = p.wave ? 4 : 1;
+  p.lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)p.groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)p.run) +
+          (n_mels ? mel_bwd_lds_bytes(p.groups, n_fft, n_mels) : 0);
+  return p;
 }
 
 // The launchers behind orcai_spectrogram_bwd (ENERGY = false) and orcai_stft_energy_bwd (ENERGY = true: stats_dev and top_db are not looked at).
@@ -1089,29 +1176,21 @@ int spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int h
   if (!pcm || !gout || (!ENERGY && !stats_dev) || !dpcm || n_samples <= 0 || hop <= 0 || n_frames <= 0 || k_crop < 1 || n_fft < 2) return ORCAI_E_BADARG;
   if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // powers of two from 32 to 4096 only
   if (k_crop > 1 + n_fft / 2 || n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;         // librosa's centred frame count (n_fft is even)
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) ++log2n;
-  // Run of output samples per group: 2048 for the wave-per-run kernel (LDS 2 KiB twiddles + 4 x (4 + 8) KiB at 512: three workgroups per compute unit),
-  // 4 n_fft for the workgroup-per-run kernel, n_fft at 4096 (twiddles + frame + accumulator = 64 KiB, the most a launch gets without opting in).
-  const bool wave = n_fft <= 512;
-  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
-  const int groups = wave ? 4 : 1;
-  const int64_t n_runs = (n_samples + run - 1) / run;
-  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run);
-  if (lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: 64 KiB at n_fft = 4096 is the largest request)
-  int64_t blocks = (n_runs + groups - 1) / groups;
-  if (blocks > 256 * 12) blocks = 256 * 12;
-  const dim3 grid((unsigned)blocks);
+  const BwdPlan p = bwd_plan(n_fft, 0);
+  if (p.lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: 64 KiB at n_fft = 4096 is the largest request)
+  const dim3 grid = p.grid(n_samples);
+  const int64_t n_runs = p.n_runs(n_samples);
+  const int log2n = ilog2(n_fft);
   hipStream_t st = (hipStream_t)stream;
   if constexpr (ENERGY) {
-    if (wave) hipLaunchKernelGGL((stft_energy_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, run, n_runs);
-    else hipLaunchKernelGGL((stft_energy_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, run, n_runs);
+    if (p.wave) hipLaunchKernelGGL((stft_energy_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, p.run, n_runs);
+    else hipLaunchKernelGGL((stft_energy_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, p.run, n_runs);
   } else {
-    if (wave)
-      hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, run,
+    if (p.wave)
+      hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, p.run,
                          n_runs);
     else
-      hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, run,
+      hipLaunchKernelGGL((spectrogram_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, p.run,
                          n_runs);
   }
   return (int)hipGetLastError();
@@ -1128,15 +1207,7 @@ int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, i
   if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
   if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
   MelBands bands;
-  std::memset(&bands, 0, sizeof(bands));
-  const int n_bins = 1 + n_fft / 2;
-  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernel by value
-    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
-    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
-    bands.lo[m] = (uint16_t)lo;
-    bands.n[m] = (uint16_t)(hi - lo);
-    bands.off[m] = (uint16_t)off;
-  }
+  if (const int e = pack_mel_bands(band_lo, band_hi, band_off, n_mels, n_fft, n_weights, bands)) return e;
   // The per-bin gather has one even-band and one odd-band entry: bands of equal parity must not share a bin.  Checked against the running end of the
   // non-empty bands of each parity, so an empty band between two overlapping ones hides nothing.
   int end[2] = {0, 0};
@@ -1145,41 +1216,34 @@ int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, i
     if (band_lo[m] < end[m & 1]) return ORCAI_E_UNSUPPORTED;
     end[m & 1] = band_hi[m];
   }
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) ++log2n;
-  const bool wave = n_fft <= 512;  // runs and groups as orcai_spectrogram_bwd
-  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
-  const int groups = wave ? 4 : 1;
-  const int64_t n_runs = (n_samples + run - 1) / run;
-  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
-                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
+  const BwdPlan p = bwd_plan(n_fft, n_mels);
   constexpr size_t LDS_MAX = 64 * 1024 + mel_bwd_lds_bytes(1, NFFT_ANY_MAX, MEL_MAX);  // the request at n_fft = 4096 with 256 bands: 80 408 B, two per compute unit
-  if (lds > LDS_MAX) return ORCAI_E_UNSUPPORTED;  // (never)
-  if (wave && lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: the wave-per-run kernel asks for at most 58 392 B and does not opt in)
-  if (lds > 64 * 1024) {  // n_fft = 4096, and 2048 with more than 202 bands
+  if (p.lds > LDS_MAX) return ORCAI_E_UNSUPPORTED;  // (never)
+  if (p.wave && p.lds > 64 * 1024) return ORCAI_E_UNSUPPORTED;  // (never: the wave-per-run kernel asks for at most 58 392 B and does not opt in)
+  if (p.lds > 64 * 1024) {  // n_fft = 4096, and 2048 with more than 202 bands
     hipError_t e;
     if constexpr (ENERGY) e = orcai_lds::ensure_dynamic_lds<stft_mel_energy_bwd_kernel<256>>(LDS_MAX);
     else e = orcai_lds::ensure_dynamic_lds<mel_spectrogram_bwd_kernel<256>>(LDS_MAX);
     if (e != hipSuccess) return (int)e;
   }
-  int64_t blocks = (n_runs + groups - 1) / groups;
-  if (blocks > 256 * 12) blocks = 256 * 12;
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid = p.grid(n_samples);
+  const int64_t n_runs = p.n_runs(n_samples);
+  const int log2n = ilog2(n_fft);
   hipStream_t st = (hipStream_t)stream;
   if constexpr (ENERGY) {
-    if (wave)
-      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, run, n_runs, bands,
+    if (p.wave)
+      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, p.run, n_runs, bands,
                          weights);
     else
-      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, run, n_runs, bands,
+      hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, p.run, n_runs, bands,
                          weights);
   } else {
-    if (wave)
-      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm, run,
-                         n_runs, bands, weights);
+    if (p.wave)
+      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm,
+                         p.run, n_runs, bands, weights);
     else
-      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<256>), grid, dim3(256), lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm, run,
-                         n_runs, bands, weights);
+      hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm,
+                         p.run, n_runs, bands, weights);
   }
   return (int)hipGetLastError();
 }
@@ -1206,64 +1270,28 @@ int orcai_stft_db(const float* pcm, int64_t n_samples, int n_fft, int hop, int64
   if (!pcm || !out_db || !workspace || n_samples <= 0 || hop <= 0 || k_crop < 1 || n_fft < 2 || k_crop > 1 + n_fft / 2) return ORCAI_E_BADARG;
   if (n_frames != 1 + (n_samples - (n_fft & 1)) / hop) return ORCAI_E_BADARG;  // librosa, center = True: 1 + (n + 2 (n_fft / 2) - n_fft) / hop
   if (((uintptr_t)out_db & 15) || ((uintptr_t)pcm & 15)) return ORCAI_E_BADARG;
+  Workspace* ws = (Workspace*)workspace;
+  hipStream_t st = (hipStream_t)stream;
   if (n_fft != NFFT) {  // any other size up to 4096: the plain radix-2 kernel (powers of two from 32) or the direct transform, + a separate level-1 histogram pass
     if (n_fft > NFFT_ANY_MAX) return ORCAI_E_UNSUPPORTED;
     if (n_fft < 32 || (n_fft & (n_fft - 1))) {  // not a power of two (or a tiny one): the direct transform
       const size_t lds = sizeof(double) * ((size_t)n_fft + (n_fft & 1) + 2 * (size_t)n_fft);
       if (lds > 48 * 1024)
         if (const hipError_t e = orcai_lds::ensure_dynamic_lds<stft_dft_kernel>(3 * NFFT_ANY_MAX * sizeof(double)); e != hipSuccess) return (int)e;
-      const int64_t blocks = n_frames < 256 * 4 ? n_frames : 256 * 4;
-      hipLaunchKernelGGL(stft_dft_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, pcm, n_samples, n_fft, hop, n_frames, k_crop, out_db, (Workspace*)workspace);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return (int)e;
-      return orcai_hist_level1(out_db, n_frames * (int64_t)k_crop, workspace, stream);
+      hipLaunchKernelGGL(stft_dft_kernel, frames_grid(n_frames, 256 * 4), dim3(256), lds, st, pcm, n_samples, n_fft, hop, n_frames, k_crop, out_db, ws);
+    } else {
+      hipLaunchKernelGGL(stft_any_kernel, frames_grid(n_frames, 256 * 16), dim3(256), 0, st, pcm, n_samples, n_fft, ilog2(n_fft), hop, n_frames, k_crop, out_db, ws);
     }
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
-    hipLaunchKernelGGL(stft_any_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, out_db,
-                       (Workspace*)workspace);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     return orcai_hist_level1(out_db, n_frames * (int64_t)k_crop, workspace, stream);
   }
-  std::call_once(g_tables_once, init_tables);  // no-op: orcai_frontend_workspace_bytes() already ran it (kept for callers that size the workspace themselves)
-  if (g_tables_err) return g_tables_err;
-  const int64_t n_groups = (n_frames + 15) / 16;
-  Workspace* ws = (Workspace*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
-  if ((hop & 1) != 0) {
-    hipLaunchKernelGGL((stft_db_kernel<false, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws,
-                       (int64_t)0, n_groups);
-    return (int)hipGetLastError();
-  }
-  // Interior groups [g_lo, g_hi): all 16 frames exist and the samples of every wave lie inside the recording, 16-byte aligned
-  // (hop 256): t0w >= 1 for the first wave of the group, (16g + 12) * 256 + 1024 <= n_samples and 16g + 15 < n_frames for the last.
-  int64_t g_lo = n_groups, g_hi = n_groups;
-  if (hop == 256) {
-    g_lo = 1;
-    const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;  // groups g with (16g+12)*256+1024 <= n_samples
-    const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;                       // groups g with 16g + 15 < n_frames
-    g_hi = by_samples < by_frames ? by_samples : by_frames;
-    if (g_hi > n_groups) g_hi = n_groups;
-    if (g_hi < g_lo) g_lo = g_hi = n_groups;  // no interior: everything goes through the mixed kernel
-  }
-  if (g_hi > g_lo) {
-    if (k_crop == 171)
-      hipLaunchKernelGGL((stft_db_kernel<true, true, 171>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, g_lo, g_hi);
-    else
-      hipLaunchKernelGGL((stft_db_kernel<true, true, 0>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, g_lo, g_hi);
-    if (g_lo > 0)
-      hipLaunchKernelGGL((stft_db_kernel<true, false, 0>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, (int64_t)0, g_lo);
-    if (g_hi < n_groups)
-      hipLaunchKernelGGL((stft_db_kernel<true, false, 0>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, g_hi,
-                         n_groups);
-  } else {
-    hipLaunchKernelGGL((stft_db_kernel<true, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, (int64_t)0,
-                       n_groups);
-  }
-  return (int)hipGetLastError();
+  return launch_stft512(n_samples, hop, n_frames, [&](Stft512 variant, dim3 grid, int64_t g_begin, int64_t g_end) {
+    const auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out_db, ws, g_begin, g_end); };
+    if (variant == Stft512::ANY_HOP) go(stft_db_kernel<false, false, 0>);
+    else if (variant == Stft512::MIXED) go(stft_db_kernel<true, false, 0>);
+    else if (k_crop == 171) go(stft_db_kernel<true, true, 171>);
+    else go(stft_db_kernel<true, true, 0>);
+  });
 }
 
 int orcai_stft_occupancy(void) {  // workgroups of stft_db_kernel<true, true, 171> the runtime says fit one compute unit (LDS: 52 KiB each)
@@ -1280,75 +1308,29 @@ int orcai_stft_mel_db(const float* pcm, int64_t n_samples, int n_fft, int hop, i
   if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
   if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
   MelBands bands;
-  std::memset(&bands, 0, sizeof(bands));
-  const int n_bins = 1 + n_fft / 2;
-  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernels by value
-    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
-    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
-    bands.lo[m] = (uint16_t)lo;
-    bands.n[m] = (uint16_t)(hi - lo);
-    bands.off[m] = (uint16_t)off;
-  }
+  if (const int e = pack_mel_bands(band_lo, band_hi, band_off, n_mels, n_fft, n_weights, bands)) return e;
   Workspace* ws = (Workspace*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (n_fft != NFFT || n_weights > MEL_W_LDS) {  // (512 with a table wider than the tuned kernel's LDS copy -- no triangular one is -- runs here too)
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
-    hipLaunchKernelGGL(stft_mel_any_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out_db, ws, bands, weights);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(stft_mel_any_kernel, frames_grid(n_frames, 256 * 16), dim3(256), 0, st, pcm, n_samples, n_fft, ilog2(n_fft), hop, n_frames, n_mels, out_db, ws,
+                       bands, weights);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     return orcai_hist_level1(out_db, n_frames * (int64_t)n_mels, workspace, stream);
   }
-  std::call_once(g_tables_once, init_tables);
-  if (g_tables_err) return g_tables_err;
-  const int64_t n_groups = (n_frames + 15) / 16;
-  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
-  if ((hop & 1) != 0) {
-    hipLaunchKernelGGL((stft_mel_kernel<false, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0,
-                       n_groups, bands, weights, n_weights);
-    return (int)hipGetLastError();
-  }
-  int64_t g_lo = n_groups, g_hi = n_groups;  // the interior groups, by orcai_stft_db's rule
-  if (hop == 256) {
-    g_lo = 1;
-    const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;
-    const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;
-    g_hi = by_samples < by_frames ? by_samples : by_frames;
-    if (g_hi > n_groups) g_hi = n_groups;
-    if (g_hi < g_lo) g_lo = g_hi = n_groups;
-  }
-  if (g_hi > g_lo) {
-    hipLaunchKernelGGL((stft_mel_kernel<true, true>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, g_lo, g_hi, bands,
-                       weights, n_weights);
-    hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0, g_lo, bands,
-                       weights, n_weights);
-    if (g_hi < n_groups)
-      hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, g_hi,
-                         n_groups, bands, weights, n_weights);
-  } else {
-    hipLaunchKernelGGL((stft_mel_kernel<true, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, (int64_t)0, n_groups,
-                       bands, weights, n_weights);
-  }
-  return (int)hipGetLastError();
+  return launch_stft512(n_samples, hop, n_frames, [&](Stft512 variant, dim3 grid, int64_t g_begin, int64_t g_end) {
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out_db, ws, g_begin, g_end, bands, weights, n_weights);
+    };
+    if (variant == Stft512::ANY_HOP) go(stft_mel_kernel<false, false>);
+    else if (variant == Stft512::MIXED) go(stft_mel_kernel<true, false>);
+    else go(stft_mel_kernel<true, true>);
+  });
 }
 
 int orcai_stft_mel_occupancy(void) {  // workgroups of stft_mel_kernel<true, true> the runtime says fit one compute unit
   int n = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)stft_mel_kernel<true, true>, 256, 0) != hipSuccess) return -1;
   return n;
-}
-
-// The interior groups [g_lo, g_hi) of a 512-point launch at hop 256, by orcai_stft_db's rule; g_lo == g_hi == n_groups when there are none.
-static void stft_interior_groups(int64_t n_samples, int hop, int64_t n_frames, int64_t n_groups, int64_t& g_lo, int64_t& g_hi) {
-  g_lo = g_hi = n_groups;
-  if (hop != 256) return;
-  g_lo = 1;
-  const int64_t by_samples = n_samples >= 4096 ? ((n_samples - 1024) / 256 - 12) / 16 + 1 : 0;
-  const int64_t by_frames = n_frames >= 16 ? (n_frames - 16) / 16 + 1 : 0;
-  g_hi = by_samples < by_frames ? by_samples : by_frames;
-  if (g_hi > n_groups) g_hi = n_groups;
-  if (g_hi < g_lo) g_lo = g_hi = n_groups;
 }
 
 int orcai_stft_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, float* out, void* stream) {
@@ -1358,34 +1340,16 @@ int orcai_stft_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, i
   if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;  // librosa's centred frame count (n_fft is even)
   hipStream_t st = (hipStream_t)stream;
   if (n_fft != NFFT) {
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
-    hipLaunchKernelGGL(stft_any_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, out);
+    hipLaunchKernelGGL(stft_any_energy_kernel, frames_grid(n_frames, 256 * 16), dim3(256), 0, st, pcm, n_samples, n_fft, ilog2(n_fft), hop, n_frames, k_crop, out);
     return (int)hipGetLastError();
   }
-  std::call_once(g_tables_once, init_tables);
-  if (g_tables_err) return g_tables_err;
-  const int64_t n_groups = (n_frames + 15) / 16;
-  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
-  if ((hop & 1) != 0) {
-    hipLaunchKernelGGL((stft_energy_kernel<false, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, n_groups);
-    return (int)hipGetLastError();
-  }
-  int64_t g_lo, g_hi;
-  stft_interior_groups(n_samples, hop, n_frames, n_groups, g_lo, g_hi);
-  if (g_hi > g_lo) {
-    if (k_crop == 171)
-      hipLaunchKernelGGL((stft_energy_kernel<true, true, 171>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_lo, g_hi);
-    else
-      hipLaunchKernelGGL((stft_energy_kernel<true, true, 0>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_lo, g_hi);
-    hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, g_lo);
-    if (g_hi < n_groups)
-      hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_hi, n_groups);
-  } else {
-    hipLaunchKernelGGL((stft_energy_kernel<true, false, 0>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, (int64_t)0, n_groups);
-  }
-  return (int)hipGetLastError();
+  return launch_stft512(n_samples, hop, n_frames, [&](Stft512 variant, dim3 grid, int64_t g_begin, int64_t g_end) {
+    const auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, pcm, n_samples, hop, n_frames, k_crop, out, g_begin, g_end); };
+    if (variant == Stft512::ANY_HOP) go(stft_energy_kernel<false, false, 0>);
+    else if (variant == Stft512::MIXED) go(stft_energy_kernel<true, false, 0>);
+    else if (k_crop == 171) go(stft_energy_kernel<true, true, 171>);
+    else go(stft_energy_kernel<true, true, 0>);
+  });
 }
 
 int orcai_stft_mel_energy(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
@@ -1396,52 +1360,26 @@ int orcai_stft_mel_energy(const float* pcm, int64_t n_samples, int n_fft, int ho
   if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
   if (n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;
   MelBands bands;
-  std::memset(&bands, 0, sizeof(bands));
-  const int n_bins = 1 + n_fft / 2;
-  for (int m = 0; m < n_mels; ++m) {  // the table is HOST memory: checked here, handed to the kernels by value
-    const int lo = band_lo[m], hi = band_hi[m], off = band_off[m];
-    if (lo < 0 || hi < lo || hi > n_bins || off < 0 || off > n_weights - (hi - lo)) return ORCAI_E_BADARG;
-    bands.lo[m] = (uint16_t)lo;
-    bands.n[m] = (uint16_t)(hi - lo);
-    bands.off[m] = (uint16_t)off;
-  }
+  if (const int e = pack_mel_bands(band_lo, band_hi, band_off, n_mels, n_fft, n_weights, bands)) return e;
   hipStream_t st = (hipStream_t)stream;
   if (n_fft != NFFT || n_weights > MEL_W_LDS) {
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    const int64_t blocks = n_frames < 256 * 16 ? n_frames : 256 * 16;
-    hipLaunchKernelGGL(stft_mel_any_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, out, bands, weights);
+    hipLaunchKernelGGL(stft_mel_any_energy_kernel, frames_grid(n_frames, 256 * 16), dim3(256), 0, st, pcm, n_samples, n_fft, ilog2(n_fft), hop, n_frames, n_mels, out, bands,
+                       weights);
     return (int)hipGetLastError();
   }
-  std::call_once(g_tables_once, init_tables);
-  if (g_tables_err) return g_tables_err;
-  const int64_t n_groups = (n_frames + 15) / 16;
-  auto grid_for_groups = [](int64_t n) { return dim3((unsigned)(n < STFT_BLOCKS ? n : STFT_BLOCKS)); };
-  if ((hop & 1) != 0) {
-    hipLaunchKernelGGL((stft_mel_energy_kernel<false, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, n_groups,
-                       bands, weights, n_weights);
-    return (int)hipGetLastError();
-  }
-  int64_t g_lo, g_hi;
-  stft_interior_groups(n_samples, hop, n_frames, n_groups, g_lo, g_hi);
-  if (g_hi > g_lo) {
-    hipLaunchKernelGGL((stft_mel_energy_kernel<true, true>), grid_for_groups(g_hi - g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, g_lo, g_hi, bands,
-                       weights, n_weights);
-    hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(g_lo), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, g_lo, bands,
-                       weights, n_weights);
-    if (g_hi < n_groups)
-      hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(n_groups - g_hi), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, g_hi, n_groups,
-                         bands, weights, n_weights);
-  } else {
-    hipLaunchKernelGGL((stft_mel_energy_kernel<true, false>), grid_for_groups(n_groups), dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, (int64_t)0, n_groups,
-                       bands, weights, n_weights);
-  }
-  return (int)hipGetLastError();
+  return launch_stft512(n_samples, hop, n_frames, [&](Stft512 variant, dim3 grid, int64_t g_begin, int64_t g_end) {
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, pcm, n_samples, hop, n_frames, n_mels, out, g_begin, g_end, bands, weights, n_weights);
+    };
+    if (variant == Stft512::ANY_HOP) go(stft_mel_energy_kernel<false, false>);
+    else if (variant == Stft512::MIXED) go(stft_mel_energy_kernel<true, false>);
+    else go(stft_mel_energy_kernel<true, true>);
+  });
 }
 
 int orcai_hist_level1(const float* x, int64_t n, void* workspace, void* stream) {
   if (!x || !workspace || n <= 0 || ((uintptr_t)x & 15)) return ORCAI_E_BADARG;
-  int grid = grid_for(0, (n / 4 + 255) / 256);
+  int grid = grid_for((n / 4 + 255) / 256);
   hipLaunchKernelGGL(hist1_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (Workspace*)workspace);
   return (int)hipGetLastError();
 }
@@ -1452,7 +1390,7 @@ int orcai_quantile_select(const float* x, int64_t n, int64_t rank_lo, int64_t ra
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(select_scan1_kernel, dim3(1), dim3(1024), 0, s, ws, rank_lo, rank_hi);
   if ((uintptr_t)x & 15) return ORCAI_E_BADARG;
-  int grid = grid_for(0, (n / 4 + 255) / 256);
+  int grid = grid_for((n / 4 + 255) / 256);
   for (int round = 0; round < 2; ++round) {  // a level-1 bucket is at most 2^31 keys wide: two 16-bit rounds
     hipError_t e = orcai_zero::zero_async(ws->hist2, sizeof(ws->hist2) + sizeof(ws->hist2c), s);  // hist2c follows hist2
     if (e != hipSuccess) return (int)e;
@@ -1471,14 +1409,14 @@ int orcai_frontend_finalize(int use_ref, float top_db, void* workspace, void* st
 
 int orcai_clip_normalize(float* x, int64_t n, const void* workspace, void* stream) {
   if (!x || !workspace || n <= 0 || ((uintptr_t)x & 15)) return ORCAI_E_BADARG;
-  int grid = grid_for(0, (n / 4 + 255) / 256);
+  int grid = grid_for((n / 4 + 255) / 256);
   hipLaunchKernelGGL(clip_normalize_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (const Workspace*)workspace);
   return (int)hipGetLastError();
 }
 
 int orcai_db_reference(float* x, int64_t n, const void* workspace, void* stream) {
   if (!x || !workspace || n <= 0) return ORCAI_E_BADARG;
-  int grid = grid_for(0, (n + 255) / 256);
+  int grid = grid_for((n + 255) / 256);
   hipLaunchKernelGGL(db_reference_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (const Workspace*)workspace);
   return (int)hipGetLastError();
 }
@@ -1539,14 +1477,10 @@ int orcai_stft_mel_energy_bwd(const float* pcm, int64_t n_samples, int n_fft, in
 
 int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels) {  // workgroups of the mel backward the runtime says fit one compute unit; -1 on refusal
   if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1)) || n_mels < 8 || n_mels > MEL_MAX) return -1;
-  const bool wave = n_fft <= 512;
-  const int run = wave ? 2048 : (n_fft == 4096 ? 4096 : 4 * n_fft);
-  const int groups = wave ? 4 : 1;
-  const size_t lds = sizeof(float2) * (size_t)(n_fft / 2) + (size_t)groups * (sizeof(float2) * (size_t)n_fft + sizeof(float) * (size_t)run) +
-                     mel_bwd_lds_bytes(groups, n_fft, n_mels);
+  const BwdPlan p = bwd_plan(n_fft, n_mels);
   int n = -1;
-  const hipError_t e = wave ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<64>, 256, lds)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<256>, 256, lds);
+  const hipError_t e = p.wave ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<64>, 256, p.lds)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<256>, 256, p.lds);
   return e == hipSuccess ? n : -1;
 }
 
