@@ -117,6 +117,17 @@ int orcai_hist_level1(const float* x, int64_t n, void* workspace, void* stream);
  * the workspace.  Results stay in the workspace (see orcai_frontend_stats_host). */
 int orcai_quantile_select(const float* x, int64_t n, int64_t rank_lo, int64_t rank_hi, void* workspace, void* stream);
 
+/* The same exact order statistics by a radix select on the monotone key, for values that are not dB: three passes over x (key bits [31:21],
+ * [20:10], [9:0]), each a histogram in LDS whose non-zero bins are added to the workspace, and a one-workgroup scan after each.  The cost is
+ * three reads of x wherever the values lie; orcai_quantile_select's depends on its level-1 map, cut for 0.125 <= |x| < 128.  The order is the
+ * key's: -0.0 before +0.0, +-inf and subnormals ordinary values.  Needs NO orcai_hist_level1 and no orcai_frontend_reset before it: it clears
+ * what it uses (the start of the level-2 histogram area) and leaves the level-1 histogram and pmax alone.  On return the workspace holds exactly
+ * what orcai_quantile_select leaves, so orcai_frontend_finalize, orcai_clip_normalize and the statistics calls run unchanged behind it.
+ * Asynchronous on stream, no allocation, hipGraph-capturable.  ORCAI_E_BADARG, before anything is launched: null x or workspace, n <= 0 or
+ * n >= 2^32 (the bins are u32), a rank outside [0, n), x not 16-byte aligned.  rank_lo > rank_hi is allowed.  What orcai_make_pcen_spectrogram
+ * selects with. */
+int orcai_quantile_select_radix(const float* x, int64_t n, int64_t rank_lo, int64_t rank_hi, void* workspace, void* stream);
+
 /* Turn the selected raw order statistics into clip bounds.
  *   use_ref = 1: values are un-referenced dB from orcai_stft_db; ref_db = 10*log10(max(pmax,1e-10)),
  *                bound = max(selected - ref_db, -top_db)                    (spectrogram.py:51-53)
@@ -266,8 +277,8 @@ int orcai_pcen(float* x, int64_t n_frames, int k, float a, float b, float scale,
 int orcai_pcen_stage_ms(float* x, int64_t n_frames, int k, float a, float b, float scale, float gain, float bias, float power, float eps, void* scratch,
                         void* stream, float stage_ms[3]);
 
-/* One call = reset + stft_energy (band_lo null) or stft_mel_energy + pcen + hist_level1 + select + finalize(0) + clip_normalize: orcai_make_spectrogram
- * for a spectrogram parameter with "pcen" set.  k is k_crop or n_mels; the band arguments as for orcai_stft_mel_db, all ignored when band_lo is null.
+/* One call = reset + stft_energy (band_lo null) or stft_mel_energy + pcen + orcai_quantile_select_radix + finalize(0) + clip_normalize:
+ * orcai_make_spectrogram for a spectrogram parameter with "pcen" set (the same bytes as with hist_level1 + orcai_quantile_select: both are exact).  k is k_crop or n_mels; the band arguments as for orcai_stft_mel_db, all ignored when band_lo is null.
  * The percentile clip runs on the PCEN values: no dB reference, no top_db.  rank_lo / rank_hi as for orcai_quantile_select with n = n_frames * k;
  * out f32[n_frames * k] in [0, 1].  No host synchronisation; orcai_frontend_stats_dev behind it reports p_lo / p_hi as PCEN values (pmax and ref_db 0). */
 int orcai_make_pcen_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,

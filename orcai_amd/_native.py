@@ -37,6 +37,7 @@ _SIGNATURES = {
     "orcai_stft_occupancy": (C.c_int, []),
     "orcai_hist_level1": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_quantile_select": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "orcai_quantile_select_radix": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_frontend_finalize": (C.c_int, [C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "orcai_clip_normalize": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_db_reference": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),

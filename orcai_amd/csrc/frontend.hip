@@ -9,6 +9,8 @@
 //   scan1   select_scan1_kernel level-1 histogram -> key interval of each wanted rank
 //   pass C  hist2_kernel        re-read L, histogram the keys inside the two intervals (<= 2 rounds)
 //   scan2   select_scan2_kernel interval -> exact key
+//   (values that are not dB, the PCEN routes: radix_hist_kernel<1..3> / radix_scan_kernel<1..3> instead of the four steps above -- three reads
+//    of the array, one key digit each, whatever the values; orcai_quantile_select_radix)
 //   final   clip_normalize      in place: max(L - ref_db, -80) -> clip -> (v - lo)/(hi - lo)     (HBM: R L, W out)
 //   backward spectrogram_bwd     dL/dout -> dL/dpcm with ref_db / lo / hi held constant (orcai_spectrogram_bwd)   (HBM: R pcm, R g, W dpcm)
 //
@@ -860,6 +862,120 @@ __global__ __launch_bounds__(1024) void select_scan2_kernel(Workspace* __restric
   }
 }
 
+// ---------------------------------------------------------------- radix select (orcai_quantile_select_radix)
+// Three digit passes over the 32-bit key, most significant first: bits [31:21], [20:10], [9:0] (2048 / 2048 / 1024 bins).  Each pass reads x once,
+// histograms the digit of the elements whose higher digits equal the prefix found so far into LDS, and adds its non-zero bins to the global histogram
+// (integer sums: independent of launch order); a one-workgroup scan then turns the histogram into (digit, rank inside it) per rank.  Unlike the
+// level-1 map above, nothing here depends on where the values lie.  The global histograms live at the start of Workspace::hist2, in pass order:
+// [2048] shared by both ranks | [2][2048] | [2][1024]; one image serves both ranks of a later pass while their prefixes are equal.
+constexpr int RADIX_WORDS = 2048 + 2 * 2048 + 2 * 1024;
+__host__ __device__ constexpr int radix_shift(int pass) { return pass == 1 ? 21 : pass == 2 ? 10 : 0; }
+__host__ __device__ constexpr int radix_bins(int pass) { return pass == 3 ? 1024 : 2048; }
+__host__ __device__ constexpr int radix_offset(int pass) { return pass == 1 ? 0 : pass == 2 ? 2048 : 3 * 2048; }
+// Do keys a and b agree above the digit of `pass`?
+template <int PASS>
+__device__ __forceinline__ bool radix_same_prefix(uint32_t a, uint32_t b) {
+  if (PASS == 1) return true;
+  return ((a ^ b) >> (PASS == 2 ? 21 : 10)) == 0u;
+}
+
+// One element into one LDS image.  All 64 lanes of the wave call this together; hist2_add's shortcut: when every taking lane hits the same bin
+// (ties, constant input, PCEN's exact +0.0), one lane adds the population count instead of 64 atomics serialising on one address.
+__device__ __forceinline__ void radix_add(uint32_t* __restrict__ h, uint32_t bin, bool in, int lane) {
+  const unsigned long long mask = __ballot(in);
+  if (mask == 0ull) return;
+  const int first = __ffsll((long long)mask) - 1;
+  const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, first);
+  if (__ballot(in && bin != b0) == 0ull) {
+    if (lane == first) atomicAdd(&h[b0], (uint32_t)__popcll(mask));
+  } else if (in) {
+    atomicAdd(&h[bin], 1u);
+  }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void radix_hist_kernel(const float* __restrict__ x, int64_t n, Workspace* __restrict__ ws) {
+  constexpr int SH = radix_shift(PASS), NB = radix_bins(PASS), IMAGES = PASS == 1 ? 1 : 2;
+  __shared__ uint32_t h[IMAGES * NB];
+  uint32_t k0 = 0u, k1 = 0u;
+  bool on0 = true, on1 = false;
+  if (PASS > 1) {
+    const SelState s0 = ws->sel[0], s1 = ws->sel[1];
+    if (s0.done && s1.done) return;
+    k0 = s0.klo;
+    k1 = s1.klo;
+    on0 = !s0.done;
+    on1 = !s1.done && !(on0 && radix_same_prefix<PASS>(k0, k1));  // equal prefixes: image 0 is the histogram of both ranks
+  }
+  for (int i = threadIdx.x; i < IMAGES * NB; i += 256) h[i] = 0u;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const auto add = [&](uint32_t key, bool live) {
+    const uint32_t bin = (key >> SH) & (uint32_t)(NB - 1);
+    if (PASS == 1) {
+      radix_add(h, bin, live, lane);
+    } else {
+      if (on0) radix_add(h, bin, live && radix_same_prefix<PASS>(key, k0), lane);       // on0 / on1 are uniform across the grid
+      if (on1) radix_add(h + NB, bin, live && radix_same_prefix<PASS>(key, k1), lane);
+    }
+  };
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t n4 = n >> 2;
+  const int64_t n4_round = ((n4 + stride - 1) / stride) * stride;  // whole waves stay in the loop for the ballots
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4_round; i += stride) {
+    const bool live = i < n4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) v = reinterpret_cast<const float4*>(x)[i];
+    add(f2key(v.x), live);
+    add(f2key(v.y), live);
+    add(f2key(v.z), live);
+    add(f2key(v.w), live);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) {  // tail (< 4 elements), one full wave
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    const bool live = i < n;
+    add(live ? f2key(x[i]) : 0u, live);
+  }
+  __syncthreads();
+  uint32_t* __restrict__ g = &ws->hist2[0][0] + radix_offset(PASS);
+  for (int i = threadIdx.x; i < IMAGES * NB; i += 256) {
+    const uint32_t c = h[i];
+    if (c) atomicAdd(&g[i], c);
+  }
+}
+
+// 1024 threads, one workgroup: the digit of `PASS` of each pending rank.  Pass 1 writes sel[] whole (nothing of an earlier select survives);
+// after pass 3 sel[q] = {the key, done = 1, width = 1}: the state select_scan2_kernel leaves.
+template <int PASS>
+__global__ __launch_bounds__(1024) void radix_scan_kernel(Workspace* __restrict__ ws, int64_t rank_lo, int64_t rank_hi) {
+  constexpr int SH = radix_shift(PASS), NB = radix_bins(PASS);
+  SelState s[2];
+  for (int q = 0; q < 2; ++q) {
+    if (PASS == 1) {
+      s[q].klo = 0u;
+      s[q].done = 0u;
+      s[q].width = 1ull << 32;
+      s[q].rank = (uint64_t)(q == 0 ? rank_lo : rank_hi);
+    } else {
+      s[q] = ws->sel[q];
+    }
+  }
+  __syncthreads();  // every thread holds both states before thread 0 writes the first
+  const bool shared = !s[0].done && radix_same_prefix<PASS>(s[0].klo, s[1].klo);  // as radix_hist_kernel decided
+  uint32_t* g = &ws->hist2[0][0] + radix_offset(PASS);
+  for (int q = 0; q < 2; ++q) {
+    if (s[q].done) continue;  // uniform across the block
+    int bin; uint64_t prefix;
+    find_bin(g + ((q == 1 && !shared) ? NB : 0), NB, s[q].rank, false, bin, prefix);
+    if (threadIdx.x == 0) {
+      ws->sel[q].klo = s[q].klo | ((uint32_t)bin << SH);
+      ws->sel[q].width = 1ull << SH;
+      ws->sel[q].rank = s[q].rank - prefix;
+      ws->sel[q].done = SH == 0 ? 1u : 0u;
+    }
+  }
+}
+
 __device__ __forceinline__ float sub_rounded_once(float a, float b) {  // a - b that is never fused into the multiplication that produced b
 #pragma clang fp contract(off)
   return a - b;
@@ -1397,6 +1513,24 @@ int orcai_quantile_select(const float* x, int64_t n, int64_t rank_lo, int64_t ra
     hipLaunchKernelGGL(hist2_kernel, dim3(grid), dim3(256), 0, s, x, n, ws);
     hipLaunchKernelGGL(select_scan2_kernel, dim3(1), dim3(1024), 0, s, ws);
   }
+  return (int)hipGetLastError();
+}
+
+int orcai_quantile_select_radix(const float* x, int64_t n, int64_t rank_lo, int64_t rank_hi, void* workspace, void* stream) {
+  if (!x || !workspace || n <= 0 || n >= ((int64_t)1 << 32) || rank_lo < 0 || rank_hi < 0 || rank_lo >= n || rank_hi >= n || ((uintptr_t)x & 15))
+    return ORCAI_E_BADARG;  // the bins are u32
+  Workspace* ws = (Workspace*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  static_assert(RADIX_WORDS * sizeof(uint32_t) <= sizeof(ws->hist2), "the radix histograms live in hist2");
+  const hipError_t e = orcai_zero::zero_async(ws->hist2, RADIX_WORDS * sizeof(uint32_t), s);  // all three passes' histograms; hist1 and pmax_bits stay
+  if (e != hipSuccess) return (int)e;
+  const int grid = grid_for((n / 4 + 255) / 256);
+  hipLaunchKernelGGL(radix_hist_kernel<1>, dim3(grid), dim3(256), 0, s, x, n, ws);
+  hipLaunchKernelGGL(radix_scan_kernel<1>, dim3(1), dim3(1024), 0, s, ws, rank_lo, rank_hi);
+  hipLaunchKernelGGL(radix_hist_kernel<2>, dim3(grid), dim3(256), 0, s, x, n, ws);
+  hipLaunchKernelGGL(radix_scan_kernel<2>, dim3(1), dim3(1024), 0, s, ws, rank_lo, rank_hi);
+  hipLaunchKernelGGL(radix_hist_kernel<3>, dim3(grid), dim3(256), 0, s, x, n, ws);
+  hipLaunchKernelGGL(radix_scan_kernel<3>, dim3(1), dim3(1024), 0, s, ws, rank_lo, rank_hi);
   return (int)hipGetLastError();
 }
 

@@ -392,9 +392,7 @@ int orcai_make_pcen_spectrogram(const float* pcm, int64_t n_samples, int n_fft, 
   if (e) return e;
   e = orcai_pcen(out, n_frames, k, a, b, scale, gain, bias, power, eps, scratch, stream);
   if (e) return e;
-  e = orcai_hist_level1(out, n, workspace, stream);
-  if (e) return e;
-  e = orcai_quantile_select(out, n, rank_lo, rank_hi, workspace, stream);
+  e = orcai_quantile_select_radix(out, n, rank_lo, rank_hi, workspace, stream);  // PCEN values crowd below 0.125, the level-1 map's single bucket
   if (e) return e;
   e = orcai_frontend_finalize(0, 0.0f, workspace, stream);
   if (e) return e;

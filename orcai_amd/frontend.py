@@ -277,30 +277,58 @@ class FrontEnd:
         self.normalize_inplace(out, quantiles)
         return out
 
-    def normalize_inplace(self, x: torch.Tensor, quantiles) -> None:
-        """Exact percentile clip + min-max normalise of a final-dB array, in place."""
+    def _select_into_workspace(self, x: torch.Tensor, rank_lo: int, rank_hi: int, method: str) -> None:
+        """The two order statistics of x into the workspace.  method "level1": reset + orcai_hist_level1 + orcai_quantile_select, whose cost depends on
+        where the values lie (tuned for dB); "radix": orcai_quantile_select_radix, three reads of x for any values.  Both are exact: same bytes."""
         total = x.numel()
         s = N.stream_ptr()
         ws = N.ptr(self.workspace)
+        if method == "level1":
+            N.check(self.lib.orcai_frontend_reset(ws, s), "orcai_frontend_reset")
+            N.check(self.lib.orcai_hist_level1(N.ptr(x), total, ws, s), "orcai_hist_level1")
+            N.check(self.lib.orcai_quantile_select(N.ptr(x), total, rank_lo, rank_hi, ws, s), "orcai_quantile_select")
+        elif method == "radix":
+            N.check(self.lib.orcai_quantile_select_radix(N.ptr(x), total, rank_lo, rank_hi, ws, s), "orcai_quantile_select_radix")
+        else:
+            raise ValueError(f"method must be 'level1' or 'radix', got {method!r}")
+        N.check(self.lib.orcai_frontend_finalize(0, TOP_DB, ws, s), "orcai_frontend_finalize")
+
+    def normalize_inplace(self, x: torch.Tensor, quantiles, method: str = "level1") -> None:
+        """Exact percentile clip + min-max normalise of a final-dB array, in place.  method: _select_into_workspace's."""
+        total = x.numel()
         r_lo = nearest_rank_index(total, quantiles[0])
         r_hi = nearest_rank_index(total, quantiles[1])
-        N.check(self.lib.orcai_frontend_reset(ws, s), "orcai_frontend_reset")
-        N.check(self.lib.orcai_hist_level1(N.ptr(x), total, ws, s), "orcai_hist_level1")
-        N.check(self.lib.orcai_quantile_select(N.ptr(x), total, r_lo, r_hi, ws, s), "orcai_quantile_select")
-        N.check(self.lib.orcai_frontend_finalize(0, TOP_DB, ws, s), "orcai_frontend_finalize")
-        N.check(self.lib.orcai_clip_normalize(N.ptr(x), total, ws, s), "orcai_clip_normalize")
+        self._select_into_workspace(x, r_lo, r_hi, method)
+        N.check(self.lib.orcai_clip_normalize(N.ptr(x), total, N.ptr(self.workspace), N.stream_ptr()), "orcai_clip_normalize")
 
-    def select(self, x: torch.Tensor, rank_lo: int, rank_hi: int) -> tuple[float, float]:
-        """Exact rank_lo-th / rank_hi-th smallest of a device f32 array (test hook for the selection kernels)."""
-        total = x.numel()
-        s = N.stream_ptr()
-        ws = N.ptr(self.workspace)
-        N.check(self.lib.orcai_frontend_reset(ws, s), "orcai_frontend_reset")
-        N.check(self.lib.orcai_hist_level1(N.ptr(x), total, ws, s), "orcai_hist_level1")
-        N.check(self.lib.orcai_quantile_select(N.ptr(x), total, rank_lo, rank_hi, ws, s), "orcai_quantile_select")
-        N.check(self.lib.orcai_frontend_finalize(0, TOP_DB, ws, s), "orcai_frontend_finalize")
+    def select(self, x: torch.Tensor, rank_lo: int, rank_hi: int, method: str = "level1") -> tuple[float, float]:
+        """Exact rank_lo-th / rank_hi-th smallest of a device f32 array (test hook for the selection kernels).  method: _select_into_workspace's."""
+        self._select_into_workspace(x, rank_lo, rank_hi, method)
         st = self.stats()
         return st["sel_lo_raw"], st["sel_hi_raw"]
+
+    def percentiles(self, x: torch.Tensor, q) -> torch.Tensor:
+        """Exact percentiles of any contiguous f32 CUDA tensor, taken flat: element i is the nearest_rank_index(x.numel(), q[i])-th smallest value, what
+        ``np.percentile(x, 100 * q[i], method="nearest")`` returns for float32 data.  q: a sequence of fractions in [0, 1].  Returns f32[len(q)] on
+        the device with no host synchronisation.  The ranks go through the radix select two at a time (a single one twice)."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+            raise TypeError("percentiles: x must be a float32 CUDA tensor")
+        if not x.is_contiguous():
+            raise ValueError("percentiles: x must be contiguous")
+        q = [float(v) for v in q]
+        total = x.numel()
+        if not q or total == 0 or not all(0.0 <= v <= 1.0 for v in q):
+            raise ValueError(f"percentiles: q must be a non-empty sequence of fractions in [0, 1] and x non-empty, got q = {q}, {total} values")
+        ranks = [nearest_rank_index(total, v) for v in q]
+        pairs = torch.empty((len(ranks) + 1) // 2, 6, dtype=torch.float32, device=self.device)
+        s = N.stream_ptr()
+        ws = N.ptr(self.workspace)
+        for i in range(0, len(ranks), 2):
+            r_lo, r_hi = ranks[i], ranks[min(i + 1, len(ranks) - 1)]
+            N.check(self.lib.orcai_quantile_select_radix(N.ptr(x), total, r_lo, r_hi, ws, s), "orcai_quantile_select_radix")
+            N.check(self.lib.orcai_frontend_finalize(0, TOP_DB, ws, s), "orcai_frontend_finalize")
+            N.check(self.lib.orcai_frontend_stats_dev(ws, N.ptr(pairs[i // 2]), s), "orcai_frontend_stats_dev")
+        return pairs[:, 4:6].reshape(-1)[:len(ranks)].contiguous()  # sel_lo_raw, sel_hi_raw of each pair
 
     def stats(self) -> dict:
         """Synchronises; {pmax, ref_db, p_lo, p_hi, sel_lo_raw, sel_hi_raw} of the last run."""

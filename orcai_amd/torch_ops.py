@@ -10,6 +10,7 @@ known without a GPU.
     torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
                                      scale, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
+    torch.ops.orcai.percentile(x f32[...], q) -> f32[len(q)]
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -402,6 +403,50 @@ def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_
     pcen_spectrogram_wrt_pcm has it."""
     return torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale,
                                             q_lo, q_hi)
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::percentile
+# FrontEnd.percentiles: exact nearest-rank percentiles of any contiguous f32 tensor, taken flat, by the radix select (orcai_quantile_select_radix).
+# Forward only, like the front-end ops: an order statistic is held constant everywhere else in this package, so its backward raises.
+def _percentile_impl(x, q):
+    from orcai_amd.frontend import get_frontend
+
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise TypeError(f"orcai::percentile: x must be a float32 CUDA tensor, got {getattr(x, 'dtype', None)} on {getattr(x, 'device', None)}")
+    with torch.cuda.device(x.device):
+        return get_frontend(x.device).percentiles(x.detach(), q)
+
+
+def _percentile_fake(x, q):
+    return x.new_empty((len(q),), dtype=torch.float32)
+
+
+class _PercentileFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, q):
+        with torch._C._AutoDispatchBelowAutograd():
+            return torch.ops.orcai.percentile(x, q)
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("orcai::percentile has no gradient: an order statistic is a constant of every backward in this package "
+                                  "(the quantile bounds of the front ends are held constant too)")
+
+
+def _percentile_autograd(x, q):
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _PercentileFunction.apply(x, q)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.percentile(x, q)
+
+
+_register("percentile", "(Tensor x, float[] q) -> Tensor", _percentile_impl, _percentile_fake, _percentile_autograd)
+
+
+def percentile(x: Tensor, q: list[float]) -> Tensor:
+    """f32[len(q)] on x's device: element i is what ``np.percentile(x, 100 * q[i], method="nearest")`` returns for the float32 values of x, exactly;
+    x any contiguous f32 CUDA tensor, q fractions in [0, 1].  No host synchronisation, no gradient."""
+    return torch.ops.orcai.percentile(x, [float(v) for v in q])
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
