@@ -336,6 +336,47 @@ int orcai_pcen_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, i
                                const int* band_off, const float* weights, int n_weights, float a, float b, float scale, float gain, float bias, float power,
                                float eps, const float* gout, const float* stats_dev, float* dpcm, void* scratch, void* stream);
 
+/* Segmented select: out[c] = the rank-th smallest (0-based) of column c of x = f32[rows][cols] (row-major, as the front end writes [frame][bin]), for
+ * every column in one call.  Exact for any f32 data without NaN.  The order is the monotone key's of orcai_quantile_select_radix (-0.0 before +0.0,
+ * +-inf and subnormals ordinary values) and the value returned is the selected key's float: bit for bit what orcai_quantile_select_radix returns on
+ * that column alone.  Four passes over x, one 8-bit digit of the key each, most significant first: a workgroup owns 32 adjacent columns (a row piece
+ * is 128 contiguous bytes; with fewer than 17 columns the lanes of a row shrink to the next power of two) and strides over row tiles with a capped
+ * grid; an element counts into its column's LDS histogram (u32[32][257], 32.1 KiB) only when its higher digits equal ITS OWN COLUMN's prefix; the
+ * non-zero bins are then added to the global u32[cols][256] with integer atomics, and one wave per column turns its histogram into (digit, remaining
+ * rank) and clears it.  Four reads of x wherever the values lie, no global atomic per element, no float atomics: two launches give the same bytes.
+ *   scratch    orcai_column_select_scratch_bytes(cols) bytes on the device, 4-byte aligned: the histograms, the per-column state {prefix, rank} and
+ *              f32[cols] that this call leaves alone (orcai_make_denoised_spectrogram's profile when the caller passes none).  The call clears what
+ *              it accumulates into and writes its state whole: a stale or never-cleared scratch gives the same result, no reset call in front.
+ *   out        f32[cols]; nothing else is written, and the front end's workspace is not touched.
+ * Asynchronous on stream, no allocation, no host synchronisation, hipGraph-capturable; static LDS below 64 KiB, so no opt-in.  ORCAI_E_BADARG, before
+ * anything is launched: null x, out or scratch; rows <= 0 or rows >= 2^32 (the bins are u32); cols outside 1..4096; rank outside [0, rows); a pointer
+ * that is not 4-byte aligned.  cols need not be a multiple of anything and rows need not be 16-byte multiples (every load is one dword).
+ * orcai_column_select_scratch_bytes is 0 for cols outside 1..4096. */
+size_t orcai_column_select_scratch_bytes(int cols);
+int orcai_column_select(const float* x, int64_t rows, int cols, int64_t rank, float* out, void* scratch, void* stream);
+
+/* In place: x[t][c] = x[t][c] - m[c] in f32 (one rounding), x = f32[rows][cols], m = f32[cols].  One streaming pass, every element read and written
+ * once: 16-byte accesses from the first 16-byte boundary of x on, scalar accesses in front of it and behind the last whole 16 bytes.
+ * ORCAI_E_BADARG: null or not 4-byte aligned x or m, rows and cols as for orcai_column_select. */
+int orcai_subtract_columns(float* x, int64_t rows, int cols, const float* m, void* stream);
+
+/* The dB front end with a per-channel noise floor removed (the spectrogram parameter "denoise"): every column of the referenced dB spectrogram minus its
+ * own order statistic over the recording (rank_col; the median for quantile 0.5), then the global percentile clip and the normalisation.  One call =
+ *   orcai_frontend_reset, orcai_stft_db (band_lo null; k = k_crop) or orcai_stft_mel_db (k = n_mels), orcai_frontend_finalize(1, top_db),
+ *   orcai_db_reference                       -> V = max(dB - ref_db, -top_db) in out
+ *   orcai_column_select(V, n_frames, k, rank_col) -> m,   orcai_subtract_columns -> Y = V - m
+ *   orcai_quantile_select_radix(Y, rank_lo, rank_hi), orcai_frontend_finalize(0), orcai_clip_normalize
+ * in this order, byte for byte.  The clip runs on the denoised values Y, so rank_lo / rank_hi keep their meaning (n = n_frames * k); the radix select
+ * because Y is not dB-shaped.  The band arguments as for orcai_stft_mel_db, all ignored when band_lo is null.
+ *   profile    f32[k] or null: receives m, the recording's noise profile in referenced dB
+ *   scratch    orcai_column_select_scratch_bytes(k) bytes, 4-byte aligned;  out f32[n_frames * k] in [0, 1], 16-byte aligned
+ * No host synchronisation.  orcai_frontend_stats_dev behind it reports pmax of the STFT and p_lo / p_hi as values of Y; ref_db reads 0 there, as the
+ * last finalize leaves it for orcai_clip_normalize (the STFT's is 10 log10(max(pmax, 1e-10))).  ORCAI_E_BADARG before anything is launched for what the
+ * select and clip steps would refuse; the transform's own refusals are those of the STFT entry, unchanged.  Forward only: no gradient exists. */
+int orcai_make_denoised_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
+                                    const int* band_off, const float* weights, int n_weights, int64_t rank_col, int64_t rank_lo, int64_t rank_hi, float top_db,
+                                    float* out, float* profile, void* scratch, void* workspace, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Model forward, inference (architectures.py:162-241 as executed by model.predict, predict.py:265-268)

@@ -192,6 +192,11 @@ _SIGNATURES = {
     "orcai_stft_mel_energy_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
     "orcai_pcen_spectrogram_bwd_scratch_bytes": (C.c_size_t, [c_i64, C.c_int]),
     "orcai_pcen_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 7 + [C.c_void_p] * 5),
+    "orcai_column_select_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "orcai_column_select": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_subtract_columns": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
+    "orcai_make_denoised_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, c_i64, c_i64, c_i64, C.c_float]
+                                        + [C.c_void_p] * 5),
     "orcai_sigmoid_bwd":(C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_prepare_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "orcai_sepconv_dgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4),

@@ -33,6 +33,7 @@
 
 #include "lds_optin.h"
 #include "orcai_hip.h"
+#include "select_key.h"  // f2key / key2f
 #include "zero_fill.h"
 
 namespace {
@@ -69,14 +70,6 @@ __device__ float g_window[NFFT];
 __device__ float2 g_tw256[256];  // [k2*16 + n1] = exp(-2 pi i n1 k2 / 256)
 __device__ float2 g_tw512[260];  // [k] = (cos, sin)(2 pi k / 512), k = 0..256
 
-__device__ __forceinline__ uint32_t f2key(float f) {
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
 __device__ __forceinline__ float power_to_db(float p) {
   return __builtin_amdgcn_logf(fmaxf(p, AMIN_POW)) * DB_PER_LOG2;
 }

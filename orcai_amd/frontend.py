@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from orcai_amd import _native as N
+from orcai_amd import denoise
 from orcai_amd import mel
 from orcai_amd import pcen
 
@@ -85,7 +86,9 @@ class FrontEnd:
         nbytes = self.lib.orcai_frontend_workspace_bytes()
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._mel_tables: dict = {}
-        self._scratch: dict = {}  # grown on demand: "pcen" orcai_pcen's partials and carries, "pcen_bwd" orcai_pcen_spectrogram_bwd's energies, planes and carries
+        # grown on demand: "pcen" orcai_pcen's partials and carries, "pcen_bwd" orcai_pcen_spectrogram_bwd's energies, planes and carries, "column_select"
+        # orcai_column_select's histograms and per-column state
+        self._scratch: dict = {}
 
     @staticmethod
     def _check_nfft(n_fft: int) -> None:
@@ -135,15 +138,23 @@ class FrontEnd:
         route = resolve_route(spectrogram_parameter)
         return n_frames(n_samples, route.nfft, route.hop), route.K
 
-    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False, out: torch.Tensor | None = None):
+    def make_spectrogram(self, pcm: torch.Tensor, spectrogram_parameter: dict, return_stats: bool = False, out: torch.Tensor | None = None,
+                         return_profile: bool = False):
         """pcm: f32[N] on the device, already at spectrogram_parameter['sampling_rate'].
         With the parameter's pcen key set the values are PCEN (orcai_amd/pcen.py) of the magnitudes -- of the mel band powers when mel is set too --
         clipped and normalised by the same quantiles; the statistics then hold p_lo / p_hi as PCEN values, pmax and ref_db 0.
         Returns f32[T, K] on the device, values in [0, 1]; with return_stats also the run's statistics {pmax, ref_db, p_lo, p_hi, sel_lo_raw,
         sel_hi_raw} as a device tensor f32[6] (orcai_frontend_stats_dev: no host synchronisation), which backward needs -- the
         workspace itself is overwritten by the next recording.  out: a contiguous f32[T, K] of this device to write into (a recording's rows of a
-        batch buffer, predict.predict_wavs) instead of a new tensor."""
+        batch buffer, predict.predict_wavs) instead of a new tensor.
+        With the parameter's denoise key set (orcai_amd/denoise.py; linear or mel route) every channel of the referenced dB spectrogram loses its own
+        noise floor -- the order statistic denoise.quantile of the channel over the recording, the median by default -- before the quantile clip, which
+        then runs on the denoised values (orcai_make_denoised_spectrogram); the statistics hold p_lo / p_hi as denoised values, pmax of the STFT and
+        ref_db 0.  return_profile (denoise only): the f32[K] device tensor of the subtracted floors, in referenced dB, is returned last."""
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
+        dn = denoise.denoise_config(spectrogram_parameter)  # beside the route: Route keeps its five fields
+        if return_profile and dn is None:
+            raise ValueError("make_spectrogram: return_profile needs the spectrogram parameter denoise (the profile is the per-channel floor it subtracts)")
         pcm = self._check_pcm(pcm)
         n = pcm.numel()
         T = n_frames(n, n_fft, hop)
@@ -155,7 +166,17 @@ class FrontEnd:
         r_lo = nearest_rank_index(total, spectrogram_parameter["quantiles"][0])
         r_hi = nearest_rank_index(total, spectrogram_parameter["quantiles"][1])
         signal = (N.ptr(pcm), n, n_fft, hop, T, K)
-        if pc is not None:  # PCEN of the magnitudes, or of the mel band powers when mel is set as well
+        profile = None
+        if dn is not None:  # the dB spectrogram, linear or mel, minus every channel's own floor
+            if T < 1:
+                raise ValueError(f"make_spectrogram: spectrogram parameter denoise needs at least one frame, got {T}")
+            profile = torch.empty(K, dtype=torch.float32, device=self.device) if return_profile else None
+            scratch = self._grown("column_select", self.lib.orcai_column_select_scratch_bytes(K) // 4)
+            rc = self.lib.orcai_make_denoised_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), nearest_rank_index(T, dn["quantile"]), r_lo, r_hi, TOP_DB,
+                                                          N.ptr(out), None if profile is None else N.ptr(profile), N.ptr(scratch), N.ptr(self.workspace),
+                                                          N.stream_ptr())
+            N.check(rc, "orcai_make_denoised_spectrogram")
+        elif pc is not None:  # PCEN of the magnitudes, or of the mel band powers when mel is set as well
             a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
             scratch = self._grown("pcen", self.lib.orcai_pcen_scratch_bytes(T, K) // 4)
             rc = self.lib.orcai_make_pcen_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"],
@@ -167,7 +188,8 @@ class FrontEnd:
             N.check(rc, "orcai_make_mel_spectrogram")
         else:
             N.check(self.lib.orcai_make_spectrogram(*signal, r_lo, r_hi, TOP_DB, N.ptr(out), N.ptr(self.workspace), N.stream_ptr()), "orcai_make_spectrogram")
-        return (out, self._stats_dev()) if return_stats else out
+        res = (out,) + ((self._stats_dev(),) if return_stats else ()) + ((profile,) if return_profile else ())
+        return res if len(res) > 1 else out
 
     # -- the gradient of make_spectrogram w.r.t. the audio (the statistics are held constant) -----------------
     @staticmethod
@@ -181,7 +203,9 @@ class FrontEnd:
         """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
         returned for the same pcm, on the route the parameter asks for: orcai_pcen_spectrogram_bwd with pcen set (on the mel bands when mel is set
         too), orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  ref_db, p_lo and p_hi are constants of the backward; the
-        filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry."""
+        filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry.  A parameter with denoise
+        set is refused first (denoise.no_gradient: forward only)."""
+        denoise.no_gradient(spectrogram_parameter, who)
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
             self._check_nfft_backward(n_fft)
@@ -224,6 +248,7 @@ class FrontEnd:
 
     def spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """backward for the linear dB front end only (orcai_spectrogram_bwd): a parameter whose mel or pcen key is set is refused."""
+        denoise.no_gradient(spectrogram_parameter, "spectrogram_backward")
         self._no_pcen_gradient(spectrogram_parameter, "spectrogram_backward")
         if mel.mel_config(spectrogram_parameter) is not None:
             raise NotImplementedError("spectrogram_backward is the linear front end's gradient and the spectrogram parameter mel is set: "
@@ -233,6 +258,7 @@ class FrontEnd:
     def mel_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """backward for the mel dB front end only (orcai_mel_spectrogram_bwd): grad is f32[T, n_mels]; a parameter without mel, or with pcen, is
         refused.  The parameter's refusals are mel.mel_config's."""
+        denoise.no_gradient(spectrogram_parameter, "mel_spectrogram_backward")
         self._no_pcen_gradient(spectrogram_parameter, "mel_spectrogram_backward")
         if mel.mel_config(spectrogram_parameter) is None:
             raise ValueError("mel_spectrogram_backward: the spectrogram parameter mel is absent or null; FrontEnd.spectrogram_backward is the gradient "
@@ -241,6 +267,7 @@ class FrontEnd:
 
     def pcen_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict) -> torch.Tensor:
         """backward for the PCEN front end only, on either route (orcai_pcen_spectrogram_bwd): a parameter without pcen is refused."""
+        denoise.no_gradient(spectrogram_parameter, "pcen_spectrogram_backward")
         if pcen.pcen_config(spectrogram_parameter) is None:
             raise ValueError("pcen_spectrogram_backward: the spectrogram parameter pcen is absent or null; FrontEnd.spectrogram_backward and "
                              "FrontEnd.mel_spectrogram_backward are the gradients of the dB front ends")
@@ -307,10 +334,13 @@ class FrontEnd:
         st = self.stats()
         return st["sel_lo_raw"], st["sel_hi_raw"]
 
-    def percentiles(self, x: torch.Tensor, q) -> torch.Tensor:
+    def percentiles(self, x: torch.Tensor, q, dim: int | None = None) -> torch.Tensor:
         """Exact percentiles of any contiguous f32 CUDA tensor, taken flat: element i is the nearest_rank_index(x.numel(), q[i])-th smallest value, what
         ``np.percentile(x, 100 * q[i], method="nearest")`` returns for float32 data.  q: a sequence of fractions in [0, 1].  Returns f32[len(q)] on
-        the device with no host synchronisation.  The ranks go through the radix select two at a time (a single one twice)."""
+        the device with no host synchronisation.  The ranks go through the radix select two at a time (a single one twice).
+        dim=0: per column instead -- x of at least two dimensions is read as [R, C], C the product of the others (at most 4096), and the result is
+        f32[len(q), *x.shape[1:]], what ``np.percentile(x, 100 * q, axis=0, method="nearest")`` returns: one orcai_column_select per q with rank
+        nearest_rank_index(R, q[i]).  No other dim is implemented."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
             raise TypeError("percentiles: x must be a float32 CUDA tensor")
         if not x.is_contiguous():
@@ -319,6 +349,20 @@ class FrontEnd:
         total = x.numel()
         if not q or total == 0 or not all(0.0 <= v <= 1.0 for v in q):
             raise ValueError(f"percentiles: q must be a non-empty sequence of fractions in [0, 1] and x non-empty, got q = {q}, {total} values")
+        if dim is not None:
+            if dim != 0 or isinstance(dim, bool):
+                raise ValueError(f"percentiles: dim must be None (flat) or 0 (per column of [R, C]), got {dim!r}; selects along other dimensions are not implemented")
+            if x.dim() < 2:
+                raise ValueError(f"percentiles: dim=0 needs a tensor of at least two dimensions, got shape {tuple(x.shape)}")
+            R, cols = x.shape[0], total // x.shape[0]
+            if cols > 4096:
+                raise ValueError(f"percentiles: dim=0 takes at most 4096 columns (orcai_column_select), got {cols} for shape {tuple(x.shape)}")
+            res = torch.empty((len(q), *x.shape[1:]), dtype=torch.float32, device=self.device)
+            scratch = self._grown("column_select", self.lib.orcai_column_select_scratch_bytes(cols) // 4)
+            for i, v in enumerate(q):
+                rc = self.lib.orcai_column_select(N.ptr(x), R, cols, nearest_rank_index(R, v), N.ptr(res[i]), N.ptr(scratch), N.stream_ptr())
+                N.check(rc, "orcai_column_select")
+            return res
         ranks = [nearest_rank_index(total, v) for v in q]
         pairs = torch.empty((len(ranks) + 1) // 2, 6, dtype=torch.float32, device=self.device)
         s = N.stream_ptr()

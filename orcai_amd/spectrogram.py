@@ -15,6 +15,7 @@ import pandas as pd
 import torch
 from tqdm import tqdm
 
+from orcai_amd import denoise
 from orcai_amd import frontend as fe
 from orcai_amd import mel
 from orcai_amd import pcen
@@ -72,6 +73,8 @@ def _linear_only(spectrogram_parameter: dict, what: str) -> None:
         raise NotImplementedError(f"{what}: the two-step API is linear-only; with spectrogram parameter mel set use make_spectrogram (or set mel to null)")
     if spectrogram_parameter.get("pcen") is not None:
         raise NotImplementedError(f"{what}: the two-step API is the dB spectrum; with spectrogram parameter pcen set use make_spectrogram (or set pcen to null)")
+    if spectrogram_parameter.get("denoise") is not None:
+        raise NotImplementedError(f"{what}: the two-step API is the plain dB spectrum; with spectrogram parameter denoise set use make_spectrogram (or set denoise to null)")
 
 
 def calculate_spectrogram(wav_file_path: Path, channel: int, spectrogram_parameter: dict, msgr: Messenger = Messenger(verbosity=0)):
@@ -103,6 +106,7 @@ def make_spectrogram_device(wav_file_path: Path | str, channel: int, orcai_param
     sp = orcai_parameter["spectrogram"]
     cfg = mel.mel_config(sp)  # the parameter's refusals, before the file is read
     pcen.pcen_config(sp)
+    denoise.denoise_config(sp)
     pcm = load_wav(wav_file_path, sp["sampling_rate"], channel, msgr)
     spec = fe.get_frontend().make_spectrogram(pcm, sp)
     if cfg is not None:  # the mel route: one frequency per column, the bands' centres

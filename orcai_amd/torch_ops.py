@@ -11,6 +11,7 @@ known without a GPU.
                                      scale, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
     torch.ops.orcai.percentile(x f32[...], q) -> f32[len(q)]
+    torch.ops.orcai.column_percentile(x f32[R, ...], q) -> f32[len(q), ...]   (per column of [R, C]: np.percentile(x, 100 q, axis=0, method="nearest"))
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -449,6 +450,50 @@ def percentile(x: Tensor, q: list[float]) -> Tensor:
     return torch.ops.orcai.percentile(x, [float(v) for v in q])
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::column_percentile
+# FrontEnd.percentiles(dim=0): the same exact nearest-rank percentiles per column of x read as [R, C] (C the product of the dimensions after the first, at
+# most 4096), by the segmented radix select (orcai_column_select), one call per q.  Forward only, for the reason orcai::percentile is.
+def _column_percentile_impl(x, q):
+    from orcai_amd.frontend import get_frontend
+
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise TypeError(f"orcai::column_percentile: x must be a float32 CUDA tensor, got {getattr(x, 'dtype', None)} on {getattr(x, 'device', None)}")
+    with torch.cuda.device(x.device):
+        return get_frontend(x.device).percentiles(x.detach(), q, dim=0)
+
+
+def _column_percentile_fake(x, q):
+    return x.new_empty((len(q), *x.shape[1:]), dtype=torch.float32)
+
+
+class _ColumnPercentileFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, q):
+        with torch._C._AutoDispatchBelowAutograd():
+            return torch.ops.orcai.column_percentile(x, q)
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("orcai::column_percentile has no gradient: an order statistic is a constant of every backward in this package "
+                                  "(the quantile bounds of the front ends are held constant too)")
+
+
+def _column_percentile_autograd(x, q):
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _ColumnPercentileFunction.apply(x, q)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.column_percentile(x, q)
+
+
+_register("column_percentile", "(Tensor x, float[] q) -> Tensor", _column_percentile_impl, _column_percentile_fake, _column_percentile_autograd)
+
+
+def column_percentile(x: Tensor, q: list[float]) -> Tensor:
+    """f32[len(q), *x.shape[1:]] on x's device: what ``np.percentile(x, 100 * q, axis=0, method="nearest")`` returns for the float32 values of x, exactly;
+    x a contiguous f32 CUDA tensor of at least two dimensions with at most 4096 columns, q fractions in [0, 1].  No host synchronisation, no gradient."""
+    return torch.ops.orcai.column_percentile(x, [float(v) for v in q])
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
 # forward_wrt_input is orcai::forward with the gradient w.r.t. the snippets as well: for something trainable or differentiable IN FRONT of the
 # detector (a learnable gain / equaliser / denoiser on the spectrogram, differentiable augmentation, adversarial or gradient-penalty training,
@@ -665,6 +710,13 @@ def _no_pcen(spectrogram_parameter: dict, who: str) -> None:
                                   "torch_ops.PcenWaveformFrontEnd(spectrogram_parameter, native_rate) is the differentiable PCEN front end")
 
 
+def _no_denoise(spectrogram_parameter: dict, who: str) -> None:
+    """The differentiable modules run the *_wrt_pcm ops, which have no denoise argument: a parameter that asks for it is refused, not silently run without."""
+    from orcai_amd import denoise
+
+    denoise.no_gradient(spectrogram_parameter, who)
+
+
 def _check_rates(sr_in, sr_out, who: str) -> None:
     if sr_in <= 0 or sr_out <= 0:
         raise ValueError(f"{who}: sr_in and sr_out must be positive, got {sr_in} and {sr_out}")
@@ -796,6 +848,7 @@ class _WaveformFrontEnd(torch.nn.Module):
     def __init__(self, spectrogram_parameter: dict, native_rate: int):
         super().__init__()
         sp = spectrogram_parameter
+        _no_denoise(sp, type(self).__name__)
         self._route(sp)
         self.native_rate = int(native_rate)
         self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
@@ -895,7 +948,9 @@ class PcenWaveformFrontEnd(_WaveformFrontEnd):
 
 def waveform_front_end(spectrogram_parameter: dict, native_rate: int) -> torch.nn.Module:
     """The differentiable dB front end of a parameter file's "spectrogram" section: MelWaveformFrontEnd when its ``mel`` key is set, WaveformFrontEnd
-    when it is absent or null.  A parameter whose ``pcen`` key is set is refused by both (NotImplementedError): PcenWaveformFrontEnd is its class."""
+    when it is absent or null.  A parameter whose ``pcen`` key is set is refused by both (NotImplementedError): PcenWaveformFrontEnd is its class.  A
+    parameter whose ``denoise`` key is set is refused by all of them (NotImplementedError that names denoise: forward only)."""
+    _no_denoise(spectrogram_parameter, "waveform_front_end")
     if spectrogram_parameter.get("mel") is not None:
         return MelWaveformFrontEnd(spectrogram_parameter, native_rate)
     return WaveformFrontEnd(spectrogram_parameter, native_rate)
