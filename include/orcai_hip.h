@@ -372,10 +372,40 @@ int orcai_subtract_columns(float* x, int64_t rows, int cols, const float* m, voi
  *   scratch    orcai_column_select_scratch_bytes(k) bytes, 4-byte aligned;  out f32[n_frames * k] in [0, 1], 16-byte aligned
  * No host synchronisation.  orcai_frontend_stats_dev behind it reports pmax of the STFT and p_lo / p_hi as values of Y; ref_db reads 0 there, as the
  * last finalize leaves it for orcai_clip_normalize (the STFT's is 10 log10(max(pmax, 1e-10))).  ORCAI_E_BADARG before anything is launched for what the
- * select and clip steps would refuse; the transform's own refusals are those of the STFT entry, unchanged.  Forward only: no gradient exists. */
+ * select and clip steps would refuse; the transform's own refusals are those of the STFT entry, unchanged.  Its gradient w.r.t. the audio is
+ * orcai_denoised_spectrogram_bwd below (orcai_spectrogram_bwd and orcai_mel_spectrogram_bwd do not know the floor and are not it). */
 int orcai_make_denoised_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
                                     const int* band_off, const float* weights, int n_weights, int64_t rank_col, int64_t rank_lo, int64_t rank_hi, float top_db,
                                     float* out, float* profile, void* scratch, void* workspace, void* stream);
+
+/* Gradient of orcai_make_denoised_spectrogram w.r.t. the audio.  Notation as at orcai_spectrogram_bwd (band_lo null) and orcai_mel_spectrogram_bwd
+ * (band_lo set); dB is 10 log10(max(P, 1e-10)) on the linear route and 10 log10(max(M[m], 1e-10)) on the mel route.  With
+ *   v = max(dB - ref_db, -top_db),  y = v - m[k] (f32, one rounding),  out = (clip(y, p_lo, p_hi) - p_lo) / (p_hi - p_lo)  and  g = dL/dout:
+ *   g_db[t][k] = g[t][k] / (p_hi - p_lo)  where P (or M) > 1e-10, dB - ref_db > -top_db and p_lo < fl32(v - m[k]) < p_hi (all strict); 0 otherwise
+ * and everything behind g_db -- dP or dM, the mel gather, dRe and dIm, the inverse transform, the window and the frame-ordered overlap sum into dpcm --
+ * is that of the plain entry of the route, unchanged.  The gate forms v - m[k] first, in f32, and then compares, as the forward's clip does; the floor is
+ * never folded into the bounds.
+ * The floor m[k] is HELD CONSTANT, like ref_db, p_lo and p_hi and for the reason given at orcai_spectrogram_bwd: it is an order statistic of channel k,
+ * depends on the data through a single STFT bin (band) of that channel, and that dependence is ill-defined under ties.  There is no gradient "through
+ * the median".
+ *   pcm ... n_weights   as for orcai_make_denoised_spectrogram: band_lo null selects the linear route with k = k_crop (the other band arguments are then
+ *              ignored); otherwise the band arrays in HOST memory and the packed weights on the device, k = n_mels
+ *   gout       f32[n_frames * k], layout [frame][channel]
+ *   stats_dev  f32[6] from orcai_frontend_stats_dev after orcai_make_denoised_spectrogram of the same pcm.  Its ref_db slot reads 0 there, so ref_db is
+ *              recomputed on the device from stats_dev[0] = pmax, 10 log10(max(pmax, 1e-10)) as orcai_frontend_finalize computes it; stats_dev[1] is
+ *              never read.  p_lo and p_hi (values of y) are stats_dev[2] and [3].
+ *   profile    f32[k] on the device: m, what the forward wrote to its `profile`
+ *   dpcm       f32[n_samples]: every element is WRITTEN; no float atomics, two launches give identical bytes
+ * No allocation, no host synchronisation; the launch geometry and the LDS request are the plain entry's (the floor is read through the cache), so the
+ * first call per device with more than 64 KiB of LDS (mel, n_fft = 4096) must come outside a stream capture.  With profile all zero and the statistics
+ * of the plain forward the bytes are those of orcai_spectrogram_bwd / orcai_mel_spectrogram_bwd.
+ * Refusals come before anything is launched and leave dpcm untouched.  ORCAI_E_BADARG: a null pcm, gout, stats_dev, profile or dpcm, one of them not
+ * 4-byte aligned, and what the route's plain entry answers with it (sizes, n_frames other than 1 + n_samples / hop, the mel route's alignment and band
+ * checks).  ORCAI_E_UNSUPPORTED: n_fft that is no power of two from 32 (linear) or 128 (mel) to 4096; two mel bands of equal parity that overlap. */
+int orcai_denoised_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
+                                   const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, const float* profile,
+                                   float top_db, float* dpcm, void* stream);
+int orcai_denoised_spectrogram_bwd_occupancy(int n_fft, int n_mels); /* workgroups of that launch per compute unit as the runtime computes it (n_mels = 0: the linear route); -1 if refused */
 
 
 /* ------------------------------------------------------------------------------------------

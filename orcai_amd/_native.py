@@ -197,6 +197,9 @@ _SIGNATURES = {
     "orcai_subtract_columns": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_make_denoised_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, c_i64, c_i64, c_i64, C.c_float]
                                         + [C.c_void_p] * 5),
+    "orcai_denoised_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
+                                       + [C.c_float, C.c_void_p, C.c_void_p]),
+    "orcai_denoised_spectrogram_bwd_occupancy": (C.c_int, [C.c_int, C.c_int]),
     "orcai_sigmoid_bwd":(C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "orcai_prepare_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "orcai_sepconv_dgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4),

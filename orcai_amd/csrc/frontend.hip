@@ -1104,6 +1104,8 @@ __global__ __launch_bounds__(256) void spectrogram_bwd_kernel(const float* __res
   constexpr bool ENERGY = false;
   const MelBands* const bands = nullptr;
   const float* const weights = nullptr;
+  constexpr bool DENOISE = false;
+  const float* const floor = nullptr;
 #include "spectrogram_bwd_body.inc"
 }
 
@@ -1116,6 +1118,8 @@ __global__ __launch_bounds__(256) void stft_energy_bwd_kernel(const float* __res
   constexpr bool ENERGY = true;
   const MelBands* const bands = nullptr;
   const float* const weights = nullptr;
+  constexpr bool DENOISE = false;
+  const float* const floor = nullptr;
   const float* const stats = nullptr;
   const float top_db = 0.0f;
 #include "spectrogram_bwd_body.inc"
@@ -1131,6 +1135,8 @@ __global__ __launch_bounds__(256) void mel_spectrogram_bwd_kernel(const float* _
   constexpr bool ENERGY = false;
   const MelBands* const bands = &bands_by_value;
   const int k_crop = n_mels;
+  constexpr bool DENOISE = false;
+  const float* const floor = nullptr;
 #include "spectrogram_bwd_body.inc"
 }
 
@@ -1144,8 +1150,40 @@ __global__ __launch_bounds__(256) void stft_mel_energy_bwd_kernel(const float* _
   constexpr bool ENERGY = true;
   const MelBands* const bands = &bands_by_value;
   const int k_crop = n_mels;
+  constexpr bool DENOISE = false;
+  const float* const floor = nullptr;
   const float* const stats = nullptr;
   const float top_db = 0.0f;
+#include "spectrogram_bwd_body.inc"
+}
+
+// orcai_denoised_spectrogram_bwd, linear and mel: the dB kernels with the per-channel floor in their clip gates (DENOISE in the body).  Kernels of their
+// own, as the energy ones are, so that the plain kernels compile to what they were; launch geometry and LDS are those of the plain twin.
+template <int NT>
+__global__ __launch_bounds__(256) void denoised_spectrogram_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop, int64_t n_frames,
+                                                                        int k_crop, const float* __restrict__ gout, const float* __restrict__ stats, float top_db,
+                                                                        float* __restrict__ dpcm, int run, int64_t n_runs, const float* __restrict__ floor) {
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = false;
+  constexpr bool ENERGY = false;
+  constexpr bool DENOISE = true;
+  const MelBands* const bands = nullptr;
+  const float* const weights = nullptr;
+#include "spectrogram_bwd_body.inc"
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void denoised_mel_spectrogram_bwd_kernel(const float* __restrict__ pcm, int64_t n_samples, int n_fft, int log2n, int hop,
+                                                                            int64_t n_frames, int n_mels, const float* __restrict__ gout,
+                                                                            const float* __restrict__ stats, float top_db, float* __restrict__ dpcm, int run,
+                                                                            int64_t n_runs, const MelBands bands_by_value, const float* __restrict__ weights,
+                                                                            const float* __restrict__ floor) {
+  extern __shared__ float4 bwd_lds[];
+  constexpr bool MEL = true;
+  constexpr bool ENERGY = false;
+  constexpr bool DENOISE = true;
+  const MelBands* const bands = &bands_by_value;
+  const int k_crop = n_mels;
 #include "spectrogram_bwd_body.inc"
 }
 
@@ -1279,10 +1317,13 @@ BwdPlan bwd_plan(int n_fft, int n_mels) {
 }
 
 // The launchers behind orcai_spectrogram_bwd (ENERGY = false) and orcai_stft_energy_bwd (ENERGY = true: stats_dev and top_db are not looked at).
-template <bool ENERGY>
+// DENOISE (orcai_denoised_spectrogram_bwd, linear route): the same checks and the same plan, the kernel with the floor f32[k_crop] in its gates.
+template <bool ENERGY, bool DENOISE = false>
 int spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, const float* gout, const float* stats_dev,
-                           float top_db, float* dpcm, void* stream) {
+                           float top_db, float* dpcm, void* stream, const float* floor = nullptr) {
+  static_assert(!(ENERGY && DENOISE), "the energy epilogue has no clip gates");
   if (!pcm || !gout || (!ENERGY && !stats_dev) || !dpcm || n_samples <= 0 || hop <= 0 || n_frames <= 0 || k_crop < 1 || n_fft < 2) return ORCAI_E_BADARG;
+  if (DENOISE && !floor) return ORCAI_E_BADARG;
   if (n_fft < 32 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;  // powers of two from 32 to 4096 only
   if (k_crop > 1 + n_fft / 2 || n_frames != 1 + n_samples / hop) return ORCAI_E_BADARG;         // librosa's centred frame count (n_fft is even)
   const BwdPlan p = bwd_plan(n_fft, 0);
@@ -1294,6 +1335,13 @@ int spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int h
   if constexpr (ENERGY) {
     if (p.wave) hipLaunchKernelGGL((stft_energy_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, p.run, n_runs);
     else hipLaunchKernelGGL((stft_energy_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, dpcm, p.run, n_runs);
+  } else if constexpr (DENOISE) {
+    if (p.wave)
+      hipLaunchKernelGGL((denoised_spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm,
+                         p.run, n_runs, floor);
+    else
+      hipLaunchKernelGGL((denoised_spectrogram_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm,
+                         p.run, n_runs, floor);
   } else {
     if (p.wave)
       hipLaunchKernelGGL((spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, k_crop, gout, stats_dev, top_db, dpcm, p.run,
@@ -1305,12 +1353,13 @@ int spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int h
   return (int)hipGetLastError();
 }
 
-// Likewise behind orcai_mel_spectrogram_bwd and orcai_stft_mel_energy_bwd.
-template <bool ENERGY>
+// Likewise behind orcai_mel_spectrogram_bwd and orcai_stft_mel_energy_bwd, and with DENOISE behind orcai_denoised_spectrogram_bwd's mel route.
+template <bool ENERGY, bool DENOISE = false>
 int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int n_mels, const int* band_lo, const int* band_hi,
                                const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, float top_db, float* dpcm,
-                               void* stream) {
-  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !gout || (!ENERGY && !stats_dev) || !dpcm) return ORCAI_E_BADARG;
+                               void* stream, const float* floor = nullptr) {
+  static_assert(!(ENERGY && DENOISE), "the energy epilogue has no clip gates");
+  if (!pcm || !band_lo || !band_hi || !band_off || !weights || !gout || (!ENERGY && !stats_dev) || !dpcm || (DENOISE && !floor)) return ORCAI_E_BADARG;
   if (n_samples <= 0 || hop <= 0 || n_frames <= 0 || n_fft < 2 || n_mels < 8 || n_mels > MEL_MAX || n_weights < 1 || n_weights > 65535) return ORCAI_E_BADARG;
   if (((uintptr_t)pcm & 15) || ((uintptr_t)weights & 15) || ((uintptr_t)gout & 3) || ((uintptr_t)stats_dev & 3) || ((uintptr_t)dpcm & 3)) return ORCAI_E_BADARG;
   if (n_fft < 128 || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1))) return ORCAI_E_UNSUPPORTED;
@@ -1332,6 +1381,7 @@ int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, i
   if (p.lds > 64 * 1024) {  // n_fft = 4096, and 2048 with more than 202 bands
     hipError_t e;
     if constexpr (ENERGY) e = orcai_lds::ensure_dynamic_lds<stft_mel_energy_bwd_kernel<256>>(LDS_MAX);
+    else if constexpr (DENOISE) e = orcai_lds::ensure_dynamic_lds<denoised_mel_spectrogram_bwd_kernel<256>>(LDS_MAX);
     else e = orcai_lds::ensure_dynamic_lds<mel_spectrogram_bwd_kernel<256>>(LDS_MAX);
     if (e != hipSuccess) return (int)e;
   }
@@ -1346,6 +1396,13 @@ int mel_spectrogram_bwd_launch(const float* pcm, int64_t n_samples, int n_fft, i
     else
       hipLaunchKernelGGL((stft_mel_energy_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, dpcm, p.run, n_runs, bands,
                          weights);
+  } else if constexpr (DENOISE) {
+    if (p.wave)
+      hipLaunchKernelGGL((denoised_mel_spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db,
+                         dpcm, p.run, n_runs, bands, weights, floor);
+    else
+      hipLaunchKernelGGL((denoised_mel_spectrogram_bwd_kernel<256>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db,
+                         dpcm, p.run, n_runs, bands, weights, floor);
   } else {
     if (p.wave)
       hipLaunchKernelGGL((mel_spectrogram_bwd_kernel<64>), grid, dim3(256), p.lds, st, pcm, n_samples, n_fft, log2n, hop, n_frames, n_mels, gout, stats_dev, top_db, dpcm,
@@ -1609,6 +1666,26 @@ int orcai_mel_spectrogram_bwd_occupancy(int n_fft, int n_mels) {  // workgroups 
   const hipError_t e = p.wave ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<64>, 256, p.lds)
                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mel_spectrogram_bwd_kernel<256>, 256, p.lds);
   return e == hipSuccess ? n : -1;
+}
+
+int orcai_denoised_spectrogram_bwd(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo, const int* band_hi,
+                                   const int* band_off, const float* weights, int n_weights, const float* gout, const float* stats_dev, const float* profile,
+                                   float top_db, float* dpcm, void* stream) {
+  if (!pcm || !gout || !stats_dev || !profile || !dpcm) return ORCAI_E_BADARG;
+  if (((uintptr_t)pcm & 3) || ((uintptr_t)gout & 3) || ((uintptr_t)stats_dev & 3) || ((uintptr_t)profile & 3) || ((uintptr_t)dpcm & 3)) return ORCAI_E_BADARG;
+  if (!band_lo)  // the linear route: k is k_crop, the other band arguments are not looked at
+    return spectrogram_bwd_launch<false, true>(pcm, n_samples, n_fft, hop, n_frames, k, gout, stats_dev, top_db, dpcm, stream, profile);
+  return mel_spectrogram_bwd_launch<false, true>(pcm, n_samples, n_fft, hop, n_frames, k, band_lo, band_hi, band_off, weights, n_weights, gout, stats_dev, top_db, dpcm,
+                                                 stream, profile);
+}
+
+int orcai_denoised_spectrogram_bwd_occupancy(int n_fft, int n_mels) {  // n_mels = 0: the linear route; -1 on refusal
+  if (n_fft < (n_mels ? 128 : 32) || n_fft > NFFT_ANY_MAX || (n_fft & (n_fft - 1)) || (n_mels && (n_mels < 8 || n_mels > MEL_MAX))) return -1;
+  const BwdPlan p = bwd_plan(n_fft, n_mels);
+  const void* f = n_mels ? (p.wave ? (const void*)denoised_mel_spectrogram_bwd_kernel<64> : (const void*)denoised_mel_spectrogram_bwd_kernel<256>)
+                         : (p.wave ? (const void*)denoised_spectrogram_bwd_kernel<64> : (const void*)denoised_spectrogram_bwd_kernel<256>);
+  int n = -1;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, p.lds) == hipSuccess ? n : -1;
 }
 
 int orcai_make_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k_crop, int64_t rank_lo,

@@ -4,7 +4,10 @@
 // linear kernel's parameters under their names (k_crop = n_mels with MEL), `constexpr bool MEL`, `constexpr bool ENERGY`, `const MelBands* bands`,
 // `const float* weights` (null without MEL) and `extern __shared__ float4 bwd_lds[]`.  ENERGY (orcai_stft_energy_bwd / orcai_stft_mel_energy_bwd): gout is
 // the gradient w.r.t. the magnitude |X[k]| (linear) or the band power (MEL) itself -- no dB gates, no 10 / (ln 10 P); stats is null and never read, top_db
-// unused.  Layout of bwd_lds: tw[n_fft/2] | per group: buf[n_fft] complex | per group:
+// unused.  DENOISE (orcai_denoised_spectrogram_bwd; the including kernel provides `constexpr bool DENOISE` and `const float* floor`, null without): the
+// clip gates test fl32(v - floor[k]) as orcai_subtract_columns formed it, ref_db is recomputed from stats[0] = pmax as finalize_kernel computes it and
+// stats[1] is never read; floor[k] is a plain global load beside g[k] (K floats, shared by every frame of every workgroup: the cache's), so the LDS
+// layout and the launch plan are the plain kernels'.  Layout of bwd_lds: tw[n_fft/2] | per group: buf[n_fft] complex | per group:
 // acc[run] | MEL: MelBwdLds.
   constexpr int GROUPS = 256 / NT;
   const int half = n_fft >> 1;
@@ -50,7 +53,7 @@
     tw[j] = make_float2(cs, sn);
   }
   __syncthreads();
-  const float ref_db = ENERGY ? 0.0f : stats[1], p_lo = ENERGY ? 0.0f : stats[2], p_hi = ENERGY ? 0.0f : stats[3];
+  const float ref_db = ENERGY ? 0.0f : DENOISE ? power_to_db(stats[0]) : stats[1], p_lo = ENERGY ? 0.0f : stats[2], p_hi = ENERGY ? 0.0f : stats[3];
   const float range = p_hi - p_lo;
   auto window = [&](int n) { return 0.5f - 0.5f * (n < half ? tw[n].x : -tw[n - half].x); };  // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
 
@@ -103,7 +106,8 @@
           float dM = 0.0f;
           if (M > AMIN_POW) {
             const float v = power_to_db(M) - ref_db;
-            if (v > -top_db && v > p_lo && v < p_hi) dM = (g[m] / range) * DB_GRAD / M;
+            const float y = DENOISE ? sub_rounded_once(v, floor[m]) : v;  // the forward's Y = V - m[k], formed before it is compared
+            if (v > -top_db && y > p_lo && y < p_hi) dM = (g[m] / range) * DB_GRAD / M;
           }
           if (sl == 0) ml.dM[m] = dM;
         }
@@ -132,7 +136,8 @@
             }
           } else if (P > AMIN_POW) {
             const float v = power_to_db(P) - ref_db;
-            if (v > -top_db && v > p_lo && v < p_hi) {
+            const float y = DENOISE ? sub_rounded_once(v, floor[k]) : v;
+            if (v > -top_db && y > p_lo && y < p_hi) {
               const float dP = (g[k] / range) * DB_GRAD / P;
               G = make_float2(2.0f * z.x * dP, 2.0f * z.y * dP);
             }

@@ -11,8 +11,12 @@ amounts to dividing the channel by its median magnitude.  The reference has no s
     Y = V - m                              float32, one rounding
 
 and then the exact percentile clip and the normalisation to [0, 1] on Y (``quantiles`` keeps its meaning).  PCEN (orcai_amd/pcen.py) is the adaptive
-version of the same idea and already normalises each channel by its own level, so the two keys together are refused.  Forward only: every backward
-entry refuses a parameter with ``denoise`` set (the gradient needs the per-channel offset in the backward kernels' clip gates).
+version of the same idea and already normalises each channel by its own level, so the two keys together are refused.
+
+The gradient w.r.t. the audio is FrontEnd.denoised_spectrogram_backward (orcai_denoised_spectrogram_bwd: the dB backward kernels with m[k] in their clip
+gates, p_lo < fl32(V - m[k]) < p_hi, and m held constant like ref_db, p_lo and p_hi); torch_ops.denoised_spectrogram_wrt_pcm and
+torch_ops.DenoisedWaveformFrontEnd are built on it.  The plain backward entries and modules do not know the floor and keep refusing a parameter with
+``denoise`` set (no_gradient).
 """
 
 from __future__ import annotations
@@ -48,10 +52,11 @@ def denoise_config(spectrogram_parameter: dict) -> dict | None:
 
 
 def no_gradient(spectrogram_parameter: dict, who: str) -> None:
-    """The refusal of every backward entry and differentiable module for a parameter whose ``denoise`` key is set."""
+    """The refusal of every plain backward entry and differentiable module for a parameter whose ``denoise`` key is set."""
     if spectrogram_parameter.get("denoise") is not None:
-        raise NotImplementedError(f"{who}: spectrogram parameter denoise is set; the forward of the denoised front end is implemented (make_spectrogram) and its "
-                                  "gradient is not -- the backward kernels' clip gates do not know the per-channel offset.  Set denoise to null to differentiate")
+        raise NotImplementedError(f"{who}: spectrogram parameter denoise is set, and this entry's forward and gradient are those of the plain front end, whose clip "
+                                  "gates do not know the per-channel offset.  FrontEnd.denoised_spectrogram_backward is the gradient of the denoised front end "
+                                  "and torch_ops.DenoisedWaveformFrontEnd(spectrogram_parameter, native_rate) its differentiable module; or set denoise to null")
 
 
 def denoise_ref(V, quantile: float):

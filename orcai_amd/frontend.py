@@ -150,7 +150,8 @@ class FrontEnd:
         With the parameter's denoise key set (orcai_amd/denoise.py; linear or mel route) every channel of the referenced dB spectrogram loses its own
         noise floor -- the order statistic denoise.quantile of the channel over the recording, the median by default -- before the quantile clip, which
         then runs on the denoised values (orcai_make_denoised_spectrogram); the statistics hold p_lo / p_hi as denoised values, pmax of the STFT and
-        ref_db 0.  return_profile (denoise only): the f32[K] device tensor of the subtracted floors, in referenced dB, is returned last."""
+        ref_db 0.  return_profile (denoise only): the f32[K] device tensor of the subtracted floors, in referenced dB, is returned last.  The statistics
+        and the profile together are what denoised_spectrogram_backward, the gradient of this route, reads (it recomputes ref_db from pmax)."""
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         dn = denoise.denoise_config(spectrogram_parameter)  # beside the route: Route keeps its five fields
         if return_profile and dn is None:
@@ -204,7 +205,7 @@ class FrontEnd:
         returned for the same pcm, on the route the parameter asks for: orcai_pcen_spectrogram_bwd with pcen set (on the mel bands when mel is set
         too), orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  ref_db, p_lo and p_hi are constants of the backward; the
         filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry.  A parameter with denoise
-        set is refused first (denoise.no_gradient: forward only)."""
+        set is refused first (denoise.no_gradient): its gradient is denoised_spectrogram_backward, which also takes the profile."""
         denoise.no_gradient(spectrogram_parameter, who)
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
@@ -272,6 +273,42 @@ class FrontEnd:
             raise ValueError("pcen_spectrogram_backward: the spectrogram parameter pcen is absent or null; FrontEnd.spectrogram_backward and "
                              "FrontEnd.mel_spectrogram_backward are the gradients of the dB front ends")
         return self.backward(pcm, grad, stats, spectrogram_parameter, who="pcen_spectrogram_backward")
+
+    def denoised_spectrogram_backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, profile: torch.Tensor,
+                                      spectrogram_parameter: dict) -> torch.Tensor:
+        """The gradient of the denoised front end (orcai_denoised_spectrogram_bwd), on the linear or the mel route: dL/dpcm f32[N] from grad =
+        dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics and f32[K] profile that make_spectrogram(..., return_stats=True,
+        return_profile=True) returned for the same pcm and parameter.  ref_db (recomputed from the statistics' pmax), p_lo, p_hi and the per-channel
+        floor are constants of the backward (include/orcai_hip.h).  A parameter without denoise is refused (ValueError naming the plain entries), one
+        with pcen as denoise.denoise_config refuses it."""
+        who = "denoised_spectrogram_backward"
+        if denoise.denoise_config(spectrogram_parameter) is None:
+            raise ValueError(f"{who}: the spectrogram parameter denoise is absent or null; FrontEnd.spectrogram_backward and FrontEnd.mel_spectrogram_backward "
+                             "are the gradients of the plain dB front ends (FrontEnd.pcen_spectrogram_backward of the PCEN one)")
+        n_fft, hop, K, cfg, _ = resolve_route(spectrogram_parameter)
+        if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
+            self._check_nfft_backward(n_fft)
+        if hop < 1:
+            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
+        pcm = self._check_pcm(pcm)
+        n = pcm.numel()
+        T = n_frames(n, n_fft, hop)
+        sizes = f"nfft = {n_fft}" if cfg is None else f"nfft = {n_fft}, n_mels = {K}"
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, K)):
+            raise ValueError(f"{who}: grad must be a float32 CUDA tensor [{T}, {K}] ({sizes}, hop = {hop}, {n} samples), got "
+                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
+            raise ValueError(f"{who} ({sizes}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
+        if not (isinstance(profile, torch.Tensor) and profile.is_cuda and profile.dtype == torch.float32 and tuple(profile.shape) == (K,)):
+            raise ValueError(f"{who} ({sizes}): profile must be the float32 CUDA tensor [{K}] of make_spectrogram(..., return_profile=True)")
+        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dpcm
+        grad, stats, profile = grad.contiguous(), stats.contiguous(), profile.contiguous()
+        rc = self.lib.orcai_denoised_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, K, *self._bands(spectrogram_parameter, cfg), N.ptr(grad), N.ptr(stats),
+                                                     N.ptr(profile), TOP_DB, N.ptr(dpcm), N.stream_ptr())
+        N.check(rc, "orcai_denoised_spectrogram_bwd")
+        return dpcm
 
     # -- calculate_spectrogram (spectrogram.py:15-55): dB of all bins, referenced and floored ----
     def calculate_db(self, pcm: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:

@@ -700,6 +700,134 @@ def pcen_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: in
                                                     scale, q_lo, q_hi)
 
 
+# ---------------------------------------------------------------------------------------------------------------- orcai::denoised_spectrogram(_wrt_pcm)
+# The dB front end with the spectrogram parameter "denoise" set (orcai_make_denoised_spectrogram), on the linear bins 0 .. freq_hi (n_mels = 0) or on the mel
+# bands, as orcai::pcen_spectrogram chooses its route.  orcai::denoised_spectrogram is forward only, as the other plain front-end ops are (its backward
+# raises and names the differentiable op).  orcai::denoised_spectrogram_wrt_pcm is the same launch sequence (same bits); with a pcm that requires grad its
+# Autograd kernel runs orcai::denoised_spectrogram_with_stats, which also returns the six statistics and the noise profile f32[K], and its backward is the
+# functional op orcai::denoised_spectrogram_backward (FrontEnd.denoised_spectrogram_backward: orcai_denoised_spectrogram_bwd), which holds the
+# statistics AND the profile constant.  Not wired through _register_wrt_pcm: one more saved tensor, and FrontEnd.backward keeps refusing denoise.
+_DENOISED_ARGUMENTS = ("SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
+                       "float quantile, float q_lo, float q_hi")
+
+
+def _denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo=0.0, q_hi=1.0) -> dict:
+    if n_mels > 0:
+        sp = _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    else:
+        sp = _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+    sp["denoise"] = {"quantile": quantile}
+    return sp
+
+
+def _denoised_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, *rest):
+    return _spec_fake(pcm, nfft, hop, n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi))
+
+
+class _DenoisedSpectrogramFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pcm, *args):
+        with torch._C._AutoDispatchBelowAutograd():
+            return torch.ops.orcai.denoised_spectrogram(pcm, *args)
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("orcai::denoised_spectrogram has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
+                                  "orcai::denoised_spectrogram_wrt_pcm is the same computation with the gradient w.r.t. pcm")
+
+
+def _denoised_spectrogram_autograd(pcm, *args):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _DenoisedSpectrogramFunction.apply(pcm, *args)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.denoised_spectrogram(pcm, *args)
+
+
+_register("denoised_spectrogram", f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::denoised_spectrogram", _denoised_parameter),
+          _denoised_spectrogram_fake, _denoised_spectrogram_autograd)
+
+
+def _denoised_with_stats_impl(pcm, *args):
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::denoised_spectrogram_with_stats")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _denoised_parameter(*args), return_stats=True, return_profile=True)
+
+
+def _denoised_with_stats_fake(pcm, *args):
+    spec = _denoised_spectrogram_fake(pcm, *args)
+    return spec, pcm.new_empty((6,), dtype=torch.float32), pcm.new_empty((spec.shape[1],), dtype=torch.float32)
+
+
+def _denoised_backward_impl(grad, pcm, stats, profile, *args):
+    from orcai_amd.frontend import get_frontend
+
+    _check_pcm(pcm, "orcai::denoised_spectrogram_backward")
+    with torch.cuda.device(pcm.device):
+        return get_frontend(pcm.device).denoised_spectrogram_backward(pcm.detach(), grad.contiguous(), stats, profile, _denoised_parameter(*args))
+
+
+_FRONT_END_OPS["denoised_spectrogram_with_stats"] = torch.library.custom_op(
+    "orcai::denoised_spectrogram_with_stats", _denoised_with_stats_impl, mutates_args=(), schema=f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> (Tensor, Tensor, Tensor)")
+_FRONT_END_OPS["denoised_spectrogram_with_stats"].register_fake(_denoised_with_stats_fake)
+_FRONT_END_OPS["denoised_spectrogram_backward"] = torch.library.custom_op(
+    "orcai::denoised_spectrogram_backward", _denoised_backward_impl, mutates_args=(),
+    schema=f"(Tensor grad, Tensor pcm, Tensor stats, Tensor profile, {_DENOISED_ARGUMENTS.removesuffix(', float q_lo, float q_hi')}) -> Tensor")
+_FRONT_END_OPS["denoised_spectrogram_backward"].register_fake(lambda grad, pcm, stats, profile, *args: pcm.new_empty((pcm.shape[0],), dtype=torch.float32))
+
+
+def _denoised_gradient_sizes(sampling_rate, nfft, hop, freq_hi, n_mels, *rest) -> None:
+    """The linear route's forward takes sizes its backward does not (the mel route's refusals are mel.mel_config's, in the forward)."""
+    from orcai_amd.frontend import FrontEnd
+
+    if n_mels <= 0:
+        FrontEnd._check_nfft_backward(nfft)
+
+
+class _DenoisedWrtPcmFunction(torch.autograd.Function):
+    """forward(pcm, *args) of orcai::denoised_spectrogram_wrt_pcm(pcm, *args); the backward reads pcm, the statistics and the profile of that forward."""
+
+    @staticmethod
+    def forward(ctx, pcm, *args):
+        _denoised_gradient_sizes(*args)
+        with torch._C._AutoDispatchBelowAutograd():
+            spec, stats, profile = torch.ops.orcai.denoised_spectrogram_with_stats(pcm, *args)
+        ctx.args = args[:-2]
+        ctx.save_for_backward(pcm, stats, profile)
+        return spec
+
+    @staticmethod
+    def backward(ctx, grad):
+        pcm, stats, profile = ctx.saved_tensors
+        return (torch.ops.orcai.denoised_spectrogram_backward(grad, pcm, stats, profile, *ctx.args),) + (None,) * (2 + len(ctx.args))
+
+
+def _denoised_wrt_pcm_autograd(pcm, *args):
+    if torch.is_grad_enabled() and pcm.requires_grad:
+        return _DenoisedWrtPcmFunction.apply(pcm, *args)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.denoised_spectrogram_wrt_pcm(pcm, *args)
+
+
+_register("denoised_spectrogram_wrt_pcm", f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::denoised_spectrogram", _denoised_parameter),
+          _denoised_spectrogram_fake, _denoised_wrt_pcm_autograd)
+
+
+def denoised_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                         quantile: float, q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the denoise parameter {quantile}: n_mels = 0 on the bins 0 .. freq_hi,
+    n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1].  No gradient: denoised_spectrogram_wrt_pcm has it."""
+    return torch.ops.orcai.denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi)
+
+
+def denoised_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool,
+                                 slaney_norm: bool, quantile: float, q_lo: float, q_hi: float) -> Tensor:
+    """orcai::denoised_spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad, the per-channel floor held constant like the other
+    statistics; nfft a power of two from 32 (n_mels > 0: 128) to 4096.  No second derivative."""
+    return torch.ops.orcai.denoised_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi)
+
+
 # ---------------------------------------------------------------------------------------------------------------- orcai::resample
 # The project's polyphase resampler (orcai_amd/resample.py, what `orcai predict` runs on a recording that is not at the model's rate) as an op with
 # autograd w.r.t. the audio.  It is linear, so its backward is its adjoint with the same table: the functional op orcai::resample_backward
@@ -711,7 +839,8 @@ def _no_pcen(spectrogram_parameter: dict, who: str) -> None:
 
 
 def _no_denoise(spectrogram_parameter: dict, who: str) -> None:
-    """The differentiable modules run the *_wrt_pcm ops, which have no denoise argument: a parameter that asks for it is refused, not silently run without."""
+    """The plain differentiable modules run *_wrt_pcm ops that have no denoise argument: a parameter that asks for it is refused, not silently run without
+    (DenoisedWaveformFrontEnd is the module for it)."""
     from orcai_amd import denoise
 
     denoise.no_gradient(spectrogram_parameter, who)
@@ -840,15 +969,18 @@ _register("decode_pcm", "(Tensor frames, SymInt channels, SymInt channel, SymInt
 
 
 class _WaveformFrontEnd(torch.nn.Module):
-    """What the three front-end modules share: forward(pcm f32[n] at native_rate) = orcai::<_op>(resample(pcm, native_rate, sampling_rate), sampling_rate,
-    nfft, hop, *_args, q_lo, q_hi).  A subclass names its op, refuses in _route what is not its route and keeps there what _args and extra_repr read."""
+    """What the four front-end modules share: forward(pcm f32[n] at native_rate) = orcai::<_op>(resample(pcm, native_rate, sampling_rate), sampling_rate,
+    nfft, hop, *_args, q_lo, q_hi).  A subclass names its op, refuses in _route what is not its route and keeps there what _args and extra_repr read.
+    Only the subclass whose op takes the denoise quantile (_denoised) accepts a parameter with ``denoise`` set."""
 
     _op: str
+    _denoised = False
 
     def __init__(self, spectrogram_parameter: dict, native_rate: int):
         super().__init__()
         sp = spectrogram_parameter
-        _no_denoise(sp, type(self).__name__)
+        if not self._denoised:
+            _no_denoise(sp, type(self).__name__)
         self._route(sp)
         self.native_rate = int(native_rate)
         self.sampling_rate, self.nfft, self.hop = int(sp["sampling_rate"]), int(sp["nfft"]), int(sp["n_overlap"])
@@ -946,10 +1078,47 @@ class PcenWaveformFrontEnd(_WaveformFrontEnd):
                 + f", time_constant={self.pcen[0]}, gain={self.pcen[1]}, bias={self.pcen[2]}, power={self.pcen[3]}, eps={self.pcen[4]}, scale={self.pcen[5]}")
 
 
+class DenoisedWaveformFrontEnd(_WaveformFrontEnd):
+    """WaveformFrontEnd for a spectrogram parameter whose ``denoise`` key is set, on either route (the mel one when ``mel`` is set as well):
+    forward(pcm f32[n] at native_rate) = denoised_spectrogram_wrt_pcm(resample(pcm, native_rate, sampling_rate), ...) -> [T, K], differentiable down to
+    those samples.  The parameter is validated as denoise.denoise_config (which refuses ``pcen`` beside it) and mel.mel_config do; ref_db, p_lo, p_hi and
+    the per-channel floor are held constant in the backward."""
+
+    _op = "denoised_spectrogram_wrt_pcm"
+    _denoised = True
+
+    def _route(self, sp: dict) -> None:
+        from orcai_amd import denoise, mel
+        from orcai_amd.frontend import FrontEnd
+
+        dn = denoise.denoise_config(sp)
+        if dn is None:
+            raise ValueError("DenoisedWaveformFrontEnd: spectrogram parameter denoise is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
+                             "native_rate) returns the dB front end for it")
+        cfg = mel.mel_config(sp)
+        if cfg is None:
+            FrontEnd._check_nfft_backward(sp["nfft"])
+            if float(sp["freq_range"][0]) != 0.0:
+                raise ValueError(f"DenoisedWaveformFrontEnd: freq_range must start at 0 (orcai::denoised_spectrogram keeps the leading bins), got {sp['freq_range']}")
+            self.route = (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
+        else:
+            self.route = (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
+        self.quantile = dn["quantile"]
+
+    @property
+    def _args(self) -> tuple:
+        return (*self.route, self.quantile)
+
+    def extra_repr(self) -> str:
+        freq_hi, n_mels = self.route[:2]
+        return super().extra_repr() + (f"n_mels={n_mels}" if n_mels else f"freq_hi={freq_hi}") + f", denoise.quantile={self.quantile}"
+
+
 def waveform_front_end(spectrogram_parameter: dict, native_rate: int) -> torch.nn.Module:
     """The differentiable dB front end of a parameter file's "spectrogram" section: MelWaveformFrontEnd when its ``mel`` key is set, WaveformFrontEnd
     when it is absent or null.  A parameter whose ``pcen`` key is set is refused by both (NotImplementedError): PcenWaveformFrontEnd is its class.  A
-    parameter whose ``denoise`` key is set is refused by all of them (NotImplementedError that names denoise: forward only)."""
+    parameter whose ``denoise`` key is set is refused here and by all three (NotImplementedError that names denoise and DenoisedWaveformFrontEnd, its
+    class: these run the plain dB ops, whose forward and gradient know no floor)."""
     _no_denoise(spectrogram_parameter, "waveform_front_end")
     if spectrogram_parameter.get("mel") is not None:
         return MelWaveformFrontEnd(spectrogram_parameter, native_rate)
