@@ -200,13 +200,12 @@ class FrontEnd:
             raise NotImplementedError(f"spectrogram parameter nfft = {n_fft}: the gradient w.r.t. the audio is implemented for powers of two from 32 to "
                                       "4096 (512, the value of orcai-V1, included); the forward runs every size from 2 to 4096")
 
-    def backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict, who: str = "backward") -> torch.Tensor:
-        """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
-        returned for the same pcm, on the route the parameter asks for: orcai_pcen_spectrogram_bwd with pcen set (on the mel bands when mel is set
-        too), orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  ref_db, p_lo and p_hi are constants of the backward; the
-        filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry.  A parameter with denoise
-        set is refused first (denoise.no_gradient): its gradient is denoised_spectrogram_backward, which also takes the profile."""
-        denoise.no_gradient(spectrogram_parameter, who)
+    def _backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict, who: str, profile: torch.Tensor | None = None):
+        """The one body behind backward and denoised_spectrogram_backward: the parameter's and the tensors' refusals under the name who, then the C call
+        of the route -- orcai_denoised_spectrogram_bwd with denoise set (the only route that reads profile), else orcai_pcen_spectrogram_bwd with pcen
+        set, orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  denoise.denoise_config has already run in either caller's own
+        refusal; running it here again is what keeps the order of the refusals with one body."""
+        dn = denoise.denoise_config(spectrogram_parameter)  # before the route: {denoise, pcen} is refused, not resolved as a PCEN route
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
             self._check_nfft_backward(n_fft)
@@ -221,12 +220,19 @@ class FrontEnd:
                              f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
         if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
             raise ValueError(f"{who} ({sizes}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
+        if dn is not None and not (isinstance(profile, torch.Tensor) and profile.is_cuda and profile.dtype == torch.float32 and tuple(profile.shape) == (K,)):
+            raise ValueError(f"{who} ({sizes}): profile must be the float32 CUDA tensor [{K}] of make_spectrogram(..., return_profile=True)")
         dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
         if n == 0:
             return dpcm
         signal = (N.ptr(pcm), n, n_fft, hop, T, K)
         grad, stats = grad.contiguous(), stats.contiguous()
-        if pc is not None:
+        if dn is not None:
+            profile = profile.contiguous()
+            rc = self.lib.orcai_denoised_spectrogram_bwd(*signal, *self._bands(spectrogram_parameter, cfg), N.ptr(grad), N.ptr(stats), N.ptr(profile), TOP_DB,
+                                                         N.ptr(dpcm), N.stream_ptr())
+            N.check(rc, "orcai_denoised_spectrogram_bwd")
+        elif pc is not None:
             a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
             scratch = self._grown("pcen_bwd", self.lib.orcai_pcen_spectrogram_bwd_scratch_bytes(T, K) // 4)
             rc = self.lib.orcai_pcen_spectrogram_bwd(*signal, *self._bands(spectrogram_parameter, cfg), a, b, pc["scale"], pc["gain"], pc["bias"], pc["power"],
@@ -240,7 +246,16 @@ class FrontEnd:
             N.check(self.lib.orcai_spectrogram_bwd(*signal, N.ptr(grad), N.ptr(stats), TOP_DB, N.ptr(dpcm), N.stream_ptr()), "orcai_spectrogram_bwd")
         return dpcm
 
-    # The three named entries: each insists on its own route and is `backward` otherwise.
+    def backward(self, pcm: torch.Tensor, grad: torch.Tensor, stats: torch.Tensor, spectrogram_parameter: dict, who: str = "backward") -> torch.Tensor:
+        """dL/dpcm f32[N] from grad = dL/d(make_spectrogram(pcm)) f32[T, K] and the f32[6] statistics make_spectrogram(..., return_stats=True)
+        returned for the same pcm, on the route the parameter asks for: orcai_pcen_spectrogram_bwd with pcen set (on the mel bands when mel is set
+        too), orcai_mel_spectrogram_bwd with mel alone, orcai_spectrogram_bwd otherwise.  ref_db, p_lo and p_hi are constants of the backward; the
+        filterbank weights and the PCEN parameters get no gradient (include/orcai_hip.h).  who: the name the refusals carry.  A parameter with denoise
+        set is refused first (denoise.no_gradient): its gradient is denoised_spectrogram_backward, which also takes the profile."""
+        denoise.no_gradient(spectrogram_parameter, who)
+        return self._backward(pcm, grad, stats, spectrogram_parameter, who)
+
+    # The named entries: each insists on its own route and is `_backward` otherwise.
     @staticmethod
     def _no_pcen_gradient(spectrogram_parameter: dict, who: str) -> None:
         if pcen.pcen_config(spectrogram_parameter) is not None:
@@ -285,30 +300,7 @@ class FrontEnd:
         if denoise.denoise_config(spectrogram_parameter) is None:
             raise ValueError(f"{who}: the spectrogram parameter denoise is absent or null; FrontEnd.spectrogram_backward and FrontEnd.mel_spectrogram_backward "
                              "are the gradients of the plain dB front ends (FrontEnd.pcen_spectrogram_backward of the PCEN one)")
-        n_fft, hop, K, cfg, _ = resolve_route(spectrogram_parameter)
-        if cfg is None:  # (mel.mel_config has refused what the mel route does not differentiate)
-            self._check_nfft_backward(n_fft)
-        if hop < 1:
-            raise ValueError(f"spectrogram parameter n_overlap = {hop} (the hop) must be positive; nfft = {n_fft}")
-        pcm = self._check_pcm(pcm)
-        n = pcm.numel()
-        T = n_frames(n, n_fft, hop)
-        sizes = f"nfft = {n_fft}" if cfg is None else f"nfft = {n_fft}, n_mels = {K}"
-        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32 and tuple(grad.shape) == (T, K)):
-            raise ValueError(f"{who}: grad must be a float32 CUDA tensor [{T}, {K}] ({sizes}, hop = {hop}, {n} samples), got "
-                             f"{getattr(grad, 'dtype', None)} {tuple(getattr(grad, 'shape', ()))}")
-        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (6,)):
-            raise ValueError(f"{who} ({sizes}): stats must be the float32 CUDA tensor [6] of make_spectrogram(..., return_stats=True)")
-        if not (isinstance(profile, torch.Tensor) and profile.is_cuda and profile.dtype == torch.float32 and tuple(profile.shape) == (K,)):
-            raise ValueError(f"{who} ({sizes}): profile must be the float32 CUDA tensor [{K}] of make_spectrogram(..., return_profile=True)")
-        dpcm = torch.empty(n, dtype=torch.float32, device=self.device)
-        if n == 0:
-            return dpcm
-        grad, stats, profile = grad.contiguous(), stats.contiguous(), profile.contiguous()
-        rc = self.lib.orcai_denoised_spectrogram_bwd(N.ptr(pcm), n, n_fft, hop, T, K, *self._bands(spectrogram_parameter, cfg), N.ptr(grad), N.ptr(stats),
-                                                     N.ptr(profile), TOP_DB, N.ptr(dpcm), N.stream_ptr())
-        N.check(rc, "orcai_denoised_spectrogram_bwd")
-        return dpcm
+        return self._backward(pcm, grad, stats, spectrogram_parameter, who, profile=profile)
 
     # -- calculate_spectrogram (spectrogram.py:15-55): dB of all bins, referenced and floored ----
     def calculate_db(self, pcm: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:

@@ -10,6 +10,8 @@ known without a GPU.
     torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
                                      scale, q_lo, q_hi) -> f32[T, K]
     torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
+    torch.ops.orcai.denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi) -> f32[T, K]
+    torch.ops.orcai.denoised_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
     torch.ops.orcai.percentile(x f32[...], q) -> f32[len(q)]
     torch.ops.orcai.column_percentile(x f32[R, ...], q) -> f32[len(q), ...]   (per column of [R, C]: np.percentile(x, 100 q, axis=0, method="nearest"))
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
@@ -33,18 +35,23 @@ still alive raises instead of overwriting what that graph's backward needs (``fo
 whose training-mode backward also delivers dL/dx (``orcai_conv0_bn_bwd_dx``), for anything trainable or differentiable in front of the
 detector.
 
-The front end has three routes, one op each, all ``FrontEnd.make_spectrogram``: ``spectrogram`` (the bins 0 .. freq_hi in dB; ``orcai_make_spectrogram``),
-``mel_spectrogram`` (the spectrogram parameter ``mel``: filterbank and dB fused into the STFT kernel, no frequency crop; ``orcai_make_mel_spectrogram``) and
-``pcen_spectrogram`` (the spectrogram parameter ``pcen``, orcai_amd/pcen.py; ``orcai_make_pcen_spectrogram``: n_mels = 0 is PCEN of the magnitudes of the bins
-0 .. freq_hi and the mel arguments are ignored, n_mels > 0 PCEN of the mel band powers and freq_hi is ignored).  These three are forward only: they have fake
-implementations and NO autograd of their own (a backward through ``pcen_spectrogram`` raises NotImplementedError that names ``pcen_spectrogram_wrt_pcm``).  Each has a
-differentiable twin built by one wiring (``_register_wrt_pcm``): ``<op>_wrt_pcm`` is the same computation (same bits) whose backward delivers dL/dpcm through
-the functional op ``orcai::<op>_backward(grad, pcm, stats, <the arguments but the quantiles>)`` -- ``FrontEnd.backward``, i.e. ``orcai_spectrogram_bwd``,
-``orcai_mel_spectrogram_bwd`` or ``orcai_pcen_spectrogram_bwd`` -- from the six statistics ``orcai::<op>_with_stats`` returned beside the forward; the
-normalisation statistics are held constant, the filterbank weights and the PCEN parameters get no gradient.  So the chain pcm -> spectrogram -> snippets ->
-probabilities is differentiable down to the waveform.  ``WaveformFrontEnd``, ``MelWaveformFrontEnd`` and ``PcenWaveformFrontEnd`` are resample + the route's
-``_wrt_pcm`` op as a ``torch.nn.Module``; each refuses a parameter of another route, and ``waveform_front_end(spectrogram_parameter, native_rate)`` returns
-whichever of the first two the parameter asks for (a parameter whose ``pcen`` key is set: NotImplementedError that names ``PcenWaveformFrontEnd``).
+The front end has four routes, one op each, all ``FrontEnd.make_spectrogram``: ``spectrogram`` (the bins 0 .. freq_hi in dB; ``orcai_make_spectrogram``),
+``mel_spectrogram`` (the spectrogram parameter ``mel``: filterbank and dB fused into the STFT kernel, no frequency crop; ``orcai_make_mel_spectrogram``),
+``pcen_spectrogram`` (the spectrogram parameter ``pcen``, orcai_amd/pcen.py; ``orcai_make_pcen_spectrogram``) and ``denoised_spectrogram`` (the spectrogram
+parameter ``denoise``, orcai_amd/denoise.py; ``orcai_make_denoised_spectrogram``; its arguments are pcen_spectrogram's with ``quantile`` in place of the six PCEN
+values).  The last two choose between the linear and the mel route themselves: n_mels = 0 is the bins 0 .. freq_hi and the mel arguments are ignored,
+n_mels > 0 the mel bands and freq_hi is ignored.  These four are forward only: they have fake implementations and no gradient (``spectrogram`` and
+``mel_spectrogram`` have NO autograd of their own; a backward through ``pcen_spectrogram`` or ``denoised_spectrogram`` raises NotImplementedError that names the
+op's ``_wrt_pcm`` twin).  Each has a differentiable twin built by one wiring (``_register_wrt_pcm``): ``<op>_wrt_pcm`` is the same computation (same bits) whose
+backward delivers dL/dpcm through the functional op ``orcai::<op>_backward(grad, pcm, stats, <the arguments but the quantiles>)`` -- ``FrontEnd.backward``, i.e.
+``orcai_spectrogram_bwd``, ``orcai_mel_spectrogram_bwd`` or ``orcai_pcen_spectrogram_bwd`` -- from the six statistics ``orcai::<op>_with_stats`` returned beside
+the forward.  The denoised route saves one tensor more: ``orcai::denoised_spectrogram_with_stats`` also returns the noise profile f32[K], and
+``orcai::denoised_spectrogram_backward(grad, pcm, stats, profile, ...)`` is ``FrontEnd.denoised_spectrogram_backward`` (``orcai_denoised_spectrogram_bwd``).  The
+normalisation statistics and the profile are held constant, the filterbank weights and the PCEN parameters get no gradient.  So the chain pcm -> spectrogram ->
+snippets -> probabilities is differentiable down to the waveform.  ``WaveformFrontEnd``, ``MelWaveformFrontEnd``, ``PcenWaveformFrontEnd`` and
+``DenoisedWaveformFrontEnd`` are resample + the route's ``_wrt_pcm`` op as a ``torch.nn.Module``; each refuses a parameter of another route, and
+``waveform_front_end(spectrogram_parameter, native_rate)`` returns whichever of the first two the parameter asks for (a parameter whose ``pcen`` or ``denoise`` key
+is set: NotImplementedError that names ``PcenWaveformFrontEnd`` or ``DenoisedWaveformFrontEnd``).
 ``resample`` is the polyphase resampler ``orcai predict`` runs on a recording that is not at the model's rate (``resample_device``,
 same bits) with autograd w.r.t. the audio: it is linear, so its backward, the functional op ``orcai::resample_backward(grad, n_in, sr_in,
 sr_out)``, is its adjoint with the same filter table (``orcai_resample_polyphase_bwd``; no float atomics, two runs give the same bits).
@@ -75,7 +82,7 @@ What does not exist: a weight gradient in eval mode on the f16 path, the CLI ``o
 a backward of ``orcai::predict_spectrogram`` itself (the shared-trunk kernels are not differentiated: ``detect_recording`` recomputes the snippets as a batch),
 any input gradient on the f16 path (f32 models only); ``orcai::spectrogram`` and ``orcai::mel_spectrogram``
 themselves have no backward, the mel filterbank weights and the three normalisation statistics get no gradient, and ``orcai::resample`` /
-``orcai::resample_backward`` and the three front-end backwards have no second derivative.
+``orcai::resample_backward`` and the four front-end backwards have no second derivative.
 """
 
 from __future__ import annotations
@@ -299,7 +306,7 @@ def _spec_fake(pcm, nfft, hop, K):
     return pcm.new_empty((n_frames(pcm.shape[0], nfft, hop), K), dtype=torch.float32)
 
 
-def _front_end_impl(who: str, parameter, return_stats: bool = False):
+def _front_end_impl(who: str, parameter, return_stats: bool = False, return_profile: bool = False):
     """The kernel of a front-end op (pcm, *args): FrontEnd.make_spectrogram with the spectrogram parameter that `parameter` makes of args."""
 
     def impl(pcm, *args):
@@ -307,7 +314,7 @@ def _front_end_impl(who: str, parameter, return_stats: bool = False):
 
         _check_pcm(pcm, who)
         with torch.cuda.device(pcm.device):
-            return get_frontend(pcm.device).make_spectrogram(pcm.detach(), parameter(*args), return_stats=return_stats)
+            return get_frontend(pcm.device).make_spectrogram(pcm.detach(), parameter(*args), return_stats=return_stats, return_profile=return_profile)
 
     return impl
 
@@ -356,45 +363,65 @@ def _mel_spectrogram_fake(pcm, sampling_rate, nfft, hop, n_mels, fmin, fmax, htk
     return _spec_fake(pcm, nfft, hop, n_mels)
 
 
-# ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram
-# The front end with the spectrogram parameter "pcen" set (orcai_make_pcen_spectrogram), beside the linear and the mel op.  Forward only: the op HAS
-# an autograd registration, whose backward raises a NotImplementedError that names orcai::pcen_spectrogram_wrt_pcm (further down), the differentiable one.
-def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo=0.0, q_hi=1.0) -> dict:
+# ---------------------------------------------------------------------------------------------------------------- orcai::pcen_spectrogram, orcai::denoised_spectrogram
+# The front end with the spectrogram parameter "pcen" (orcai_make_pcen_spectrogram) or "denoise" (orcai_make_denoised_spectrogram) set, beside the linear
+# and the mel op.  Both choose their route by n_mels: 0 is the bins 0 .. freq_hi and the mel arguments are ignored, n_mels > 0 the mel bands and freq_hi
+# is ignored.  Forward only: each op HAS an autograd registration (_register_forward_only), whose backward raises a NotImplementedError that names
+# orcai::<op>_wrt_pcm (further down), the differentiable one.
+def _linear_or_mel_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi) -> dict:
     if n_mels > 0:
-        sp = _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-    else:
-        sp = _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+        return _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    return _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
+
+
+def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale, q_lo=0.0, q_hi=1.0) -> dict:
+    sp = _linear_or_mel_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
     sp["pcen"] = {"time_constant": time_constant, "gain": gain, "bias": bias, "power": power, "eps": eps, "scale": scale}
     return sp
 
 
-def _pcen_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, *rest):
+def _denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo=0.0, q_hi=1.0) -> dict:
+    sp = _linear_or_mel_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    sp["denoise"] = {"quantile": quantile}
+    return sp
+
+
+def _linear_or_mel_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, *rest):
     return _spec_fake(pcm, nfft, hop, n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi))
 
 
-class _PcenSpectrogramFunction(torch.autograd.Function):
+class _ForwardOnlyFunction(torch.autograd.Function):
+    """forward(pcm, base, *args) of orcai::<base>(pcm, *args), an op that runs under autograd and has no gradient."""
+
     @staticmethod
-    def forward(ctx, pcm, *args):
+    def forward(ctx, pcm, base, *args):
+        ctx.base = base
         with torch._C._AutoDispatchBelowAutograd():
-            return torch.ops.orcai.pcen_spectrogram(pcm, *args)
+            return getattr(torch.ops.orcai, base)(pcm, *args)
 
     @staticmethod
     def backward(ctx, grad):
-        raise NotImplementedError("orcai::pcen_spectrogram has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
-                                  "orcai::pcen_spectrogram_wrt_pcm is the same computation with the gradient w.r.t. pcm")
+        raise NotImplementedError(f"orcai::{ctx.base} has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
+                                  f"orcai::{ctx.base}_wrt_pcm is the same computation with the gradient w.r.t. pcm")
 
 
-def _pcen_spectrogram_autograd(pcm, *args):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _PcenSpectrogramFunction.apply(pcm, *args)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.pcen_spectrogram(pcm, *args)
+def _register_forward_only(base: str, schema: str, parameter) -> None:
+    """orcai::<base>(pcm, <schema>), one of the two ops above."""
+
+    def autograd(pcm, *args):
+        if torch.is_grad_enabled() and pcm.requires_grad:
+            return _ForwardOnlyFunction.apply(pcm, base, *args)
+        with torch._C._AutoDispatchBelowAutograd():
+            return getattr(torch.ops.orcai, base)(pcm, *args)
+
+    _register(base, f"(Tensor pcm, {schema}) -> Tensor", _front_end_impl("orcai::" + base, parameter), _linear_or_mel_fake, autograd)
 
 
-_PCEN_ARGUMENTS = ("SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
-                   "float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi")
-_register("pcen_spectrogram", f"(Tensor pcm, {_PCEN_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::pcen_spectrogram", _pcen_parameter), _pcen_spectrogram_fake,
-          _pcen_spectrogram_autograd)
+_ROUTE_ARGUMENTS = "SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
+_PCEN_ARGUMENTS = _ROUTE_ARGUMENTS + "float time_constant, float gain, float bias, float power, float eps, float scale, float q_lo, float q_hi"
+_DENOISED_ARGUMENTS = _ROUTE_ARGUMENTS + "float quantile, float q_lo, float q_hi"
+_register_forward_only("pcen_spectrogram", _PCEN_ARGUMENTS, _pcen_parameter)
+_register_forward_only("denoised_spectrogram", _DENOISED_ARGUMENTS, _denoised_parameter)
 
 
 def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
@@ -404,6 +431,13 @@ def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_
     pcen_spectrogram_wrt_pcm has it."""
     return torch.ops.orcai.pcen_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps, scale,
                                             q_lo, q_hi)
+
+
+def denoised_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
+                         quantile: float, q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the denoise parameter {quantile}: n_mels = 0 on the bins 0 .. freq_hi,
+    n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1].  No gradient: denoised_spectrogram_wrt_pcm has it."""
+    return torch.ops.orcai.denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::percentile
@@ -611,47 +645,59 @@ _register("forward_wrt_input", _FORWARD_SCHEMA, _forward_impl, _probs_fake, _tra
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::*_wrt_pcm
-# The three front-end ops with the gradient w.r.t. the audio, for anything trainable or differentiable in the WAVEFORM domain in front of the detector
+# The four front-end ops with the gradient w.r.t. the audio, for anything trainable or differentiable in the WAVEFORM domain in front of the detector
 # (a learnable band-pass or denoiser on the hydrophone signal, adversarial or gradient-penalty robustness on audio, saliency of a detection in the
-# recording).  Each is its own op, as forward_wrt_input is: the schema and behaviour of orcai::<base> stay what they are.  One wiring serves the three
+# recording).  Each is its own op, as forward_wrt_input is: the schema and behaviour of orcai::<base> stay what they are.  One wiring serves the four
 # routes (_register_wrt_pcm): orcai::<base>_wrt_pcm runs the same launch sequence as orcai::<base> (same bits); with a pcm that requires grad its
-# Autograd kernel runs orcai::<base>_with_stats instead, which also returns the run's six statistics (orcai_frontend_stats_dev), and its backward is the
-# functional op orcai::<base>_backward (FrontEnd.backward), which holds the statistics constant (include/orcai_hip.h).
+# Autograd kernel runs orcai::<base>_with_stats instead, which also returns the run's six statistics (orcai_frontend_stats_dev) -- and, on the denoised
+# route, the noise profile f32[K] -- and its backward is the functional op orcai::<base>_backward (FrontEnd.backward; FrontEnd.denoised_spectrogram_backward
+# on the denoised route), which holds what the forward saved constant (include/orcai_hip.h).
 class _WrtPcmFunction(torch.autograd.Function):
     """forward(pcm, base, check, *args) of orcai::<base>_wrt_pcm(pcm, *args); check(*args), when given, refuses before the forward what the backward
-    could not differentiate.  All of args but the two quantiles go to the backward op."""
+    could not differentiate.  What orcai::<base>_with_stats returns after the spectrogram is saved beside pcm and goes to the backward op in that order,
+    followed by all of args but the two quantiles."""
 
     @staticmethod
     def forward(ctx, pcm, base, check, *args):
         if check is not None:
             check(*args)
         with torch._C._AutoDispatchBelowAutograd():
-            spec, stats = getattr(torch.ops.orcai, base + "_with_stats")(pcm, *args)
+            spec, stats, *extras = getattr(torch.ops.orcai, base + "_with_stats")(pcm, *args)
         ctx.backward_op, ctx.args, ctx.n_inputs = getattr(torch.ops.orcai, base + "_backward"), args[:-2], 2 + len(args)
-        ctx.save_for_backward(pcm, stats)
+        ctx.save_for_backward(pcm, stats, *extras)
         return spec
 
     @staticmethod
     def backward(ctx, grad):
-        pcm, stats = ctx.saved_tensors
-        return (ctx.backward_op(grad, pcm, stats, *ctx.args),) + (None,) * ctx.n_inputs
+        pcm, stats, *extras = ctx.saved_tensors
+        return (ctx.backward_op(grad, pcm, stats, *extras, *ctx.args),) + (None,) * ctx.n_inputs
 
 
 _FRONT_END_OPS: dict = {}  # name -> CustomOpDef of the inner ops (torch refers to a definition weakly: dropping it would unregister the op)
 
 
-def _register_wrt_pcm(base: str, schema: str, parameter, fake, check=None) -> None:
+def _register_wrt_pcm(base: str, schema: str, parameter, fake, check=None, profile: bool = False) -> None:
     """orcai::<base>_wrt_pcm, orcai::<base>_with_stats and orcai::<base>_backward.  schema: the arguments of orcai::<base> after pcm, the two
-    quantiles last; parameter: the spectrogram parameter of those arguments (the quantiles optional); fake: orcai::<base>'s fake implementation."""
+    quantiles last; parameter: the spectrogram parameter of those arguments (the quantiles optional); fake: orcai::<base>'s fake implementation.
+    profile: the route's backward also reads the noise profile f32[K] -- orcai::<base>_with_stats returns it third, orcai::<base>_backward takes it
+    after stats."""
     no_quantiles = schema.removesuffix(", float q_lo, float q_hi")
     assert no_quantiles != schema, schema
 
-    def backward_impl(grad, pcm, stats, *args):
+    def with_stats_fake(pcm, *args):
+        spec = fake(pcm, *args)
+        shapes = ((6,), (spec.shape[1],)) if profile else ((6,),)
+        return (spec, *(pcm.new_empty(shape, dtype=torch.float32) for shape in shapes))
+
+    def backward_impl(grad, pcm, stats, *rest):
         from orcai_amd.frontend import get_frontend
 
         _check_pcm(pcm, f"orcai::{base}_backward")
         with torch.cuda.device(pcm.device):
-            return get_frontend(pcm.device).backward(pcm.detach(), grad.contiguous(), stats, parameter(*args), who=base + "_backward")
+            fe = get_frontend(pcm.device)
+            if profile:
+                return fe.denoised_spectrogram_backward(pcm.detach(), grad.contiguous(), stats, rest[0], parameter(*rest[1:]))
+            return fe.backward(pcm.detach(), grad.contiguous(), stats, parameter(*rest), who=base + "_backward")
 
     def autograd(pcm, *args):
         if torch.is_grad_enabled() and pcm.requires_grad:
@@ -659,27 +705,35 @@ def _register_wrt_pcm(base: str, schema: str, parameter, fake, check=None) -> No
         with torch._C._AutoDispatchBelowAutograd():
             return getattr(torch.ops.orcai, base + "_wrt_pcm")(pcm, *args)
 
-    with_stats = torch.library.custom_op(f"orcai::{base}_with_stats", _front_end_impl(f"orcai::{base}_with_stats", parameter, return_stats=True), mutates_args=(),
-                                         schema=f"(Tensor pcm, {schema}) -> (Tensor, Tensor)")
-    with_stats.register_fake(lambda pcm, *args: (fake(pcm, *args), pcm.new_empty((6,), dtype=torch.float32)))
-    backward = torch.library.custom_op(f"orcai::{base}_backward", backward_impl, mutates_args=(), schema=f"(Tensor grad, Tensor pcm, Tensor stats, {no_quantiles}) -> Tensor")
-    backward.register_fake(lambda grad, pcm, stats, *args: pcm.new_empty((pcm.shape[0],), dtype=torch.float32))
+    saved, returns = ("Tensor stats, Tensor profile", "(Tensor, Tensor, Tensor)") if profile else ("Tensor stats", "(Tensor, Tensor)")
+    with_stats = torch.library.custom_op(f"orcai::{base}_with_stats", _front_end_impl(f"orcai::{base}_with_stats", parameter, return_stats=True, return_profile=profile),
+                                         mutates_args=(), schema=f"(Tensor pcm, {schema}) -> {returns}")
+    with_stats.register_fake(with_stats_fake)
+    backward = torch.library.custom_op(f"orcai::{base}_backward", backward_impl, mutates_args=(), schema=f"(Tensor grad, Tensor pcm, {saved}, {no_quantiles}) -> Tensor")
+    backward.register_fake(lambda grad, pcm, *rest: pcm.new_empty((pcm.shape[0],), dtype=torch.float32))
     _FRONT_END_OPS[base + "_with_stats"], _FRONT_END_OPS[base + "_backward"] = with_stats, backward
     _register(base + "_wrt_pcm", f"(Tensor pcm, {schema}) -> Tensor", _front_end_impl("orcai::" + base, parameter), fake, autograd)
 
 
 def _linear_gradient_sizes(sampling_rate, nfft, *rest) -> None:
-    """Of the three routes only the linear one has a forward that takes sizes its backward does not."""
+    """The linear route has a forward that takes sizes its backward does not."""
     from orcai_amd.frontend import FrontEnd
 
     FrontEnd._check_nfft_backward(nfft)
+
+
+def _denoised_gradient_sizes(sampling_rate, nfft, hop, freq_hi, n_mels, *rest) -> None:
+    """So has the denoised route on the linear bins (the mel route's refusals are mel.mel_config's, in the forward)."""
+    if n_mels <= 0:
+        _linear_gradient_sizes(sampling_rate, nfft)
 
 
 _register_wrt_pcm("spectrogram", "SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, float q_lo, float q_hi", _spectrogram_parameter, _spectrogram_fake,
                   check=_linear_gradient_sizes)
 _register_wrt_pcm("mel_spectrogram", "SymInt sampling_rate, SymInt nfft, SymInt hop, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
                   "float q_lo, float q_hi", _mel_parameter, _mel_spectrogram_fake)
-_register_wrt_pcm("pcen_spectrogram", _PCEN_ARGUMENTS, _pcen_parameter, _pcen_spectrogram_fake)
+_register_wrt_pcm("pcen_spectrogram", _PCEN_ARGUMENTS, _pcen_parameter, _linear_or_mel_fake)
+_register_wrt_pcm("denoised_spectrogram", _DENOISED_ARGUMENTS, _denoised_parameter, _linear_or_mel_fake, check=_denoised_gradient_sizes, profile=True)
 
 
 def spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, q_lo: float, q_hi: float) -> Tensor:
@@ -698,127 +752,6 @@ def pcen_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: in
     """orcai::pcen_spectrogram (same bits) whose backward returns dL/dpcm when pcm requires grad; nfft a power of two from 32 (n_mels > 0: 128) to 4096."""
     return torch.ops.orcai.pcen_spectrogram_wrt_pcm(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, time_constant, gain, bias, power, eps,
                                                     scale, q_lo, q_hi)
-
-
-# ---------------------------------------------------------------------------------------------------------------- orcai::denoised_spectrogram(_wrt_pcm)
-# The dB front end with the spectrogram parameter "denoise" set (orcai_make_denoised_spectrogram), on the linear bins 0 .. freq_hi (n_mels = 0) or on the mel
-# bands, as orcai::pcen_spectrogram chooses its route.  orcai::denoised_spectrogram is forward only, as the other plain front-end ops are (its backward
-# raises and names the differentiable op).  orcai::denoised_spectrogram_wrt_pcm is the same launch sequence (same bits); with a pcm that requires grad its
-# Autograd kernel runs orcai::denoised_spectrogram_with_stats, which also returns the six statistics and the noise profile f32[K], and its backward is the
-# functional op orcai::denoised_spectrogram_backward (FrontEnd.denoised_spectrogram_backward: orcai_denoised_spectrogram_bwd), which holds the
-# statistics AND the profile constant.  Not wired through _register_wrt_pcm: one more saved tensor, and FrontEnd.backward keeps refusing denoise.
-_DENOISED_ARGUMENTS = ("SymInt sampling_rate, SymInt nfft, SymInt hop, float freq_hi, SymInt n_mels, float fmin, float fmax, bool htk, bool slaney_norm, "
-                       "float quantile, float q_lo, float q_hi")
-
-
-def _denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo=0.0, q_hi=1.0) -> dict:
-    if n_mels > 0:
-        sp = _mel_parameter(sampling_rate, nfft, hop, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
-    else:
-        sp = _spectrogram_parameter(sampling_rate, nfft, hop, freq_hi, q_lo, q_hi)
-    sp["denoise"] = {"quantile": quantile}
-    return sp
-
-
-def _denoised_spectrogram_fake(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, *rest):
-    return _spec_fake(pcm, nfft, hop, n_mels if n_mels > 0 else _bins(sampling_rate, nfft, freq_hi))
-
-
-class _DenoisedSpectrogramFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pcm, *args):
-        with torch._C._AutoDispatchBelowAutograd():
-            return torch.ops.orcai.denoised_spectrogram(pcm, *args)
-
-    @staticmethod
-    def backward(ctx, grad):
-        raise NotImplementedError("orcai::denoised_spectrogram has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
-                                  "orcai::denoised_spectrogram_wrt_pcm is the same computation with the gradient w.r.t. pcm")
-
-
-def _denoised_spectrogram_autograd(pcm, *args):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _DenoisedSpectrogramFunction.apply(pcm, *args)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.denoised_spectrogram(pcm, *args)
-
-
-_register("denoised_spectrogram", f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::denoised_spectrogram", _denoised_parameter),
-          _denoised_spectrogram_fake, _denoised_spectrogram_autograd)
-
-
-def _denoised_with_stats_impl(pcm, *args):
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::denoised_spectrogram_with_stats")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).make_spectrogram(pcm.detach(), _denoised_parameter(*args), return_stats=True, return_profile=True)
-
-
-def _denoised_with_stats_fake(pcm, *args):
-    spec = _denoised_spectrogram_fake(pcm, *args)
-    return spec, pcm.new_empty((6,), dtype=torch.float32), pcm.new_empty((spec.shape[1],), dtype=torch.float32)
-
-
-def _denoised_backward_impl(grad, pcm, stats, profile, *args):
-    from orcai_amd.frontend import get_frontend
-
-    _check_pcm(pcm, "orcai::denoised_spectrogram_backward")
-    with torch.cuda.device(pcm.device):
-        return get_frontend(pcm.device).denoised_spectrogram_backward(pcm.detach(), grad.contiguous(), stats, profile, _denoised_parameter(*args))
-
-
-_FRONT_END_OPS["denoised_spectrogram_with_stats"] = torch.library.custom_op(
-    "orcai::denoised_spectrogram_with_stats", _denoised_with_stats_impl, mutates_args=(), schema=f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> (Tensor, Tensor, Tensor)")
-_FRONT_END_OPS["denoised_spectrogram_with_stats"].register_fake(_denoised_with_stats_fake)
-_FRONT_END_OPS["denoised_spectrogram_backward"] = torch.library.custom_op(
-    "orcai::denoised_spectrogram_backward", _denoised_backward_impl, mutates_args=(),
-    schema=f"(Tensor grad, Tensor pcm, Tensor stats, Tensor profile, {_DENOISED_ARGUMENTS.removesuffix(', float q_lo, float q_hi')}) -> Tensor")
-_FRONT_END_OPS["denoised_spectrogram_backward"].register_fake(lambda grad, pcm, stats, profile, *args: pcm.new_empty((pcm.shape[0],), dtype=torch.float32))
-
-
-def _denoised_gradient_sizes(sampling_rate, nfft, hop, freq_hi, n_mels, *rest) -> None:
-    """The linear route's forward takes sizes its backward does not (the mel route's refusals are mel.mel_config's, in the forward)."""
-    from orcai_amd.frontend import FrontEnd
-
-    if n_mels <= 0:
-        FrontEnd._check_nfft_backward(nfft)
-
-
-class _DenoisedWrtPcmFunction(torch.autograd.Function):
-    """forward(pcm, *args) of orcai::denoised_spectrogram_wrt_pcm(pcm, *args); the backward reads pcm, the statistics and the profile of that forward."""
-
-    @staticmethod
-    def forward(ctx, pcm, *args):
-        _denoised_gradient_sizes(*args)
-        with torch._C._AutoDispatchBelowAutograd():
-            spec, stats, profile = torch.ops.orcai.denoised_spectrogram_with_stats(pcm, *args)
-        ctx.args = args[:-2]
-        ctx.save_for_backward(pcm, stats, profile)
-        return spec
-
-    @staticmethod
-    def backward(ctx, grad):
-        pcm, stats, profile = ctx.saved_tensors
-        return (torch.ops.orcai.denoised_spectrogram_backward(grad, pcm, stats, profile, *ctx.args),) + (None,) * (2 + len(ctx.args))
-
-
-def _denoised_wrt_pcm_autograd(pcm, *args):
-    if torch.is_grad_enabled() and pcm.requires_grad:
-        return _DenoisedWrtPcmFunction.apply(pcm, *args)
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.orcai.denoised_spectrogram_wrt_pcm(pcm, *args)
-
-
-_register("denoised_spectrogram_wrt_pcm", f"(Tensor pcm, {_DENOISED_ARGUMENTS}) -> Tensor", _front_end_impl("orcai::denoised_spectrogram", _denoised_parameter),
-          _denoised_spectrogram_fake, _denoised_wrt_pcm_autograd)
-
-
-def denoised_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
-                         quantile: float, q_lo: float, q_hi: float) -> Tensor:
-    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the denoise parameter {quantile}: n_mels = 0 on the bins 0 .. freq_hi,
-    n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1].  No gradient: denoised_spectrogram_wrt_pcm has it."""
-    return torch.ops.orcai.denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi)
 
 
 def denoised_spectrogram_wrt_pcm(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool,
@@ -994,6 +927,15 @@ class _WaveformFrontEnd(torch.nn.Module):
     def extra_repr(self) -> str:
         return f"{self.native_rate} Hz -> {self.sampling_rate} Hz, nfft={self.nfft}, hop={self.hop}, "
 
+    def _linear_or_mel(self, sp: dict, cfg: dict | None) -> tuple:
+        """(freq_hi, n_mels, fmin, fmax, htk, slaney_norm) of an op that chooses its route by n_mels, from cfg = mel.mel_config(sp)."""
+        if cfg is not None:
+            return (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
+        if float(sp["freq_range"][0]) != 0.0:
+            raise ValueError(f"{type(self).__name__}: freq_range must start at 0 (orcai::{self._op.removesuffix('_wrt_pcm')} keeps the leading bins), "
+                             f"got {sp['freq_range']}")
+        return (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
+
 
 class WaveformFrontEnd(_WaveformFrontEnd):
     """A recording at the rate it was made at -> the [T, K] spectrogram the detector reads, differentiable down to those samples:
@@ -1059,13 +1001,7 @@ class PcenWaveformFrontEnd(_WaveformFrontEnd):
         if pc is None:
             raise ValueError("PcenWaveformFrontEnd: spectrogram parameter pcen is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
                              "native_rate) returns the dB front end for it")
-        cfg = mel.mel_config(sp)
-        if cfg is None and float(sp["freq_range"][0]) != 0.0:
-            raise ValueError(f"PcenWaveformFrontEnd: freq_range must start at 0 (orcai::pcen_spectrogram keeps the leading bins), got {sp['freq_range']}")
-        if cfg is None:
-            self.route = (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
-        else:
-            self.route = (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
+        self.route = self._linear_or_mel(sp, mel.mel_config(sp))
         self.pcen = tuple(pc[k] for k in pcen.PCEN_KEYS)  # time_constant, gain, bias, power, eps, scale: the op's order
 
     @property
@@ -1098,11 +1034,7 @@ class DenoisedWaveformFrontEnd(_WaveformFrontEnd):
         cfg = mel.mel_config(sp)
         if cfg is None:
             FrontEnd._check_nfft_backward(sp["nfft"])
-            if float(sp["freq_range"][0]) != 0.0:
-                raise ValueError(f"DenoisedWaveformFrontEnd: freq_range must start at 0 (orcai::denoised_spectrogram keeps the leading bins), got {sp['freq_range']}")
-            self.route = (float(sp["freq_range"][1]), 0, 0.0, 0.0, False, True)
-        else:
-            self.route = (0.0, cfg["n_mels"], cfg["fmin"], cfg["fmax"], cfg["htk"], cfg["norm"] == "slaney")
+        self.route = self._linear_or_mel(sp, cfg)
         self.quantile = dn["quantile"]
 
     @property

@@ -100,14 +100,22 @@ def test_tie_share_of_the_scan_cases(name):
 
 
 def test_the_pinned_refusals_name_the_new_entry_points():
-    """The four refusals tests/test_pcen_gpu.py pins keep raising; what they say now points at the gradient's own names (checked by string: raising them
-    for real needs the GPU and is what that file does)."""
+    """The four refusals tests/test_pcen_gpu.py pins keep raising; what they say now points at the gradient's own names (the methods' by string: raising
+    them for real needs the GPU and is what that file does; the forward-only ops' by a backward on fake tensors)."""
+    from torch._subclasses.fake_tensor import FakeTensorMode
+
     from orcai_amd import frontend, torch_ops
 
     assert "FrontEnd.pcen_spectrogram_backward" in inspect.getsource(frontend.FrontEnd._no_pcen_gradient)
     for method in (frontend.FrontEnd.spectrogram_backward, frontend.FrontEnd.mel_spectrogram_backward):
         assert "_no_pcen_gradient" in inspect.getsource(method)
-    assert "pcen_spectrogram_wrt_pcm" in inspect.getsource(torch_ops._PcenSpectrogramFunction.backward)
+    route = (48000, 512, 256, 16000.0, 0, 0.0, 0.0, False, True)
+    for base, tail in (("pcen_spectrogram", (0.4, 0.98, 2.0, 0.5, 1e-6, 2.0**31)), ("denoised_spectrogram", (0.5,))):  # the two forward-only ops, for real
+        with FakeTensorMode():
+            x = torch.empty(4113, requires_grad=True)
+            y = getattr(torch.ops.orcai, base)(x, *route, *tail, 0.01, 0.999)
+            with pytest.raises(NotImplementedError, match=f"orcai::{base}_wrt_pcm"):
+                torch.autograd.grad(y.sum(), x)
     sp = {"sampling_rate": 48000, "nfft": 512, "n_overlap": 256, "freq_range": [0, 16000], "quantiles": [0.01, 0.999], "pcen": {}}
     for make in (torch_ops.waveform_front_end, torch_ops.WaveformFrontEnd, torch_ops.MelWaveformFrontEnd):
         with pytest.raises(NotImplementedError, match="PcenWaveformFrontEnd"):
