@@ -378,6 +378,49 @@ int orcai_make_denoised_spectrogram(const float* pcm, int64_t n_samples, int n_f
                                     const int* band_off, const float* weights, int n_weights, int64_t rank_col, int64_t rank_lo, int64_t rank_hi, float top_db,
                                     float* out, float* profile, void* scratch, void* workspace, void* stream);
 
+/* The time-varying noise floor (the spectrogram parameter "denoise" with "segment" set).  The rows of x = f32[rows][cols] are cut into
+ * S = max(1, rows / seg_rows) segments: segment s < S - 1 is rows [s seg_rows, (s + 1) seg_rows), the last one [(S - 1) seg_rows, rows) -- it absorbs the
+ * remainder, so it has seg_rows .. 2 seg_rows - 1 rows (all the rows when S == 1, which may be fewer than seg_rows).
+ *
+ * orcai_segment_column_select: out[s][c] = the rank-th smallest of column c inside segment s (rank_last-th inside the last segment), bit for bit what
+ * orcai_column_select(x + s seg_rows cols, n_s, cols, rank_s) returns.  Two routes with the same bytes, chosen by one rule
+ * (orcai_segment_column_select_route: 1 fused, 0 loop): while 61 ns x the rows of the longest segment <= 45 us x S (a lone workgroup's time per row of its
+ * slab against the launches of one orcai_column_select, both measured: DESIGN 4.25) ONE launch in which a workgroup owns one (segment, 32 adjacent
+ * columns), keeps the u32[32][257] histogram and the columns' {prefix, rank} in LDS (33.2 KiB static, no opt-in), runs all four digit passes itself and
+ * re-reads its own slab (n_s rows x 128 bytes) between them: no global histogram, no global atomics, out written with ordinary stores; columns of a
+ * partial group idle their lanes (no lane packing).  Few, long segments would leave most compute units idle while each workgroup walks megabytes, and the
+ * entry loops over orcai_column_select on the row ranges instead, through scratch.  orcai_segment_column_select_fused runs the one-launch route whatever the rule says
+ * (the measurement's and the tests' handle; no scratch).
+ *   rank       0 <= rank < seg_rows, read for the segments in front of the last (not checked when S == 1);  rank_last  0 <= rank_last < rows of the last
+ *   out        f32[S][cols];  scratch  orcai_segment_column_select_scratch_bytes(rows, cols, seg_rows) bytes, 4-byte aligned: orcai_column_select's
+ *              histograms and state, then f32[S][cols] this call leaves alone (orcai_make_segment_denoised_spectrogram's profile when none is passed)
+ * Asynchronous, no allocation, no host synchronisation.  ORCAI_E_BADARG before anything is launched: a null or not 4-byte aligned pointer, rows < 1 or
+ * >= 2^32, cols outside 1..4096, seg_rows < 1, a rank outside its segment.  The scratch size is 0 and the route ORCAI_E_BADARG for such sizes. */
+size_t orcai_segment_column_select_scratch_bytes(int64_t rows, int cols, int64_t seg_rows);
+int orcai_segment_column_select_route(int64_t rows, int cols, int64_t seg_rows);
+int orcai_segment_column_select(const float* x, int64_t rows, int cols, int64_t seg_rows, int64_t rank, int64_t rank_last, float* out, void* scratch,
+                                void* stream);
+int orcai_segment_column_select_fused(const float* x, int64_t rows, int cols, int64_t seg_rows, int64_t rank, int64_t rank_last, float* out, void* stream);
+
+/* In place: x[t][c] = fl32(x[t][c] - F[t][c]), F the floors m = f32[S][cols] interpolated linearly in time between the segment centres and held constant
+ * outside the first and the last.  In doubled integer coordinates u = 2 t and c2_s = 2 s seg_rows + n_s - 1 (n_s the rows of segment s):
+ *   u <= c2_0: F = m[0];   u >= c2_{S-1}: F = m[S-1];   else with c2_s <= u < c2_{s+1}:
+ *   a = (float)((double)(u - c2_s) / (double)(c2_{s+1} - c2_s)),   F = fl32(m[s] + fl32(a * fl32(m[s+1] - m[s])))   -- no fused multiply-add
+ * which is orcai_amd/denoise.py's segment_denoise_ref byte for byte; with S == 1 the bytes of orcai_subtract_columns.  One streaming pass shaped as
+ * orcai_subtract_columns' (16-byte accesses from the first 16-byte boundary of x, scalars in front and behind); {s, a} is computed in the kernel, once
+ * per 16-byte piece and again only where the piece crosses into the next row.  ORCAI_E_BADARG: null or not 4-byte aligned x or m, rows, cols and
+ * seg_rows as above. */
+int orcai_subtract_segment_floor(float* x, int64_t rows, int cols, int64_t seg_rows, const float* m, void* stream);
+
+/* orcai_make_denoised_spectrogram with orcai_segment_column_select(V, n_frames, k, seg_rows, rank_seg, rank_seg_last) -> m and
+ * orcai_subtract_segment_floor in place of orcai_column_select and orcai_subtract_columns; every other step, their order and the statistics contract
+ * are that entry's, byte for byte.  profile: f32[S][k] or null.  scratch: orcai_segment_column_select_scratch_bytes(n_frames, k, seg_rows) bytes.
+ * Forward only: orcai_denoised_spectrogram_bwd is the gradient of the global floor, not of this one. */
+int orcai_make_segment_denoised_spectrogram(const float* pcm, int64_t n_samples, int n_fft, int hop, int64_t n_frames, int k, const int* band_lo,
+                                            const int* band_hi, const int* band_off, const float* weights, int n_weights, int64_t seg_rows, int64_t rank_seg,
+                                            int64_t rank_seg_last, int64_t rank_lo, int64_t rank_hi, float top_db, float* out, float* profile, void* scratch,
+                                            void* workspace, void* stream);
+
 /* Gradient of orcai_make_denoised_spectrogram w.r.t. the audio.  Notation as at orcai_spectrogram_bwd (band_lo null) and orcai_mel_spectrogram_bwd
  * (band_lo set); dB is 10 log10(max(P, 1e-10)) on the linear route and 10 log10(max(M[m], 1e-10)) on the mel route.  With
  *   v = max(dB - ref_db, -top_db),  y = v - m[k] (f32, one rounding),  out = (clip(y, p_lo, p_hi) - p_lo) / (p_hi - p_lo)  and  g = dL/dout:

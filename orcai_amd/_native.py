@@ -197,6 +197,13 @@ _SIGNATURES = {
     "orcai_subtract_columns": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "orcai_make_denoised_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int, c_i64, c_i64, c_i64, C.c_float]
                                         + [C.c_void_p] * 5),
+    "orcai_segment_column_select_scratch_bytes": (C.c_size_t, [c_i64, C.c_int, c_i64]),
+    "orcai_segment_column_select_route": (C.c_int, [c_i64, C.c_int, c_i64]),
+    "orcai_segment_column_select": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orcai_segment_column_select_fused": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "orcai_subtract_segment_floor": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, C.c_void_p, C.c_void_p]),
+    "orcai_make_segment_denoised_spectrogram": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4
+                                                + [C.c_int, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_float] + [C.c_void_p] * 5),
     "orcai_denoised_spectrogram_bwd": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_int, c_i64, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
                                        + [C.c_float, C.c_void_p, C.c_void_p]),
     "orcai_denoised_spectrogram_bwd_occupancy": (C.c_int, [C.c_int, C.c_int]),

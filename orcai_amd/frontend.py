@@ -151,7 +151,9 @@ class FrontEnd:
         noise floor -- the order statistic denoise.quantile of the channel over the recording, the median by default -- before the quantile clip, which
         then runs on the denoised values (orcai_make_denoised_spectrogram); the statistics hold p_lo / p_hi as denoised values, pmax of the STFT and
         ref_db 0.  return_profile (denoise only): the f32[K] device tensor of the subtracted floors, in referenced dB, is returned last.  The statistics
-        and the profile together are what denoised_spectrogram_backward, the gradient of this route, reads (it recomputes ref_db from pmax)."""
+        and the profile together are what denoised_spectrogram_backward, the gradient of this route, reads (it recomputes ref_db from pmax).
+        With denoise.segment set as well the floor is time-varying (orcai_make_segment_denoised_spectrogram; denoise.segment_denoise_ref is its
+        definition) and the profile is f32[S, K], one row per segment.  Forward only."""
         n_fft, hop, K, cfg, pc = resolve_route(spectrogram_parameter)
         dn = denoise.denoise_config(spectrogram_parameter)  # beside the route: Route keeps its five fields
         if return_profile and dn is None:
@@ -171,12 +173,23 @@ class FrontEnd:
         if dn is not None:  # the dB spectrogram, linear or mel, minus every channel's own floor
             if T < 1:
                 raise ValueError(f"make_spectrogram: spectrogram parameter denoise needs at least one frame, got {T}")
-            profile = torch.empty(K, dtype=torch.float32, device=self.device) if return_profile else None
-            scratch = self._grown("column_select", self.lib.orcai_column_select_scratch_bytes(K) // 4)
-            rc = self.lib.orcai_make_denoised_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), nearest_rank_index(T, dn["quantile"]), r_lo, r_hi, TOP_DB,
-                                                          N.ptr(out), None if profile is None else N.ptr(profile), N.ptr(scratch), N.ptr(self.workspace),
-                                                          N.stream_ptr())
-            N.check(rc, "orcai_make_denoised_spectrogram")
+            if "segment" in dn:  # the time-varying floor: one order statistic per (segment, channel), interpolated between the segment centres
+                W = denoise.segment_rows(dn["segment"], spectrogram_parameter["sampling_rate"], hop)
+                S = denoise.segment_count(T, W)
+                profile = torch.empty((S, K), dtype=torch.float32, device=self.device) if return_profile else None
+                scratch = self._grown("column_select", self.lib.orcai_segment_column_select_scratch_bytes(T, K, W) // 4)
+                rc = self.lib.orcai_make_segment_denoised_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), W, nearest_rank_index(W, dn["quantile"]),
+                                                                      nearest_rank_index(T - (S - 1) * W, dn["quantile"]), r_lo, r_hi, TOP_DB, N.ptr(out),
+                                                                      None if profile is None else N.ptr(profile), N.ptr(scratch), N.ptr(self.workspace),
+                                                                      N.stream_ptr())
+                N.check(rc, "orcai_make_segment_denoised_spectrogram")
+            else:
+                profile = torch.empty(K, dtype=torch.float32, device=self.device) if return_profile else None
+                scratch = self._grown("column_select", self.lib.orcai_column_select_scratch_bytes(K) // 4)
+                rc = self.lib.orcai_make_denoised_spectrogram(*signal, *self._bands(spectrogram_parameter, cfg), nearest_rank_index(T, dn["quantile"]), r_lo, r_hi,
+                                                              TOP_DB, N.ptr(out), None if profile is None else N.ptr(profile), N.ptr(scratch),
+                                                              N.ptr(self.workspace), N.stream_ptr())
+                N.check(rc, "orcai_make_denoised_spectrogram")
         elif pc is not None:  # PCEN of the magnitudes, or of the mel band powers when mel is set as well
             a, b = pcen.smoother(pc["time_constant"], spectrogram_parameter["sampling_rate"], hop)
             scratch = self._grown("pcen", self.lib.orcai_pcen_scratch_bytes(T, K) // 4)
@@ -300,6 +313,7 @@ class FrontEnd:
         if denoise.denoise_config(spectrogram_parameter) is None:
             raise ValueError(f"{who}: the spectrogram parameter denoise is absent or null; FrontEnd.spectrogram_backward and FrontEnd.mel_spectrogram_backward "
                              "are the gradients of the plain dB front ends (FrontEnd.pcen_spectrogram_backward of the PCEN one)")
+        denoise.no_segment_gradient(spectrogram_parameter, who)  # the time-varying floor has no gradient yet: never the global floor's in its place
         return self._backward(pcm, grad, stats, spectrogram_parameter, who, profile=profile)
 
     # -- calculate_spectrogram (spectrogram.py:15-55): dB of all bins, referenced and floored ----
@@ -363,21 +377,26 @@ class FrontEnd:
         st = self.stats()
         return st["sel_lo_raw"], st["sel_hi_raw"]
 
-    def percentiles(self, x: torch.Tensor, q, dim: int | None = None) -> torch.Tensor:
+    def percentiles(self, x: torch.Tensor, q, dim: int | None = None, segment_rows: int | None = None) -> torch.Tensor:
         """Exact percentiles of any contiguous f32 CUDA tensor, taken flat: element i is the nearest_rank_index(x.numel(), q[i])-th smallest value, what
         ``np.percentile(x, 100 * q[i], method="nearest")`` returns for float32 data.  q: a sequence of fractions in [0, 1].  Returns f32[len(q)] on
         the device with no host synchronisation.  The ranks go through the radix select two at a time (a single one twice).
         dim=0: per column instead -- x of at least two dimensions is read as [R, C], C the product of the others (at most 4096), and the result is
         f32[len(q), *x.shape[1:]], what ``np.percentile(x, 100 * q, axis=0, method="nearest")`` returns: one orcai_column_select per q with rank
-        nearest_rank_index(R, q[i]).  No other dim is implemented."""
+        nearest_rank_index(R, q[i]).  No other dim is implemented.
+        segment_rows=W (dim=0 only): per column inside every segment of W rows -- S = max(1, R // W) segments, the last one taking the remainder -- by
+        orcai_segment_column_select: f32[len(q), S, *x.shape[1:]], or f32[S, *x.shape[1:]] when q is a single number instead of a sequence."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
             raise TypeError("percentiles: x must be a float32 CUDA tensor")
         if not x.is_contiguous():
             raise ValueError("percentiles: x must be contiguous")
-        q = [float(v) for v in q]
+        one_q = segment_rows is not None and isinstance(q, (int, float, np.integer, np.floating))  # a single fraction: no leading q axis (segment_rows only)
+        q = [float(q)] if one_q else [float(v) for v in q]
         total = x.numel()
         if not q or total == 0 or not all(0.0 <= v <= 1.0 for v in q):
             raise ValueError(f"percentiles: q must be a non-empty sequence of fractions in [0, 1] and x non-empty, got q = {q}, {total} values")
+        if segment_rows is not None and dim is None:
+            raise ValueError("percentiles: segment_rows needs dim=0 (segments are runs of rows)")
         if dim is not None:
             if dim != 0 or isinstance(dim, bool):
                 raise ValueError(f"percentiles: dim must be None (flat) or 0 (per column of [R, C]), got {dim!r}; selects along other dimensions are not implemented")
@@ -386,6 +405,18 @@ class FrontEnd:
             R, cols = x.shape[0], total // x.shape[0]
             if cols > 4096:
                 raise ValueError(f"percentiles: dim=0 takes at most 4096 columns (orcai_column_select), got {cols} for shape {tuple(x.shape)}")
+            if segment_rows is not None:
+                W = int(segment_rows)
+                if isinstance(segment_rows, bool) or W != segment_rows or W < 1:
+                    raise ValueError(f"percentiles: segment_rows must be a positive integer, got {segment_rows!r}")
+                S = denoise.segment_count(R, W)
+                res = torch.empty((len(q), S, *x.shape[1:]), dtype=torch.float32, device=self.device)
+                scratch = self._grown("column_select", self.lib.orcai_segment_column_select_scratch_bytes(R, cols, W) // 4)
+                for i, v in enumerate(q):
+                    rc = self.lib.orcai_segment_column_select(N.ptr(x), R, cols, W, nearest_rank_index(W, v), nearest_rank_index(R - (S - 1) * W, v), N.ptr(res[i]),
+                                                              N.ptr(scratch), N.stream_ptr())
+                    N.check(rc, "orcai_segment_column_select")
+                return res[0] if one_q else res
             res = torch.empty((len(q), *x.shape[1:]), dtype=torch.float32, device=self.device)
             scratch = self._grown("column_select", self.lib.orcai_column_select_scratch_bytes(cols) // 4)
             for i, v in enumerate(q):

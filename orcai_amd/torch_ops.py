@@ -14,6 +14,8 @@ known without a GPU.
     torch.ops.orcai.denoised_spectrogram_wrt_pcm(pcm, <the same arguments>) -> f32[T, K]
     torch.ops.orcai.percentile(x f32[...], q) -> f32[len(q)]
     torch.ops.orcai.column_percentile(x f32[R, ...], q) -> f32[len(q), ...]   (per column of [R, C]: np.percentile(x, 100 q, axis=0, method="nearest"))
+    torch.ops.orcai.segment_column_percentile(x f32[R, ...], q, segment_rows) -> f32[len(q), S, ...]   (the same inside every segment of segment_rows rows)
+    torch.ops.orcai.segment_denoised_spectrogram(pcm, <denoised_spectrogram's arguments up to quantile>, segment, q_lo, q_hi) -> f32[T, K]   (forward only)
     torch.ops.orcai.resample(pcm, sr_in, sr_out) -> f32[ceil(n * sr_out / sr_in)]
     torch.ops.orcai.decode_pcm(frames uint8[nbytes], channels, channel, format) -> f32[n_frames]
     torch.ops.orcai.forward(x f32[B, H, W], weights, stats, config, training, dropout_seed) -> f32[B, steps, labels]
@@ -380,9 +382,21 @@ def _pcen_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, 
     return sp
 
 
-def _denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo=0.0, q_hi=1.0) -> dict:
+def _denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo=0.0, q_hi=1.0, segment=None) -> dict:
+    """The parameter of orcai::denoised_spectrogram and its *_wrt_pcm family, whose schemas have no segment: the global floor.  segment exists so that a
+    caller who builds the differentiable ops' parameter from a parameter file cannot drop the key silently: set, it is refused here."""
     sp = _linear_or_mel_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
     sp["denoise"] = {"quantile": quantile}
+    if segment is not None:
+        from orcai_amd import denoise
+
+        denoise.no_segment_gradient(dict(sp, denoise={"quantile": quantile, "segment": segment}), "orcai::denoised_spectrogram_wrt_pcm")
+    return sp
+
+
+def _segment_denoised_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, segment, q_lo=0.0, q_hi=1.0) -> dict:
+    sp = _linear_or_mel_parameter(sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, q_lo, q_hi)
+    sp["denoise"] = {"quantile": quantile, "segment": segment}
     return sp
 
 
@@ -401,6 +415,9 @@ class _ForwardOnlyFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
+        if ctx.base == "segment_denoised_spectrogram":
+            raise NotImplementedError("orcai::segment_denoised_spectrogram has no gradient: the time-varying floor (denoise.segment) is forward only, and "
+                                      "orcai::denoised_spectrogram_wrt_pcm differentiates the global floor, another forward")
         raise NotImplementedError(f"orcai::{ctx.base} has no gradient (as orcai::spectrogram and orcai::mel_spectrogram have none): "
                                   f"orcai::{ctx.base}_wrt_pcm is the same computation with the gradient w.r.t. pcm")
 
@@ -422,6 +439,9 @@ _PCEN_ARGUMENTS = _ROUTE_ARGUMENTS + "float time_constant, float gain, float bia
 _DENOISED_ARGUMENTS = _ROUTE_ARGUMENTS + "float quantile, float q_lo, float q_hi"
 _register_forward_only("pcen_spectrogram", _PCEN_ARGUMENTS, _pcen_parameter)
 _register_forward_only("denoised_spectrogram", _DENOISED_ARGUMENTS, _denoised_parameter)
+# the time-varying floor (denoise.segment, seconds): forward only and, unlike the two above, with no *_wrt_pcm twin yet
+_SEGMENT_DENOISED_ARGUMENTS = _ROUTE_ARGUMENTS + "float quantile, float segment, float q_lo, float q_hi"
+_register_forward_only("segment_denoised_spectrogram", _SEGMENT_DENOISED_ARGUMENTS, _segment_denoised_parameter)
 
 
 def pcen_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool, slaney_norm: bool,
@@ -438,6 +458,13 @@ def denoised_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, f
     """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the denoise parameter {quantile}: n_mels = 0 on the bins 0 .. freq_hi,
     n_mels > 0 on the mel bands {n_mels, fmin, fmax, htk, norm}.  f32[T, K] in [0, 1].  No gradient: denoised_spectrogram_wrt_pcm has it."""
     return torch.ops.orcai.denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, q_lo, q_hi)
+
+
+def segment_denoised_spectrogram(pcm: Tensor, sampling_rate: int, nfft: int, hop: int, freq_hi: float, n_mels: int, fmin: float, fmax: float, htk: bool,
+                                 slaney_norm: bool, quantile: float, segment: float, q_lo: float, q_hi: float) -> Tensor:
+    """FrontEnd.make_spectrogram of f32 pcm[n] (already at sampling_rate) with the denoise parameter {quantile, segment}: the per-channel floor taken per
+    segment of `segment` seconds and interpolated between the segment centres (orcai_make_segment_denoised_spectrogram).  f32[T, K] in [0, 1].  No gradient."""
+    return torch.ops.orcai.segment_denoised_spectrogram(pcm, sampling_rate, nfft, hop, freq_hi, n_mels, fmin, fmax, htk, slaney_norm, quantile, segment, q_lo, q_hi)
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::percentile
@@ -526,6 +553,52 @@ def column_percentile(x: Tensor, q: list[float]) -> Tensor:
     """f32[len(q), *x.shape[1:]] on x's device: what ``np.percentile(x, 100 * q, axis=0, method="nearest")`` returns for the float32 values of x, exactly;
     x a contiguous f32 CUDA tensor of at least two dimensions with at most 4096 columns, q fractions in [0, 1].  No host synchronisation, no gradient."""
     return torch.ops.orcai.column_percentile(x, [float(v) for v in q])
+
+
+# ---------------------------------------------------------------------------------------------------------------- orcai::segment_column_percentile
+# FrontEnd.percentiles(dim=0, segment_rows=W): the column percentiles inside every segment of W rows (S = max(1, R // W) segments, the last one taking the
+# remainder), by orcai_segment_column_select, one call per q.  Forward only, for the reason orcai::percentile is.
+def _segment_column_percentile_impl(x, q, segment_rows):
+    from orcai_amd.frontend import get_frontend
+
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise TypeError(f"orcai::segment_column_percentile: x must be a float32 CUDA tensor, got {getattr(x, 'dtype', None)} on {getattr(x, 'device', None)}")
+    with torch.cuda.device(x.device):
+        return get_frontend(x.device).percentiles(x.detach(), list(q), dim=0, segment_rows=segment_rows)
+
+
+def _segment_column_percentile_fake(x, q, segment_rows):
+    S = x.shape[0] // segment_rows
+    return x.new_empty((len(q), S if S > 1 else 1, *x.shape[1:]), dtype=torch.float32)
+
+
+class _SegmentColumnPercentileFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, q, segment_rows):
+        with torch._C._AutoDispatchBelowAutograd():
+            return torch.ops.orcai.segment_column_percentile(x, q, segment_rows)
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("orcai::segment_column_percentile has no gradient: an order statistic is a constant of every backward in this package "
+                                  "(the quantile bounds of the front ends are held constant too)")
+
+
+def _segment_column_percentile_autograd(x, q, segment_rows):
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _SegmentColumnPercentileFunction.apply(x, q, segment_rows)
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.orcai.segment_column_percentile(x, q, segment_rows)
+
+
+_register("segment_column_percentile", "(Tensor x, float[] q, SymInt segment_rows) -> Tensor", _segment_column_percentile_impl, _segment_column_percentile_fake,
+          _segment_column_percentile_autograd)
+
+
+def segment_column_percentile(x: Tensor, q: list[float], segment_rows: int) -> Tensor:
+    """f32[len(q), S, *x.shape[1:]] on x's device: for every segment of segment_rows rows of x (S = max(1, R // segment_rows), the last one taking the
+    remainder) what ``np.percentile(segment, 100 * q, axis=0, method="nearest")`` returns, exactly.  No host synchronisation, no gradient."""
+    return torch.ops.orcai.segment_column_percentile(x, [float(v) for v in q], int(segment_rows))
 
 
 # ---------------------------------------------------------------------------------------------------------------- orcai::forward, orcai::forward_wrt_input
@@ -1031,6 +1104,7 @@ class DenoisedWaveformFrontEnd(_WaveformFrontEnd):
         if dn is None:
             raise ValueError("DenoisedWaveformFrontEnd: spectrogram parameter denoise is absent or null; torch_ops.waveform_front_end(spectrogram_parameter, "
                              "native_rate) returns the dB front end for it")
+        denoise.no_segment_gradient(sp, "DenoisedWaveformFrontEnd")
         cfg = mel.mel_config(sp)
         if cfg is None:
             FrontEnd._check_nfft_backward(sp["nfft"])
